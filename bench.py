@@ -28,10 +28,18 @@ be placed finer than 9 % of a rank's work, and a set of one or two frames' share
 as ten.  `--shard rows` = equal-height bands, one frame per set of launches.  `--rehearse-world N` does on ONE GPU what rank 0 of
 N would do, without the collective (diagnostic).
 
-Prints one JSON line (driver contract) with `roofline` and `cpu_baseline` objects.  The roofline is the VALU roof: this
-traversal is cache-resident pointer chasing whose binding resource is vector-ALU issue, priced with the
-per-opcode SIMD cycles measured by tools/calibrate_valu.py; the algorithmic-bytes figure of SURVEY s8d is reported against the
-HBM and L2 peaks next to it, with the measured HBM traffic.
+Prints one JSON line (driver contract).  A plain run does only what the headline figure needs: it sets up, settles the clocks,
+warms up, times the K steps and prints metric, value, unit, higher_is_better, dtype, ms_per_step and the run's configuration.
+`--full` adds everything else, none of it inside the timed region: the `roofline` object (counting builds, isolated launches,
+clock probe), the random-ray leg, the 3840x2160 leg of an N-GPU run, the other configurations and the `cpu_baseline` object.
+The roofline is the VALU roof: this traversal is cache-resident pointer chasing whose binding resource is vector-ALU issue
+(DESIGN.md s5), priced with the per-opcode SIMD cycles measured by tools/calibrate_valu.py; the algorithmic-bytes figure of
+SURVEY s8d is reported against the HBM and L2 peaks next to it, with the measured HBM traffic.
+
+`--dump-outputs DIR` writes, after the timed steps, the frame the last timed step produced (with several ranks: the frame rank 0
+assembled) as DIR/pixels_rgb.npy: float32 [height, width, 3], the R, G, B bytes of each 0x00RRGGBB pixel.  The scene, camera and
+light are fixed, so the same arguments give the same inputs in every run.  `--rehearse-world` renders rank 0's share only and
+refuses it.
 """
 import argparse
 import importlib
@@ -54,6 +62,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: roofline, random rays, the N-GPU 3840x2160 leg, --other-configs, cpu_baseline "
+                         "(off by default: a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last step produced (several ranks: the frame rank 0 assembled) to "
+                         "DIR/pixels_rgb.npy (float32 [height, width, 3]); not with --rehearse-world, which renders rank 0's share only")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--level", type=int, default=8, help="atrium tessellation level; 8 -> 1,048,576 triangles")
@@ -69,14 +83,14 @@ def parse():
     ap.add_argument("--wire", choices=["auto", "rgb24", "rgba32"], default="auto",
                     help="several GPUs, --shard tilerows: a share's pixels on the link as 3 bytes (0x00RRGGBB without its zero byte; default where the width is a multiple of 4) or as they are")
     ap.add_argument("--no-leg-4k", dest="leg_4k", action="store_false",
-                    help="several GPUs: skip the second leg (BASELINE configs[3]: the same scene at 3840x2160 split over the ranks, reported under extras.leg_3840x2160)")
+                    help="--full, several GPUs: skip the second leg (BASELINE configs[3]: the same scene at 3840x2160 split over the ranks, reported under extras.leg_3840x2160)")
     ap.add_argument("--rehearse-world", type=int, default=0,
                     help="diagnostic, one GPU: do per frame what rank 0 of an N-GPU run does (its share of the frame, extraction, assembly) without the collective")
     ap.add_argument("--no-shadow", action="store_true")
     ap.add_argument("--settle-frames", type=int, default=160,
                     help="untimed frames before the warmup steps that bring the GPU clocks to their sustained state (0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU-seconds of host work for the main cpu_baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline object")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="--full: CPU-seconds of host work for the main cpu_baseline leg")
     ap.add_argument("--frames-in-flight", type=int, default=2,
                     help="frames kept in flight on as many HIP streams (vxrt_accel_frames_in_flight); 1 = strictly serial frames")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -84,12 +98,12 @@ def parse():
     ap.add_argument("--one-rank-group", action="store_true",
                     help="diagnostic, one GPU: run the N > 1 code path (process group, interleaved batches, dist.gather, barriers, all_reduce) with a group of ONE rank -- the RCCL calls of the multi-GPU run on a 1-GPU box")
     ap.add_argument("--other-configs", choices=["none", "short", "full"], default="full",
-                    help="1 GPU only: short host-timed legs of BASELINE.json's other configurations under extras.other_configs (short: bunny-class 1024^2, "
+                    help="--full, 1 GPU only: short host-timed legs of BASELINE.json's other configurations under extras.other_configs (short: bunny-class 1024^2, "
                          "the diffuse bounce, 3840x2160; full, the default: + configs[4], the 10M-triangle hairball with 16 spp AO -- 3 timed frames; its tree "
                          "takes ~6 s of host time to build)")
     ap.add_argument("--other-configs-child", choices=["short", "full"], default=None, help=argparse.SUPPRESS)
     ap.add_argument("--random-rays", type=int, default=16777216,
-                    help="second leg (SURVEY s8d 'random rays vs fixed BVH'): N incoherent rays per GPU through vxrt_trace, reported under extras; 0 = skip")
+                    help="--full: second leg (SURVEY s8d 'random rays vs fixed BVH'): N incoherent rays per GPU through vxrt_trace, reported under extras; 0 = skip")
     return ap.parse_args()
 
 
@@ -377,6 +391,26 @@ def other_configs(vrt, torch, dev, ds, scene, params, full):
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000      # all files together, .npy headers included
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: `frame` ([height, width] int32, 0x00RRGGBB) as DIR/pixels_rgb.npy, float32 [height, width, 3] (every byte is
+    exact in float32).  A frame larger than 64 MB (10^6 bytes) in that form is written as a fixed sample of its pixels instead:
+    pixels_rgb.npy [n, 3] and their row-major indices in pixel_index.npy (float64), drawn with seed 0."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    px = frame.cpu().numpy().view(np.uint32)
+    rgb = np.stack([(px >> 16) & 0xFF, (px >> 8) & 0xFF, px & 0xFF], axis=-1).astype(np.float32)
+    room = DUMP_LIMIT_BYTES - 4096      # (two .npy headers of 128 bytes, with headroom)
+    if rgb.nbytes > room:
+        n = room // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(px.size, size=n, replace=False))
+        rgb = rgb.reshape(-1, 3)[idx]
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "pixels_rgb.npy"), rgb)
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks here, as fresh child processes (one per
     GPU, `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>`), BEFORE anything in this process touches
@@ -450,6 +484,8 @@ def main():
         raise SystemExit("bench.py: --gpus %d but the launcher set WORLD_SIZE=%d" % (a.gpus, world))
     # rehearsal of rank 0 of an N-GPU run on one GPU, without the network: everything a rank does per frame except the collective
     rehearse = a.rehearse_world if (world == 1 and a.rehearse_world > 1) else 0
+    if rehearse and a.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs writes whole frames; --rehearse-world renders rank 0's share of each frame only")
     if rehearse:
         world = rehearse
     if not torch.cuda.is_available():
@@ -631,10 +667,11 @@ def main():
     assert rtapi.status(sptr) == 0, "kernel status (traversal stack overflow)"
     rays_rank = int(counters[0].item())
     algo = algo_timed = None
-    if world == 1:
+    # (--full: the roofline's counting builds)
+    if a.full and world == 1:
         algo = rtapi.render_stats(ds.accel, W, H, 0, H, params, frames[0].data_ptr(), shadow, sptr)                  # reference-order counts
         algo_timed = rtapi.render_stats(ds.accel, W, H, 0, H, params, frames[0].data_ptr(), shadow, sptr, timed=True)  # the traversal that is timed
-    elif rank == 0:
+    elif a.full and rank == 0:
         # several ranks: rank 0 counts the WHOLE frame once (into a scratch frame), so that the N-rank line can say which tree and
         # which traversal its roofline numerator belongs to; the timed region traces the ranks' bands only
         scratch = torch.zeros((H, W), dtype=torch.int32, device=dev)
@@ -646,6 +683,7 @@ def main():
     gdone = [None] * len(frames)   # per framebuffer: event of the last gather that read it
 
     no_gather = bool(rehearse and os.environ.get("VXRT_BENCH_NO_GATHER"))   # (diagnostic: the share's launches alone)
+    assembled = [None]     # rank 0: the frame(s) of the last image assembly (--dump-outputs)
 
     def step(i, ev=None, k=1):
         """Issues launch group i: k steps (k = 1 except with several ranks, where a group is a set of up to B frames)."""
@@ -669,12 +707,12 @@ def main():
             gather_stream.wait_event(done)
             with torch.cuda.stream(gather_stream):
                 if bands:
-                    bg.gather(b, k)
+                    assembled[0] = bg.gather(b, k)
                 elif a.shard == "tilerows":
-                    ig.gather(buf, b, via_cpu=(cdev == "cpu"), k=(k if B > 1 else None))
+                    assembled[0] = ig.gather(buf, b, via_cpu=(cdev == "cpu"), k=(k if B > 1 else None))
                 else:
                     band = buf[y0:y1]
-                    sharding.gather_frame(band if cdev != "cpu" else band.cpu(), H, W, rank, world)
+                    assembled[0] = sharding.gather_frame(band if cdev != "cpu" else band.cpu(), H, W, rank, world)
                 gdone[b] = torch.cuda.Event()
                 gdone[b].record(gather_stream)
         return assemble
@@ -696,16 +734,16 @@ def main():
         for fin in pend:
             fin()
 
-    # isolated duration of one step's launches (nothing else on the GPU): HIP events on the launch stream
+    # --full: isolated duration of one step's launches (nothing else on the GPU): HIP events on the launch stream
     iso = []
-    for i in range(min(10, max(3, a.steps))):
+    for i in range(min(10, max(3, a.steps)) if a.full else 0):
         e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         e[0].record(stream)
         launch(frames[0])
         e[1].record(stream)
         torch.cuda.synchronize()
         iso.append(e[0].elapsed_time(e[1]))
-    iso_ms = sum(iso) / len(iso)
+    iso_ms = sum(iso) / len(iso) if iso else None
     def groups(n):     # n steps as launch groups of at most B
         return [min(B, n - g) for g in range(0, n, B)]
     timed_groups = list(set_sizes) if set_sizes else groups(a.steps)
@@ -737,12 +775,12 @@ def main():
         issue(list(enumerate(groups(a.settle_frames) + groups(a.warmup))))
     # every frame rendered before the timed region opens (one for the ray count, two counting builds, the isolated launches,
     # the band-planning sets, the clock-settling frames, the W warmup steps): none of them is timed, none of their results is reused
-    frames_before = 1 + (2 if world == 1 else (1 if rank == 0 else 0)) + len(iso) + settled + a.warmup + (band_plan["rounds"] * 16 * (world if rehearse else 1) if band_plan else 0)
+    frames_before = 1 + (0 if algo_timed is None else (2 if world == 1 else 1)) + len(iso) + settled + a.warmup + (band_plan["rounds"] * 16 * (world if rehearse else 1) if band_plan else 0)
     torch.cuda.synchronize()
     if grouped:
         dist.barrier()
     torch.cuda.synchronize()
-    probe = ClockProbe(vrt, torch, dev) if rank == 0 else None
+    probe = ClockProbe(vrt, torch, dev) if rank == 0 and a.full else None
     if probe:
         probe.launch(0, sptr)          # (untimed: behind the warmup steps, before the region's opening synchronisation)
         torch.cuda.synchronize()
@@ -776,6 +814,13 @@ def main():
     else:
         rays_all = rays_rank
     assert rtapi.status(sptr) == 0
+    if a.dump_outputs and rank == 0:
+        if multi:
+            last = assembled[0]                     # [k, H, W] or [H, W]
+        else:
+            last = frames[(len(timed_groups) - 1) % len(frames)]
+            last = last[timed_groups[-1] - 1] if last.dim() == 3 else last
+        dump_outputs(a.dump_outputs, last[-1] if last.dim() == 3 else last)
     # HIP events on the launch streams.  With frames in flight the launches of consecutive steps overlap, so the per-launch
     # duration that prices the roofline is the span of the timed region's events divided by the launches in it (their union,
     # not their sum); the overlapped and the isolated per-launch durations are reported next to it.
@@ -788,7 +833,7 @@ def main():
 
     extras = {}
     random_sample = None
-    if a.random_rays:
+    if a.full and a.random_rays:
         # north_star's second figure: synthetic random rays against the fixed BVH, ray buffer (24 B/ray) in HBM ->
         # hit records (24 B/ray); every rank traces its own N rays (seed 12345 + rank), no collective
         n = a.random_rays
@@ -837,7 +882,7 @@ def main():
                                      "node_fetches": rstats["node_fetches"], "tri_fetches": rstats["tri_fetches"]}
         del rays, hits
 
-    if multi and a.shard == "tilerows" and a.leg_4k and (W, H, a.level) == (1920, 1080, 8) and B > 1:
+    if a.full and multi and a.shard == "tilerows" and a.leg_4k and (W, H, a.level) == (1920, 1080, 8) and B > 1:
         # BASELINE configs[3], the workload it names for 8 GPUs: the same scene at 3840x2160, the framebuffer's tile rows interleaved over
         # the ranks, one gather per set -- a second leg of the N > 1 line, through the very machinery of the first (the closures above see
         # the rebound frame size, buffers and assembly).  2 N timed frames as two sets, the last one N / 4 frames (one 1080p frame's bytes
@@ -889,7 +934,7 @@ def main():
         finally:
             W, H, ig, frames, gdone, B, frame_stride = main_leg
 
-    if world == 1 and a.other_configs != "none" and (W, H, a.level) == (1920, 1080, 8):
+    if a.full and world == 1 and a.other_configs != "none" and (W, H, a.level) == (1920, 1080, 8):
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--other-configs-child", a.other_configs], capture_output=True, text=True, timeout=600)
@@ -932,116 +977,117 @@ def main():
             if ig is not None:
                 out["config"].update({"sets_of_the_timed_steps": timed_groups, "wire_format": ig.wire,
                                       "wire_bytes_per_rank_last_set": ig.wire_bytes(timed_groups[-1])})
-        prof = load_profile_constants()
-        # one step = the launches of vxrt_render: persistent traversal kernel (dominant, > 93 % of the step), the EXACT launches
-        # for the rays with NaN-capable slabs, and the shading pass; priced together
-        clk = [probe.ghz(0), probe.ghz(1)] if probe else [None, None]
-        clock_held = (sum(clk) / 2.0) if all(clk) else None
-        clock = clock_held or CLOCK_GHZ
-        # ONE denominator: wave64 VALU instructions per second against what 1,024 SIMDs can issue at the clock held in the timed
-        # region, at the guide's 2 cycles per wave64 VALU instruction (MI355X_MICROARCH.md: "issues each VALU instruction over 2
-        # cycles").  The same fraction at the 2.2 cycles this chip measured for dense independent streams (tools/calibrate_valu.py)
-        # and at the nominal 2.4 GHz are given next to it, labelled.
-        roof = {"bound": "valu", "achieved": None, "peak": round(SIMDS * clock / 2.0, 1), "unit": "G wave64 VALU instructions/s", "frac": None, "traffic": None,
-                "peak_is": "1024 SIMDs x clock held in the timed region / 2 cycles per wave64 VALU instruction (guide constant)",
-                "clock_ghz_held": round(clock_held, 4) if clock_held else None,
-                "clock_probe_ghz_before_after": [round(c, 4) if c else None for c in clk],
-                "clock_source": "one-wavefront s_memtime / s_memrealtime probe right before the timed region opens and right after it closes (lib/libvxrt_calib.so)" if clock_held
-                                else "nominal %.1f GHz (probe library not available)" % CLOCK_GHZ,
-                "kernel": "rt_persistent_kernel<JOB_RENDER%s> (+ EXACT launches + rt_shade_kernel)" % ("_SHADOW" if shadow else ""),
-                "kernel_ms": round(kern_ms, 4), "kernel_ms_overlapped": round(ovl_ms, 4), "kernel_ms_isolated": round(iso_ms, 4),
-                "kernel_ms_is": "GPU-clock span of the timed region (HIP events: first step's start -> an event behind every stream) / steps",
-                "frames_per_launch": B, "launch_set_ms_overlapped": round(ovl_ms * a.steps / max(1, len(evs)), 4),
-                "frames_in_flight": nfl,
-                "why_valu": "the scene is cache-resident (measured HBM traffic = a few % of the HBM peak) and relieving the memory path measured neutral (LDS-staged "
-                            "top of the tree: 39 % of node steps from LDS, -17 % vector-memory instructions, +0 %: profiles/r02_b_lds_top_counters.txt); what moves the time "
-                            "is the number of VALU instructions"}
-        # what the per-frame profile constants must have been taken on to be usable here (and what a new profile pass records)
-        ident = {"width": W, "height": H, "shadow": int(shadow), "bvh_nodes": scene.n_bvh_nodes, "tree_sha16": tree_id(scene),
-                 "kernel_source_sha16": kernel_source_id(),
-                 "node_fetches_timed": algo_timed["node_fetches"] if algo_timed else None,
-                 "tri_fetches_timed": algo_timed["tri_fetches"] if algo_timed else None,
-                 "rays": algo_timed["rays"] if algo_timed else None}
-        roof["identity"] = ident
-        why_not = None
-        if not prof:
-            why_not = "profiles/valu_profile.json not found"
-        else:
-            why_not = profile_mismatch(prof, ident)
-        if why_not:
-            roof["frac_is_null_because"] = why_not
-        if prof and world > 1 and not why_not and not rehearse:
-            # N ranks: the frame's instructions are a property of the frame, whoever traces which band: the whole job's rate against
-            # N x the per-GPU roof (clock: rank 0's probe)
-            n_valu = prof["valu_instr_per_frame"]
-            ach = n_valu / (elapsed / a.steps) / 1e9
-            roof.update({"achieved": round(ach, 1), "peak": round(world * SIMDS * clock / 2.0, 1), "frac": round(ach / (world * SIMDS * clock / 2.0), 4),
-                         "peak_is": "%d GPUs x 1024 SIMDs x clock held on rank 0 / 2 cycles per wave64 VALU instruction" % world,
-                         "achieved_is": "wave64 VALU instructions of one whole frame (profile constant) x steps / max-over-ranks wall time of the timed region",
-                         "valu_instr_per_frame": n_valu, "valu_source": prof.get("source")})
-        if prof and world == 1 and not why_not:
-            # profile constants of THIS workload (instruction counts per frame are a property of the frame and the code), source named in the file
-            n_valu = prof["valu_instr_per_frame"]
-            ach = n_valu / (kern_ms * 1e-3) / 1e9
-            mk = prof.get("main_kernel", {})
-            roof.update({"achieved": round(ach, 1), "frac": round(ach / (SIMDS * clock / 2.0), 4),
-                         "frac_isolated": round(n_valu / (iso_ms * 1e-3) / 1e9 / (SIMDS * clock / 2.0), 4),
-                         "valu_instr_per_frame": n_valu, "valu_source": prof.get("source"),
-                         "same_numerator_other_denominators": {
-                             "frac_at_2.2_cycles_per_instruction_measured_on_this_chip": round(ach / (SIMDS * clock / 2.2), 4),
-                             "frac_at_nominal_2.4_GHz_and_2_cycles": round(ach / (SIMDS * CLOCK_GHZ / 2.0), 4),
-                             "frac_at_nominal_2.4_GHz_and_2.2_cycles": round(ach / (SIMDS * CLOCK_GHZ / 2.2), 4)}})
-            if mk.get("SQ_ACTIVE_INST_VALU") and mk.get("SQ_WAVE_CYCLES"):
-                roof["main_kernel_counters"] = {
-                    "lane_utilisation": round(mk["SQ_THREAD_CYCLES_VALU"] / (64.0 * mk["SQ_ACTIVE_INST_VALU"]), 4),
-                    "lane_utilisation_is": "SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU)",
-                    "wait_any_of_wave_cycles": round(mk["SQ_WAIT_ANY"] / mk["SQ_WAVE_CYCLES"], 4),
-                    "wait_inst_any_of_wave_cycles": round(mk["SQ_WAIT_INST_ANY"] / mk["SQ_WAVE_CYCLES"], 4),
-                    "salu_per_valu": round(mk["SQ_INSTS_SALU"] / mk["SQ_INSTS_VALU"], 4) if mk.get("SQ_INSTS_VALU") else None,
-                    "source": prof.get("source")}
-            roof["traffic"] = prof.get("hbm_bytes_per_frame")
-            roof["traffic_source"] = prof.get("hbm_source")
-        if algo:
-            bytes_launch = algo["bytes"]
-            gbs = bytes_launch / (kern_ms * 1e-3) / 1e9
-            roof["bytes"] = {"algorithmic_bytes_per_launch": bytes_launch, "bytes_per_ray": round(bytes_launch / rays_rank, 1),
-                             "algorithmic_GBs": round(gbs, 1),
-                             "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4), "hbm_peak_GBs": HBM_PEAK_GBS,
-                             "frac_of_l2_peak": round(gbs / L2_PEAK_GBS, 4), "l2_peak_GBs": L2_PEAK_GBS,
-                             "note": "SURVEY s8d formula (52 B per node / instance record, 36 B per triangle the reference would fetch, + shading bytes); the scene is "
-                                     "cache-resident, so this figure prices bytes the L1/L2/Infinity Cache serve: it may exceed the HBM peak and is not the bound",
-                             "measured_hbm_GBs": round(roof["traffic"] / (kern_ms * 1e-3) / 1e9, 1) if roof.get("traffic") else None,
-                             "measured_hbm_frac_of_peak": round(roof["traffic"] / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if roof.get("traffic") else None}
-            roof["counts_reference_order"] = algo
-            roof["counts_timed_traversal"] = algo_timed
-        out["roofline"] = roof
-        rr = extras.get("random_rays")
-        if rr:
-            # north_star's second figure with its own roofline block: N random rays per GPU against the fixed BVH, as absolute, against
-            # the VALU issue roof (numerator: SQ_INSTS_VALU of the ray-buffer kernel's launch, a profile constant tied to this tree, this
-            # kernel source and these rays by the fetch counts the counting build reports) and, as north_star words it, the SURVEY s8d
-            # bytes against the HBM roofline
-            blk = {"bound": "valu", "kernel": "rt_persistent_kernel<JOB_TRACE> (+ its EXACT launch)", "rays_per_gpu": rr["rays_per_gpu"], "n_gpus": world,
-                   "mrays_s": rr["mrays_s"], "ms_per_launch": rr["ms_per_launch"], "achieved": None, "peak": round(world * SIMDS * clock / 2.0, 1),
-                   "unit": "G wave64 VALU instructions/s", "frac": None,
-                   "bytes": {"bytes_per_ray": rr["bytes_per_ray"], "algorithmic_GBs": rr["algorithmic_GBs"], "hbm_peak_GBs": HBM_PEAK_GBS * world,
-                             "frac_of_hbm_peak": rr["frac_of_hbm_peak"], "frac_of_l2_peak": rr["frac_of_l2_peak"]}}
-            pr = prof.get("random_rays") if prof else None
-            why_rr = why_not
-            if not why_rr and not pr:
-                why_rr = "profiles/valu_profile.json holds no counter pass of the ray-buffer kernel"
-            near = lambda a, b: bool(a and b) and abs(a - b) <= 1e-3 * max(a, b)      # (see profile_mismatch)
-            if not why_rr and (pr.get("n") != rr["rays_per_gpu"] or not near(pr.get("node_fetches"), rr["node_fetches"]) or not near(pr.get("tri_fetches"), rr["tri_fetches"])):
-                why_rr = "the profiled ray buffer differs from this run's (rays or fetch counts)"
-            if why_rr:
-                blk["frac_is_null_because"] = why_rr
+        if a.full:
+            prof = load_profile_constants()
+            # one step = the launches of vxrt_render: persistent traversal kernel (dominant, > 93 % of the step), the EXACT launches
+            # for the rays with NaN-capable slabs, and the shading pass; priced together
+            clk = [probe.ghz(0), probe.ghz(1)] if probe else [None, None]
+            clock_held = (sum(clk) / 2.0) if all(clk) else None
+            clock = clock_held or CLOCK_GHZ
+            # ONE denominator: wave64 VALU instructions per second against what 1,024 SIMDs can issue at the clock held in the timed
+            # region, at the guide's 2 cycles per wave64 VALU instruction (MI355X_MICROARCH.md: "issues each VALU instruction over 2
+            # cycles").  The same fraction at the 2.2 cycles this chip measured for dense independent streams (tools/calibrate_valu.py)
+            # and at the nominal 2.4 GHz are given next to it, labelled.
+            roof = {"bound": "valu", "achieved": None, "peak": round(SIMDS * clock / 2.0, 1), "unit": "G wave64 VALU instructions/s", "frac": None, "traffic": None,
+                    "peak_is": "1024 SIMDs x clock held in the timed region / 2 cycles per wave64 VALU instruction (guide constant)",
+                    "clock_ghz_held": round(clock_held, 4) if clock_held else None,
+                    "clock_probe_ghz_before_after": [round(c, 4) if c else None for c in clk],
+                    "clock_source": "one-wavefront s_memtime / s_memrealtime probe right before the timed region opens and right after it closes (lib/libvxrt_calib.so)" if clock_held
+                                    else "nominal %.1f GHz (probe library not available)" % CLOCK_GHZ,
+                    "kernel": "rt_persistent_kernel<JOB_RENDER%s> (+ EXACT launches + rt_shade_kernel)" % ("_SHADOW" if shadow else ""),
+                    "kernel_ms": round(kern_ms, 4), "kernel_ms_overlapped": round(ovl_ms, 4), "kernel_ms_isolated": round(iso_ms, 4),
+                    "kernel_ms_is": "GPU-clock span of the timed region (HIP events: first step's start -> an event behind every stream) / steps",
+                    "frames_per_launch": B, "launch_set_ms_overlapped": round(ovl_ms * a.steps / max(1, len(evs)), 4),
+                    "frames_in_flight": nfl,
+                    "why_valu": "the scene is cache-resident (measured HBM traffic = a few % of the HBM peak) and relieving the memory path measured neutral (LDS-staged "
+                                "top of the tree: 39 % of node steps from LDS, -17 % vector-memory instructions, +0 %: profiles/r02_b_lds_top_counters.txt); what moves the time "
+                                "is the number of VALU instructions"}
+            # what the per-frame profile constants must have been taken on to be usable here (and what a new profile pass records)
+            ident = {"width": W, "height": H, "shadow": int(shadow), "bvh_nodes": scene.n_bvh_nodes, "tree_sha16": tree_id(scene),
+                     "kernel_source_sha16": kernel_source_id(),
+                     "node_fetches_timed": algo_timed["node_fetches"] if algo_timed else None,
+                     "tri_fetches_timed": algo_timed["tri_fetches"] if algo_timed else None,
+                     "rays": algo_timed["rays"] if algo_timed else None}
+            roof["identity"] = ident
+            why_not = None
+            if not prof:
+                why_not = "profiles/valu_profile.json not found"
             else:
-                ach = pr["valu_instr_per_launch"] * world / (rr["ms_per_launch"] * 1e-3) / 1e9
-                blk.update({"achieved": round(ach, 1), "frac": round(ach / (world * SIMDS * clock / 2.0), 4), "valu_instr_per_launch": pr["valu_instr_per_launch"],
-                            "lane_utilisation": pr.get("lane_utilisation"), "wait_any_of_wave_cycles": pr.get("wait_any_of_wave_cycles"),
-                            "valu_source": pr.get("source")})
-            out["roofline_random_rays"] = blk
-        if world == 1 and not a.no_cpu_baseline:
+                why_not = profile_mismatch(prof, ident)
+            if why_not:
+                roof["frac_is_null_because"] = why_not
+            if prof and world > 1 and not why_not and not rehearse:
+                # N ranks: the frame's instructions are a property of the frame, whoever traces which band: the whole job's rate against
+                # N x the per-GPU roof (clock: rank 0's probe)
+                n_valu = prof["valu_instr_per_frame"]
+                ach = n_valu / (elapsed / a.steps) / 1e9
+                roof.update({"achieved": round(ach, 1), "peak": round(world * SIMDS * clock / 2.0, 1), "frac": round(ach / (world * SIMDS * clock / 2.0), 4),
+                             "peak_is": "%d GPUs x 1024 SIMDs x clock held on rank 0 / 2 cycles per wave64 VALU instruction" % world,
+                             "achieved_is": "wave64 VALU instructions of one whole frame (profile constant) x steps / max-over-ranks wall time of the timed region",
+                             "valu_instr_per_frame": n_valu, "valu_source": prof.get("source")})
+            if prof and world == 1 and not why_not:
+                # profile constants of THIS workload (instruction counts per frame are a property of the frame and the code), source named in the file
+                n_valu = prof["valu_instr_per_frame"]
+                ach = n_valu / (kern_ms * 1e-3) / 1e9
+                mk = prof.get("main_kernel", {})
+                roof.update({"achieved": round(ach, 1), "frac": round(ach / (SIMDS * clock / 2.0), 4),
+                             "frac_isolated": round(n_valu / (iso_ms * 1e-3) / 1e9 / (SIMDS * clock / 2.0), 4),
+                             "valu_instr_per_frame": n_valu, "valu_source": prof.get("source"),
+                             "same_numerator_other_denominators": {
+                                 "frac_at_2.2_cycles_per_instruction_measured_on_this_chip": round(ach / (SIMDS * clock / 2.2), 4),
+                                 "frac_at_nominal_2.4_GHz_and_2_cycles": round(ach / (SIMDS * CLOCK_GHZ / 2.0), 4),
+                                 "frac_at_nominal_2.4_GHz_and_2.2_cycles": round(ach / (SIMDS * CLOCK_GHZ / 2.2), 4)}})
+                if mk.get("SQ_ACTIVE_INST_VALU") and mk.get("SQ_WAVE_CYCLES"):
+                    roof["main_kernel_counters"] = {
+                        "lane_utilisation": round(mk["SQ_THREAD_CYCLES_VALU"] / (64.0 * mk["SQ_ACTIVE_INST_VALU"]), 4),
+                        "lane_utilisation_is": "SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU)",
+                        "wait_any_of_wave_cycles": round(mk["SQ_WAIT_ANY"] / mk["SQ_WAVE_CYCLES"], 4),
+                        "wait_inst_any_of_wave_cycles": round(mk["SQ_WAIT_INST_ANY"] / mk["SQ_WAVE_CYCLES"], 4),
+                        "salu_per_valu": round(mk["SQ_INSTS_SALU"] / mk["SQ_INSTS_VALU"], 4) if mk.get("SQ_INSTS_VALU") else None,
+                        "source": prof.get("source")}
+                roof["traffic"] = prof.get("hbm_bytes_per_frame")
+                roof["traffic_source"] = prof.get("hbm_source")
+            if algo:
+                bytes_launch = algo["bytes"]
+                gbs = bytes_launch / (kern_ms * 1e-3) / 1e9
+                roof["bytes"] = {"algorithmic_bytes_per_launch": bytes_launch, "bytes_per_ray": round(bytes_launch / rays_rank, 1),
+                                 "algorithmic_GBs": round(gbs, 1),
+                                 "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4), "hbm_peak_GBs": HBM_PEAK_GBS,
+                                 "frac_of_l2_peak": round(gbs / L2_PEAK_GBS, 4), "l2_peak_GBs": L2_PEAK_GBS,
+                                 "note": "SURVEY s8d formula (52 B per node / instance record, 36 B per triangle the reference would fetch, + shading bytes); the scene is "
+                                         "cache-resident, so this figure prices bytes the L1/L2/Infinity Cache serve: it may exceed the HBM peak and is not the bound",
+                                 "measured_hbm_GBs": round(roof["traffic"] / (kern_ms * 1e-3) / 1e9, 1) if roof.get("traffic") else None,
+                                 "measured_hbm_frac_of_peak": round(roof["traffic"] / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if roof.get("traffic") else None}
+                roof["counts_reference_order"] = algo
+                roof["counts_timed_traversal"] = algo_timed
+            out["roofline"] = roof
+            rr = extras.get("random_rays")
+            if rr:
+                # north_star's second figure with its own roofline block: N random rays per GPU against the fixed BVH, as absolute, against
+                # the VALU issue roof (numerator: SQ_INSTS_VALU of the ray-buffer kernel's launch, a profile constant tied to this tree, this
+                # kernel source and these rays by the fetch counts the counting build reports) and, as north_star words it, the SURVEY s8d
+                # bytes against the HBM roofline
+                blk = {"bound": "valu", "kernel": "rt_persistent_kernel<JOB_TRACE> (+ its EXACT launch)", "rays_per_gpu": rr["rays_per_gpu"], "n_gpus": world,
+                       "mrays_s": rr["mrays_s"], "ms_per_launch": rr["ms_per_launch"], "achieved": None, "peak": round(world * SIMDS * clock / 2.0, 1),
+                       "unit": "G wave64 VALU instructions/s", "frac": None,
+                       "bytes": {"bytes_per_ray": rr["bytes_per_ray"], "algorithmic_GBs": rr["algorithmic_GBs"], "hbm_peak_GBs": HBM_PEAK_GBS * world,
+                                 "frac_of_hbm_peak": rr["frac_of_hbm_peak"], "frac_of_l2_peak": rr["frac_of_l2_peak"]}}
+                pr = prof.get("random_rays") if prof else None
+                why_rr = why_not
+                if not why_rr and not pr:
+                    why_rr = "profiles/valu_profile.json holds no counter pass of the ray-buffer kernel"
+                near = lambda a, b: bool(a and b) and abs(a - b) <= 1e-3 * max(a, b)      # (see profile_mismatch)
+                if not why_rr and (pr.get("n") != rr["rays_per_gpu"] or not near(pr.get("node_fetches"), rr["node_fetches"]) or not near(pr.get("tri_fetches"), rr["tri_fetches"])):
+                    why_rr = "the profiled ray buffer differs from this run's (rays or fetch counts)"
+                if why_rr:
+                    blk["frac_is_null_because"] = why_rr
+                else:
+                    ach = pr["valu_instr_per_launch"] * world / (rr["ms_per_launch"] * 1e-3) / 1e9
+                    blk.update({"achieved": round(ach, 1), "frac": round(ach / (world * SIMDS * clock / 2.0), 4), "valu_instr_per_launch": pr["valu_instr_per_launch"],
+                                "lane_utilisation": pr.get("lane_utilisation"), "wait_any_of_wave_cycles": pr.get("wait_any_of_wave_cycles"),
+                                "valu_source": pr.get("source")})
+                out["roofline_random_rays"] = blk
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, vrt, W, H, LIGHT, a.cpu_seconds, random_sample)
         if extras:
             out["extras"] = extras

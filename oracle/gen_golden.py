@@ -212,9 +212,31 @@ def gen_raycast():
         sc.close()
 
 
+# (vfov, zoom, max_depth, spp) of tests/test_rc_twin.py::test_restatement_equals_reference_object_code_live
+RC_CAMERAS = [(45.0, 1.0, 1, 1), (46.0, 1.0, 4, 2)]
+
+
+def gen_raycast_cameras():
+    """tests/golden/rc_sphere_cone.npz: a textured scene of two different models (bricks.png / green.png, one reflective) built by
+    the reference's raycast code, and per entry of RC_CAMERAS the camera its Tracer::setup computed and the pixels its own CPU
+    path rendered through it (cam14_<i>, pixels_<i>)."""
+    sc = po.RefRcScene([RC_ASSETS + "sphere.obj", RC_ASSETS + "cone.obj"], [RC_ASSETS + "bricks.png", RC_ASSETS + "green.png"], [0.35, 0.0])
+    w, h = 72, 52
+    out = dict(sc.buffers)
+    out.update(tlas_root=np.uint32(sc.tlas_root), width=np.uint32(w), height=np.uint32(h))
+    for i, (vfov, zoom, depth, spp) in enumerate(RC_CAMERAS):
+        cam = sc.camera(vfov, zoom, w, h)
+        out["cam14_%d" % i] = cam
+        out["pixels_%d" % i] = sc.render(w, h, spp, depth, cam, po.RC_DEFAULT_LIGHT)
+    sc.close()
+    np.savez_compressed(os.path.join(OUT, "rc_sphere_cone.npz"), **out)
+
+
 if __name__ == "__main__":
     if "--raycast" in sys.argv:      # python -m oracle.gen_golden --raycast : only the software-twin fixtures
         gen_raycast()
+        gen_raycast_cameras()
     else:
         main()
         gen_raycast()
+        gen_raycast_cameras()

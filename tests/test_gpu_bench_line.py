@@ -1,5 +1,5 @@
-"""GPU: the driver's contract on bench.py -- one JSON line with BASELINE.json's metric, the roofline object (a fraction of a roof,
-not above 1) and the cpu_baseline object, for the command the driver runs."""
+"""GPU: the driver's contract on bench.py -- one JSON line with BASELINE.json's metric; with --full also the roofline object (a
+fraction of a roof, not above 1) and the cpu_baseline object; --dump-outputs writes the frame the last timed step produced."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_driver_command_prints_one_well_formed_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--random-rays", "1048576"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "2", "--random-rays", "1048576"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -56,6 +56,41 @@ def test_driver_command_prints_one_well_formed_line():
     assert d["extras"]["random_rays_mrays_s"] > 500
 
 
+def test_plain_command_prints_the_headline_only_and_dumps_the_last_frame(tmp_path):
+    """Without --full the line carries the headline and the run's configuration and nothing that takes runs of its own; the frame
+    --dump-outputs writes is the last of the 7 timed steps (sets of 4 + 3 frames on 2 streams) and equals the frame vxrt_render
+    gives for the same scene and light."""
+    import numpy as np
+    import torch
+    r = _bench(["--gpus", "1", "--steps", "7", "--warmup", "2", "--settle-frames", "4", "--level", "5", "--width", "320", "--height", "200",
+                "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - d["config"]["rays_per_step"] / d["ms_per_step"] / 1e3) / d["value"] < 1e-3 and "320x200" in d["metric"]
+    assert d["config"]["frames_per_launch_group"] == 4 and d["config"]["frames_rendered_before_the_timed_region"] == 1 + 4 + 2
+    assert not {"roofline", "roofline_random_rays", "cpu_baseline", "extras"} & set(d)
+    got = np.load(tmp_path / "pixels_rgb.npy")
+    assert got.dtype == np.float32 and got.shape == (200, 320, 3) and sorted(os.listdir(tmp_path)) == ["pixels_rgb.npy"]
+    sys.path.insert(0, ROOT)
+    import importlib
+    vrt = importlib.import_module("vortex-raytracing_amd")
+    ds = vrt.tracer.DeviceScene(vrt.scene.procedural("atrium", 5, 0, 3), "cuda:0")
+    params = vrt.rtapi.default_shade_params()
+    params.light_pos[:] = (300.0, 480.0, 60.0)
+    px = torch.zeros((200, 320), dtype=torch.int32, device="cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    vrt.rtapi.render(ds.accel, 320, 200, 0, 200, params, px.data_ptr(), 1, None, None, None, s)
+    assert vrt.rtapi.status(s) == 0
+    p = px.cpu().numpy().view(np.uint32)
+    want = np.stack([(p >> 16) & 0xFF, (p >> 8) & 0xFF, p & 0xFF], axis=-1).astype(np.float32)
+    np.testing.assert_array_equal(got, want)
+    assert len(np.unique(p)) > 10
+    ds.close()
+
+
 def _bench(args, timeout=900, env=None):
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
 
@@ -65,13 +100,14 @@ def test_plain_command_with_two_gpus_starts_two_ranks_by_itself():
     its ranks as child processes before touching HIP.  Here the two ranks share the box's one GPU and gather over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = _bench(["--gpus", "2", "--dist-backend", "gloo", "--steps", "6", "--warmup", "2", "--settle-frames", "4", "--level", "4",
-                "--no-cpu-baseline", "--random-rays", "65536"], timeout=600, env=env)
+                "--full", "--no-cpu-baseline", "--random-rays", "65536"], timeout=600, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-1500:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["world_size"] == 2 and len(d["config"]["rank_devices"]) == 2 and d["config"]["dist_backend"] == "gloo"
     assert d["steps"] == 6 and d["value"] > 0 and d["config"]["rays_per_step"] > d["config"]["rays_per_step_rank0"] > 0
+    assert d["extras"]["random_rays_n"] == 65536 * 2 and d["roofline"]["identity"]["rays"] == d["config"]["rays_per_step"]
 
 
 def test_more_gpus_than_the_box_has_is_an_error_not_a_one_gpu_line():
@@ -131,10 +167,11 @@ def test_the_multi_rank_code_path_of_bench_runs_over_rccl_with_a_one_rank_group(
     all_reduce of the timing -- with a group of one rank on the box's GPU (--one-rank-group)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = _bench(["--gpus", "1", "--one-rank-group", "--steps", "20", "--warmup", "5", "--settle-frames", "10", "--level", "5",
-                "--no-cpu-baseline", "--random-rays", "65536"], timeout=600, env=env)
+                "--full", "--no-cpu-baseline", "--random-rays", "65536"], timeout=600, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-1500:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["config"]["dist_backend"] == "nccl" and d["config"]["world_size"] == 1
     assert d["config"]["frames_per_launch_group"] == 10 and "interleaved" in d["config"]["parallelism"] and d["value"] > 0
+    assert d["extras"]["random_rays_n"] == 65536 and d["roofline"]["identity"]["rays"] == d["config"]["rays_per_step"]

@@ -25,24 +25,26 @@ def test_restatement_matches_reference_cpu_path(po, golden, name):
     np.testing.assert_array_equal(po.rc_camera_rays(a)[::5], g["rays"])
 
 
-@pytest.mark.ref
-@pytest.mark.parametrize("vfov,zoom,depth,spp", [(45.0, 1.0, 1, 1), (46.0, 1.0, 4, 2)])
+RC_CAMERAS = [(45.0, 1.0, 1, 1), (46.0, 1.0, 4, 2)]      # (oracle/gen_golden.py RC_CAMERAS: entry i -> cam14_<i>, pixels_<i>)
+
+
+@pytest.mark.parametrize("vfov,zoom,depth,spp", RC_CAMERAS)
 def test_restatement_equals_reference_object_code_live(po, golden, vfov, zoom, depth, spp):
-    """Fresh cameras on reference-built scenes, through oracle/_ref/libvxref_rc.so (skipped where it was not built)."""
-    import os
-    A = "/root/reference/tests/regression/raycast/assets/"
-    if not po.have_ref_rc() or not os.path.isdir(A):
-        pytest.skip("oracle/_ref/libvxref_rc.so or the reference assets are not here")
-    sc = po.RefRcScene([A + "sphere.obj", A + "cone.obj"], [A + "bricks.png", A + "green.png"], [0.35, 0.0])
-    w, h = 72, 52
-    cam = sc.camera(vfov, zoom, w, h)
-    ref = sc.render(w, h, spp, depth, cam, po.RC_DEFAULT_LIGHT)
-    b = dict(sc.buffers)
-    b["tlas_root"] = sc.tlas_root
+    """Fresh cameras on a reference-built textured scene of two different models (tests/golden/rc_sphere_cone.npz: the buffers, the
+    reference's cameras and what its own CPU path rendered through them); where oracle/_ref/libvxref_rc.so is built, the reference's
+    render loop also runs live on the same buffers."""
+    g = golden("rc_sphere_cone")
+    i = RC_CAMERAS.index((vfov, zoom, depth, spp))
+    b = {k: g[k] for k in po.RC_BUFFERS}
+    b["tlas_root"] = int(g["tlas_root"])
+    w, h = int(g["width"]), int(g["height"])
+    cam, ref = g["cam14_%d" % i], g["pixels_%d" % i]
     px, _ = po.rc_render(po.rc_args(b, w, h, cam, po.RC_DEFAULT_LIGHT, spp, depth))
-    sc.close()
     np.testing.assert_array_equal(px, ref)
     assert (ref != ref[0, 0]).mean() > 0.01
+    if po.have_ref_rc():
+        live, _ = po.ref_rc_render_buffers(b, w, h, 0, h, cam, po.RC_DEFAULT_LIGHT, spp=spp, max_depth=depth)
+        np.testing.assert_array_equal(live, ref)
 
 
 def test_png_decoder_equals_stb_on_a_reference_asset(vrt, golden, tmp_path):

@@ -332,9 +332,12 @@ def test_two_rank_frame_assembly_on_the_hip_path(mode, po):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shard", ["bands", "tilerows"])
-def test_bench_two_ranks_end_to_end(shard):
+def test_bench_two_ranks_end_to_end(shard, tmp_path):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one process per rank), here with two ranks sharing the
-    box's GPU and gloo for the collectives: the band plan / the sets of frames, the assembly and the one JSON line of rank 0."""
+    box's GPU and gloo for the collectives: the band plan / the sets of frames, the assembly and the one JSON line of rank 0, with
+    --full's legs (rank 0's counting build, the random rays of every rank); the frame rank 0 assembled in the last timed step
+    (--dump-outputs) equals the whole frame rendered by one rank."""
+    import importlib
     import json
     import subprocess
     s = socket.socket()
@@ -343,7 +346,7 @@ def test_bench_two_ranks_end_to_end(shard):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--settle-frames", "4", "--level", "4",
-           "--dist-backend", "gloo", "--no-cpu-baseline", "--random-rays", "65536", "--shard", shard]
+           "--dist-backend", "gloo", "--full", "--no-cpu-baseline", "--random-rays", "65536", "--shard", shard, "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -359,6 +362,22 @@ def test_bench_two_ranks_end_to_end(shard):
         # 6 steps on 2 ranks: a last set of 2 frames (one frame's bytes per link), the 4 steps before it as one set; 3 bytes per pixel on the wire
         assert d["config"]["sets_of_the_timed_steps"] == [4, 2] and d["config"]["frames_per_launch_group"] == 4 and "interleaved" in d["config"]["parallelism"]
         assert d["config"]["wire_format"] == "rgb24" and d["config"]["wire_bytes_per_rank_last_set"] == 2 * 544 * 1920 * 3
+    assert d["extras"]["random_rays_n"] == 65536 * 2 and d["roofline"]["identity"]["rays"] == d["config"]["rays_per_step"]
+    got = np.load(tmp_path / "pixels_rgb.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 3)
+    sys.path.insert(0, ROOT)
+    vrt = importlib.import_module("vortex-raytracing_amd")
+    ds = vrt.tracer.DeviceScene(vrt.scene.procedural("atrium", 4, 0, 3), "cuda:0")
+    params = vrt.rtapi.default_shade_params()
+    params.light_pos[:] = (300.0, 480.0, 60.0)
+    px = torch.zeros((1080, 1920), dtype=torch.int32, device="cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    vrt.rtapi.render(ds.accel, 1920, 1080, 0, 1080, params, px.data_ptr(), 1, None, None, None, st)
+    assert vrt.rtapi.status(st) == 0
+    p = px.cpu().numpy().view(np.uint32)
+    np.testing.assert_array_equal(got, np.stack([(p >> 16) & 0xFF, (p >> 8) & 0xFF, p & 0xFF], axis=-1).astype(np.float32))
+    assert len(np.unique(p)) > 10
+    ds.close()
 
 
 @pytest.mark.gpu

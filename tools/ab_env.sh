@@ -7,7 +7,7 @@ OUT=$1; REPS=$2; shift 2
 mkdir -p "$(dirname "$OUT")"
 for rep in $(seq $REPS); do
   for kv in "$@"; do
-    env $kv python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$kv  driver cmd (20 steps):', d['value'], d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])"
-    env $kv python bench.py --steps 200 --warmup 10 --no-cpu-baseline --random-rays 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$kv  200 steps:', d['value'], d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])"
+    env $kv python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$kv  driver cmd (20 steps):', d['value'], d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])"
+    env $kv python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --random-rays 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$kv  200 steps:', d['value'], d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])"
   done
 done | tee "$OUT"

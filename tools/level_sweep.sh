@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 for lv in ${@:-3 4 5 6 7 8}; do
   for fif in 1 2; do
-    python bench.py --level $lv --steps 100 --warmup 10 --no-cpu-baseline --random-rays 0 --frames-in-flight $fif 2>/dev/null | python -c "
+    python bench.py --full --level $lv --steps 100 --warmup 10 --no-cpu-baseline --random-rays 0 --frames-in-flight $fif 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']; c = r.get('counts_timed_traversal') or r.get('counts_reference_order')
 steps = c['node_fetches']; rays = c['rays']

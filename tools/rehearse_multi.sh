@@ -11,6 +11,6 @@ for n in 2 4 8; do
   done
 done
 echo "rehearse-world 8, 3840x2160 leg (extras.leg_3840x2160):"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 --other-configs none --rehearse-world 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('   ', d['extras']['leg_3840x2160'])"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 --other-configs none --rehearse-world 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('   ', d['extras']['leg_3840x2160'])"
 echo "one-rank nccl group, full size, 20 steps (the collectives with one rank):"
 run python bench.py --gpus 1 --one-rank-group --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 --other-configs none

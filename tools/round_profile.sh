@@ -17,17 +17,17 @@ cp "$OUT/pmc/summary.txt" "$OUT/pmc_summary.txt"; cp "$OUT/pmc/summary_rr.txt" "
 # (the 4th argument: a bench line of the counter passes' own session -- its roofline.identity block ties the constants to the tree and the kernel source)
 python tools/roofline_from_pmc.py "$OUT/pmc_summary.txt" "$ROOT/profiles/valu_profile.json" "profiles/${TAG}_pmc.txt" "$OUT/pmc/pass1.log" "$OUT/pmc/pass_rr.log" "$OUT/pmc/summary_rr.txt" > "$OUT/valu_profile.log" 2>&1
 cp "$ROOT/profiles/valu_profile.json" "$OUT/valu_profile.json"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 cut -c1-600 "$OUT/bench.json"
-python bench.py --frames-in-flight 1 --no-cpu-baseline > "$OUT/bench_serial.json" 2>> "$OUT/bench.err" || exit 1
+python bench.py --full --frames-in-flight 1 --no-cpu-baseline > "$OUT/bench_serial.json" 2>> "$OUT/bench.err" || exit 1
 cut -c1-300 "$OUT/bench_serial.json"
-for i in 1 2 3 4 5; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('driver command (--gpus 1 --steps 20 --warmup 5):', d['value'], d['ms_per_step'], 'frac', d['roofline']['frac'], 'clock', d['roofline']['clock_ghz_held'])"; done > "$OUT/driver_cmd.txt" 2>&1
+for i in 1 2 3 4 5; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --random-rays 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('driver command (--gpus 1 --steps 20 --warmup 5):', d['value'], d['ms_per_step'], 'frac', d['roofline']['frac'], 'clock', d['roofline']['clock_ghz_held'])"; done > "$OUT/driver_cmd.txt" 2>&1
 cat "$OUT/driver_cmd.txt"
 tools/rehearse_multi.sh > "$OUT/multi_gpu_rehearsal.txt" 2>&1; tail -4 "$OUT/multi_gpu_rehearsal.txt"
 python tools/config_bench.py 2 3 4 5 6 7 8 2>/dev/null | grep "^{" > "$OUT/configs.jsonl"; cut -c1-260 "$OUT/configs.jsonl"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_pipelined" -- python "$ROOT/bench.py" --no-cpu-baseline --other-configs none > "$OUT/stats_pipelined.log" 2>&1 || { echo "rocprof pipelined failed"; exit 1; }
-timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_serial" -- python "$ROOT/bench.py" --no-cpu-baseline --frames-in-flight 1 --other-configs none > "$OUT/stats_serial.log" 2>&1 || { echo "rocprof serial failed"; exit 1; }
+timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_pipelined" -- python "$ROOT/bench.py" --full --no-cpu-baseline --other-configs none > "$OUT/stats_pipelined.log" 2>&1 || { echo "rocprof pipelined failed"; exit 1; }
+timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_serial" -- python "$ROOT/bench.py" --full --no-cpu-baseline --frames-in-flight 1 --other-configs none > "$OUT/stats_serial.log" 2>&1 || { echo "rocprof serial failed"; exit 1; }
 for m in pipelined serial; do
   f=$(find "$OUT/stats_$m" -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cut -c1-400 "$f" | head -12 > "$OUT/kernel_stats_$m.csv" && head -6 "$OUT/kernel_stats_$m.csv" | cut -c1-200

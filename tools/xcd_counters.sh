@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 for b in $BASES; do
   pmc=""; for k in 0 1 2 3 4 5 6 7; do pmc="$pmc ${b}_XCC$k"; done
   RAW=$(mktemp -d /tmp/xcdc_XXXXXX)
-  timeout -k 5 200 rocprofv3 -E "$ROOT/tools/xcd_counters.yaml" --pmc $pmc --output-format csv -d "$RAW" -- python "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --frames-in-flight 1 --random-rays 0 --other-configs none --settle-frames 20 > "$OUT/$b.log" 2>&1 || { echo "pass $b failed"; tail -3 "$OUT/$b.log"; continue; }
+  timeout -k 5 200 rocprofv3 -E "$ROOT/tools/xcd_counters.yaml" --pmc $pmc --output-format csv -d "$RAW" -- python "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --frames-in-flight 1 --random-rays 0 --other-configs none --settle-frames 20 > "$OUT/$b.log" 2>&1 || { echo "pass $b failed"; tail -3 "$OUT/$b.log"; continue; }
   f=$(find "$RAW" -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python "$ROOT/tools/xcd_counters_summary.py" "$f" "$b" | tee -a "$OUT/summary.txt"
 done
