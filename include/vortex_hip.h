@@ -194,7 +194,8 @@ typedef struct {
  * texels inside [tex, tex + tex_bytes) with non-zero dimensions).  With RT_TOP_NODES > 0 (build flag) the first internal
  * nodes in breadth-first order are also laid out as an image each workgroup stages in LDS.
  * The vxrt_scene_t buffers must stay alive and unchanged while the accel
- * is in use (shading reads blas/triEx/mat/tex from them).  Synchronous with respect to `stream`. */
+ * is in use (shading reads blas/triEx/mat/tex from them); moved instances or vertices go through vxrt_accel_set_transforms /
+ * vxrt_accel_refit below, never through the buffers alone.  Synchronous with respect to `stream`. */
 typedef struct vxrt_accel vxrt_accel_t;
 int vxrt_accel_build(const vxrt_scene_t* scene, void* stream, vxrt_accel_t** out);
 int vxrt_accel_destroy(vxrt_accel_t* accel);
@@ -204,6 +205,33 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* accel);
  * reference's 32 levels, 96 entries + the LDS part); 2 -> 1 if the TLAS root is a single identity instance; 3 -> 1 if the scene
  * takes the ldexp decode / generic slab form. */
 int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
+
+/* Refit: new boxes for a scene whose instances or vertices moved, in place, without a rebuild (extension; the reference has no refit,
+ * its pieces are blas_node_t::applyTransform + mat4_t::inverted(), common.h:95-98 / geometry.h:1149-1192, the TLAS leaf box of
+ * bvh.cpp:290-304 and the quantiser of bvh.cpp:215-264).
+ *   VXRT_REFIT_INSTANCES  instance transforms changed: instance boxes + TLAS
+ *   VXRT_REFIT_GEOMETRY   triangle vertices changed (same count, same order): edge-form triangles, every BLAS, then instance boxes + TLAS
+ * Topology is kept: leftFirst, leafData, imask, node counts and the triangle order are never touched, only boxes move -- every node's
+ * origin and exponents and its children's quantised bytes (the builder's quantiser, csrc/bvh_quant.h), in scene.tlas and, for
+ * GEOMETRY, scene.bvh, rewritten in place: the caller's buffers stay a valid reference-format scene.  The accel then behaves exactly
+ * like vxrt_accel_build on the updated buffers (compact nodes, edge-form triangles, the LDS top-of-tree image, info 2 and 3);
+ * info 0 and 1 cannot change.  An instance's object box is the refit's own box of its BLAS root after a GEOMETRY pass, else the
+ * union of the root's decoded child boxes (the triangle box for a leaf root); its 8 corners go through `transform` in fp32 without
+ * contraction.  The first refit of an accel builds a plan of the trees' levels (one synchronisation, a host copy of the nodes).
+ * Ordered after every call already issued on this accel, on any stream; synchronous with respect to `stream` (one host
+ * synchronisation at the end), so every later call is ordered after it.
+ * Returns -1 for a null accel, unknown bits in `what`, a non-finite vertex or transformed box, or a box that cannot be quantised.
+ * A refit that fails after it has started writing marks the accel STALE: every render, trace or stats call on it returns -1
+ * without launching anything until a later refit succeeds (a refit of a stale accel redoes the BLAS boxes as well). */
+#define VXRT_REFIT_INSTANCES 1u
+#define VXRT_REFIT_GEOMETRY 2u
+int vxrt_accel_refit(vxrt_accel_t* accel, uint32_t what, void* stream);
+/* transforms: DEVICE, count x 16 floats, mat4_t::cell order (row-major, translation in cells 3/7/11).  Writes transform and
+ * invTransform (= mat4_t::inverted(), MESA operation order, no contraction) into instance records first .. first+count-1 of the
+ * scene's blas buffer, then refits as vxrt_accel_refit(accel, VXRT_REFIT_INSTANCES).  Returns -1 for first + count > n_blas, a
+ * non-finite matrix or a singular one (det == 0, for which the reference would silently keep the identity); the matrices are
+ * checked before any record is written, so then every record is left as it was. */
+int vxrt_accel_set_transforms(vxrt_accel_t* accel, uint32_t first, uint32_t count, const float* transforms, void* stream);
 
 /* Number of frames (vxrt_render / vxrt_trace calls) this accel keeps in flight, 1..8, default 1.
  * Each in-flight frame has its own hit-record buffer, deferred-ray list and side stream; calls take

@@ -37,6 +37,7 @@
 #include <mutex>
 #include <vector>
 #include "rt_types.h"
+#include "bvh_quant.h"
 #include "../../include/vortex_hip.h"
 
 #ifndef BB_EXTENDED_MORTON
@@ -768,31 +769,7 @@ __global__ __launch_bounds__(1024) void bb_ri_refit_tail_kernel(RiArgs A, uint32
 }
 
 // ---- 5. collapse + quantise + emit ----
-// smallest e with extent / 255 <= 2^e (bvh.cpp:215-264 picks ceil(log2(extent / 255))), from the float's own exponent: exact
-__device__ __forceinline__ int bb_pick_exp(float extent) {
-  if (!(extent > 0.0f) || extent > 3.0e38f) return 0;
-  int k;
-  const float m = frexpf(extent / 255.0f, &k);   // extent / 255 = m * 2^k, m in [0.5, 1)
-  int e = m == 0.5f ? k - 1 : k;
-  return max(-126, min(126, e));
-}
-
-// q_lo, q_hi of one axis of one child at scale s = 2^e (inv = 2^-e, both exact: |e| <= 126); false if the child does not fit 8 bits there
-__device__ __forceinline__ bool bb_quant_axis(float origin, float s, float inv, float cmin, float cmax, uint32_t& qlo, uint32_t& qhi) {
-  float fl = floorf((cmin - origin) * inv), fh = ceilf((cmax - origin) * inv);
-  if (!(fl >= 0.0f)) fl = 0.0f;
-  if (!(fh >= fl)) fh = fl;
-  if (fh > 255.0f) return false;
-  int lo = (int)fl, hi = (int)fh;
-  if (lo > 255) return false;
-  // conservative after the decode's own rounding (origin + q * 2^e rounds once; q * 2^e itself is exact)
-  while (lo > 0 && origin + (float)lo * s > cmin) --lo;
-  while (hi < 255 && origin + (float)hi * s < cmax) ++hi;
-  if (origin + (float)hi * s < cmax) return false;
-  qlo = (uint32_t)lo; qhi = (uint32_t)hi;
-  return true;
-}
-__device__ __forceinline__ float bb_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // e in [-126, 127]
+// bb_pick_exp, bb_quant_axis, bb_pow2 and the exponent bump loop (bb_quant_children): bvh_quant.h, shared with the refit
 
 struct CollapseArgs {
   const BNode* rec;
@@ -999,21 +976,16 @@ __global__ __launch_bounds__(256) void bb_collapse_kernel(CollapseArgs A) {
     const float org[3] = {bx.lx, bx.ly, bx.lz};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      for (;;) {
-        bool ok = true;
-        const float sc = bb_pow2(e[a]), inv = bb_pow2(-e[a]);
+      float cmin[4], cmax[4];
+      uint32_t qla[4] = {0, 0, 0, 0}, qha[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if ((uint32_t)k < nc && ok) {
-            const float cmin = a == 0 ? cr[k].box.lx : (a == 1 ? cr[k].box.ly : cr[k].box.lz);
-            const float cmax = a == 0 ? cr[k].box.hx : (a == 1 ? cr[k].box.hy : cr[k].box.hz);
-            ok = bb_quant_axis(org[a], sc, inv, cmin, cmax, ql[k][a], qh[k][a]);
-          }
-        }
-        if (ok) break;
-        if (e[a] >= 126) { atomicOr(A.counters + 4, 2u); break; }
-        ++e[a];
+      for (int k = 0; k < 4; ++k) {
+        cmin[k] = a == 0 ? cr[k].box.lx : (a == 1 ? cr[k].box.ly : cr[k].box.lz);
+        cmax[k] = a == 0 ? cr[k].box.hx : (a == 1 ? cr[k].box.hy : cr[k].box.hz);
       }
+      if (!bb_quant_children(org[a], e[a], cmin, cmax, (1u << nc) - 1u, qla, qha)) atomicOr(A.counters + 4, 2u);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { ql[k][a] = qla[k]; qh[k][a] = qha[k]; }
     }
     w[4] = first;     // relative to this BLAS's first node (rt_traversal.cpp:92,119); TLAS: to its node 0
     w[5] = A.order ? 0u : 0xffffffffu;   // internal TLAS nodes carry UINT32_MAX (bvh.cpp:417)

@@ -106,6 +106,27 @@ def tlas_build(boxes_ptr, n_instances, nodes_ptr, node_capacity, stream=None):
     return info
 
 
+REFIT_INSTANCES, REFIT_GEOMETRY = 1, 2   # VXRT_REFIT_*
+
+
+def accel_refit(accel, what, stream=None):
+    """vxrt_accel_refit: new boxes for moved instances (REFIT_INSTANCES) or moved vertices (REFIT_GEOMETRY), topology kept; raises on
+    failure (the accel is then stale until a refit succeeds)."""
+    L = _lib()
+    L.vxrt_accel_refit.restype = C.c_int
+    L.vxrt_accel_refit.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    check(L.vxrt_accel_refit(accel, int(what), stream), "vxrt_accel_refit")
+
+
+def accel_set_transforms(accel, first, count, ptr, stream=None):
+    """vxrt_accel_set_transforms: `count` object-to-world matrices (device, 16 floats each, row-major) into instance records
+    first.. (transform + MESA inverse), then the instance refit; raises on failure (a refused matrix leaves every record as it was)."""
+    L = _lib()
+    L.vxrt_accel_set_transforms.restype = C.c_int
+    L.vxrt_accel_set_transforms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    check(L.vxrt_accel_set_transforms(accel, int(first), int(count), ptr, stream), "vxrt_accel_set_transforms")
+
+
 def accel_destroy(accel):
     if accel:
         check(_lib().vxrt_accel_destroy(accel), "vxrt_accel_destroy")

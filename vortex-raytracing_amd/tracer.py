@@ -187,6 +187,24 @@ class DeviceScene:
             self.accel = rtapi.accel_build(s, stream)
         return self
 
+    def set_transforms(self, transforms, first=0):
+        """Move instances first, first+1, ...: a list of 4x4 object-to-world matrices (row-major, translation in the last column).
+        Writes transform + inverse into the instance records and refits the TLAS on the GPU (vxrt_accel_set_transforms)."""
+        import torch
+        m = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in transforms]).reshape(-1), np.float32)
+        dev = self.t["blas"].device
+        with torch.cuda.device(dev):
+            t = torch.from_numpy(m).to(dev)
+            rtapi.accel_set_transforms(self.accel, first, len(transforms), t.data_ptr(), torch.cuda.current_stream().cuda_stream)
+
+    def refit(self, geometry=True):
+        """Refit after the caller has written new vertices into self.t["tri"] (geometry=True: every BLAS, then the TLAS) or new
+        transforms into self.t["blas"] (geometry=False: the TLAS only).  The topology stays; the boxes in self.t are rewritten."""
+        import torch
+        dev = self.t["blas"].device
+        with torch.cuda.device(dev):
+            rtapi.accel_refit(self.accel, rtapi.REFIT_GEOMETRY if geometry else rtapi.REFIT_INSTANCES, torch.cuda.current_stream().cuda_stream)
+
     def to_host(self):
         """The scene buffers as a scene.Scene (numpy), e.g. to hand a GPU-built tree to the oracle."""
         from .scene import Scene
