@@ -220,7 +220,10 @@ int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
  * contraction.  The first refit of an accel builds a plan of the trees' levels (one synchronisation, a host copy of the nodes).
  * Ordered after every call already issued on this accel, on any stream; synchronous with respect to `stream` (one host
  * synchronisation at the end), so every later call is ordered after it.
+ * what == 0 moves nothing and writes nothing: it returns 0, or -1 for a stale accel (or a tree the plan refuses).
  * Returns -1 for a null accel, unknown bits in `what`, a non-finite vertex or transformed box, or a box that cannot be quantised.
+ * A tree with an internal node that has no present child is refused (-1) when the plan is built, before anything is written; the
+ * accel is then not stale.
  * A refit that fails after it has started writing marks the accel STALE: every render, trace or stats call on it returns -1
  * without launching anything until a later refit succeeds (a refit of a stale accel redoes the BLAS boxes as well). */
 #define VXRT_REFIT_INSTANCES 1u

@@ -16,12 +16,14 @@ class RefitError(ValueError):
 
 
 def pick_exp(extent):
-    """bb_pick_exp: smallest e with extent / 255 <= 2^e, clamped to [-126, 126]; 0 for an extent that is not > 0 or above 3e38."""
+    """bb_pick_exp: smallest e with extent / 255 <= 2^e, clamped to [-126, 126] (-126 where the fp32 quotient underflows to 0); 0 for
+    an extent that is not > 0 or above 3e38."""
     ext = np.asarray(extent, F)
-    with np.errstate(invalid="ignore", over="ignore"):
-        m, k = np.frexp(ext / F(255.0))
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        q = ext / F(255.0)
+        m, k = np.frexp(q)
         e = np.where(m == F(0.5), k - 1, k)
-        e = np.clip(e, -126, 126)
+        e = np.where(q == 0, -126, np.clip(e, -126, 126))
         bad = ~(ext > 0) | (ext > F(3.0e38))
     return np.where(bad, 0, e).astype(np.int32)
 
@@ -153,7 +155,8 @@ def decode_children(n):
 
 
 def _walk(nodes, roots, bases, tlas):
-    """Breadth-first from every root: leaves [k] and internal levels [(node, child 0)] from the roots down."""
+    """Breadth-first from every root: leaves [k] and internal levels [(node, child 0)] from the roots down.  Raises RefitError on an
+    internal node without a present child (the plan refuses such a tree before anything is written)."""
     idx = np.asarray(roots, np.int64)
     base = np.asarray(bases, np.int64)
     leaves, levels = [], []
@@ -165,6 +168,8 @@ def _walk(nodes, roots, bases, tlas):
         c0 = bb + nn["lf"].astype(np.int64)
         levels.append((ii, c0))
         present = nn["ch"][:, :, 0] != 0
+        if not present.any(1).all():
+            raise RefitError("an internal node without a child")
         kids = c0[:, None] + np.arange(4)[None, :]
         idx = kids[present]
         base = np.repeat(bb, present.sum(1))
@@ -227,9 +232,10 @@ def refit(bufs, geometry=True):
     rec = np.asarray(bufs["blas"], np.uint8).view(F).reshape(-1, BLAS_WORDS)
     offs = rec[:, 0].view(np.uint32).astype(np.int64)
     fb_bvh = np.zeros((len(bvh), 6), F)
+    bases = np.unique(offs)
+    leaves, levels = _walk(bvh, bases, bases, tlas=False)    # (the plan walks every tree, whatever the refit moves)
+    tleaves, tlevels = _walk(tlas, [0], [0], tlas=True)
     if geometry:
-        bases = np.unique(offs)
-        leaves, levels = _walk(bvh, bases, bases, tlas=False)
         if len(leaves):
             lo, hi, ok = _tri_boxes(tri, bvh["lf"][leaves], bvh["ld"][leaves])
             if not ok:
@@ -237,7 +243,6 @@ def refit(bufs, geometry=True):
             _set_origin(bvh, leaves, lo, hi)
             fb_bvh[leaves, :3], fb_bvh[leaves, 3:] = lo, hi
         _refit_levels(bvh, levels, fb_bvh)
-    tleaves, tlevels = _walk(tlas, [0], [0], tlas=True)
     inst = tlas["ld"][tleaves].astype(np.int64)
     root = offs[inst]
     if geometry:

@@ -11,8 +11,10 @@
 // smallest e with extent / 255 <= 2^e (bvh.cpp:215-264 picks ceil(log2(extent / 255))), from the float's own exponent: exact
 __device__ __forceinline__ int bb_pick_exp(float extent) {
   if (!(extent > 0.0f) || extent > 3.0e38f) return 0;
+  const float q = extent / 255.0f;
+  if (q == 0.0f) return -126;   // a subnormal extent whose quotient underflows: the clamp (the CPU builder's log2(0) = -inf)
   int k;
-  const float m = frexpf(extent / 255.0f, &k);   // extent / 255 = m * 2^k, m in [0.5, 1)
+  const float m = frexpf(q, &k);   // extent / 255 = m * 2^k, m in [0.5, 1)
   int e = m == 0.5f ? k - 1 : k;
   return max(-126, min(126, e));
 }

@@ -3420,11 +3420,14 @@ static RefitPlan* refit_plan_build(vxrt_accel* a, hipStream_t st) {
       const uint64_t c0 = (uint64_t)base + n[4];
       items.push_back({L, make_uint2(i, (uint32_t)c0)});
       const uint8_t* b = (const uint8_t*)n;
+      bool any = false;
       for (uint32_t k = 0; k < 4; ++k) {
         if (b[24 + 7 * k] == 0) continue;
         if (c0 + k >= end || c0 + k <= i) return false;
         q.push_back({(uint32_t)(c0 + k), L + 1u});
+        any = true;
       }
+      if (!any) return false;   // an internal node without a child has no box to refit from: refused before anything is written
     }
     return true;
   };
