@@ -107,6 +107,12 @@ int vx_dev_init(callbacks_t* callbacks);
  * rt_traversal.cpp:91-92 reads here what it reads there.  Slow (one thread per ray, the address space copied when an allocation
  * changed); closest-hit frames only (no shadow-ray extension, no row stride). */
 #define VX_DCR_HIP_REFERENCE_QUIRKS 0x7F4
+/* Backend extension: 1 = render the RTU test's frames from the pinhole camera of kernel_arg_t camera_pos .. viewplane (the fields
+ * tracer.cpp:171-202 fills; see vxrt_camera_t) through vxrt_render_camera instead of the fixed GenerateRay of kernel.cpp:28-39.
+ * Default 0 = the fixed camera, unchanged.  ROW_BEGIN / ROW_END and samples_per_pixel work as without it; vx_start returns -1 with
+ * REFERENCE_QUIRKS set, with a ROW_STRIDE above 1 (there is no interleaved camera form), for a camera field that is not finite and
+ * for a value above 1.  With several VORTEX_HIP_DEVICES a camera run stays on the first device, as a restricted run does. */
+#define VX_DCR_HIP_CAMERA 0x7F5
 
 /* CSRs answered by mpm_query (read by vx_dump_perf at vx_dev_close: stub/perf.cpp:195-227). */
 #define VX_CSR_MPM_BASE 0xB00
@@ -340,6 +346,35 @@ int vxrt_render_rows_batch(vxrt_accel_t* accel, uint32_t width, uint32_t height,
 int vxrt_render_batch(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t n_frames, const vxrt_shade_params_t* params, int shadow,
                       uint32_t* dst, uint64_t dst_frame_stride, unsigned long long* rays_traced, void* stream);
 
+/* A pinhole camera: 14 floats, the layout of kernel_arg_t camera_pos .. viewplane (tracer.cpp:171-202 fills them) and of the head of
+ * vxrc_params_t.  The ray of pixel (x, y) of a W x H frame is the reference's GenerateRay (raycast/render.h:192-211), operation for
+ * operation (no FMA contraction):
+ *   x_ndc = (float)((double)(((float)x + 0.5f) / (float)W) - 0.5), y_ndc likewise with y and H
+ *   x_vp = x_ndc * viewplane[0], y_vp = y_ndc * viewplane[1]
+ *   pt_cam = (x_vp * right + y_vp * up) + forward, pt_w = pt_cam + pos, d = pt_w - pos, d *= 1 / sqrtf(dot(d, d)); origin = pos
+ * Every camera whose 14 fields are finite is legal, degenerate ones included (zero viewplane, a basis that is not orthonormal, a
+ * direction that normalises to zero or NaN): such rays are traced as the reference would trace them. */
+typedef struct vxrt_camera {
+  float pos[3], forward[3], right[3], up[3], viewplane[2];
+} vxrt_camera_t;
+
+/* vxrt_render seen from `cam` instead of the RTU test's fixed camera: the same arguments and outputs (closest hit, the optional
+ * occlusion ray and its bit 31 in hits[].blasIdx, shading, the mirror bounce up to params->max_depth, the RGB8 pack, colours,
+ * rays_traced).  `cam` is a host pointer read during the call; the launches stay asynchronous on `stream` and no host
+ * synchronisation is added: the camera's tables are built on the stream in the frame context's own storage, so frames in flight
+ * with different cameras do not see each other's.  Returns -1 before anything is launched (dst untouched) for a null camera, a
+ * camera field that is not finite, a stale accel, and whatever vxrt_render refuses. */
+int vxrt_render_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                       const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits /* optional */, float* colors /* optional */,
+                       unsigned long long* rays_traced, void* stream);
+
+/* vxrt_render_batch with a camera per frame: frame f is seen from cams[f], lit and shaded with params[f] and written to
+ * dst + f * dst_frame_stride -- a fly-through in one set of launches.  The limits of vxrt_render_batch (1..VXRT_MAX_BATCH frames,
+ * no optional outputs, no reflective instances with max_depth > 1) and the refusals of vxrt_render_camera apply. */
+int vxrt_render_batch_camera(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t n_frames, const vxrt_camera_t* cams,
+                             const vxrt_shade_params_t* params, int shadow, uint32_t* dst, uint64_t dst_frame_stride,
+                             unsigned long long* rays_traced, void* stream);
+
 /* vxrt_render with the fetch counters compiled in (diagnostic build of the same kernel, never
  * timed): counters = device u64[7]: rays, node fetches, instance fetches, triangle fetches,
  * shaded hits, textured hits, pixels written.  Counts are what the reference logs per ray in
@@ -452,6 +487,10 @@ int vxrt_shade_rays(vxrt_accel_t* accel, const float* rays, const vxrt_hit_t* hi
 /* Camera rays of rows [y0, y1) of the RTU test's frame (kernel.cpp:28-39) as a ray buffer: 6 floats per ray, ray of pixel (x, y) at
  * index x + (y - y0) * width. */
 int vxrt_camera_rays(uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, float* rays, void* stream);
+
+/* The rays of rows [y0, y1) of pinhole camera `cam` (see vxrt_camera_t), laid out as vxrt_camera_rays': 6 floats per ray, the ray
+ * of pixel (x, y) at index x + (y - y0) * width.  `cam` is a host pointer read during the call; -1 for a null or non-finite camera. */
+int vxrt_pinhole_rays(const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, float* rays, void* stream);
 
 /* Opt-in REFERENCE-QUIRKS traversal.  vxrt_trace / vxrt_render implement the canonical algorithm: the reference RTU's result
  * wherever the RTU addresses its own data.  With a TLAS deeper than one level it does not: children of a TLAS internal node popped

@@ -77,7 +77,7 @@ def build_test_variant(force=False):
     os.makedirs(d, exist_ok=True)
     so = os.path.join(d, "libvortex-hip.so")
     src = [os.path.join(CSRC, f) for f in PRODUCT_HIP_SOURCES]
-    hdrs = [os.path.join(CSRC, "rt_types.h"), os.path.join(CSRC, "bvh_quant.h"), os.path.join(HERE, "..", "include", "vortex_hip.h")]
+    hdrs = [os.path.join(CSRC, "rt_types.h"), os.path.join(CSRC, "bvh_quant.h"), os.path.join(CSRC, "pinhole.h"), os.path.join(HERE, "..", "include", "vortex_hip.h")]
     if force or _newer(so, src + hdrs):
         _run([HIPCC] + HIP_FLAGS + TEST_VARIANT_FLAGS + ["-shared", "-o", so] + src)
     for f in ("libvortex.so", "libvxrt_scene.so"):
@@ -87,7 +87,7 @@ def build_test_variant(force=False):
 
 def build(force=False, verbose=True):
     os.makedirs(LIB, exist_ok=True)
-    hdrs = [os.path.join(CSRC, "rt_types.h"), os.path.join(CSRC, "bvh_quant.h"), os.path.join(HERE, "..", "include", "vortex_hip.h")]
+    hdrs = [os.path.join(CSRC, "rt_types.h"), os.path.join(CSRC, "bvh_quant.h"), os.path.join(CSRC, "pinhole.h"), os.path.join(HERE, "..", "include", "vortex_hip.h")]
     if not os.path.exists(HIPCC):
         raise RuntimeError("hipcc not found at %s: the HIP path cannot be built" % HIPCC)
 

@@ -31,6 +31,7 @@
 #include <new>
 #include <vector>
 #include "../../include/vortex_hip.h"
+#include "pinhole.h"
 
 #define RC_LARGE_FLOAT 1e30f
 #define RC_EPSILON 1e-6f
@@ -358,17 +359,11 @@ __global__ __launch_bounds__(256, RC_WAVES) void rc_persistent_kernel(RcDev sc, 
   };
   // render.h:192-211 GenerateRay
   auto primary_ray = [&]() {
-    const float x_ndc = (float)((double)(((float)px + 0.5f) / (float)A.W) - 0.5);
-    const float y_ndc = (float)((double)(((float)py + 0.5f) / (float)A.H) - 0.5);
-    const float x_vp = x_ndc * p.viewplane[0], y_vp = y_ndc * p.viewplane[1];
-    const float cx = x_vp * p.cright[0] + y_vp * p.cup[0] + p.cfwd[0];
-    const float cy = x_vp * p.cright[1] + y_vp * p.cup[1] + p.cfwd[1];
-    const float cz = x_vp * p.cright[2] + y_vp * p.cup[2] + p.cfwd[2];
-    const float wx = cx + p.cpos[0], wy = cy + p.cpos[1], wz = cz + p.cpos[2];
-    const float vx = wx - p.cpos[0], vy = wy - p.cpos[1], vz = wz - p.cpos[2];
-    const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
+    const float x_vp = pinhole_ndc(px, A.W) * p.viewplane[0], y_vp = pinhole_ndc(py, A.H) * p.viewplane[1];
+    float dx, dy, dz;
+    pinhole_dir(x_vp, y_vp, p.cpos, p.cfwd, p.cright, p.cup, dx, dy, dz);
     rr = 0.f; rg = 0.f; rb = 0.f; thr = 1.0f; bounce = 0;
-    start_ray(p.cpos[0], p.cpos[1], p.cpos[2], vx * inv, vy * inv, vz * inv);
+    start_ray(p.cpos[0], p.cpos[1], p.cpos[2], dx, dy, dz);
   };
 
   for (;;) {

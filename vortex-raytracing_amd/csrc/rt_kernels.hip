@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "rt_types.h"
 #include "bvh_quant.h"
+#include "pinhole.h"
 #include "../../include/vortex_hip.h"
 
 #define STATUS_STACK_OVERFLOW 1u
@@ -387,6 +388,27 @@ __device__ __forceinline__ void generate_ray(float u, float v,
   dx = vx * inv; dy = vy * inv; dz = vz * inv;
 }
 
+// Camera frames (JOB_CAM, vxrt_render_camera): the frame context's camera block, written on the stream by rt_camera_prep_kernel.  Its
+// head holds VXRT_MAX_BATCH cameras of CAM_HDR floats (pos, forward, right, up); behind it, frame f's x_vp[W] then y_vp[H] start at
+// CAM_TAB + f * (W + H) (see pinhole.h).  The kernels take the head as `utab` and the tables as `vtab`.
+#define CAM_HDR 12
+#define CAM_TAB (VXRT_MAX_BATCH * CAM_HDR)
+__device__ __forceinline__ void camera_ray(const float* c, const float* tab, uint32_t W, uint32_t x, uint32_t y,
+                                           float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
+  ox = c[0]; oy = c[1]; oz = c[2];
+  pinhole_dir(tab[x], tab[W + y], c, c + 3, c + 6, c + 9, dx, dy, dz);
+}
+// the primary ray of pixel (x, y) of frame `frame` (0 unless a batch): the fixed camera's tables, or the camera block
+template <bool CAM>
+__device__ __forceinline__ void frame_pixel_ray(const float* utab, const float* vtab, uint32_t W, uint32_t H, uint32_t frame, uint32_t x, uint32_t y,
+                                                float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
+  if constexpr (CAM) camera_ray(utab + frame * CAM_HDR, vtab + (size_t)frame * (W + H), W, x, y, ox, oy, oz, dx, dy, dz);
+  else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+}
+// LDS copy of the camera block's head (camera traversal kernels only: the fixed-camera instantiations never reference it)
+template <int N>
+__device__ __forceinline__ float* cam_lds() { __shared__ float s[N]; return s; }
+
 __device__ __forceinline__ uint32_t wang_hash(uint32_t s) {   // common.h:129-135
   s = (s ^ 61u) ^ (s >> 16);
   s *= 9u; s = s ^ (s >> 4);
@@ -549,6 +571,11 @@ static_assert(RT_TOP_NODES <= RT_TOP_MAX, "top-of-tree image");
 // no path maxima).  vxrt_trace's VXRT_MODE_ANY returns the reference's FIRST accepted candidate and keeps JOB_TRACE.
 enum { JOB_RENDER = 0, JOB_RENDER_SHADOW = 1, JOB_TRACE = 2, JOB_RENDER_GI = 3, JOB_TRACE_UNORDERED = 4 };
 __host__ __device__ constexpr bool is_trace_job(int job) { return job == JOB_TRACE || job == JOB_TRACE_UNORDERED; }
+// JOB_CAM: a render job seen from a caller-supplied pinhole camera (vxrt_render_camera) instead of the fixed GenerateRay: its own
+// instantiations, so the fixed-camera kernels do not change.  JOB_RENDER | JOB_CAM and JOB_RENDER_SHADOW | JOB_CAM only.
+enum { JOB_CAM = 8 };
+__host__ __device__ constexpr int job_base(int job) { return job & ~JOB_CAM; }
+__host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) != 0; }
 // JOB_RENDER_GI: the whole "one diffuse bounce" frame (BASELINE configs[2] as worded; recipe: oracle/rt_oracle.c:orc_render_gi) in ONE
 // persistent launch -- a lane traces its pixel's primary ray, shades the hit (closest.cpp's else arm), draws the pixel's bounce ray
 // (ao_sample_ray, sample 0 of 1), traces it for its closest hit in the same lane, shades that hit and writes the pixel:
@@ -686,7 +713,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   constexpr uint32_t DEAD_MAX = is_trace_job(JOB) ? RT_TRACE_DEAD_MAX : (JOB == JOB_RENDER_GI ? RT_GI_DEAD_MAX : RT_DEAD_MAX);
   // render-with-shadow jobs: retire finished primary rays (their lanes continue with the occlusion ray
   // of the same pixel - same traversal code, so no phase mixing) before the whole tile is done
-  constexpr uint32_t FINISH_MIN = JOB == JOB_RENDER_SHADOW ? RT_SHADOW_FINISH_MIN : 65u;
+  constexpr uint32_t FINISH_MIN = job_base(JOB) == JOB_RENDER_SHADOW ? RT_SHADOW_FINISH_MIN : 65u;
   const uint32_t lane = threadIdx.x & 63u;
   // EXACT launch: the jobs are the entries of the deferral list the main launch left behind
   const uint32_t n_jobs = EXACT ? min(*A.defer_count, A.defer_cap) : (A.total_dev ? min(*A.total_dev, A.total) : A.total);
@@ -700,6 +727,12 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   __shared__ uint32_t s_ctx[WG_WAVES][NCTX][64];
   __shared__ uint32_t s_dry;      // bit s: a wavefront of this workgroup found queue shard s handed out
   if (threadIdx.x == 0) s_dry = 0u;
+  // camera frames: the cameras live in LDS (wave-uniform data; a lane reads its frame's camera when it derives a ray)
+  float* s_cam = nullptr;
+  if constexpr (is_cam_job(JOB)) {
+    s_cam = cam_lds<CAM_TAB>();
+    for (uint32_t i = threadIdx.x; i < (uint32_t)CAM_TAB; i += blockDim.x) s_cam[i] = A.utab[i];
+  }
   __syncthreads();
   uint2* const lstk = &s_stk[threadIdx.x >> 6][0][lane];
   uint32_t* const ctx = &s_ctx[threadIdx.x >> 6][0][lane];
@@ -776,6 +809,13 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     asm volatile("" : "+v"(j));
     return A.hits + j;
   };
+  // the primary ray of pixel (x, y) of the lane's job
+  auto pixel_ray = [&](uint32_t x, uint32_t y, float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
+    if constexpr (is_cam_job(JOB)) {
+      const uint32_t f = A.pbatch ? fast_div(job >> 6, A.div_frame_tiles) : 0u;
+      camera_ray(s_cam + f * CAM_HDR, A.vtab + (size_t)f * (A.W + A.H), A.W, x, y, ox, oy, oz, dx, dy, dz);
+    } else generate_ray(A.utab[x], A.vtab[y], ox, oy, oz, dx, dy, dz);
+  };
   // the lane's world-space ray, re-derived from its job (deterministic: same bits every time)
   auto world_ray = [&](float& ox, float& oy, float& oz, float& dx, float& dy, float& dz, float& tmax_) {
     tmax_ = RT_LARGE_FLOAT;
@@ -789,11 +829,11 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     } else {
       uint32_t x, y;
       pixel_of(job, x, y);
-      generate_ray(A.utab[x], A.vtab[y], ox, oy, oz, dx, dy, dz);
+      pixel_ray(x, y, ox, oy, oz, dx, dy, dz);
       if (JOB == JOB_RENDER_GI && (flags & F_SHADOW)) {   // bounce phase: the ray drawn when the primary ray finished
         ox = g_ray[0]; oy = g_ray[1]; oz = g_ray[2]; dx = g_ray[3]; dy = g_ray[4]; dz = g_ray[5];
       }
-      if (JOB == JOB_RENDER_SHADOW && (flags & F_SHADOW)) {
+      if (job_base(JOB) == JOB_RENDER_SHADOW && (flags & F_SHADOW)) {
         const float pd = __uint_as_float(CTX(5));   // distance of this pixel's primary hit
         float sox, soy, soz, sdx, sdy, sdz, sdist;
         float lpx = p.lpos[0], lpy = p.lpos[1], lpz = p.lpos[2];
@@ -811,7 +851,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     // -- same hit by construction -- and goes on from there; the primary ray this launch counted is taken back)
     if (JOB == JOB_RENDER_GI && (flags & F_SHADOW)) nrays--;
     if (slot < A.defer_cap) A.defer_list[slot] = job | ((flags & F_SHADOW) && JOB != JOB_RENDER_GI ? 0x80000000u : 0u);
-    if (JOB == JOB_RENDER_SHADOW && (flags & F_SHADOW)) {
+    if (job_base(JOB) == JOB_RENDER_SHADOW && (flags & F_SHADOW)) {
       // the EXACT launch resumes this pixel's occlusion ray from the primary hit record in memory
       HitRec h;
       h.bx = __uint_as_float(CTX(3)); h.by = __uint_as_float(CTX(4)); h.bz = 1 - h.bx - h.by;
@@ -854,8 +894,9 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     flags = (flags & (F_SHADOW | F_RESUMED)) | F_WORLD | (any_ ? F_ANYHIT : 0u);
     if (!EXACT && !safe) {
       // camera rays with a zero direction component are known before the launch (u == 0 or v == 0): the
-      // host lists them and a concurrent EXACT launch traces them; everything else is deferred
-      if (!is_trace_job(JOB) && !(flags & F_SHADOW)) cur = DESC_IDLE; else defer(false);
+      // host lists them and a concurrent EXACT launch traces them; everything else is deferred -- the primary
+      // rays of camera frames (JOB_CAM) too: no host list predicts them
+      if (!is_trace_job(JOB) && !is_cam_job(JOB) && !(flags & F_SHADOW)) cur = DESC_IDLE; else defer(false);
       return;
     }
     hitd = tmax_ > RT_LARGE_FLOAT ? RT_LARGE_FLOAT : tmax_;   // (a bound above 1e30 is 1e30: a missed box reports 1e30, rt_traversal.cpp:338, and must stay filtered by `d < hit.dist`)
@@ -996,7 +1037,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
             if (EXACT) {
               const uint32_t wd = A.defer_list[job];
               job = wd & 0x7fffffffu;
-              if (wd >> 31) { flags = F_SHADOW | F_RESUMED; if (JOB == JOB_RENDER_SHADOW) CTX(5) = __float_as_uint(hit_slot()->dist); }
+              if (wd >> 31) { flags = F_SHADOW | F_RESUMED; if (job_base(JOB) == JOB_RENDER_SHADOW) CTX(5) = __float_as_uint(hit_slot()->dist); }
             }
             float ox, oy, oz, dx, dy, dz, tm;
             if (is_trace_job(JOB)) {
@@ -1073,7 +1114,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
         if (STATS) fx.node++;
         Cand c[4];
         eval_children<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
-        if (((JOB == JOB_RENDER_SHADOW && RT_UNORDERED_OCCLUSION) || JOB == JOB_TRACE_UNORDERED) && STATS != 1 && __all((flags & F_ANYHIT) != 0u)) {   // STATS keeps the reference's order, hence its fetch counts
+        if (((job_base(JOB) == JOB_RENDER_SHADOW && RT_UNORDERED_OCCLUSION) || JOB == JOB_TRACE_UNORDERED) && STATS != 1 && __all((flags & F_ANYHIT) != 0u)) {   // STATS keeps the reference's order, hence its fetch counts
           // occlusion rays of a frame only feed a boolean (is anything hit before the light?): the set
           // of triangles an any-hit traversal can reach does not depend on the visiting order, so the
           // ordering network and the path_m bookkeeping are skipped (vxrt_trace's MODE_ANY, which
@@ -1225,7 +1266,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
                 hitd = d;
                 flags |= F_FOUND;
                 // (a frame's occlusion ray only feeds a boolean; slots 3-7 keep the pixel's primary hit meanwhile)
-                if (!(JOB == JOB_RENDER_SHADOW && (flags & F_SHADOW))) { CTX(3) = __float_as_uint(bx); CTX(4) = __float_as_uint(by); CTX(6) = CTX(8); CTX(7) = triIdx; }
+                if (!(job_base(JOB) == JOB_RENDER_SHADOW && (flags & F_SHADOW))) { CTX(3) = __float_as_uint(bx); CTX(4) = __float_as_uint(by); CTX(6) = CTX(8); CTX(7) = triIdx; }
                 if (flags & F_ANYHIT) { stop = true; break; }
                 // the reference re-descends from the root with the shrunken hit.dist; if any box on the
                 // current path no longer passes `d < hit.dist` it abandons this subtree
@@ -1311,12 +1352,12 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       } else if (!(flags & F_SHADOW)) {
         // deferred shading: finishing a ray costs one store, not a chain of dependent loads
         if (STATS && found) nhit++;
-        if (JOB == JOB_RENDER_SHADOW && found) {
+        if (job_base(JOB) == JOB_RENDER_SHADOW && found) {
           // continue this lane with the pixel's occlusion ray; the record is written when that ray has finished
           uint32_t x, y;
           pixel_of(job, x, y);
           float ox, oy, oz, dx, dy, dz, sox, soy, soz, sdx, sdy, sdz, sdist;
-          generate_ray(A.utab[x], A.vtab[y], ox, oy, oz, dx, dy, dz);
+          pixel_ray(x, y, ox, oy, oz, dx, dy, dz);
           float lpx = p.lpos[0], lpy = p.lpos[1], lpz = p.lpos[2];
           if (A.pbatch) { const ShadeParams* q = A.pbatch + fast_div(job >> 6, A.div_frame_tiles); lpx = q->lpos[0]; lpy = q->lpos[1]; lpz = q->lpos[2]; }
           shadow_ray(lpx, lpy, lpz, ox, oy, oz, dx, dy, dz, hitd, sox, soy, soz, sdx, sdy, sdz, sdist);
@@ -2013,16 +2054,17 @@ __device__ void lpt_order_block(uint32_t shard, const uint32_t* __restrict__ cos
 
 // Deferred shading pass: one thread per pixel of rows [y0,y1), x fastest, so hit records are read
 // and pixels written fully coalesced.
-template <bool STATS>
-__global__ __launch_bounds__(256) void rt_shade_kernel(SceneDev sc, ShadeParams p, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t row_step,
-                                                      uint32_t n_rows, const float* __restrict__ utab, const float* __restrict__ vtab,
-                                                      const HitRec* __restrict__ hb, uint32_t* __restrict__ dst,
-                                                      HitRec* __restrict__ hits, float* __restrict__ colors,
-                                                      unsigned long long* counters, uint32_t* __restrict__ ctl_reset,
-                                                      uint32_t lpt_blocks, const uint32_t* __restrict__ lpt_cost, uint32_t* __restrict__ lpt_order,
-                                                      uint32_t lpt_tiles, uint32_t lpt_per_shard,
-                                                      uint32_t batch = 1, const ShadeParams* __restrict__ pbatch = nullptr, uint64_t dst_frame_stride = 0,
-                                                      const uint32_t* __restrict__ lpt_base = nullptr) {
+// (CAM: camera frames -- utab / vtab are the camera block, see CAM_HDR)
+template <bool STATS, bool CAM>
+__device__ __forceinline__ void shade_pass(SceneDev sc, ShadeParams p, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t row_step,
+                                           uint32_t n_rows, const float* __restrict__ utab, const float* __restrict__ vtab,
+                                           const HitRec* __restrict__ hb, uint32_t* __restrict__ dst,
+                                           HitRec* __restrict__ hits, float* __restrict__ colors,
+                                           unsigned long long* counters, uint32_t* __restrict__ ctl_reset,
+                                           uint32_t lpt_blocks, const uint32_t* __restrict__ lpt_cost, uint32_t* __restrict__ lpt_order,
+                                           uint32_t lpt_tiles, uint32_t lpt_per_shard,
+                                           uint32_t batch, const ShadeParams* __restrict__ pbatch, uint64_t dst_frame_stride,
+                                           const uint32_t* __restrict__ lpt_base) {
   // the first lpt_blocks workgroups sort the frame's tiles by cost for the context's next frame (see lpt_order_block)
   __shared__ uint32_t s_hist[2048 + 8];
   if (blockIdx.x < lpt_blocks) { lpt_order_block(blockIdx.x, lpt_cost, lpt_order, lpt_tiles, lpt_per_shard, s_hist, lpt_base); return; }
@@ -2045,7 +2087,7 @@ __global__ __launch_bounds__(256) void rt_shade_kernel(SceneDev sc, ShadeParams 
     h.blasIdx &= 0x7fffffffu;
     const bool found = h.dist != RT_LARGE_FLOAT;
     float ox, oy, oz, dx, dy, dz;
-    generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+    frame_pixel_ray<CAM>(utab, vtab, W, H, frame, x, y, ox, oy, oz, dx, dy, dz);
     float r, g, b;
     shade_eval<STATS>(sc, p, ox, oy, oz, dx, dy, dz, h, found, occ, r, g, b, &ntex);
     dst[idx] = pack_rgb8(r, g, b);
@@ -2063,6 +2105,33 @@ __global__ __launch_bounds__(256) void rt_shade_kernel(SceneDev sc, ShadeParams 
       if (lane == 0 && s) atomicAdd(counters + 5 + k, (unsigned long long)s);
     }
   }
+}
+template <bool STATS>
+__global__ __launch_bounds__(256) void rt_shade_kernel(SceneDev sc, ShadeParams p, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t row_step,
+                                                      uint32_t n_rows, const float* __restrict__ utab, const float* __restrict__ vtab,
+                                                      const HitRec* __restrict__ hb, uint32_t* __restrict__ dst,
+                                                      HitRec* __restrict__ hits, float* __restrict__ colors,
+                                                      unsigned long long* counters, uint32_t* __restrict__ ctl_reset,
+                                                      uint32_t lpt_blocks, const uint32_t* __restrict__ lpt_cost, uint32_t* __restrict__ lpt_order,
+                                                      uint32_t lpt_tiles, uint32_t lpt_per_shard,
+                                                      uint32_t batch = 1, const ShadeParams* __restrict__ pbatch = nullptr, uint64_t dst_frame_stride = 0,
+                                                      const uint32_t* __restrict__ lpt_base = nullptr) {
+  shade_pass<STATS, false>(sc, p, W, H, y0, y1, row_step, n_rows, utab, vtab, hb, dst, hits, colors, counters, ctl_reset, lpt_blocks, lpt_cost, lpt_order,
+                           lpt_tiles, lpt_per_shard, batch, pbatch, dst_frame_stride, lpt_base);
+}
+// the shading pass of camera frames (vxrt_render_camera / vxrt_render_batch_camera): cam = the frame context's camera block.
+// BATCH = false: one frame, whose camera head every lane reads at the same address -- scalar loads, the camera stays in SGPRs
+template <bool BATCH>
+__global__ __launch_bounds__(256) void rt_shade_camera_kernel(SceneDev sc, ShadeParams p, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t row_step,
+                                                             uint32_t n_rows, const float* __restrict__ cam,
+                                                             const HitRec* __restrict__ hb, uint32_t* __restrict__ dst,
+                                                             HitRec* __restrict__ hits, float* __restrict__ colors, uint32_t* __restrict__ ctl_reset,
+                                                             uint32_t lpt_blocks, const uint32_t* __restrict__ lpt_cost, uint32_t* __restrict__ lpt_order,
+                                                             uint32_t lpt_tiles, uint32_t lpt_per_shard,
+                                                             uint32_t batch, const ShadeParams* __restrict__ pbatch, uint64_t dst_frame_stride,
+                                                             const uint32_t* __restrict__ lpt_base) {
+  shade_pass<false, true>(sc, p, W, H, y0, y1, row_step, n_rows, cam, cam + CAM_TAB, hb, dst, hits, colors, nullptr, ctl_reset, lpt_blocks, lpt_cost, lpt_order,
+                          lpt_tiles, lpt_per_shard, BATCH ? batch : 1u, pbatch, dst_frame_stride, lpt_base);
 }
 
 // closest-hit / miss shader of arbitrary (ray, hit record) pairs: what the RTU test's shaders compute for the ray a payload belongs
@@ -2091,9 +2160,9 @@ __global__ __launch_bounds__(256) void rt_shade_rays_kernel(SceneDev sc, ShadePa
 // Shade level `level`.  LEVEL0: entry = pixel of rows [y0,y1), hit record from the traversal (occlusion
 // in bit 31 of blasIdx); else entry i = ray rays[6i..] with hit hits[i] (occluded iff shits[i] hit).
 // Entries that bounce leave (term, reflectivity) in term[] and append a ray; the others are final.
-template <bool LEVEL0>
-__global__ __launch_bounds__(256) void rt_shade_bounce_kernel(SceneDev sc, ShadeParams p, uint32_t level, uint64_t n,
-    uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
+template <bool LEVEL0, bool CAM>
+__device__ __forceinline__ void shade_bounce_pass(SceneDev sc, ShadeParams p, uint32_t level, uint64_t n,
+    uint32_t W, uint32_t H, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
     const HitRec* __restrict__ hb, const float* __restrict__ rays, const HitRec* __restrict__ shits,
     float4* __restrict__ term, float* __restrict__ col, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
     float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent,
@@ -2113,7 +2182,7 @@ __global__ __launch_bounds__(256) void rt_shade_bounce_kernel(SceneDev sc, Shade
     occ = (h.blasIdx & 0x80000000u) != 0u;
     if (hits_out) hits_out[e] = h;
     h.blasIdx &= 0x7fffffffu;
-    generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+    frame_pixel_ray<CAM>(utab, vtab, W, H, 0u, x, y, ox, oy, oz, dx, dy, dz);
   } else {
     const float* rp = rays + e * 6;
     ox = rp[0]; oy = rp[1]; oz = rp[2]; dx = rp[3]; dy = rp[4]; dz = rp[5];
@@ -2149,6 +2218,23 @@ __global__ __launch_bounds__(256) void rt_shade_bounce_kernel(SceneDev sc, Shade
       col[3 * e] = r; col[3 * e + 1] = g; col[3 * e + 2] = b;
     }
   }
+}
+template <bool LEVEL0>
+__global__ __launch_bounds__(256) void rt_shade_bounce_kernel(SceneDev sc, ShadeParams p, uint32_t level, uint64_t n,
+    uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
+    const HitRec* __restrict__ hb, const float* __restrict__ rays, const HitRec* __restrict__ shits,
+    float4* __restrict__ term, float* __restrict__ col, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
+    float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent,
+    uint32_t* __restrict__ ctl_reset) {
+  shade_bounce_pass<LEVEL0, false>(sc, p, level, n, W, 0u, y0, utab, vtab, hb, rays, shits, term, col, dst, hits_out, colors_out, next_count, next_rays,
+                                   next_parent, ctl_reset);
+}
+// level 0 of a camera frame's mirror bounce (the deeper levels hold ray buffers: rt_shade_bounce_kernel<false>)
+__global__ __launch_bounds__(256) void rt_shade_bounce_camera_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t H, uint32_t y0,
+    const float* __restrict__ cam, const HitRec* __restrict__ hb, float4* __restrict__ term, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
+    float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent, uint32_t* __restrict__ ctl_reset) {
+  shade_bounce_pass<true, true>(sc, p, 0u, n, W, H, y0, cam, cam + CAM_TAB, hb, nullptr, nullptr, term, nullptr, dst, hits_out, colors_out, next_count,
+                                next_rays, next_parent, ctl_reset);
 }
 
 // occlusion rays of a bounce level (shadow extension at every depth); a miss gets a ray nothing can hit
@@ -2523,6 +2609,36 @@ __global__ __launch_bounds__(256) void rt_camera_rays_kernel(uint32_t W, uint32_
   const float u = (float)(((double)x * 2.0 - (double)W) / (double)H), v = (float)(((double)y * 2.0 - (double)H) / (double)H);
   float* o = rays + i * 6;
   generate_ray(u, v, o[0], o[1], o[2], o[3], o[4], o[5]);
+}
+
+// rays of rows [y0, y1) of a caller-supplied pinhole camera (vxrt_pinhole_rays; pinhole.h), laid out as rt_camera_rays_kernel's
+__global__ __launch_bounds__(256) void rt_pinhole_rays_kernel(vxrt_camera_t c, uint32_t W, uint32_t H, uint32_t y0, uint64_t n, float* __restrict__ rays) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t x = (uint32_t)(i % W), y = y0 + (uint32_t)(i / W);
+  float* o = rays + i * 6;
+  o[0] = c.pos[0]; o[1] = c.pos[1]; o[2] = c.pos[2];
+  pinhole_dir(pinhole_ndc(x, W) * c.viewplane[0], pinhole_ndc(y, H) * c.viewplane[1], c.pos, c.forward, c.right, c.up, o[3], o[4], o[5]);
+}
+
+// the camera block of a camera frame / batch (see CAM_HDR), on the frame's stream: the cameras come by value through the kernel
+// arguments, so nothing waits on the host and frames in flight on other contexts keep their own blocks
+struct CamBatch { vxrt_camera_t c[VXRT_MAX_BATCH]; };
+__global__ __launch_bounds__(256) void rt_camera_prep_kernel(CamBatch b, uint32_t n, uint32_t W, uint32_t H, float* __restrict__ out) {
+  const uint32_t per = W + H;
+  const uint64_t total = CAM_TAB + (uint64_t)n * per;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256u) {
+    if (i < CAM_TAB) {   // heads of every slot (slots past n repeat camera 0)
+      const uint32_t f = (uint32_t)i / CAM_HDR, k = (uint32_t)i % CAM_HDR;
+      const vxrt_camera_t& c = b.c[f < n ? f : 0u];
+      out[i] = k < 3 ? c.pos[k] : (k < 6 ? c.forward[k - 3] : (k < 9 ? c.right[k - 6] : c.up[k - 9]));
+    } else {
+      const uint64_t j = i - CAM_TAB;
+      const uint32_t f = (uint32_t)(j / per), t = (uint32_t)(j % per);
+      const vxrt_camera_t& c = b.c[f];
+      out[i] = t < W ? pinhole_ndc(t, W) * c.viewplane[0] : pinhole_ndc(t - W, H) * c.viewplane[1];
+    }
+  }
 }
 
 struct ShadeBatch { ShadeParams p[VXRT_MAX_BATCH]; };
@@ -2996,6 +3112,7 @@ __global__ __launch_bounds__(256) void refit_xform_commit_kernel(const float* __
 // host entry points (C ABI, include/vortex_hip.h level 2)
 // ---------------------------------------------------------------------------------------------
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -3064,6 +3181,7 @@ struct FrameCtx {
   uint64_t defer_cap = 0;
   uint32_t* ctl = nullptr;     // control block (CTL_DWORDS), zero between frames
   ShadeParams* pbatch = nullptr;   // per-frame shading parameters of a batch launch (VXRT_MAX_BATCH entries)
+  float* cam = nullptr; uint64_t cam_floats = 0;   // camera block of the context's camera frames (see CAM_HDR)
   bool ctl_dirty = false;      // a call failed after touching it: clear before the next use
   // mirror-bounce levels (allocated on first use; level 0 only holds `term`, one entry per pixel)
   struct Level {
@@ -3152,7 +3270,7 @@ static void accel_free(vxrt_accel* a) {
       (void)hipFree(l.rays); (void)hipFree(l.hits); (void)hipFree(l.parent); (void)hipFree(l.term); (void)hipFree(l.col);
       (void)hipFree(l.srays); (void)hipFree(l.stmax); (void)hipFree(l.shits);
     }
-    (void)hipFree(c.pbatch); (void)hipFree(c.pool_spill);
+    (void)hipFree(c.pbatch); (void)hipFree(c.pool_spill); (void)hipFree(c.cam);
     if (c.side) (void)hipStreamDestroy(c.side);
     if (c.ev_in) (void)hipEventDestroy(c.ev_in);
     if (c.ev_side) (void)hipEventDestroy(c.ev_side);
@@ -3691,7 +3809,7 @@ static bool level_reserve(FrameCtx::Level& l, uint64_t n, bool shadow, bool only
 // to the host between levels, so this path synchronises the stream (it is not the benchmarked one).
 static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p, uint32_t width, uint32_t y0, uint32_t y1,
                               int shadow, const float* utab, const float* vtab, uint32_t* dst, HitRec* hits, float* colors,
-                              unsigned long long* rays_traced, hipStream_t s) {
+                              unsigned long long* rays_traced, hipStream_t s, uint32_t height = 0, const float* cam = nullptr) {
   const SceneDev& sc = a->dev;
   const uint64_t npix = (uint64_t)width * (y1 - y0);          // entries of level 0 (addressed by pixel index)
   const uint64_t pix_span = (uint64_t)width * y1;              // term[] of level 0 is indexed by x + y*W
@@ -3702,9 +3820,11 @@ static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p
   if (!level_reserve(c->lv[1], npix, shadow != 0, false)) return -1;
   dim3 block(256);
   if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
-  hipLaunchKernelGGL(rt_shade_bounce_kernel<true>, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, 0u, npix, width, y0, utab, vtab,
-                     (const HitRec*)c->hitbuf, (const float*)nullptr, (const HitRec*)nullptr, c->lv[0].term, (float*)nullptr, dst, hits, colors,
-                     c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
+  if (cam) hipLaunchKernelGGL(rt_shade_bounce_camera_kernel, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, npix, width, height, y0, cam,
+                              (const HitRec*)c->hitbuf, c->lv[0].term, dst, hits, colors, c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
+  else hipLaunchKernelGGL(rt_shade_bounce_kernel<true>, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, 0u, npix, width, y0, utab, vtab,
+                          (const HitRec*)c->hitbuf, (const float*)nullptr, (const HitRec*)nullptr, c->lv[0].term, (float*)nullptr, dst, hits, colors,
+                          c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
   if (hipGetLastError() != hipSuccess) return -1;
   c->ctl_dirty = false;
   uint32_t depth = 0;   // deepest level that holds rays
@@ -3816,8 +3936,10 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
                          const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits, float* colors,
                          unsigned long long* counters, int stats, void* stream, unsigned long long* wave_log = nullptr,
                          const vxrt_ao_params_t* ao = nullptr, uint32_t* unoccluded = nullptr, uint32_t stride = 1,
-                         uint32_t batch = 1, uint64_t dst_frame_stride = 0) {
+                         uint32_t batch = 1, uint64_t dst_frame_stride = 0, const vxrt_camera_t* cams = nullptr) {
   if (!a || a->stale || !params || !dst) return -1;
+  // camera frames (cams[f] per frame of the batch): plain and shadow frames, whole rows, the timed build only
+  if (cams && (stride != 1 || ao || stats || wave_log || unoccluded)) return -1;
   // batch > 1: `params` is an array of `batch` entries, frame f goes to dst + f * dst_frame_stride; plain frames without optional outputs
   if (batch == 0 || batch > VXRT_MAX_BATCH || (batch > 1 && (hits || colors || ao || ((stats || wave_log) && !(stats == 2 && wave_log))))) return -1;   // (a batch with the wave log: diagnostic, traversal only -- its shading launch is the single-frame one)
   if (ao && (stats || shadow)) return -1;
@@ -3865,7 +3987,7 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
     if (hipMalloc(&c->hitbuf, pixels * sizeof(HitRec)) != hipSuccess) return fail();
     c->hitbuf_pixels = pixels;
   }
-  if (a->uv_w != width || a->uv_h != height) {
+  if (!cams && (a->uv_w != width || a->uv_h != height)) {
     // kernel.cpp:32-33 evaluated on the host in double, once per column and row
     std::vector<float> tab((size_t)width + height);
     for (uint32_t x = 0; x < width; ++x) tab[x] = (float)(((double)x * 2.0 - (double)width) / (double)height);
@@ -3882,6 +4004,24 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
   A.div_tiles_x = fast_div_make(tiles_x); A.div_frame_tiles = fast_div_make(frame_tiles); A.frame_tiles = frame_tiles;
   A.hits = (HitRec*)c->hitbuf; A.counters = counters; A.status = st; A.wave_log = wave_log; A.end_log = a->end_log;
   A.utab = a->uvtab; A.vtab = a->uvtab + width;
+  if (cams) {
+    // the camera block lives in the frame context and is written on the frame's stream: the fixed camera's tables and a-priori
+    // list stay untouched, and frames in flight on other contexts keep their own cameras
+    const uint64_t need = CAM_TAB + (uint64_t)batch * (width + height);
+    if (c->cam_floats < need) {
+      if (hipStreamSynchronize(s) != hipSuccess) return fail();
+      (void)hipFree(c->cam);
+      c->cam = nullptr; c->cam_floats = 0;
+      if (hipMalloc((void**)&c->cam, need * sizeof(float)) != hipSuccess) return fail();
+      c->cam_floats = need;
+    }
+    CamBatch cb;
+    for (uint32_t f = 0; f < VXRT_MAX_BATCH; ++f) cb.c[f] = cams[f < batch ? f : 0];
+    const uint32_t g = (uint32_t)std::min<uint64_t>((need + 255) / 256, 1024);
+    hipLaunchKernelGGL(rt_camera_prep_kernel, dim3(g), dim3(256), 0, s, cb, batch, width, height, c->cam);
+    if (hipGetLastError() != hipSuccess) return fail();
+    A.utab = c->cam; A.vtab = c->cam + CAM_TAB;
+  }
   if (batch > 1) {
     if (!c->pbatch && hipMalloc((void**)&c->pbatch, VXRT_MAX_BATCH * sizeof(ShadeParams)) != hipSuccess) return fail();
     ShadeParams pb[VXRT_MAX_BATCH];
@@ -3954,7 +4094,8 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
       if (hipMalloc((void**)&L.cost, (size_t)n_tiles * 4 * 4) != hipSuccess || hipMalloc((void**)&L.order, (size_t)n_tiles * 4) != hipSuccess) return fail();
       L.cap = n_tiles;
     }
-    const uint32_t key[6] = {width, height, y0, y1, (uint32_t)shadow | (stride << 1), (ao ? 1u : 0u) | (batch << 1)};
+    // (camera frames learn their own order: they do not share the fixed camera's tiles' costs)
+    const uint32_t key[6] = {width, height, y0, y1, (uint32_t)shadow | (stride << 1), (ao ? 1u : 0u) | (batch << 1) | (cams ? 0x80000000u : 0u)};
     if (memcmp(key, L.key, sizeof key) != 0) { L.valid = false; memcpy(L.key, key, sizeof key); }
     if (!L.cost || !L.order) return fail();   // (whatever happened above: no launch with a missing table)
     A.tile_cost = L.cost;
@@ -3963,7 +4104,8 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
   }
   // a-priori EXACT list (camera rays with u == 0 or v == 0), rebuilt only when the window changes.  The list of a batch is the
   // frames' lists one after the other, so a list built for F frames serves every batch <= F: the launch takes a prefix.
-  if (a->ap_key[0] != width || a->ap_key[1] != height || a->ap_key[2] != y0 || a->ap_key[3] != y1 || a->ap_key[4] != stride || a->ap_key[5] < batch || !a->apriori) {
+  // (camera frames have none: their primary rays outside the fast domain are deferred to the EXACT launch behind the main one)
+  if (!cams && (a->ap_key[0] != width || a->ap_key[1] != height || a->ap_key[2] != y0 || a->ap_key[3] != y1 || a->ap_key[4] != stride || a->ap_key[5] < batch || !a->apriori)) {
     std::vector<uint32_t> list(1, 0u);
     for (uint32_t t = 0; t < frame_tiles; ++t)
       for (uint32_t l = 0; l < 64; ++l) {
@@ -3988,7 +4130,7 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
     a->ap_count = (uint32_t)per_frame;      // per frame
     a->ap_key[0] = width; a->ap_key[1] = height; a->ap_key[2] = y0; a->ap_key[3] = y1; a->ap_key[4] = stride; a->ap_key[5] = batch;
   }
-  const uint32_t ap_count = a->ap_count * batch;   // of this launch: the first `batch` frames of the list
+  const uint32_t ap_count = cams ? 0u : a->ap_count * batch;   // of this launch: the first `batch` frames of the list
   // EXACT launch over the a-priori list on the side stream (ordered after everything already queued on
   // `s`: it writes hit records the previous frame's shading pass may still be reading), concurrent with
   // the main launch; then the main launch and the EXACT launch over whatever the main one deferred
@@ -4052,6 +4194,7 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
   } else
   if (stats == 2)  { if (shadow) LAUNCH_PD(JOB_RENDER_SHADOW, 2, false); else LAUNCH_PD(JOB_RENDER, 2, false); }
   else if (stats)  { if (shadow) LAUNCH_PD(JOB_RENDER_SHADOW, 1, false); else LAUNCH_PD(JOB_RENDER, 1, false); }
+  else if (cams)   { if (shadow) LAUNCH_PDS(JOB_RENDER_SHADOW | JOB_CAM, false); else LAUNCH_PDS(JOB_RENDER | JOB_CAM, false); }
   else if (packed) { if (shadow) LAUNCH_PDS(JOB_RENDER_SHADOW, true); else LAUNCH_PDS(JOB_RENDER, true); }
   else             { if (shadow) LAUNCH_PDS(JOB_RENDER_SHADOW, false); else LAUNCH_PDS(JOB_RENDER, false); }
 #undef LAUNCH_PDS
@@ -4075,13 +4218,17 @@ static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint3
   }
   if (p.max_depth > 1 && a->max_reflectivity > 0.0f) {
     // reflective instances: the shading pass becomes the level-0 step of the mirror-bounce wavefront
-    if (render_bounce_tail(a, c, p, width, y0, y1, shadow, A.utab, A.vtab, dst, (HitRec*)hits, colors, counters, s) != 0) return fail();
+    if (render_bounce_tail(a, c, p, width, y0, y1, shadow, A.utab, A.vtab, dst, (HitRec*)hits, colors, counters, s, height, cams ? A.utab : nullptr) != 0) return fail();
     return release_ctx(a, c, s);
   }
   const uint64_t npx = (uint64_t)width * tiles_y * 8u * batch;
   const uint32_t lpt_blocks = lpt_sort ? QUEUE_SHARDS : 0u;
   dim3 sgrid((uint32_t)((npx + 255) / 256) + lpt_blocks);
-  if (stats) hipLaunchKernelGGL(rt_shade_kernel<true>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step, tiles_y * 8u, A.utab, A.vtab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, counters, c->ctl,
+  if (cams) hipLaunchKernelGGL(batch > 1 ? rt_shade_camera_kernel<true> : rt_shade_camera_kernel<false>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step,
+                               tiles_y * 8u, (const float*)A.utab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, c->ctl, lpt_blocks, (const uint32_t*)L.cost,
+                               L.order, n_tiles, A.per_shard >> 6, batch, (const ShadeParams*)c->pbatch, dst_frame_stride,
+                               batch > 1 ? (const uint32_t*)a->batch_order[batch] : (const uint32_t*)nullptr);
+  else if (stats) hipLaunchKernelGGL(rt_shade_kernel<true>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step, tiles_y * 8u, A.utab, A.vtab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, counters, c->ctl,
                                 lpt_blocks, (const uint32_t*)L.cost, L.order, n_tiles, A.per_shard >> 6, 1u, (const ShadeParams*)nullptr, (uint64_t)0,
                                 batch > 1 ? (const uint32_t*)a->batch_order[batch] : (const uint32_t*)nullptr);
   else       hipLaunchKernelGGL(rt_shade_kernel<false>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step, tiles_y * 8u, A.utab, A.vtab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, counters, c->ctl,
@@ -4148,6 +4295,34 @@ int vxrt_render_interleaved_batch_wave_log(vxrt_accel_t* accel, uint32_t width, 
 int vxrt_render_batch(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t n_frames, const vxrt_shade_params_t* params, int shadow,
                       uint32_t* dst, uint64_t dst_frame_stride, unsigned long long* rays_traced, void* stream) {
   return vxrt_render_interleaved_batch(accel, width, height, 0, 1, n_frames, params, shadow, dst, dst_frame_stride, rays_traced, stream);
+}
+
+// A camera whose every field is finite (what the camera entry points accept)
+static bool camera_ok(const vxrt_camera_t* c) {
+  if (!c) return false;
+  const float* f = &c->pos[0];
+  for (int i = 0; i < 14; ++i) if (!std::isfinite(f[i])) return false;
+  return true;
+}
+
+// vxrt_render from a caller-supplied pinhole camera (see the header)
+int vxrt_render_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                       const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits, float* colors,
+                       unsigned long long* rays_traced, void* stream) {
+  if (!camera_ok(cam)) return -1;
+  return render_common(accel, width, height, y0, y1, params, shadow, dst, hits, colors, rays_traced, false, stream, nullptr, nullptr, nullptr, 1, 1, 0, cam);
+}
+
+// vxrt_render_batch with cams[f] per frame (see the header)
+int vxrt_render_batch_camera(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t n_frames, const vxrt_camera_t* cams,
+                             const vxrt_shade_params_t* params, int shadow, uint32_t* dst, uint64_t dst_frame_stride,
+                             unsigned long long* rays_traced, void* stream) {
+  if (!cams || n_frames == 0 || n_frames > VXRT_MAX_BATCH) return -1;
+  for (uint32_t f = 0; f < n_frames; ++f) if (!camera_ok(cams + f)) return -1;
+  if (!accel || accel->stale || !params || !dst) return -1;
+  if (height == 0) return 0;   // (as vxrt_render_batch: no tile row to render)
+  return render_common(accel, width, height, 0, height, params, shadow, dst, nullptr, nullptr, rays_traced, false, stream, nullptr, nullptr, nullptr, 1,
+                       n_frames, dst_frame_stride, cams);
 }
 
 // Same launches as vxrt_render with the fetch counters compiled in (slower; never the timed path).
@@ -4246,6 +4421,14 @@ int vxrt_camera_rays(uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, 
   const uint64_t n = (uint64_t)width * (y1 - y0);
   if (n == 0) return 0;
   hipLaunchKernelGGL(rt_camera_rays_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, width, height, y0, n, rays);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int vxrt_pinhole_rays(const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, float* rays, void* stream) {
+  if (!camera_ok(cam) || !rays || width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_pinhole_rays_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cam, width, height, y0, n, rays);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

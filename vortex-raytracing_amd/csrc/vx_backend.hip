@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -780,6 +781,21 @@ int vx_device::start(uint64_t krnl_va, uint64_t args_va) {
   if (y1 == 0 || y1 > ka.dst_height) y1 = ka.dst_height;
   if (y0 > y1) y0 = y1;
   if (row_stride > 1 && ((y0 & 7u) != 0 || y0 / 8u >= row_stride)) { VXLOG("start: DCR 0x7F3 (tile-row stride) needs ROW_BEGIN = 8 * phase with phase < stride"); return -1; }
+  // DCR 0x7F5: the frame seen from kernel_arg_t's pinhole camera (vxrt_render_camera)
+  uint32_t use_camera = 0, quirks_set = 0;
+  dcr(VX_DCR_HIP_CAMERA, &use_camera);
+  dcr(VX_DCR_HIP_REFERENCE_QUIRKS, &quirks_set);
+  vxrt_camera_t cam;
+  for (int i = 0; i < 3; ++i) {
+    cam.pos[i] = ka.camera_pos[i]; cam.forward[i] = ka.camera_forward[i]; cam.right[i] = ka.camera_right[i]; cam.up[i] = ka.camera_up[i];
+  }
+  cam.viewplane[0] = ka.viewplane[0]; cam.viewplane[1] = ka.viewplane[1];
+  if (use_camera > 1) { VXLOG("start: DCR 0x7F5 (camera) takes 0 or 1"); return -1; }
+  if (use_camera && (quirks_set || row_stride > 1)) { VXLOG("start: DCR 0x7F5 (camera) renders neither in reference-quirks mode nor with a tile-row stride"); return -1; }
+  if (use_camera) {
+    const float* cf = &cam.pos[0];
+    for (int i = 0; i < 14; ++i) if (!std::isfinite(cf[i])) { VXLOG("start: DCR 0x7F5 (camera): a camera field of kernel_arg_t is not finite"); return -1; }
+  }
 
   // (triEx / mat versions: the build also validates the indices shading follows, so a re-upload of those rebuilds too)
   const uint64_t key[14] = {(uint64_t)sc.tlas, r_tlas.a->version, (uint64_t)sc.blas, r_blas.a->version, (uint64_t)sc.bvh, r_bvh.a->version,
@@ -871,9 +887,9 @@ int vx_device::start(uint64_t krnl_va, uint64_t args_va) {
     }
   };
   const uint32_t n_dev = (uint32_t)helpers.size() + 1;
-  if (n_dev > 1 && row_stride <= 1 && y0 == 0 && y1 == ka.dst_height && (ka.dst_height + 7) / 8 >= n_dev) {
+  if (n_dev > 1 && !use_camera && row_stride <= 1 && y0 == 0 && y1 == ka.dst_height && (ka.dst_height + 7) / 8 >= n_dev) {
     // VORTEX_HIP_DEVICES: a whole frame is split by interleaved 8-row tile rows over the listed devices (the split bench.py's ranks use);
-    // a run the host already restricted (DCR 0x7F0-0x7F3) stays on the first device
+    // a run the host already restricted (DCR 0x7F0-0x7F3), and a camera run (DCR 0x7F5), stays on the first device
     const uint64_t ver[7] = {r_tlas.a->version, r_blas.a->version, r_bvh.a->version, r_tri.a->version, r_triex.a->version, r_mat.a->version, r_tex.a ? r_tex.a->version : 0};
     const uint64_t bytes[7] = {r_tlas.a->size - r_tlas.off, r_blas.a->size - r_blas.off, r_bvh.a->size - r_bvh.off, r_tri.a->size - r_tri.off,
                                r_triex.a->size - r_triex.off, r_mat.a->size - r_mat.off, r_tex.a ? r_tex.a->size - r_tex.off : 0};
@@ -907,7 +923,18 @@ int vx_device::start(uint64_t krnl_va, uint64_t args_va) {
     run_pending = true;
     return 0;
   }
-  if (row_stride > 1)
+  if (use_camera)   // (the samples of a whole frame in one set of launches; a row window takes them one by one: there is no camera rows batch)
+    samples([&] { return vxrt_render_camera(accel, &cam, ka.dst_width, ka.dst_height, y0, y1, &sp, (int)shadow, dstp, nullptr, nullptr, d_rays, stream); },
+            [&](const vxrt_shade_params_t* pv, uint32_t n) {
+              if (y0 == 0 && y1 == ka.dst_height) {
+                std::vector<vxrt_camera_t> cams(n, cam);
+                return vxrt_render_batch_camera(accel, ka.dst_width, ka.dst_height, n, cams.data(), pv, (int)shadow, dstp, 0, d_rays, stream);
+              }
+              int r = 0;
+              for (uint32_t k = 0; k < n && r == 0; ++k) r = vxrt_render_camera(accel, &cam, ka.dst_width, ka.dst_height, y0, y1, pv + k, (int)shadow, dstp, nullptr, nullptr, d_rays, stream);
+              return r;
+            });
+  else if (row_stride > 1)
     samples([&] { return vxrt_render_interleaved(accel, ka.dst_width, ka.dst_height, y0 / 8u, row_stride, &sp, (int)shadow, dstp, nullptr, nullptr, d_rays, stream); },
             [&](const vxrt_shade_params_t* pv, uint32_t n) { return vxrt_render_interleaved_batch(accel, ka.dst_width, ka.dst_height, y0 / 8u, row_stride, n, pv, (int)shadow, dstp, 0, d_rays, stream); });
   else

@@ -393,3 +393,81 @@ def status(stream=None):
 
 def version():
     return _lib().vxrt_version().decode()
+
+
+class Camera(C.Structure):    # vxrt_camera_t: the 14 floats of kernel_arg_t camera_pos .. viewplane
+    _fields_ = [("pos", C.c_float * 3), ("forward", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
+                ("viewplane", C.c_float * 2)]
+
+    @classmethod
+    def from_cam14(cls, cam14):
+        c = cls()
+        v = [float(x) for x in cam14]
+        if len(v) != 14:
+            raise ValueError("a camera is 14 floats (pos, forward, right, up, viewplane)")
+        c.pos[:] = v[0:3]; c.forward[:] = v[3:6]; c.right[:] = v[6:9]; c.up[:] = v[9:12]; c.viewplane[:] = v[12:14]
+        return c
+
+    def cam14(self):
+        return list(self.pos) + list(self.forward) + list(self.right) + list(self.up) + list(self.viewplane)
+
+
+def _camera(cam):
+    return cam if isinstance(cam, Camera) else Camera.from_cam14(cam)
+
+
+def look_at(eye, target, up, vfov_deg, width, height):
+    """The camera tracer.cpp:184-202 sets up, in fp32: forward = normalize(target - eye), right = normalize(cross(forward, up)),
+    up' = cross(right, forward), viewplane = (h * W / H, h) with h = 2 tan(vfov_deg * 0.5).  As in the reference, normalize multiplies
+    by 1 / sqrtf(dot), and the viewplane uses the vfov number as radians: tracer.cpp:198 applies tan() to the degree value it was
+    given (its framing distance converts degrees to radians, its viewplane does not).  Returns a Camera."""
+    import numpy as np
+    f32 = np.float32
+    e, t, u = (np.asarray(v, np.float32) for v in (eye, target, up))
+
+    def normalize(v):
+        inv = f32(1.0) / np.sqrt(f32(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]))
+        return (v * inv).astype(np.float32)
+
+    def cross(a, b):
+        return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], np.float32)
+
+    fwd = normalize((t - e).astype(np.float32))
+    right = normalize(cross(fwd, u))
+    up2 = cross(right, fwd)
+    aspect = f32(width) / f32(height)
+    vh = f32(2.0) * np.tan(f32(vfov_deg) * f32(0.5))
+    vw = f32(vh * aspect)
+    return Camera.from_cam14(list(e) + list(fwd) + list(right) + list(up2) + [vw, vh])
+
+
+def render_camera(accel, cam, width, height, y0, y1, params, dst_ptr, shadow=0, hits_ptr=None, colors_ptr=None, rays_ptr=None, stream=None):
+    """vxrt_render_camera: vxrt_render seen from pinhole camera `cam` (a Camera or 14 floats)."""
+    L = _lib()
+    L.vxrt_render_camera.restype = C.c_int
+    L.vxrt_render_camera.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams), C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.vxrt_render_camera(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), int(shadow), dst_ptr, hits_ptr,
+                               colors_ptr, rays_ptr, stream), "vxrt_render_camera")
+
+
+def render_batch_camera(accel, width, height, cams, params_list, dst_ptr, dst_frame_stride, shadow=0, rays_ptr=None, stream=None):
+    """vxrt_render_batch_camera: frame f seen from cams[f] and shaded with params_list[f], written to dst + f * dst_frame_stride pixels."""
+    if len(cams) != len(params_list):
+        raise ValueError("one camera per frame")
+    L = _lib()
+    L.vxrt_render_batch_camera.restype = C.c_int
+    L.vxrt_render_batch_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Camera), C.POINTER(ShadeParams), C.c_int,
+                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    carr = (Camera * len(cams))(*[_camera(c) for c in cams])
+    parr = (ShadeParams * len(params_list))(*params_list)
+    check(L.vxrt_render_batch_camera(accel, width, height, len(params_list), carr, parr, int(shadow), dst_ptr, dst_frame_stride, rays_ptr, stream),
+          "vxrt_render_batch_camera")
+
+
+def pinhole_rays(cam, width, height, y0, y1, rays_ptr, stream=None):
+    """vxrt_pinhole_rays: the rays of rows [y0, y1) of pinhole camera `cam`, 6 floats each, pixel (x, y) at x + (y - y0) * width."""
+    L = _lib()
+    L.vxrt_pinhole_rays.restype = C.c_int
+    L.vxrt_pinhole_rays.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    check(L.vxrt_pinhole_rays(C.byref(_camera(cam)), width, height, y0, y1, rays_ptr, stream), "vxrt_pinhole_rays")

@@ -49,7 +49,10 @@ class Tracer:
         return 0
 
     def setup(self, light_pos=DEFAULT_LIGHT_POS, light_color=DEFAULT_LIGHT_COLOR, ambient=DEFAULT_AMBIENT,
-              background=DEFAULT_BACKGROUND, row_window=None, shadow=False):
+              background=DEFAULT_BACKGROUND, row_window=None, shadow=False, camera=None):
+        """camera: None = the RTU test's fixed camera (kernel.cpp:28-39); a cam14 (pos, forward, right, up, viewplane -- e.g.
+        rtapi.look_at(...).cam14()) is written into kernel_arg_t's camera fields, as tracer.cpp:184-202 does, and DCR 0x7F5
+        makes vx_start render from it."""
         d = self.dev
         for k in ("tri", "triEx", "triIdx", "tlas", "blas", "bvh", "mat", "tex"):
             self.bufs[k].write(self.scene[k])
@@ -64,11 +67,15 @@ class Tracer:
         d.dcr_write(runtime.VX_DCR_HIP_ROW_BEGIN, y0)
         d.dcr_write(runtime.VX_DCR_HIP_ROW_END, y1)
         d.dcr_write(runtime.VX_DCR_HIP_SHADOW_RAYS, 1 if shadow else 0)
+        d.dcr_write(runtime.VX_DCR_HIP_CAMERA, 0 if camera is None else 1)
+        # (without a camera the fields hold the fixed camera's values: the RTU kernel does not read them)
+        cam = [0.0, 100.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0, 1.0] if camera is None else [float(v) for v in camera]
+        if len(cam) != 14:
+            raise ValueError("camera: 14 floats (pos, forward, right, up, viewplane)")
         self.kernel_arg = struct.pack(
             KERNEL_ARG_FMT, self.width, self.height, a["out"], a["tri"], a["triEx"], a["triIdx"], a["mat"], a["tex"],
             a["bvh2"], a["bvh"], a["blas"], a["tlas"], 0,
-            0.0, 100.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0,   # camera_* are unused by the RTU kernel
-            1.0, 1.0, self.spp, self.max_depth, *light_pos, *light_color, *ambient, *background, a["sbt"])
+            *cam, self.spp, self.max_depth, *light_pos, *light_color, *ambient, *background, a["sbt"])
         return 0
 
     def run(self):
