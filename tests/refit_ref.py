@@ -1,4 +1,4 @@
-"""numpy restatement of the refit (vxrt_accel_refit / vxrt_accel_set_transforms, csrc/rt_kernels.hip) in fp32 without fused
+"""numpy restatement of the refit (vxrt_accel_refit / vxrt_accel_set_transforms, csrc/rt_accel.hip) in fp32 without fused
 operations: the quantiser the GPU builder and the refit share (csrc/bvh_quant.h: bb_pick_exp, bb_quant_axis and the exponent bump
 loop), the MESA inverse (mat4_t::inverted), the corner transform of an instance box (TransformPosition) and a whole bottom-up refit
 of a reference-format scene's tlas / bvh buffers.  Not a test module: the refit tests import it."""

@@ -4,6 +4,7 @@ Round 2 lost a GPU to this: written as `s_n == 0` on a select, the "queue shard 
 persistent kernel's fetch section was folded by the optimiser into a form that is true for every shard past the end, the EXACT
 launch's wavefronts ran past the deferral list and the launch faulted.  The test is now an asm statement (s_cmp_lt_u32 + marker) the
 optimiser cannot look into; this check makes sure every instantiation still carries it, ahead of its first queue atomic."""
+import glob
 import os
 import re
 import subprocess
@@ -13,6 +14,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
+CSRC = os.path.join(ROOT, "vortex-raytracing_amd", "csrc")
+
+
+def _stale(out, src):
+    """the cached listing is older than the unit, or than a header or fragment the unit may include"""
+    deps = [src] + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [os.path.join(ROOT, "include", "vortex_hip.h")]
+    return not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(d) for d in deps)
 
 
 @pytest.fixture(scope="module")
@@ -20,8 +28,8 @@ def listing():
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
     out = os.path.join(tempfile.gettempdir(), "vxrt_guard_listing.s")
-    src = os.path.join(ROOT, "vortex-raytracing_amd", "csrc", "rt_kernels.hip")
-    if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
+    src = os.path.join(CSRC, "rt_kernels.hip")
+    if _stale(out, src):
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17", "-S", "--cuda-device-only",
                         "-o", out, src], check=True, stderr=subprocess.DEVNULL)
     return open(out).read().split("\n")
@@ -63,8 +71,8 @@ def test_the_software_twin_kernel_carries_the_same_guard():
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
     out = os.path.join(tempfile.gettempdir(), "vxrc_guard_listing.s")
-    src = os.path.join(ROOT, "vortex-raytracing_amd", "csrc", "rc_kernels.hip")
-    if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
+    src = os.path.join(CSRC, "rc_kernels.hip")
+    if _stale(out, src):
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17", "-S", "--cuda-device-only",
                         "-o", out, src], check=True, stderr=subprocess.DEVNULL)
     lines = open(out).read().split("\n")

@@ -30,7 +30,13 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-ffp-contract=off", "-fno-slp-vec
 HIP_FLAGS += os.environ.get("VXRT_EXTRA_HIPFLAGS", "").split()   # experiments only (e.g. -DLDS_STACK=8)
 CXX_FLAGS = ["-O2", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall"]
 
-PRODUCT_HIP_SOURCES = ("rt_kernels.hip", "rc_kernels.hip", "vx_backend.hip", "bvh_builder.hip")
+PRODUCT_HIP_SOURCES = ("rt_kernels.hip", "rt_accel.hip", "rc_kernels.hip", "vx_backend.hip", "bvh_builder.hip")
+
+
+def hip_library_deps():
+    """Every file a rebuild of libvortex-hip.so depends on: the product sources, every header and fragment in csrc/, the public header."""
+    incs = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
+    return [os.path.join(CSRC, f) for f in PRODUCT_HIP_SOURCES + tuple(incs)] + [os.path.join(HERE, "..", "include", "vortex_hip.h")]
 
 # fixed VMAs of the four images of the RTU test (tests/regression/raytracing/Makefile:104-107)
 SELECTORS = {
@@ -77,8 +83,7 @@ def build_test_variant(force=False):
     os.makedirs(d, exist_ok=True)
     so = os.path.join(d, "libvortex-hip.so")
     src = [os.path.join(CSRC, f) for f in PRODUCT_HIP_SOURCES]
-    hdrs = [os.path.join(CSRC, "rt_types.h"), os.path.join(CSRC, "bvh_quant.h"), os.path.join(CSRC, "pinhole.h"), os.path.join(HERE, "..", "include", "vortex_hip.h")]
-    if force or _newer(so, src + hdrs):
+    if force or _newer(so, hip_library_deps()):
         _run([HIPCC] + HIP_FLAGS + TEST_VARIANT_FLAGS + ["-shared", "-o", so] + src)
     for f in ("libvortex.so", "libvxrt_scene.so"):
         shutil.copy2(os.path.join(LIB, f), os.path.join(d, f))
@@ -87,13 +92,13 @@ def build_test_variant(force=False):
 
 def build(force=False, verbose=True):
     os.makedirs(LIB, exist_ok=True)
-    hdrs = [os.path.join(CSRC, "rt_types.h"), os.path.join(CSRC, "bvh_quant.h"), os.path.join(CSRC, "pinhole.h"), os.path.join(HERE, "..", "include", "vortex_hip.h")]
+    hdrs = hip_library_deps()   # (the g++ targets too: rebuilding them once too often is harmless)
     if not os.path.exists(HIPCC):
         raise RuntimeError("hipcc not found at %s: the HIP path cannot be built" % HIPCC)
 
     hip_so = os.path.join(LIB, "libvortex-hip.so")
     hip_src = [os.path.join(CSRC, f) for f in PRODUCT_HIP_SOURCES]
-    if force or _newer(hip_so, hip_src + hdrs):
+    if force or _newer(hip_so, hdrs):
         _run([HIPCC] + HIP_FLAGS + ["-shared", "-o", hip_so] + hip_src)
 
     # measurement only (VALU calibration loops, clock probe): its own library, not part of the product

@@ -1,0 +1,129 @@
+// Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
+// level-2 entry points) and rt_accel.hip (acceleration-layout build, refit) share.  The constants of the compact layout are in
+// rt_types.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+#include "rt_types.h"
+#include "../../include/vortex_hip.h"
+
+#define STATUS_STACK_OVERFLOW 1u
+#define STATUS_ITER_LIMIT 2u
+#define STATUS_BAD_SCENE 4u
+#define STATUS_FMA_DECODE_DIFFERS 8u   // build-time only: selects the ldexp decode for the scene
+
+// ---------------------------------------------------------------------------------------------
+// Device-side acceleration layout, derived once per scene from the reference-format buffers by the
+// accel_* kernels of rt_accel.hip (the reference bytes stay the source of truth).
+//
+// Work descriptor, 32 bit: [31:30] kind, [29:0] payload
+//     kind 0  TLAS internal node   payload = compact node index (TLAS nodes come first)
+//     kind 1  BLAS internal node   payload = compact node index (n_tlas + index in the bvh buffer)
+//     kind 2  BLAS leaf            payload = count<<26 | firstTriangle   (count 1..15; count 0:
+//                                  payload = index of the reference leaf node, range read from it)
+//     kind 3  instance (TLAS leaf) payload = blasIdx
+//     0xFFFFFFFF = empty child slot, 0xFFFFFFFE = ray finished, 0xFFFFFFFD = lane idle
+//
+// Compact node, 64 B = half a cache line, one per INTERNAL node, TLAS and BLAS nodes in one index space:
+//     q0 = origin.xyz, 2^ex as float
+//     q1 = plane words lo.x, lo.y, lo.z, hi.x     one byte per child: byte k of word j = plane j of child k
+//     q2 = plane words hi.y, hi.z, desc0, desc1   desc k = complete work descriptor of child k
+//     q3 = desc2, desc3, 2^ey, 2^ez
+//   -> a node visit is four 16-byte loads per lane (the vector-memory return path, not HBM, is what
+//      saturates first on MI355X for wider nodes: profiles/r01_b_*), no index arithmetic on children,
+//      a leaf or instance never costs a node fetch of its own, and stack entries are 2 dwords.
+// Wide triangle, 48 B: v0, edge1 = v1 - v0, edge2 = v2 - v0 (the subtractions of
+//     rt_traversal.cpp:272-278 done once), three aligned 16-byte loads.
+// ---------------------------------------------------------------------------------------------
+struct SceneDev {
+  const uint4* nodes_c;      // compact nodes: the TLAS nodes, then the BLAS nodes (one index space, no per-lane base select)
+  const uint32_t* ref_tlas;  // reference TLAS nodes (13 dwords each): exponents for the ldexp decode
+  uint32_t n_tlas;           // compact index of BLAS node j = n_tlas + j
+  const float4* tri_w;       // wide triangles
+  const uint32_t* blas_root; // per instance record: descriptor of its BLAS root
+  uint32_t tlas_root;        // descriptor of the TLAS root
+  uint32_t exact_decode;     // 1: decode child boxes with ldexp instead of the exact-product fma
+  const uint32_t* ref_bvh;   // reference bvh nodes (13 dwords each): ranges of leaves > 15 triangles
+  const uint32_t* blas;      // reference blas_node_t records (40 dwords each)
+  const rt_triex_t* triEx;
+  const rt_material_t* mat;
+  const uint8_t* tex;
+  // top of the tree for LDS staging (accel_top_kernel): the first n_top internal nodes in breadth-first order from the
+  // TLAS root, as four planes of n_top uint4 (q0[], q1[], q2[], q3[]: conflict-free ds_read_b128 for neighbouring slots);
+  // child descriptors inside the image and the *_top roots address staged nodes by slot (DESC_TOP_FLAG)
+  const uint4* top_img;
+  uint32_t n_top;
+  uint32_t tlas_root_top;
+  const uint32_t* blas_root_top;
+  uint32_t ident_root;       // 1: the TLAS root is an instance leaf whose inverse transform is the identity (see start_ray)
+};
+
+struct HitRec { float dist, bx, by, bz; uint32_t blasIdx, triIdx; };
+
+struct ShadeParams { float amb[3], lcol[3], lpos[3], bg[3]; uint32_t max_depth; };
+
+// Mutable per-frame state.  An accel owns up to MAX_FRAMES_IN_FLIGHT of these and hands them out round
+// robin, so that renders issued on different streams overlap on the GPU (the tail of one persistent
+// launch, where most wavefronts have drained, is filled by the head of the next frame's launch); a
+// context is handed out again only behind the event of its previous render.
+#define MAX_FRAMES_IN_FLIGHT 8
+struct FrameCtx {
+  void* hitbuf = nullptr;      // W*H hit records between the traversal and the shading pass
+  uint64_t hitbuf_pixels = 0;
+  uint32_t* defer = nullptr;   // job list of the EXACT launch
+  uint64_t defer_cap = 0;
+  uint32_t* ctl = nullptr;     // control block (CTL_DWORDS), zero between frames
+  ShadeParams* pbatch = nullptr;   // per-frame shading parameters of a batch launch (VXRT_MAX_BATCH entries)
+  float* cam = nullptr; uint64_t cam_floats = 0;   // camera block of the context's camera frames (see CAM_HDR)
+  bool ctl_dirty = false;      // a call failed after touching it: clear before the next use
+  // mirror-bounce levels (allocated on first use; level 0 only holds `term`, one entry per pixel)
+  struct Level {
+    float* rays = nullptr; HitRec* hits = nullptr; uint32_t* parent = nullptr; float4* term = nullptr; float* col = nullptr;
+    float* srays = nullptr; float* stmax = nullptr; HitRec* shits = nullptr;
+    uint64_t cap = 0; uint32_t n = 0;
+  };
+  std::vector<Level> lv;
+  uint32_t* bcount = nullptr;  // device: rays appended to the level being built
+  // tile cost of the last frame and the order derived from it (render jobs, see lpt_order_kernel)
+  // one slot per batch size (slot 1 = single frames): a frame loop that alternates batch sizes keeps what it learned for each
+  struct Lpt { uint32_t* cost = nullptr; uint32_t* order = nullptr; uint32_t cap = 0; uint32_t key[6] = {0, 0, 0, 0, 0, 0}; bool valid = false; };
+  Lpt lpt[VXRT_MAX_BATCH + 1];
+  // ambient-occlusion pass (allocated on first use), one entry per pixel of the window
+  float4* ao_geo = nullptr; float4* ao_nrm = nullptr; float4* ao_col = nullptr; uint32_t* ao_cnt = nullptr;
+  uint32_t* ao_list = nullptr; uint32_t* ao_hdr = nullptr;   // pixels with a hit; [0] their number, [1] rays of the current batch
+  float* ao_rays = nullptr; float* ao_tmax = nullptr; HitRec* ao_hits = nullptr; uint64_t ao_cap = 0, ao_ray_cap = 0;
+  uint32_t* bin_hist = nullptr; uint32_t* bin_keys = nullptr; uint32_t* bin_order = nullptr; uint64_t bin_cap = 0, bin_ray_cap = 0;   // secondary-ray binning
+  void* pool_spill = nullptr; uint64_t pool_spill_bytes = 0;   // ray-pool trace kernel: the part of the slots' stacks that does not fit LDS
+  hipStream_t side = nullptr;
+  hipEvent_t ev_in = nullptr, ev_side = nullptr, ev_done = nullptr;
+  bool busy = false, inited = false, done_recorded = false;
+  hipStream_t last_stream = nullptr;
+};
+
+struct vxrt_accel {
+  SceneDev dev{};
+  vxrt_scene_t ref{};
+  void* nodes_c = nullptr; void* tri_w = nullptr; void* blas_root = nullptr;
+  void* top_img = nullptr; uint32_t* top_roots = nullptr;   // LDS-staged top of the tree: image; [0] n, [1] TLAS root, [2..] BLAS roots
+  FrameCtx ctx[MAX_FRAMES_IN_FLIGHT];
+  uint32_t n_ctx = 1, next_ctx = 0;
+  bool stream_seen = false, multi_stream = false; hipStream_t first_stream = nullptr;   // (see release_ctx)
+  float* uvtab = nullptr;      // camera tables: u[W] then v[H]
+  uint32_t uv_w = 0, uv_h = 0;
+  // camera pixels whose primary ray has a zero direction component (u == 0 or v == 0): listed on the
+  // host per (W, H, y0, y1) and traced by an EXACT launch on a side stream, concurrently with the main one
+  uint32_t* apriori = nullptr; // [0] count, [1..] job ids
+  uint32_t* batch_order[VXRT_MAX_BATCH + 1] = {}; uint32_t bo_tiles = 0;   // band-major tile order of a batch of k frames of bo_tiles tiles each, per k
+  uint32_t ap_count = 0, ap_key[6] = {0, 0, 0, 0, 0, 0};
+  uint64_t ap_cap = 0;
+  float max_reflectivity = 0.0f;   // over the instance records: > 0 enables the mirror-bounce path
+  unsigned long long* trace_wave_log = nullptr;   // diagnostic (vxrt_debug_trace_wave_log): per-wavefront log of the counting build's ray-buffer launches
+  unsigned long long* end_log = nullptr;   // diagnostic (vxrt_debug_end_log): where the main launches leave their wavefronts' end times
+  uint32_t levels = 0;             // internal levels on the longest root-to-leaf path (TLAS + BLAS), counted up to RT_SHALLOW_LEVELS + 1
+  bool shallow = false;            // levels <= RT_SHALLOW_LEVELS: the timed launches take the SHALLOW instantiations
+  int device = 0;
+  struct RefitPlan* refit = nullptr;   // vxrt_accel_refit: built at the first refit
+  uint32_t blas_status = 0;        // STATUS_FMA_DECODE_DIFFERS of the BLAS region as its last re-layout found it (build or GEOMETRY refit)
+  bool stale = false;              // a refit failed after it had started writing: every render / trace refuses until a refit succeeds
+};

@@ -15,82 +15,13 @@
 // The trail/short-stack/restart machinery of the simulator is replaced by one pass over a full
 // per-lane stack whose entries carry m = max(entry distance along the path); DESIGN.md s3 proves
 // this returns the same hit (index included) as the reference's accept-and-re-descend loop.
+// What is not timed lives elsewhere: the acceleration-layout build and the refit in rt_accel.hip, the two ray-compaction
+// experiments (VXRT_POOL) in rt_trace_experiments.inc; SceneDev, HitRec, ShadeParams, FrameCtx and vxrt_accel in rt_internal.h,
+// the constants of the compact layout in rt_types.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "rt_types.h"
-#include "bvh_quant.h"
+#include "rt_internal.h"
 #include "pinhole.h"
-#include "../../include/vortex_hip.h"
-
-#define STATUS_STACK_OVERFLOW 1u
-#define STATUS_ITER_LIMIT 2u
-#define STATUS_BAD_SCENE 4u
-#define STATUS_FMA_DECODE_DIFFERS 8u   // build-time only: selects the ldexp decode for the scene
-
-// ---------------------------------------------------------------------------------------------
-// Device-side acceleration layout, derived once per scene from the reference-format buffers by the
-// accel_* kernels below (the reference bytes stay the source of truth).
-//
-// Work descriptor, 32 bit: [31:30] kind, [29:0] payload
-//     kind 0  TLAS internal node   payload = compact node index (TLAS nodes come first)
-//     kind 1  BLAS internal node   payload = compact node index (n_tlas + index in the bvh buffer)
-//     kind 2  BLAS leaf            payload = count<<26 | firstTriangle   (count 1..15; count 0:
-//                                  payload = index of the reference leaf node, range read from it)
-//     kind 3  instance (TLAS leaf) payload = blasIdx
-//     0xFFFFFFFF = empty child slot, 0xFFFFFFFE = ray finished, 0xFFFFFFFD = lane idle
-//
-// Compact node, 64 B = half a cache line, one per INTERNAL node, TLAS and BLAS nodes in one index space:
-//     q0 = origin.xyz, 2^ex as float
-//     q1 = plane words lo.x, lo.y, lo.z, hi.x     one byte per child: byte k of word j = plane j of child k
-//     q2 = plane words hi.y, hi.z, desc0, desc1   desc k = complete work descriptor of child k
-//     q3 = desc2, desc3, 2^ey, 2^ez
-//   -> a node visit is four 16-byte loads per lane (the vector-memory return path, not HBM, is what
-//      saturates first on MI355X for wider nodes: profiles/r01_b_*), no index arithmetic on children,
-//      a leaf or instance never costs a node fetch of its own, and stack entries are 2 dwords.
-// Wide triangle, 48 B: v0, edge1 = v1 - v0, edge2 = v2 - v0 (the subtractions of
-//     rt_traversal.cpp:272-278 done once), three aligned 16-byte loads.
-// ---------------------------------------------------------------------------------------------
-#define DK_TLAS 0u
-#define DK_BLAS 1u
-#define DK_LEAF 2u
-#define DK_INST 3u
-#define DESC(kind, payload) (((kind) << 30) | (payload))
-#define DESC_DONE 0xFFFFFFFEu   // traversal of the lane's ray has ended
-#define DESC_IDLE 0xFFFFFFFDu   // lane has no ray
-#define DESC_NONE 0xFFFFFFFFu   // compact node: empty child slot
-#define PAYLOAD_MASK 0x3FFFFFFFu
-#define DESC_TOP_FLAG 0x20000000u   // node descriptor: payload = slot of the LDS-staged top-of-tree image (kernels with USE_TOP only)
-#define DESC_TOP_SLOT 0x0000FFFFu
-#define LEAF_FIRST_BITS 26
-#define LEAF_FIRST_MASK 0x03FFFFFFu
-#define LEAF_MAX_INLINE 15u
-#define CNODE_VEC4 4
-#define WTRI_FLOATS 12
-
-struct SceneDev {
-  const uint4* nodes_c;      // compact nodes: the TLAS nodes, then the BLAS nodes (one index space, no per-lane base select)
-  const uint32_t* ref_tlas;  // reference TLAS nodes (13 dwords each): exponents for the ldexp decode
-  uint32_t n_tlas;           // compact index of BLAS node j = n_tlas + j
-  const float4* tri_w;       // wide triangles
-  const uint32_t* blas_root; // per instance record: descriptor of its BLAS root
-  uint32_t tlas_root;        // descriptor of the TLAS root
-  uint32_t exact_decode;     // 1: decode child boxes with ldexp instead of the exact-product fma
-  const uint32_t* ref_bvh;   // reference bvh nodes (13 dwords each): ranges of leaves > 15 triangles
-  const uint32_t* blas;      // reference blas_node_t records (40 dwords each)
-  const rt_triex_t* triEx;
-  const rt_material_t* mat;
-  const uint8_t* tex;
-  // top of the tree for LDS staging (accel_top_kernel): the first n_top internal nodes in breadth-first order from the
-  // TLAS root, as four planes of n_top uint4 (q0[], q1[], q2[], q3[]: conflict-free ds_read_b128 for neighbouring slots);
-  // child descriptors inside the image and the *_top roots address staged nodes by slot (DESC_TOP_FLAG)
-  const uint4* top_img;
-  uint32_t n_top;
-  uint32_t tlas_root_top;
-  const uint32_t* blas_root_top;
-  uint32_t ident_root;       // 1: the TLAS root is an instance leaf whose inverse transform is the identity (see start_ray)
-};
-
-struct HitRec { float dist, bx, by, bz; uint32_t blasIdx, triIdx; };
 
 // libstdc++ std::min / std::max (rt_traversal.cpp:327-337 use them; NaN behaviour is part of parity)
 __device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
@@ -247,8 +178,6 @@ struct Fetches { unsigned node = 0, inst = 0, tri = 0; };
 // ---------------------------------------------------------------------------------------------
 // shading (closest.cpp:57-127 / miss.cpp:9-14)
 // ---------------------------------------------------------------------------------------------
-struct ShadeParams { float amb[3], lcol[3], lpos[3], bg[3]; uint32_t max_depth; };
-
 __device__ __forceinline__ uint32_t f2u_x86(float f) { return (uint32_t)(long long)f; } // rtx_shading.h:7-8 as x86-64 g++ lowers it
 
 // Occlusion ray of the shadow extension (no reference counterpart): from the hit point toward the
@@ -557,14 +486,6 @@ __device__ __forceinline__ void ao_sample_ray(uint32_t x, uint32_t y, uint32_t W
 #define RT_WG_WAVES 4       // wavefronts per workgroup of the persistent kernels (the staged top of the tree is shared by them)
 #endif
 #define RT_WG_THREADS (64 * RT_WG_WAVES)
-#ifndef RT_SHALLOW_LEVELS
-#define RT_SHALLOW_LEVELS 16  // internal levels (TLAS + BLAS) up to which a scene takes the SHALLOW instantiations: 48 stack entries instead of 96 + the LDS levels
-#endif
-#ifndef RT_TOP_NODES
-#define RT_TOP_NODES 0      // internal nodes of the top of the tree staged in LDS per workgroup (64 B each); 0 = off
-#endif
-#define RT_TOP_MAX 1024
-static_assert(RT_TOP_NODES <= RT_TOP_MAX, "top-of-tree image");
 
 // JOB_TRACE_UNORDERED: a ray buffer of any-hit rays whose caller only wants "blocked or not" (ambient occlusion, the occlusion rays of a
 // bounce level): JOB_TRACE's kernel with the children visited in slot order, as the frame's occlusion rays are (no sorting by distance,
@@ -675,11 +596,6 @@ __device__ __forceinline__ bool ray_in_fast_domain(float ox, float oy, float oz,
 // max of two values neither of which is a NaN: one v_max_f32 (fmaxf adds a canonicalising v_max_f32 x, x for a signalling NaN the
 // compiler cannot rule out)
 __device__ __forceinline__ float vmax_nonan(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-__device__ __forceinline__ bool is_node_desc(uint32_t d) { return d < 0x80000000u; }
-__device__ __forceinline__ bool is_leaf_desc(uint32_t d) { return (d >> 30) == DK_LEAF; }
-__device__ __forceinline__ bool is_inst_desc(uint32_t d) { return d >= 0xC0000000u && d < DESC_IDLE; }
-__device__ __forceinline__ bool is_work_desc(uint32_t d) { return d < DESC_IDLE; }
 
 // per-lane flag bits
 #define F_FOUND 1u
@@ -1427,578 +1343,6 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Ray-pool trace kernel (ray buffers only; round 5, VERDICT item 2: incoherent rays compacted through LDS).
-//
-// The persistent kernel above gives every lane ONE ray and runs, per loop iteration, the node body for the lanes that hold a node and the
-// leaf body for the lanes that hold a leaf: with incoherent rays half the lanes of every instruction are masked (lane utilisation 0.50 on the
-// 16 Mi random rays: profiles/r04_zz_pmc_summary_random_rays.txt) -- rays of a wavefront are in different phases, and a refilled lane does not
-// change that.  Here a wavefront owns a POOL of RT_POOL_SLOTS rays (more than it has lanes) whose whole state lives in LDS -- active ray,
-// hit distance, path maximum, current work item, stack -- and every iteration it picks up to 64 slots that are in the SAME phase (a
-// ballot + prefix count over the slots' work items), loads their state, runs that one body at full width and stores the state back.  Lanes
-// are workers, not owners: nothing of a ray lives in registers between two iterations.  Per-ray arithmetic is the persistent kernel's, step
-// by step (same eval_children / order_children / ray_tri, same push order, same `m < hit.dist` rule), so the hit records are the same bits;
-// the schedule is what differs.  One wavefront per workgroup: no barrier couples wavefronts.
-//   * the stack's first RT_POOL_LSTK entries of a slot are in LDS, deeper ones in a global spill area (a lane's scratch cannot follow a ray
-//     from lane to lane); there is no register top;
-//   * an accepted hit is written to the ray's record at once (closest hit: the last accept is the record; records of misses are written
-//     when the ray ends), so barycentrics and indices need no LDS;
-//   * rays outside the fast domain go to the deferral list and the EXACT launch, as in the persistent kernel.
-// ---------------------------------------------------------------------------------------------
-#ifndef RT_POOL_SLOTS
-#define RT_POOL_SLOTS 96        // rays a wavefront holds (64 lanes work on them)
-#endif
-#ifndef RT_POOL_LSTK
-#define RT_POOL_LSTK 5          // stack entries of a slot kept in LDS
-#endif
-#ifndef RT_POOL_WAVES
-#define RT_POOL_WAVES 4         // wavefronts per SIMD the kernel is compiled for (LDS: (15 + 2 * RT_POOL_LSTK) * 4 * RT_POOL_SLOTS bytes per wavefront)
-#endif
-#ifndef RT_POOL_LEAF_MIN
-#define RT_POOL_LEAF_MIN 48     // the leaf body runs once this many slots hold a leaf (or nothing else can run)
-#endif
-#ifndef RT_POOL_NODE_KEEP
-#define RT_POOL_NODE_KEEP 44    // a node pass goes on with the same slots while at least this many of its lanes are still at a node (65: one step per pass)
-#endif
-#ifndef RT_POOL_REFILL_MIN
-#define RT_POOL_REFILL_MIN 16   // finished / empty slots are serviced (records of misses written, new rays started) once there are this many
-#endif
-enum { PF_OX = 0, PF_OY, PF_OZ, PF_IX, PF_IY, PF_IZ, PF_HITD, PF_PATHM, PF_CUR, PF_JOB, PF_FLAGS, PF_DX, PF_DY, PF_DZ, PF_BLAS, PF_STK };
-#define PF_SP_SHIFT 8           // PF_FLAGS: per-ray flag bits in [7:0], stack entries in [15:8]
-
-template <bool LDEXP, bool SHALLOW>
-__global__ __launch_bounds__(64, RT_POOL_WAVES) void rt_pool_trace_kernel(SceneDev sc, PersistArgs A, uint2* __restrict__ spill) {
-  constexpr int S = RT_POOL_SLOTS, L = RT_POOL_LSTK;
-  static_assert(S >= 64 && S <= 128, "a lane classifies at most two slots");
-  constexpr int CAP = SHALLOW ? 3 * RT_SHALLOW_LEVELS : 3 * RT_MAX_LEVELS + L;   // entries a ray's stack may hold
-  constexpr int OVF = CAP - L;
-  __shared__ uint32_t pool[PF_STK + 2 * L][S];
-  __shared__ uint32_t list[64];
-  const uint32_t lane = threadIdx.x;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  uint2* const my_spill = spill + (size_t)blockIdx.x * S * OVF;
-  const uint32_t n_jobs = A.total_dev ? min(*A.total_dev, A.total) : A.total;
-  const uint32_t per_shard = A.total_dev ? (((n_jobs + QUEUE_SHARDS - 1) / QUEUE_SHARDS + 63u) & ~63u) : A.per_shard;
-  const uint32_t root_desc = sc.tlas_root;
-  const uint32_t xcc_id = RT_XCC_HOME ? (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) : blockIdx.x;
-  const uint32_t shard = (xcc_id + A.shard_rot) % QUEUE_SHARDS;
-  uint32_t tries = 0, loc_next = 0, loc_end = 0;
-  bool queue_empty = false;
-  unsigned nrays = 0;
-  for (uint32_t s = lane; s < (uint32_t)S; s += 64u) { pool[PF_CUR][s] = DESC_IDLE; pool[PF_FLAGS][s] = 0u; }
-  __syncthreads();
-
-  // ---- per-slot state of the lane's current slot, in registers for the length of one pass ----
-  uint32_t slot = 0, cur = DESC_IDLE, job = 0, flags = 0, sp = 0;
-  float arx = 0, ary = 0, arz = 0, aix = 0, aiy = 0, aiz = 0, hitd = 0, path_m = 0;
-  auto push = [&](uint32_t d, float m) {
-    if (sp < (uint32_t)L) { pool[PF_STK + 2 * sp][slot] = d; pool[PF_STK + 2 * sp + 1][slot] = __float_as_uint(m); }
-    else my_spill[(size_t)slot * OVF + (sp - L)] = make_uint2(d, __float_as_uint(m));
-    ++sp;
-  };
-  auto pop_next = [&]() {      // next pending work item with m < hit.dist, or the end of the ray
-    cur = DESC_DONE;
-    while (sp > 0u) {
-      --sp;
-      uint32_t d; float m;
-      if (sp < (uint32_t)L) { d = pool[PF_STK + 2 * sp][slot]; m = __uint_as_float(pool[PF_STK + 2 * sp + 1][slot]); }
-      else { const uint2 e = my_spill[(size_t)slot * OVF + (sp - L)]; d = e.x; m = __uint_as_float(e.y); }
-      if (m < hitd) { cur = d; path_m = m; break; }
-    }
-  };
-  auto defer = [&]() {
-    const uint32_t q = atomicAdd(A.defer_count, 1u);
-    if (q < A.defer_cap) A.defer_list[q] = job;
-    cur = DESC_IDLE;
-  };
-  auto world_ray = [&](float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
-    const float* rp = A.rays + (size_t)job * 6;
-    ox = rp[0]; oy = rp[1]; oz = rp[2]; dx = rp[3]; dy = rp[4]; dz = rp[5];
-  };
-  // TLAS leaf (rt_traversal.cpp:109-121): the instance record, the ray in object space
-  auto enter_instance = [&](uint32_t blasIdx, float ox, float oy, float oz, float dx, float dy, float dz, bool counted) {
-    const uint32_t* bp = sc.blas + (size_t)blasIdx * (RT_BLAS_STRIDE / 4);
-    uint32_t bw[13];
-#pragma unroll
-    for (int i = 0; i < 13; ++i) bw[i] = bp[i];
-    const float m00 = __uint_as_float(bw[1]), m01 = __uint_as_float(bw[2]), m02 = __uint_as_float(bw[3]), m03 = __uint_as_float(bw[4]);
-    const float m10 = __uint_as_float(bw[5]), m11 = __uint_as_float(bw[6]), m12 = __uint_as_float(bw[7]), m13 = __uint_as_float(bw[8]);
-    const float m20 = __uint_as_float(bw[9]), m21 = __uint_as_float(bw[10]), m22 = __uint_as_float(bw[11]), m23 = __uint_as_float(bw[12]);
-    arx = m00 * ox + m01 * oy + m02 * oz + m03;   // :231-261
-    ary = m10 * ox + m11 * oy + m12 * oz + m13;
-    arz = m20 * ox + m21 * oy + m22 * oz + m23;
-    const float cdx = m00 * dx + m01 * dy + m02 * dz;
-    const float cdy = m10 * dx + m11 * dy + m12 * dz;
-    const float cdz = m20 * dx + m21 * dy + m22 * dz;
-    aix = 1.0f / cdx; aiy = 1.0f / cdy; aiz = 1.0f / cdz;
-    if (!ray_in_fast_domain(arx, ary, arz, aix, aiy, aiz)) { if (counted) nrays--; defer(); return; }   // (the EXACT launch counts the ray when it starts it again)
-    flags &= ~F_WORLD;
-    pool[PF_DX][slot] = __float_as_uint(cdx); pool[PF_DY][slot] = __float_as_uint(cdy); pool[PF_DZ][slot] = __float_as_uint(cdz);
-    pool[PF_BLAS][slot] = blasIdx;
-    cur = sc.blas_root[blasIdx];
-  };
-  auto load_state = [&]() {
-    cur = pool[PF_CUR][slot]; job = pool[PF_JOB][slot];
-    const uint32_t f = pool[PF_FLAGS][slot]; flags = f & 0xFFu; sp = f >> PF_SP_SHIFT;
-    arx = __uint_as_float(pool[PF_OX][slot]); ary = __uint_as_float(pool[PF_OY][slot]); arz = __uint_as_float(pool[PF_OZ][slot]);
-    aix = __uint_as_float(pool[PF_IX][slot]); aiy = __uint_as_float(pool[PF_IY][slot]); aiz = __uint_as_float(pool[PF_IZ][slot]);
-    hitd = __uint_as_float(pool[PF_HITD][slot]); path_m = __uint_as_float(pool[PF_PATHM][slot]);
-  };
-  auto store_ray = [&]() {
-    pool[PF_OX][slot] = __float_as_uint(arx); pool[PF_OY][slot] = __float_as_uint(ary); pool[PF_OZ][slot] = __float_as_uint(arz);
-    pool[PF_IX][slot] = __float_as_uint(aix); pool[PF_IY][slot] = __float_as_uint(aiy); pool[PF_IZ][slot] = __float_as_uint(aiz);
-  };
-  auto store_walk = [&]() {
-    pool[PF_CUR][slot] = cur; pool[PF_FLAGS][slot] = flags | (sp << PF_SP_SHIFT);
-    pool[PF_HITD][slot] = __float_as_uint(hitd); pool[PF_PATHM][slot] = __float_as_uint(path_m);
-  };
-
-  for (;;) {
-    // ---- what phase is every slot in?  (a lane looks at slots lane and lane + 64) ----
-    const uint32_t c0 = pool[PF_CUR][lane];
-    const uint32_t c1 = lane + 64u < (uint32_t)S ? pool[PF_CUR][lane + 64u] : DESC_IDLE;
-    enum { P_NODE, P_LEAF, P_INST, P_SERVICE };
-    int pass = -1;
-    unsigned long long m0, m1;
-    // (the masks of the phases are formed only as far as the decision needs them: a full node pass, the common case, costs two compares)
-    const unsigned long long node0 = __ballot(is_node_desc(c0)), node1 = __ballot(is_node_desc(c1));
-    const uint32_t n_node = (uint32_t)(__popcll(node0) + __popcll(node1));
-    if (n_node >= 64u) { pass = P_NODE; m0 = node0; m1 = node1; }
-    else {
-      const unsigned long long leaf0 = __ballot(is_leaf_desc(c0)), leaf1 = __ballot(is_leaf_desc(c1));
-      const uint32_t n_leaf = (uint32_t)(__popcll(leaf0) + __popcll(leaf1));
-      if (n_leaf >= (uint32_t)RT_POOL_LEAF_MIN) { pass = P_LEAF; m0 = leaf0; m1 = leaf1; }
-      else {
-        const bool more_jobs = !(queue_empty && loc_next == loc_end);
-        const unsigned long long slots1 = S < 128 ? ((1ull << (S - 64)) - 1ull) : ~0ull;
-        const unsigned long long srv0 = __ballot(c0 == DESC_DONE || (more_jobs && c0 == DESC_IDLE));
-        const unsigned long long srv1 = __ballot(c1 == DESC_DONE || (more_jobs && c1 == DESC_IDLE)) & slots1;
-        const uint32_t n_service = (uint32_t)(__popcll(srv0) + __popcll(srv1));
-        const unsigned long long inst0 = __ballot(is_inst_desc(c0)), inst1 = __ballot(is_inst_desc(c1));
-        if (n_service >= (uint32_t)RT_POOL_REFILL_MIN) { pass = P_SERVICE; m0 = srv0; m1 = srv1; }
-        else if (inst0 | inst1) { pass = P_INST; m0 = inst0; m1 = inst1; }
-        else if (n_node) { pass = P_NODE; m0 = node0; m1 = node1; }
-        else if (n_leaf) { pass = P_LEAF; m0 = leaf0; m1 = leaf1; }
-        else if (n_service) { pass = P_SERVICE; m0 = srv0; m1 = srv1; }
-        else break;                                    // every slot empty, nothing left in the queue
-      }
-    }
-    const uint32_t k0 = (uint32_t)__popcll(m0), n_sel = min(64u, k0 + (uint32_t)__popcll(m1));
-    // (one wavefront per workgroup: its LDS instructions execute in order, so the list written here is what the reads below see -- the
-    // compiler must only keep them in program order; no s_barrier and, above all, no wait for the global loads and stores in flight)
-    __builtin_amdgcn_wave_barrier();
-    if ((m0 >> lane) & 1ull) list[(uint32_t)__popcll(m0 & lt_mask)] = lane;
-    if ((m1 >> lane) & 1ull) { const uint32_t r = k0 + (uint32_t)__popcll(m1 & lt_mask); if (r < 64u) list[r] = lane + 64u; }
-    __builtin_amdgcn_wave_barrier();
-    const bool act = lane < n_sel;
-    slot = act ? list[lane] : 0u;
-
-    if (pass == P_NODE) {
-      if (act) load_state();
-      // a lane keeps its slot while enough of the pass's lanes are still at a node: the pool's cost -- finding the slots, loading and storing
-      // their state -- is paid once for several steps, at the price of the lanes that have meanwhile reached a leaf or the end waiting masked
-      for (;;) {
-      if (act && is_node_desc(cur)) {
-        const bool top = (cur >> 30) == DK_TLAS;
-        if (top && !(flags & F_WORLD)) {               // back at TLAS level after an instance (multi-instance scenes only)
-          float dx, dy, dz;
-          world_ray(arx, ary, arz, dx, dy, dz);
-          aix = 1.0f / dx; aiy = 1.0f / dy; aiz = 1.0f / dz;
-          flags |= F_WORLD;
-          store_ray();
-        }
-        const uint32_t ni = cur & PAYLOAD_MASK;
-        const uint4* np = sc.nodes_c + (size_t)ni * CNODE_VEC4;
-        const uint4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-        const uint32_t* ref_node = nullptr;
-        if (LDEXP) ref_node = top ? sc.ref_tlas + (size_t)ni * RT_NODE_DWORDS : sc.ref_bvh + (size_t)(ni - sc.n_tlas) * RT_NODE_DWORDS;
-        Cand c[4];
-        eval_children<false, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
-        order_children(c);
-        if (c[0].d < __builtin_inff()) {
-          bool more = true;
-          if (sp + 3u > (uint32_t)CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-          if (more && c[3].d < __builtin_inff()) push(c[3].desc, vmax_nonan(path_m, c[3].d));   // far first (:98-103)
-          if (more && c[2].d < __builtin_inff()) push(c[2].desc, vmax_nonan(path_m, c[2].d));
-          if (more && c[1].d < __builtin_inff()) push(c[1].desc, vmax_nonan(path_m, c[1].d));
-          cur = c[0].desc;
-          path_m = vmax_nonan(path_m, c[0].d);
-        } else pop_next();
-      }
-      if ((uint32_t)__popcll(__ballot(act && is_node_desc(cur))) < (uint32_t)RT_POOL_NODE_KEEP) break;
-      }
-      if (act) store_walk();
-    } else if (pass == P_LEAF) {
-      if (act) {
-        load_state();
-        uint32_t leftFirst = cur & LEAF_FIRST_MASK, triCount = (cur >> LEAF_FIRST_BITS) & LEAF_MAX_INLINE;
-        if (triCount == 0u) { const uint32_t* rn = sc.ref_bvh + (size_t)leftFirst * RT_NODE_DWORDS; leftFirst = rn[4]; triCount = rn[5]; }
-        const float cdx = __uint_as_float(pool[PF_DX][slot]), cdy = __uint_as_float(pool[PF_DY][slot]), cdz = __uint_as_float(pool[PF_DZ][slot]);
-        const uint32_t blasIdx = pool[PF_BLAS][slot];
-        bool stop = false;
-        float4 n0, n1, n2;
-        { const float4* tp0 = sc.tri_w + (size_t)leftFirst * 3; n0 = tp0[0]; n1 = tp0[1]; n2 = tp0[2]; }
-        for (uint32_t i = 0; i < triCount; ++i) {
-          const uint32_t triIdx = leftFirst + i;
-          const float4 t0 = n0, t1 = n1, t2 = n2;
-          if (i + 1u < triCount) { const float4* tn = sc.tri_w + (size_t)(triIdx + 1u) * 3; n0 = tn[0]; n1 = tn[1]; n2 = tn[2]; }
-          float bx, by, bz;
-          const float d = ray_tri(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz);
-          if (d < hitd) {
-            hitd = d;
-            flags |= F_FOUND;
-            HitRec h; h.dist = d; h.bx = bx; h.by = by; h.bz = 1 - bx - by; h.blasIdx = blasIdx; h.triIdx = triIdx;   // rt_traversal.cpp:311-313
-            A.hits[job] = h;                           // the record of the best hit so far: the last accept stands
-            if (flags & F_ANYHIT) { stop = true; break; }
-            if (!(path_m < hitd)) break;               // the reference abandons this subtree
-          }
-        }
-        if (stop) { sp = 0; cur = DESC_DONE; } else pop_next();
-        store_walk();
-      }
-    } else if (pass == P_INST) {
-      if (act) {
-        load_state();
-        float ox, oy, oz, dx, dy, dz;
-        world_ray(ox, oy, oz, dx, dy, dz);
-        enter_instance(cur & PAYLOAD_MASK, ox, oy, oz, dx, dy, dz, true);
-        store_ray();
-        store_walk();
-      }
-    } else {
-      // ---- service: rays that ended leave (a miss gets its record now), empty slots take new rays ----
-      bool empty = false;
-      if (act) {
-        load_state();
-        if (cur == DESC_DONE) {
-          if (!(flags & F_FOUND)) { HitRec h; h.dist = RT_LARGE_FLOAT; h.bx = 0; h.by = 0; h.bz = 0; h.blasIdx = 0; h.triIdx = 0; A.hits[job] = h; }
-          cur = DESC_IDLE;
-        }
-        empty = true;
-      }
-      const unsigned long long want = __ballot(empty);
-      uint32_t n_want = (uint32_t)__popcll(want);
-      uint32_t given = 0;                               // lanes want & ((1 << given) - 1) ... have their ray
-      while (n_want > given && !queue_empty) {
-        if (loc_next == loc_end) {                     // reserve the next chunk (the persistent kernel's queue: home shard = physical XCD, then the others)
-          while (tries < QUEUE_SHARDS) {
-            const uint32_t sid = (shard + tries) % QUEUE_SHARDS;
-            const uint32_t s_lo = sid * per_shard;
-            uint32_t in_range;
-            asm volatile("s_cmp_lt_u32 %1, %2\n\ts_cselect_b32 %0, 1, 0 ; RTGUARD shard_range" : "=s"(in_range)
-                         : "s"(__builtin_amdgcn_readfirstlane(s_lo)), "s"(__builtin_amdgcn_readfirstlane(n_jobs)) : "scc");
-            if (!in_range) { ++tries; continue; }
-            const uint32_t s_n = min(per_shard, n_jobs - s_lo);
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(A.queue + sid * QUEUE_STRIDE, (uint32_t)RT_CHUNK);
-            base = __shfl(base, 0);
-            if (base < s_n) { loc_next = s_lo + base; loc_end = s_lo + min(base + (uint32_t)RT_CHUNK, s_n); break; }
-            ++tries;
-          }
-          if (tries >= QUEUE_SHARDS) { queue_empty = true; break; }
-        }
-        const uint32_t take = min(n_want - given, loc_end - loc_next);
-        const uint32_t rank = (uint32_t)__popcll(want & lt_mask);
-        if (empty && rank >= given && rank < given + take) {
-          job = loc_next + (rank - given);
-          if (A.order) job = A.order[job];
-          float ox, oy, oz, dx, dy, dz;
-          world_ray(ox, oy, oz, dx, dy, dz);
-          const float tmax_ = A.tmax ? A.tmax[job] : RT_LARGE_FLOAT;
-          arx = ox; ary = oy; arz = oz;
-          aix = 1.0f / dx; aiy = 1.0f / dy; aiz = 1.0f / dz;
-          flags = F_WORLD | (A.any_hit ? F_ANYHIT : 0u);
-          sp = 0;
-          if (!ray_in_fast_domain(ox, oy, oz, aix, aiy, aiz)) defer();
-          else {
-            hitd = tmax_ > RT_LARGE_FLOAT ? RT_LARGE_FLOAT : tmax_;
-            path_m = -__builtin_inff();
-            cur = root_desc;
-            nrays++;
-            if (is_inst_desc(root_desc)) {
-              const bool no_neg_zero = __float_as_uint(ox) != 0x80000000u && __float_as_uint(oy) != 0x80000000u && __float_as_uint(oz) != 0x80000000u;
-              if (sc.ident_root && no_neg_zero) {       // (see start_ray of the persistent kernel: the object-space ray IS the world ray)
-                flags &= ~F_WORLD;
-                pool[PF_DX][slot] = __float_as_uint(dx); pool[PF_DY][slot] = __float_as_uint(dy); pool[PF_DZ][slot] = __float_as_uint(dz);
-                pool[PF_BLAS][slot] = root_desc & PAYLOAD_MASK;
-                cur = sc.blas_root[root_desc & PAYLOAD_MASK];
-              } else enter_instance(root_desc & PAYLOAD_MASK, ox, oy, oz, dx, dy, dz, true);
-            }
-          }
-          pool[PF_JOB][slot] = job;
-          store_ray();
-          empty = false;                               // (this lane's slot is taken -- or went to the deferral list and stays empty for the next pass)
-        }
-        given += take; loc_next += take;
-      }
-      if (act) store_walk();
-    }
-  }
-
-  if (A.end_log) {
-    unsigned s = nrays;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if (lane == 0) {
-      unsigned long long* w = A.end_log + 2ull * (blockIdx.x & 8191u);
-      w[0] = wall_clock64();
-      w[1] = (unsigned long long)s | ((unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) << 56);
-    }
-  }
-  if (A.counters) {
-    unsigned s = nrays;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if (lane == 0 && s) atomicAdd(A.counters, (unsigned long long)s);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Two rays per lane (ray buffers only; round 5, VERDICT item 2, second form: the state stays in REGISTERS).
-//
-// What masks half the lanes of the persistent kernel on incoherent rays is the phase: every iteration runs the node body for the lanes whose
-// ray is at a node (39.5 of 64 on the random rays) and, when enough have gathered, the leaf body for those at a leaf (22.7 of 64); the others
-// wait.  The ray-pool kernel above cures that by moving every ray's state through LDS, which costs more than it saves.  Here a lane OWNS two
-// rays: the active one in the registers the bodies work on, the parked one in a second set.  Before a body runs, a lane whose active ray is
-// not in that body's phase but whose parked ray is exchanges the two (v_swap_b32 under the lane's execution mask: 14 instructions for the
-// wavefront, whoever swaps) -- so the node body sees a lane unless NEITHER of its rays is at a node.  Nothing moves through memory: each
-// ray keeps its own stack rows in LDS and scratch (selected by the half the lane is working on), an accepted hit goes straight to the
-// ray's record.  Per-ray arithmetic is the persistent kernel's, step by step; only the interleaving of independent rays differs.
-// ---------------------------------------------------------------------------------------------
-#ifndef RT_PAIR_LSTK
-#define RT_PAIR_LSTK 5          // stack entries of each of a lane's two rays kept in LDS
-#endif
-#ifndef RT_PAIR_WAVES
-#define RT_PAIR_WAVES 5         // wavefronts per SIMD the kernel is compiled for
-#endif
-#ifndef RT_PAIR_LEAF_MIN
-#define RT_PAIR_LEAF_MIN 32     // the leaf body runs once this many lanes hold a leaf in either ray (or no lane holds a node)
-#endif
-#ifndef RT_PAIR_DEAD_MAX
-#define RT_PAIR_DEAD_MAX 32     // of the wavefront's 128 ray slots: finished / empty ones are serviced once there are this many
-#endif
-
-template <bool LDEXP, bool SHALLOW>
-__global__ __launch_bounds__(64, RT_PAIR_WAVES) void rt_pair_trace_kernel(SceneDev sc, PersistArgs A) {
-  constexpr int L = RT_PAIR_LSTK;
-  constexpr int CAP = SHALLOW ? 3 * RT_SHALLOW_LEVELS : 3 * RT_MAX_LEVELS + L;
-  constexpr int OVF = CAP - L;
-  __shared__ uint2 s_stk[2][L][64];
-  __shared__ uint32_t s_ctx[2][4][64];     // per ray: object-space direction (triangle tests), instance index
-  const uint32_t lane = threadIdx.x;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  const uint32_t n_jobs = A.total_dev ? min(*A.total_dev, A.total) : A.total;
-  const uint32_t per_shard = A.total_dev ? (((n_jobs + QUEUE_SHARDS - 1) / QUEUE_SHARDS + 63u) & ~63u) : A.per_shard;
-  const uint32_t root_desc = sc.tlas_root;
-  const uint32_t root_blas_desc = is_inst_desc(root_desc) ? sc.blas_root[root_desc & PAYLOAD_MASK] : DESC_DONE;
-  const uint32_t xcc_id = RT_XCC_HOME ? (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) : blockIdx.x;
-  const uint32_t shard = (xcc_id + A.shard_rot) % QUEUE_SHARDS;
-  uint32_t tries = 0, loc_next = 0, loc_end = 0;
-  bool queue_empty = false;
-  unsigned nrays = 0;
-  // the active ray (what the bodies work on) and the parked one; `half` = which of the lane's two stack / context rows the active ray owns
-  float arx = 0, ary = 0, arz = 0, aix = 0, aiy = 0, aiz = 0, hitd = 0, path_m = 0;
-  uint32_t cur = DESC_IDLE, job = 0, flags = 0, sp = 0, half = 0;
-  float q_arx = 0, q_ary = 0, q_arz = 0, q_aix = 0, q_aiy = 0, q_aiz = 0, q_hitd = 0, q_path_m = 0;
-  uint32_t q_cur = DESC_IDLE, q_job = 0, q_flags = 0, q_sp = 0, q_half = 1;
-  uint2 ovf[2 * OVF];
-#define PSWAPF(a, b) asm volatile("v_swap_b32 %0, %1" : "+v"(a), "+v"(b))
-  auto swap_rays = [&]() {       // (called under a divergent condition: the lanes that take the branch exchange their two rays)
-    PSWAPF(arx, q_arx); PSWAPF(ary, q_ary); PSWAPF(arz, q_arz); PSWAPF(aix, q_aix); PSWAPF(aiy, q_aiy); PSWAPF(aiz, q_aiz);
-    PSWAPF(hitd, q_hitd); PSWAPF(path_m, q_path_m); PSWAPF(cur, q_cur); PSWAPF(job, q_job); PSWAPF(flags, q_flags); PSWAPF(sp, q_sp); PSWAPF(half, q_half);
-  };
-  auto push = [&](uint32_t d, float m) {
-    if (sp < (uint32_t)L) s_stk[half][sp][lane] = make_uint2(d, __float_as_uint(m));
-    else ovf[half * OVF + (sp - L)] = make_uint2(d, __float_as_uint(m));
-    ++sp;
-  };
-  auto pop_next = [&]() {
-    cur = DESC_DONE;
-    while (sp > 0u) {
-      --sp;
-      const uint2 e = sp < (uint32_t)L ? s_stk[half][sp][lane] : ovf[half * OVF + (sp - L)];
-      if (__uint_as_float(e.y) < hitd) { cur = e.x; path_m = __uint_as_float(e.y); break; }
-    }
-  };
-  auto defer = [&]() {
-    const uint32_t q = atomicAdd(A.defer_count, 1u);
-    if (q < A.defer_cap) A.defer_list[q] = job;
-    cur = DESC_IDLE;
-  };
-  auto world_ray = [&](float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
-    const float* rp = A.rays + (size_t)job * 6;
-    ox = rp[0]; oy = rp[1]; oz = rp[2]; dx = rp[3]; dy = rp[4]; dz = rp[5];
-  };
-  auto enter_instance = [&](uint32_t blasIdx, float ox, float oy, float oz, float dx, float dy, float dz) {   // rt_traversal.cpp:109-121, :231-261
-    const uint32_t* bp = sc.blas + (size_t)blasIdx * (RT_BLAS_STRIDE / 4);
-    uint32_t bw[13];
-#pragma unroll
-    for (int i = 0; i < 13; ++i) bw[i] = bp[i];
-    const float m00 = __uint_as_float(bw[1]), m01 = __uint_as_float(bw[2]), m02 = __uint_as_float(bw[3]), m03 = __uint_as_float(bw[4]);
-    const float m10 = __uint_as_float(bw[5]), m11 = __uint_as_float(bw[6]), m12 = __uint_as_float(bw[7]), m13 = __uint_as_float(bw[8]);
-    const float m20 = __uint_as_float(bw[9]), m21 = __uint_as_float(bw[10]), m22 = __uint_as_float(bw[11]), m23 = __uint_as_float(bw[12]);
-    arx = m00 * ox + m01 * oy + m02 * oz + m03;
-    ary = m10 * ox + m11 * oy + m12 * oz + m13;
-    arz = m20 * ox + m21 * oy + m22 * oz + m23;
-    const float cdx = m00 * dx + m01 * dy + m02 * dz;
-    const float cdy = m10 * dx + m11 * dy + m12 * dz;
-    const float cdz = m20 * dx + m21 * dy + m22 * dz;
-    aix = 1.0f / cdx; aiy = 1.0f / cdy; aiz = 1.0f / cdz;
-    if (!ray_in_fast_domain(arx, ary, arz, aix, aiy, aiz)) { nrays--; defer(); return; }   // (the EXACT launch counts the ray when it starts it again)
-    flags &= ~F_WORLD;
-    s_ctx[half][0][lane] = __float_as_uint(cdx); s_ctx[half][1][lane] = __float_as_uint(cdy); s_ctx[half][2][lane] = __float_as_uint(cdz);
-    s_ctx[half][3][lane] = blasIdx;
-    cur = sc.blas_root[blasIdx];
-  };
-  auto dead = [&](uint32_t d, bool more_jobs) { return d == DESC_DONE || (more_jobs && d == DESC_IDLE); };
-
-  for (;;) {
-    // ================= service: rays that ended leave (a miss gets its record), empty slots take new rays =================
-    const bool more_jobs = !(queue_empty && loc_next == loc_end);
-    const uint32_t n_dead = (uint32_t)(__popcll(__ballot(dead(cur, more_jobs))) + __popcll(__ballot(dead(q_cur, more_jobs))));
-    const bool any_work = __ballot(is_work_desc(cur) || is_work_desc(q_cur)) != 0ull;
-    if (n_dead >= (uint32_t)RT_PAIR_DEAD_MAX || (!any_work && n_dead)) {
-#pragma unroll 1
-      for (int h = 0; h < 2; ++h) {        // the active rays, then (everything exchanged) the parked ones; two exchanges restore the order
-        if (cur == DESC_DONE) {
-          if (!(flags & F_FOUND)) { HitRec m; m.dist = RT_LARGE_FLOAT; m.bx = 0; m.by = 0; m.bz = 0; m.blasIdx = 0; m.triIdx = 0; A.hits[job] = m; }
-          cur = DESC_IDLE;
-        }
-        const unsigned long long want = __ballot(cur == DESC_IDLE);
-        const uint32_t n_want = (uint32_t)__popcll(want);
-        uint32_t given = 0;
-        while (n_want > given && !queue_empty) {
-          if (loc_next == loc_end) {
-            while (tries < QUEUE_SHARDS) {
-              const uint32_t sid = (shard + tries) % QUEUE_SHARDS;
-              const uint32_t s_lo = sid * per_shard;
-              uint32_t in_range;
-              asm volatile("s_cmp_lt_u32 %1, %2\n\ts_cselect_b32 %0, 1, 0 ; RTGUARD shard_range" : "=s"(in_range)
-                           : "s"(__builtin_amdgcn_readfirstlane(s_lo)), "s"(__builtin_amdgcn_readfirstlane(n_jobs)) : "scc");
-              if (!in_range) { ++tries; continue; }
-              const uint32_t s_n = min(per_shard, n_jobs - s_lo);
-              uint32_t base = 0;
-              if (lane == 0) base = atomicAdd(A.queue + sid * QUEUE_STRIDE, (uint32_t)RT_TRACE_CHUNK);
-              base = __shfl(base, 0);
-              if (base < s_n) { loc_next = s_lo + base; loc_end = s_lo + min(base + (uint32_t)RT_TRACE_CHUNK, s_n); break; }
-              ++tries;
-            }
-            if (tries >= QUEUE_SHARDS) { queue_empty = true; break; }
-          }
-          const uint32_t take = min(n_want - given, loc_end - loc_next);
-          const uint32_t rank = (uint32_t)__popcll(want & lt_mask);
-          if (cur == DESC_IDLE && ((want >> lane) & 1ull) && rank >= given && rank < given + take) {
-            job = loc_next + (rank - given);
-            if (A.order) job = A.order[job];
-            float ox, oy, oz, dx, dy, dz;
-            world_ray(ox, oy, oz, dx, dy, dz);
-            const float tmax_ = A.tmax ? A.tmax[job] : RT_LARGE_FLOAT;
-            arx = ox; ary = oy; arz = oz;
-            aix = 1.0f / dx; aiy = 1.0f / dy; aiz = 1.0f / dz;
-            flags = F_WORLD | (A.any_hit ? F_ANYHIT : 0u);
-            sp = 0;
-            if (!ray_in_fast_domain(ox, oy, oz, aix, aiy, aiz)) defer();
-            else {
-              hitd = tmax_ > RT_LARGE_FLOAT ? RT_LARGE_FLOAT : tmax_;
-              path_m = -__builtin_inff();
-              cur = root_desc;
-              nrays++;
-              if (is_inst_desc(root_desc)) {
-                const bool no_neg_zero = __float_as_uint(ox) != 0x80000000u && __float_as_uint(oy) != 0x80000000u && __float_as_uint(oz) != 0x80000000u;
-                if (sc.ident_root && no_neg_zero) {     // (see start_ray of the persistent kernel: the object-space ray IS the world ray)
-                  flags &= ~F_WORLD;
-                  s_ctx[half][0][lane] = __float_as_uint(dx); s_ctx[half][1][lane] = __float_as_uint(dy); s_ctx[half][2][lane] = __float_as_uint(dz);
-                  s_ctx[half][3][lane] = root_desc & PAYLOAD_MASK;
-                  cur = root_blas_desc;
-                } else enter_instance(root_desc & PAYLOAD_MASK, ox, oy, oz, dx, dy, dz);
-              }
-            }
-          }
-          given += take; loc_next += take;
-        }
-        swap_rays();
-      }
-    }
-    if (__ballot(is_work_desc(cur) || is_work_desc(q_cur)) == 0ull) {
-      if (queue_empty && loc_next == loc_end) break;
-      continue;
-    }
-
-    // ================= instance steps (TLAS leaves of multi-instance scenes): whichever of a lane's rays holds one =================
-    if (__ballot(is_inst_desc(cur) || is_inst_desc(q_cur)) != 0ull) {
-      if (!is_inst_desc(cur) && is_inst_desc(q_cur)) swap_rays();
-      if (is_inst_desc(cur)) {
-        float ox, oy, oz, dx, dy, dz;
-        world_ray(ox, oy, oz, dx, dy, dz);
-        enter_instance(cur & PAYLOAD_MASK, ox, oy, oz, dx, dy, dz);
-      }
-    }
-    // ================= node body: a lane takes part unless NEITHER of its rays is at a node =================
-    if (!is_node_desc(cur) && is_node_desc(q_cur)) swap_rays();
-    if (is_node_desc(cur)) {
-      const bool top = (cur >> 30) == DK_TLAS;
-      if (top && !(flags & F_WORLD)) {                 // back at TLAS level after an instance (multi-instance scenes only)
-        float dx, dy, dz;
-        world_ray(arx, ary, arz, dx, dy, dz);
-        aix = 1.0f / dx; aiy = 1.0f / dy; aiz = 1.0f / dz;
-        flags |= F_WORLD;
-      }
-      const uint32_t ni = cur & PAYLOAD_MASK;
-      const uint4* np = sc.nodes_c + (size_t)ni * CNODE_VEC4;
-      const uint4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-      const uint32_t* ref_node = nullptr;
-      if (LDEXP) ref_node = top ? sc.ref_tlas + (size_t)ni * RT_NODE_DWORDS : sc.ref_bvh + (size_t)(ni - sc.n_tlas) * RT_NODE_DWORDS;
-      Cand c[4];
-      eval_children<false, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
-      order_children(c);
-      if (c[0].d < __builtin_inff()) {
-        bool more = true;
-        if (sp + 3u > (uint32_t)CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-        if (more && c[3].d < __builtin_inff()) push(c[3].desc, vmax_nonan(path_m, c[3].d));   // far first (:98-103)
-        if (more && c[2].d < __builtin_inff()) push(c[2].desc, vmax_nonan(path_m, c[2].d));
-        if (more && c[1].d < __builtin_inff()) push(c[1].desc, vmax_nonan(path_m, c[1].d));
-        cur = c[0].desc;
-        path_m = vmax_nonan(path_m, c[0].d);
-      } else pop_next();
-    }
-    // ================= leaf body: once enough lanes hold a leaf in either ray, or no lane has a node left =================
-    const unsigned long long leafm = __ballot(is_leaf_desc(cur) || is_leaf_desc(q_cur));
-    if (leafm != 0ull && ((uint32_t)__popcll(leafm) >= (uint32_t)RT_PAIR_LEAF_MIN ||
-                          __ballot(is_node_desc(cur) || is_node_desc(q_cur) || is_inst_desc(cur) || is_inst_desc(q_cur)) == 0ull)) {
-      if (!is_leaf_desc(cur) && is_leaf_desc(q_cur)) swap_rays();
-      if (is_leaf_desc(cur)) {
-        uint32_t leftFirst = cur & LEAF_FIRST_MASK, triCount = (cur >> LEAF_FIRST_BITS) & LEAF_MAX_INLINE;
-        if (triCount == 0u) { const uint32_t* rn = sc.ref_bvh + (size_t)leftFirst * RT_NODE_DWORDS; leftFirst = rn[4]; triCount = rn[5]; }
-        const float cdx = __uint_as_float(s_ctx[half][0][lane]), cdy = __uint_as_float(s_ctx[half][1][lane]), cdz = __uint_as_float(s_ctx[half][2][lane]);
-        const uint32_t blasIdx = s_ctx[half][3][lane];
-        bool stop = false;
-        float4 n0, n1, n2;
-        { const float4* tp0 = sc.tri_w + (size_t)leftFirst * 3; n0 = tp0[0]; n1 = tp0[1]; n2 = tp0[2]; }
-        for (uint32_t i = 0; i < triCount; ++i) {
-          const uint32_t triIdx = leftFirst + i;
-          const float4 t0 = n0, t1 = n1, t2 = n2;
-          if (i + 1u < triCount) { const float4* tn = sc.tri_w + (size_t)(triIdx + 1u) * 3; n0 = tn[0]; n1 = tn[1]; n2 = tn[2]; }
-          float bx, by, bz;
-          const float d = ray_tri(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz);
-          if (d < hitd) {
-            hitd = d;
-            flags |= F_FOUND;
-            HitRec hr; hr.dist = d; hr.bx = bx; hr.by = by; hr.bz = 1 - bx - by; hr.blasIdx = blasIdx; hr.triIdx = triIdx;   // rt_traversal.cpp:311-313
-            A.hits[job] = hr;                          // the record of the best hit so far: the last accept stands
-            if (flags & F_ANYHIT) { stop = true; break; }
-            if (!(path_m < hitd)) break;               // the reference abandons this subtree
-          }
-        }
-        if (stop) { sp = 0; cur = DESC_DONE; } else pop_next();
-      }
-    }
-  }
-#undef PSWAPF
-  if (A.counters) {
-    unsigned s = nrays;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if (lane == 0 && s) atomicAdd(A.counters, (unsigned long long)s);
-  }
-}
-
 // Tile order for the next frame of a context: within each queue shard's band of tiles (a contiguous part of the
 // frame, whose tiles share BVH nodes in the L2 of the XCD that works on it), most expensive first; cost = 100 MHz
 // clocks the tile occupied its wavefront in the frame just traced.  A launch ends when its last tile ends, and a
@@ -2687,428 +2031,6 @@ __global__ __launch_bounds__(256) void wire_unpack_kernel(const uint32_t* __rest
 __global__ void add_counter_kernel(unsigned long long* c, unsigned long long v) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(c, v); }
 
 // ---------------------------------------------------------------------------------------------
-// acceleration-layout build (one pass over the reference-format buffers; validates every index the
-// traversal will follow so that a malformed scene is rejected on the host instead of faulting the GPU)
-// ---------------------------------------------------------------------------------------------
-// one thread per reference node of one buffer.  bases/ends: sorted BLAS node ranges (nb of them).
-__global__ void accel_nodes_kernel(const uint32_t* __restrict__ ref, uint32_t n_nodes, uint4* __restrict__ out, int is_tlas,
-                                   const uint32_t* __restrict__ bases, const uint32_t* __restrict__ ends, uint32_t nb,
-                                   uint32_t n_tris, uint32_t n_blas, uint32_t bias, uint32_t* status) {
-  // bias: compact index of this buffer's node 0 (0 for the TLAS pass, n_tlas for the BLAS pass); `out` is already offset by it
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_nodes) return;
-  const uint32_t* w = ref + (size_t)i * RT_NODE_DWORDS;
-  const uint32_t imask = w[3] >> 24, leftFirst = w[4], leafData = w[5];
-  uint32_t base = 0, end = n_nodes;
-  if (!is_tlas) {
-    bool in = false;
-    for (uint32_t j = 0; j < nb; ++j) if (i >= bases[j] && i < ends[j]) { base = bases[j]; end = ends[j]; in = true; }
-    if (!in) return;   // node outside every instance's range: unreachable, leave untouched
-  }
-  if (imask != (is_tlas ? 1u : 0u)) return;   // not a node of this kind (e.g. unused tail): reachable nodes are checked via their parent
-  const bool leaf = is_tlas ? (leafData != 0xffffffffu) : (leafData != 0u);
-  if (leaf) return;
-  const float px = __uint_as_float(w[0]), py = __uint_as_float(w[1]), pz = __uint_as_float(w[2]);
-  const float po[3] = {px, py, pz};
-  const int ev[3] = {(int)(int8_t)(w[3] & 0xff), (int)(int8_t)((w[3] >> 8) & 0xff), (int)(int8_t)((w[3] >> 16) & 0xff)};
-  const uint8_t* bytes = (const uint8_t*)w;
-  uint32_t pay[4] = {DESC_NONE, DESC_NONE, DESC_NONE, DESC_NONE};   // complete descriptors of the children
-  uint8_t qb[24];
-  for (int k = 0; k < 4; ++k) {
-    const uint8_t* c = bytes + 24 + 7 * k;
-    for (int j = 0; j < 6; ++j) qb[4 * j + k] = c[1 + j];   // plane-major: word j = plane j (lo xyz, hi xyz) of the four children
-    if (c[0] == 0) continue;   // meta (rt_traversal.cpp:60)
-    // the sign-selected slab form needs lo <= hi per axis (child_box); an inverted box falls back to min/max
-    if (c[1] > c[4] || c[2] > c[5] || c[3] > c[6]) atomicOr(status, STATUS_FMA_DECODE_DIFFERS);
-    // fma decode must reproduce origin + ldexp(float(q), e) bit for bit (eval_children)
-    for (int j = 0; j < 6; ++j) {
-      const float q = (float)c[1 + j];
-      const float a = po[j % 3] + ldexpf(q, ev[j % 3]);
-      const float b = __fmaf_rn(q, ldexpf(1.0f, ev[j % 3]), po[j % 3]);
-      if (__float_as_uint(a) != __float_as_uint(b) && !(a != a && b != b)) atomicOr(status, STATUS_FMA_DECODE_DIFFERS);
-    }
-    const uint64_t ci64 = (uint64_t)base + leftFirst + (uint32_t)k;   // calcNodePtr(base_ptr, leftFirst + childIdx), :91-92
-    // children are allocated after their parent by the builders (bvh.cpp:94-97, 371-402): requiring
-    // that makes every accepted tree acyclic, so traversal terminates
-    if (ci64 >= end || ci64 <= i || ci64 + bias > PAYLOAD_MASK) { atomicOr(status, STATUS_BAD_SCENE); continue; }
-    const uint32_t ci = (uint32_t)ci64;
-    const uint32_t* cw = ref + (size_t)ci * RT_NODE_DWORDS;
-    const uint32_t c_imask = cw[3] >> 24, c_lf = cw[4], c_ld = cw[5];
-    if (c_imask != (is_tlas ? 1u : 0u)) { atomicOr(status, STATUS_BAD_SCENE); continue; }
-    if (is_tlas) {
-      if (c_ld != 0xffffffffu) {
-        if (c_ld >= n_blas || c_ld >= 0x3FFFFFF0u) { atomicOr(status, STATUS_BAD_SCENE); continue; }
-        pay[k] = DESC(DK_INST, c_ld);
-      } else pay[k] = DESC(DK_TLAS, ci + bias);
-    } else {
-      if (c_ld != 0u) {
-        if ((uint64_t)c_lf + c_ld > n_tris) { atomicOr(status, STATUS_BAD_SCENE); continue; }
-        pay[k] = DESC(DK_LEAF, (c_ld <= LEAF_MAX_INLINE && c_lf <= LEAF_FIRST_MASK) ? ((c_ld << LEAF_FIRST_BITS) | c_lf) : ci);   // else by reference
-        if (!(c_ld <= LEAF_MAX_INLINE && c_lf <= LEAF_FIRST_MASK) && ci > LEAF_FIRST_MASK) { atomicOr(status, STATUS_BAD_SCENE); pay[k] = DESC_NONE; }
-      } else pay[k] = DESC(DK_BLAS, ci + bias);
-    }
-  }
-  uint32_t qw[6];
-  for (int v = 0; v < 6; ++v) qw[v] = (uint32_t)qb[4 * v] | ((uint32_t)qb[4 * v + 1] << 8) | ((uint32_t)qb[4 * v + 2] << 16) | ((uint32_t)qb[4 * v + 3] << 24);
-  uint4* o = out + (size_t)i * CNODE_VEC4;
-  o[0] = make_uint4(w[0], w[1], w[2], __float_as_uint(ldexpf(1.0f, ev[0])));
-  o[1] = make_uint4(qw[0], qw[1], qw[2], qw[3]);
-  o[2] = make_uint4(qw[4], qw[5], pay[0], pay[1]);
-  o[3] = make_uint4(pay[2], pay[3], __float_as_uint(ldexpf(1.0f, ev[1])), __float_as_uint(ldexpf(1.0f, ev[2])));
-}
-
-__global__ void accel_tris_kernel(const float* __restrict__ tri, uint32_t n, float4* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* t = tri + (size_t)i * 9;
-  const float v0x = t[0], v0y = t[1], v0z = t[2];
-  // edge1 = v1 - v0, edge2 = v2 - v0 exactly as rt_traversal.cpp:272-278 computes them per test
-  out[(size_t)i * 3 + 0] = make_float4(v0x, v0y, v0z, t[3] - v0x);
-  out[(size_t)i * 3 + 1] = make_float4(t[4] - v0y, t[5] - v0z, t[6] - v0x, t[7] - v0y);
-  out[(size_t)i * 3 + 2] = make_float4(t[8] - v0z, 0.f, 0.f, 0.f);
-}
-
-// root descriptors: thread 0 -> TLAS root, thread 1+j -> BLAS root of instance record j
-__global__ void accel_roots_kernel(const uint32_t* __restrict__ tlas, const uint32_t* __restrict__ bvh, const uint32_t* __restrict__ blas,
-                                   uint32_t n_tlas, uint32_t n_bvh, uint32_t n_blas, uint32_t n_tris, uint32_t* tlas_root, uint32_t* blas_root,
-                                   uint32_t* status) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) {
-    const uint32_t imask = tlas[3] >> 24, ld = tlas[5];
-    *tlas_root = DESC_DONE;
-    if (imask != 1u) atomicOr(status, STATUS_BAD_SCENE);
-    else if (ld != 0xffffffffu) {
-      if (ld >= n_blas || ld >= 0x3FFFFFF0u) atomicOr(status, STATUS_BAD_SCENE);
-      else *tlas_root = DESC(DK_INST, ld);
-    } else *tlas_root = DESC(DK_TLAS, 0u);   // compact index 0
-  } else if (t - 1 < n_blas) {
-    const uint32_t j = t - 1;
-    const uint32_t off = blas[(size_t)j * (RT_BLAS_STRIDE / 4)];
-    blas_root[j] = DESC_DONE;
-    if (off >= n_bvh || off > LEAF_FIRST_MASK) { atomicOr(status, STATUS_BAD_SCENE); return; }
-    const uint32_t* w = bvh + (size_t)off * RT_NODE_DWORDS;
-    const uint32_t imask = w[3] >> 24, lf = w[4], ld = w[5];
-    if (imask != 0u) atomicOr(status, STATUS_BAD_SCENE);
-    else if (ld != 0u) {
-      if ((uint64_t)lf + ld > n_tris) atomicOr(status, STATUS_BAD_SCENE);
-      else blas_root[j] = DESC(DK_LEAF, (ld <= LEAF_MAX_INLINE && lf <= LEAF_FIRST_MASK) ? ((ld << LEAF_FIRST_BITS) | lf) : off);
-    } else if ((uint64_t)off + n_tlas > PAYLOAD_MASK) atomicOr(status, STATUS_BAD_SCENE);
-    else blas_root[j] = DESC(DK_BLAS, off + n_tlas);
-  }
-}
-
-// Depth of the scene in INTERNAL levels on a root-to-leaf path, TLAS and BLAS together: what bounds a lane's stack (a node step leaves at most
-// three pending siblings; instance and leaf steps leave none).  One pass per level over the compact nodes (children lie after their parents, so
-// the trees are acyclic): pass t gives every internal child of a node of level t - 1 the level t; a TLAS leaf hands its level on to the root of
-// its instance's BLAS.  `deepest` ends as the last level any node reached.  Only reached nodes are read (unreached slots are not initialised).
-__global__ void accel_depth_kernel(const uint4* __restrict__ nodes_c, uint32_t n_nodes, uint32_t tlas_root, const uint32_t* __restrict__ blas_root,
-                                   uint32_t level, uint32_t* __restrict__ depth, uint32_t* __restrict__ deepest) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  auto reach = [&](uint32_t d) {
-    if (is_inst_desc(d)) d = blas_root[d & PAYLOAD_MASK];
-    if (!is_node_desc(d)) return;
-    const uint32_t c = d & PAYLOAD_MASK;
-    if (c < n_nodes) { atomicMax(&depth[c], level); *deepest = level; }   // (every writer of a pass stores the same value)
-  };
-  if (level == 1u) {
-    if (i == 0) reach(tlas_root);
-    return;
-  }
-  if (i >= n_nodes || depth[i] != level - 1u) return;
-  const uint4* np = nodes_c + (size_t)i * CNODE_VEC4;
-  const uint4 q2 = np[2], q3 = np[3];
-  reach(q2.z); reach(q2.w); reach(q3.x); reach(q3.y);
-}
-
-// Top of the tree for LDS staging: breadth-first from the TLAS root through the instance roots, the first `cap` internal
-// nodes get slots 0..n-1 (so the levels every ray walks come first).  The image holds their compact nodes as four planes of
-// `cap` uint4 with the child descriptors of staged children rewritten to DESC_TOP_FLAG | slot; the *_top roots likewise.
-// The global compact nodes stay untouched: kernels that do not stage (EXACT, ldexp decode) start from the plain roots and
-// never meet a slot descriptor.  One wavefront; a few hundred nodes, once per scene.
-__global__ __launch_bounds__(64) void accel_top_kernel(const uint4* __restrict__ nodes_c, uint32_t tlas_root, const uint32_t* __restrict__ blas_root,
-                                                       uint32_t n_blas, uint32_t cap, uint4* __restrict__ img, uint32_t* __restrict__ out_n,
-                                                       uint32_t* __restrict__ tlas_root_top, uint32_t* __restrict__ blas_root_top) {
-  __shared__ uint32_t q[RT_TOP_MAX];
-  __shared__ uint32_t n_s;
-  const uint32_t lane = threadIdx.x;
-  auto find = [&](uint32_t idx, uint32_t n) -> uint32_t {   // wave-wide search; returns slot or 0xFFFFFFFF
-    uint32_t hit = 0xFFFFFFFFu;
-    for (uint32_t b = 0; b < n; b += 64u) {
-      const unsigned long long m = __ballot(b + lane < n && q[b + lane] == idx);
-      if (m) { hit = b + (uint32_t)__ffsll((long long)m) - 1u; break; }
-    }
-    return hit;
-  };
-  uint32_t n = 0;
-  auto push = [&](uint32_t d) {   // wave-uniform d
-    if (!is_node_desc(d)) return;
-    const uint32_t idx = d & PAYLOAD_MASK;
-    if (n >= cap || find(idx, n) != 0xFFFFFFFFu) return;
-    if (lane == 0) q[n] = idx;
-    ++n;
-    __syncthreads();
-  };
-  if (is_inst_desc(tlas_root)) push(blas_root[tlas_root & PAYLOAD_MASK]); else push(tlas_root);
-  for (uint32_t head = 0; head < n && n < cap; ++head) {
-    const uint4* np = nodes_c + (size_t)q[head] * CNODE_VEC4;
-    const uint4 q2 = np[2], q3 = np[3];
-    const uint32_t d[4] = {q2.z, q2.w, q3.x, q3.y};
-    for (int k = 0; k < 4; ++k) {
-      if (is_inst_desc(d[k])) push(blas_root[d[k] & PAYLOAD_MASK]); else push(d[k]);
-    }
-  }
-  __syncthreads();
-  auto patch = [&](uint32_t d) -> uint32_t {
-    if (!is_node_desc(d)) return d;
-    const uint32_t slot = find(d & PAYLOAD_MASK, n);
-    return slot == 0xFFFFFFFFu ? d : ((d & 0xC0000000u) | DESC_TOP_FLAG | slot);
-  };
-  for (uint32_t sidx = 0; sidx < n; ++sidx) {
-    const uint4* np = nodes_c + (size_t)q[sidx] * CNODE_VEC4;
-    uint4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-    q2.z = patch(q2.z); q2.w = patch(q2.w); q3.x = patch(q3.x); q3.y = patch(q3.y);
-    if (lane == 0) { img[sidx] = q0; img[cap + sidx] = q1; img[2 * (size_t)cap + sidx] = q2; img[3 * (size_t)cap + sidx] = q3; }
-  }
-  for (uint32_t j = 0; j < n_blas; ++j) {
-    const uint32_t v = patch(blas_root[j]);
-    if (lane == 0) blas_root_top[j] = v;
-  }
-  const uint32_t tr = patch(tlas_root);
-  if (lane == 0) { *tlas_root_top = tr; *out_n = n; }
-  (void)n_s;
-}
-
-// shading inputs (closest.cpp:52-77 dereferences them unchecked; here a scene that would read outside its buffers is rejected
-// when the acceleration layout is built): every triangle's texId names a material, and every textured material's texels lie
-// inside the texture buffer with non-zero dimensions (texSample takes `% width`, rtx_shading.h:9-10)
-__global__ void accel_check_shading_kernel(const rt_triex_t* __restrict__ triEx, uint32_t n_tris, const rt_material_t* __restrict__ mat, uint32_t n_mats,
-                                           uint64_t tex_bytes, int have_tex, uint32_t* status) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_tris && triEx[i].texId >= n_mats) atomicOr(status, STATUS_BAD_SCENE);
-  if (i < n_mats && mat[i].diffuse_tex_id >= 0) {
-    const uint64_t w = mat[i].tex_width, h = mat[i].tex_height, off = mat[i].tex_offset;
-    if (!have_tex || w == 0 || h == 0 || (off & 3u) != 0 || off > tex_bytes || w * h > (tex_bytes - off) / 4u) atomicOr(status, STATUS_BAD_SCENE);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// refit (vxrt_accel_refit / vxrt_accel_set_transforms): new boxes for a fixed topology, written into the reference nodes in place
-// and re-laid out as the build lays them out.  A plan built once per accel lists every tree's leaves and its internal nodes by level
-// (the TLAS and each distinct BLAS range); one launch per level from the deepest to the roots, so that the kernel boundary makes the
-// children's float boxes visible to their parent ("Refit").
-// ---------------------------------------------------------------------------------------------
-#define REFIT_ERR_NONFINITE 1u   // a vertex, a transform or a transformed box is not finite
-#define REFIT_ERR_QUANT 2u       // a box cannot be quantised (the builder's counters[4] & 2)
-#define REFIT_ERR_SINGULAR 4u    // set_transforms: a transform with det == 0 (or a non-finite inverse)
-// result block of one refit, device u32: [0] status of the TLAS re-layout, [1] REFIT_ERR_* of the refit, [2] identity root instance,
-// [3] staged top-of-tree nodes, [4] staged TLAS root, [5] status of the BLAS re-layout, [6] REFIT_ERR_* of set_transforms' matrices
-#define REFIT_RES_WORDS 8
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// origin and exponents of a node whose float box is lo / hi (every node, leaves included: bb_emit_leaf writes them too); imask kept
-__device__ __forceinline__ void refit_write_origin(uint32_t* __restrict__ w, const float lo[3], const float hi[3], const int e[3]) {
-  w[0] = __float_as_uint(lo[0]); w[1] = __float_as_uint(lo[1]); w[2] = __float_as_uint(lo[2]);
-  w[3] = (uint32_t)(uint8_t)(int8_t)e[0] | ((uint32_t)(uint8_t)(int8_t)e[1] << 8) | ((uint32_t)(uint8_t)(int8_t)e[2] << 16) | (w[3] & 0xff000000u);
-}
-__device__ __forceinline__ void refit_store_box(float* __restrict__ fbox, uint32_t i, const float lo[3], const float hi[3]) {
-  float* f = fbox + (size_t)i * 6;
-  f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = hi[0]; f[4] = hi[1]; f[5] = hi[2];
-}
-
-// min / max over the vertices of triangles [first, first + count)
-__device__ __forceinline__ bool refit_tri_box(const float* __restrict__ tri, uint32_t first, uint32_t count, float lo[3], float hi[3]) {
-  bool fin = true;
-  lo[0] = lo[1] = lo[2] = __builtin_inff(); hi[0] = hi[1] = hi[2] = -__builtin_inff();
-  for (uint32_t t = first; t < first + count; ++t) {
-    const float* v = tri + (size_t)t * 9;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      const float x = v[j];
-      fin = fin && isfinite(x);
-      lo[j % 3] = fminf(lo[j % 3], x); hi[j % 3] = fmaxf(hi[j % 3], x);
-    }
-  }
-  return fin;
-}
-
-// one thread per BLAS leaf of the plan: the box of its triangles
-__global__ __launch_bounds__(256) void refit_blas_leaf_kernel(uint32_t* __restrict__ bvh, const float* __restrict__ tri, const uint32_t* __restrict__ leaves,
-                                                              uint32_t n, float* __restrict__ fbox, uint32_t* __restrict__ res) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t i = leaves[j];
-  uint32_t* w = bvh + (size_t)i * RT_NODE_DWORDS;
-  float lo[3], hi[3];
-  if (!refit_tri_box(tri, w[4], w[5], lo, hi)) atomicOr(res + 1, REFIT_ERR_NONFINITE);
-  const int e[3] = {bb_pick_exp(hi[0] - lo[0]), bb_pick_exp(hi[1] - lo[1]), bb_pick_exp(hi[2] - lo[2])};
-  refit_write_origin(w, lo, hi, e);
-  refit_store_box(fbox, i, lo, hi);
-}
-
-// TransformPosition (geometry.h:1280-1289): ((c0 x + c1 y) + c2 z) + c3 * 1, fp32, no contraction
-__device__ __forceinline__ float refit_row(const float* __restrict__ m, float x, float y, float z) {
-  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], x), __fmul_rn(m[1], y)), __fmul_rn(m[2], z)), m[3]);
-}
-
-// one thread per TLAS leaf of the plan: the world box of its instance, the 8 corners of the object box through `transform` (bvh.cpp:
-// 290-304).  Object box: the refit's own box of the BLAS root after a GEOMETRY pass (fbox_bvh), else the union of the root's decoded
-// child boxes, or the triangle box when the root is a leaf.
-__global__ __launch_bounds__(256) void refit_instance_kernel(uint32_t* __restrict__ tlas, const uint32_t* __restrict__ leaves, uint32_t n,
-                                                             const uint32_t* __restrict__ blas, const uint32_t* __restrict__ bvh, const float* __restrict__ tri,
-                                                             const float* __restrict__ fbox_bvh, float* __restrict__ fbox, uint32_t* __restrict__ res) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t i = leaves[j];
-  uint32_t* w = tlas + (size_t)i * RT_NODE_DWORDS;
-  const uint32_t* rec = blas + (size_t)w[5] * (RT_BLAS_STRIDE / 4);
-  const uint32_t off = rec[0];
-  const uint32_t* r = bvh + (size_t)off * RT_NODE_DWORDS;
-  float olo[3], ohi[3];
-  bool fin = true;
-  if (fbox_bvh) {
-    for (int a = 0; a < 3; ++a) { olo[a] = fbox_bvh[(size_t)off * 6 + a]; ohi[a] = fbox_bvh[(size_t)off * 6 + 3 + a]; }
-  } else if (r[5] != 0u) {
-    fin = refit_tri_box(tri, r[4], r[5], olo, ohi);
-  } else {
-    const uint8_t* b = (const uint8_t*)r;
-    olo[0] = olo[1] = olo[2] = __builtin_inff(); ohi[0] = ohi[1] = ohi[2] = -__builtin_inff();
-    for (int k = 0; k < 4; ++k) {
-      const uint8_t* c = b + 24 + 7 * k;
-      if (c[0] == 0) continue;
-      for (int a = 0; a < 3; ++a) {
-        const int e = (int)(int8_t)b[12 + a];
-        const float o = __uint_as_float(r[a]);
-        olo[a] = fminf(olo[a], o + ldexpf((float)c[1 + a], e));
-        ohi[a] = fmaxf(ohi[a], o + ldexpf((float)c[4 + a], e));
-      }
-    }
-  }
-  const float* m = (const float*)(rec + 17);   // blas_node_t::transform @68
-  for (int k = 0; k < 12; ++k) fin = fin && isfinite(m[k]);
-  float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-  for (int c = 0; c < 8; ++c) {
-    const float x = (c & 1) ? ohi[0] : olo[0], y = (c & 2) ? ohi[1] : olo[1], z = (c & 4) ? ohi[2] : olo[2];
-    for (int a = 0; a < 3; ++a) {
-      const float p = refit_row(m + 4 * a, x, y, z);
-      fin = fin && isfinite(p);
-      lo[a] = fminf(lo[a], p); hi[a] = fmaxf(hi[a], p);
-    }
-  }
-  if (!fin) atomicOr(res + 1, REFIT_ERR_NONFINITE);
-  const int e[3] = {bb_pick_exp(hi[0] - lo[0]), bb_pick_exp(hi[1] - lo[1]), bb_pick_exp(hi[2] - lo[2])};
-  refit_write_origin(w, lo, hi, e);
-  refit_store_box(fbox, i, lo, hi);
-}
-
-// one thread per internal node of one level (item = node, index of its child 0): the union of its children's float boxes, then
-// origin, exponents and the children's bytes with the builder's quantiser.  Meta bytes, leftFirst, leafData, imask stay.
-__global__ __launch_bounds__(256) void refit_level_kernel(uint32_t* __restrict__ nodes, const uint2* __restrict__ items, uint32_t n,
-                                                          float* __restrict__ fbox, uint32_t* __restrict__ res) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const uint2 it = items[j];
-  uint32_t* w = nodes + (size_t)it.x * RT_NODE_DWORDS;
-  uint32_t cw[7];
-#pragma unroll
-  for (int v = 0; v < 7; ++v) cw[v] = w[6 + v];
-  uint8_t* cb = (uint8_t*)cw;   // children: 4 x { meta, lo x y z, hi x y z }
-  uint32_t present = 0;
-  float cmin[3][4], cmax[3][4];
-  float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool on = cb[7 * k] != 0;
-    present |= on ? (1u << k) : 0u;
-    const float* f = fbox + (size_t)(it.y + (on ? (uint32_t)k : 0u)) * 6;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      cmin[a][k] = on ? f[a] : 0.0f; cmax[a][k] = on ? f[3 + a] : 0.0f;
-      if (on) { lo[a] = fminf(lo[a], cmin[a][k]); hi[a] = fmaxf(hi[a], cmax[a][k]); }
-    }
-  }
-  if (!present) return;
-  int e[3] = {bb_pick_exp(hi[0] - lo[0]), bb_pick_exp(hi[1] - lo[1]), bb_pick_exp(hi[2] - lo[2])};
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    uint32_t ql[4] = {0, 0, 0, 0}, qh[4] = {0, 0, 0, 0};
-    ok = bb_quant_children(lo[a], e[a], cmin[a], cmax[a], present, ql, qh) && ok;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if ((present >> k) & 1u) { cb[7 * k + 1 + a] = (uint8_t)ql[k]; cb[7 * k + 4 + a] = (uint8_t)qh[k]; }
-  }
-  if (!ok) atomicOr(res + 1, REFIT_ERR_QUANT);
-  refit_write_origin(w, lo, hi, e);
-#pragma unroll
-  for (int v = 0; v < 7; ++v) w[6 + v] = cw[v];
-  refit_store_box(fbox, it.x, lo, hi);
-}
-
-// the flags the host reads after a refit: is the TLAS root a single instance with the identity as inverse (the build's rule), and the
-// header of a re-staged top-of-tree image
-__global__ void refit_finish_kernel(const uint32_t* __restrict__ blas, uint32_t troot, const uint32_t* __restrict__ top_roots, uint32_t* __restrict__ res) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  uint32_t id = 0u;
-  if (is_inst_desc(troot)) {
-    const float* m = (const float*)(blas + (size_t)(troot & PAYLOAD_MASK) * (RT_BLAS_STRIDE / 4) + 1);
-    id = 1u;
-    for (int i = 0; i < 12; ++i) id = (id && m[i] == ((i % 5 == 0) ? 1.0f : 0.0f)) ? 1u : 0u;
-  }
-  res[2] = id;
-  if (top_roots) { res[3] = top_roots[0]; res[4] = top_roots[1]; }
-}
-
-// set_transforms, step 1: one thread per matrix -- transform and mat4_t::inverted() (geometry.h:1149-1192, MESA: operation order kept,
-// no contraction) into scratch (32 floats per record: inverse, transform); a non-finite input or inverse, or det == 0, flags res[6]
-__global__ __launch_bounds__(256) void refit_xform_kernel(const float* __restrict__ in, uint32_t n, float* __restrict__ out, uint32_t* __restrict__ res) {
-#pragma clang fp contract(off)
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  float c[16];
-  bool fin = true;
-  for (int k = 0; k < 16; ++k) { c[k] = in[(size_t)r * 16 + k]; fin = fin && isfinite(c[k]); }
-  const float inv[16] = {
-      c[5] * c[10] * c[15] - c[5] * c[11] * c[14] - c[9] * c[6] * c[15] + c[9] * c[7] * c[14] + c[13] * c[6] * c[11] - c[13] * c[7] * c[10],
-      -c[1] * c[10] * c[15] + c[1] * c[11] * c[14] + c[9] * c[2] * c[15] - c[9] * c[3] * c[14] - c[13] * c[2] * c[11] + c[13] * c[3] * c[10],
-      c[1] * c[6] * c[15] - c[1] * c[7] * c[14] - c[5] * c[2] * c[15] + c[5] * c[3] * c[14] + c[13] * c[2] * c[7] - c[13] * c[3] * c[6],
-      -c[1] * c[6] * c[11] + c[1] * c[7] * c[10] + c[5] * c[2] * c[11] - c[5] * c[3] * c[10] - c[9] * c[2] * c[7] + c[9] * c[3] * c[6],
-      -c[4] * c[10] * c[15] + c[4] * c[11] * c[14] + c[8] * c[6] * c[15] - c[8] * c[7] * c[14] - c[12] * c[6] * c[11] + c[12] * c[7] * c[10],
-      c[0] * c[10] * c[15] - c[0] * c[11] * c[14] - c[8] * c[2] * c[15] + c[8] * c[3] * c[14] + c[12] * c[2] * c[11] - c[12] * c[3] * c[10],
-      -c[0] * c[6] * c[15] + c[0] * c[7] * c[14] + c[4] * c[2] * c[15] - c[4] * c[3] * c[14] - c[12] * c[2] * c[7] + c[12] * c[3] * c[6],
-      c[0] * c[6] * c[11] - c[0] * c[7] * c[10] - c[4] * c[2] * c[11] + c[4] * c[3] * c[10] + c[8] * c[2] * c[7] - c[8] * c[3] * c[6],
-      c[4] * c[9] * c[15] - c[4] * c[11] * c[13] - c[8] * c[5] * c[15] + c[8] * c[7] * c[13] + c[12] * c[5] * c[11] - c[12] * c[7] * c[9],
-      -c[0] * c[9] * c[15] + c[0] * c[11] * c[13] + c[8] * c[1] * c[15] - c[8] * c[3] * c[13] - c[12] * c[1] * c[11] + c[12] * c[3] * c[9],
-      c[0] * c[5] * c[15] - c[0] * c[7] * c[13] - c[4] * c[1] * c[15] + c[4] * c[3] * c[13] + c[12] * c[1] * c[7] - c[12] * c[3] * c[5],
-      -c[0] * c[5] * c[11] + c[0] * c[7] * c[9] + c[4] * c[1] * c[11] - c[4] * c[3] * c[9] - c[8] * c[1] * c[7] + c[8] * c[3] * c[5],
-      -c[4] * c[9] * c[14] + c[4] * c[10] * c[13] + c[8] * c[5] * c[14] - c[8] * c[6] * c[13] - c[12] * c[5] * c[10] + c[12] * c[6] * c[9],
-      c[0] * c[9] * c[14] - c[0] * c[10] * c[13] - c[8] * c[1] * c[14] + c[8] * c[2] * c[13] + c[12] * c[1] * c[10] - c[12] * c[2] * c[9],
-      -c[0] * c[5] * c[14] + c[0] * c[6] * c[13] + c[4] * c[1] * c[14] - c[4] * c[2] * c[13] - c[12] * c[1] * c[6] + c[12] * c[2] * c[5],
-      c[0] * c[5] * c[10] - c[0] * c[6] * c[9] - c[4] * c[1] * c[10] + c[4] * c[2] * c[9] + c[8] * c[1] * c[6] - c[8] * c[2] * c[5]};
-  const float det = c[0] * inv[0] + c[1] * inv[4] + c[2] * inv[8] + c[3] * inv[12];
-  uint32_t err = fin ? 0u : REFIT_ERR_NONFINITE;
-  if (det == 0.0f) err |= REFIT_ERR_SINGULAR;
-  const float invdet = 1.0f / det;
-  float* o = out + (size_t)r * 32;
-  for (int k = 0; k < 16; ++k) {
-    const float v = inv[k] * invdet;
-    if (!isfinite(v)) err |= REFIT_ERR_SINGULAR;
-    o[k] = v;
-    o[16 + k] = c[k];
-  }
-  if (err) atomicOr(res + 6, err);
-}
-
-// set_transforms, step 2: the records take the new matrices only if every one of them passed step 1
-__global__ __launch_bounds__(256) void refit_xform_commit_kernel(const float* __restrict__ xf, uint32_t first, uint32_t n, uint32_t* __restrict__ blas,
-                                                                 const uint32_t* __restrict__ res) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * 32u || res[6] != 0u) return;
-  const uint32_t r = t / 32u, k = t % 32u;
-  blas[(size_t)(first + r) * (RT_BLAS_STRIDE / 4) + 1 + k] = __float_as_uint(xf[(size_t)r * 32 + k]);   // invTransform @4, transform @68
-}
-
-// ---------------------------------------------------------------------------------------------
 // host entry points (C ABI, include/vortex_hip.h level 2)
 // ---------------------------------------------------------------------------------------------
 #include <algorithm>
@@ -3167,116 +2089,6 @@ static uint32_t persistent_grid(K kernel, uint64_t jobs, int wg_threads = RT_WG_
   const uint64_t need = (jobs + (uint64_t)wg_threads - 1) / (uint64_t)wg_threads;
   if (g > need) g = need;
   return (uint32_t)(g ? g : 1);
-}
-
-// Mutable per-frame state.  An accel owns up to MAX_FRAMES_IN_FLIGHT of these and hands them out round
-// robin, so that renders issued on different streams overlap on the GPU (the tail of one persistent
-// launch, where most wavefronts have drained, is filled by the head of the next frame's launch); a
-// context is handed out again only behind the event of its previous render.
-#define MAX_FRAMES_IN_FLIGHT 8
-struct FrameCtx {
-  void* hitbuf = nullptr;      // W*H hit records between the traversal and the shading pass
-  uint64_t hitbuf_pixels = 0;
-  uint32_t* defer = nullptr;   // job list of the EXACT launch
-  uint64_t defer_cap = 0;
-  uint32_t* ctl = nullptr;     // control block (CTL_DWORDS), zero between frames
-  ShadeParams* pbatch = nullptr;   // per-frame shading parameters of a batch launch (VXRT_MAX_BATCH entries)
-  float* cam = nullptr; uint64_t cam_floats = 0;   // camera block of the context's camera frames (see CAM_HDR)
-  bool ctl_dirty = false;      // a call failed after touching it: clear before the next use
-  // mirror-bounce levels (allocated on first use; level 0 only holds `term`, one entry per pixel)
-  struct Level {
-    float* rays = nullptr; HitRec* hits = nullptr; uint32_t* parent = nullptr; float4* term = nullptr; float* col = nullptr;
-    float* srays = nullptr; float* stmax = nullptr; HitRec* shits = nullptr;
-    uint64_t cap = 0; uint32_t n = 0;
-  };
-  std::vector<Level> lv;
-  uint32_t* bcount = nullptr;  // device: rays appended to the level being built
-  // tile cost of the last frame and the order derived from it (render jobs, see lpt_order_kernel)
-  // one slot per batch size (slot 1 = single frames): a frame loop that alternates batch sizes keeps what it learned for each
-  struct Lpt { uint32_t* cost = nullptr; uint32_t* order = nullptr; uint32_t cap = 0; uint32_t key[6] = {0, 0, 0, 0, 0, 0}; bool valid = false; };
-  Lpt lpt[VXRT_MAX_BATCH + 1];
-  // ambient-occlusion pass (allocated on first use), one entry per pixel of the window
-  float4* ao_geo = nullptr; float4* ao_nrm = nullptr; float4* ao_col = nullptr; uint32_t* ao_cnt = nullptr;
-  uint32_t* ao_list = nullptr; uint32_t* ao_hdr = nullptr;   // pixels with a hit; [0] their number, [1] rays of the current batch
-  float* ao_rays = nullptr; float* ao_tmax = nullptr; HitRec* ao_hits = nullptr; uint64_t ao_cap = 0, ao_ray_cap = 0;
-  uint32_t* bin_hist = nullptr; uint32_t* bin_keys = nullptr; uint32_t* bin_order = nullptr; uint64_t bin_cap = 0, bin_ray_cap = 0;   // secondary-ray binning
-  void* pool_spill = nullptr; uint64_t pool_spill_bytes = 0;   // ray-pool trace kernel: the part of the slots' stacks that does not fit LDS
-  hipStream_t side = nullptr;
-  hipEvent_t ev_in = nullptr, ev_side = nullptr, ev_done = nullptr;
-  bool busy = false, inited = false, done_recorded = false;
-  hipStream_t last_stream = nullptr;
-};
-
-struct vxrt_accel {
-  SceneDev dev{};
-  vxrt_scene_t ref{};
-  void* nodes_c = nullptr; void* tri_w = nullptr; void* blas_root = nullptr;
-  void* top_img = nullptr; uint32_t* top_roots = nullptr;   // LDS-staged top of the tree: image; [0] n, [1] TLAS root, [2..] BLAS roots
-  FrameCtx ctx[MAX_FRAMES_IN_FLIGHT];
-  uint32_t n_ctx = 1, next_ctx = 0;
-  bool stream_seen = false, multi_stream = false; hipStream_t first_stream = nullptr;   // (see release_ctx)
-  float* uvtab = nullptr;      // camera tables: u[W] then v[H]
-  uint32_t uv_w = 0, uv_h = 0;
-  // camera pixels whose primary ray has a zero direction component (u == 0 or v == 0): listed on the
-  // host per (W, H, y0, y1) and traced by an EXACT launch on a side stream, concurrently with the main one
-  uint32_t* apriori = nullptr; // [0] count, [1..] job ids
-  uint32_t* batch_order[VXRT_MAX_BATCH + 1] = {}; uint32_t bo_tiles = 0;   // band-major tile order of a batch of k frames of bo_tiles tiles each, per k
-  uint32_t ap_count = 0, ap_key[6] = {0, 0, 0, 0, 0, 0};
-  uint64_t ap_cap = 0;
-  float max_reflectivity = 0.0f;   // over the instance records: > 0 enables the mirror-bounce path
-  unsigned long long* trace_wave_log = nullptr;   // diagnostic (vxrt_debug_trace_wave_log): per-wavefront log of the counting build's ray-buffer launches
-  unsigned long long* end_log = nullptr;   // diagnostic (vxrt_debug_end_log): where the main launches leave their wavefronts' end times
-  uint32_t levels = 0;             // internal levels on the longest root-to-leaf path (TLAS + BLAS), counted up to RT_SHALLOW_LEVELS + 1
-  bool shallow = false;            // levels <= RT_SHALLOW_LEVELS: the timed launches take the SHALLOW instantiations
-  int device = 0;
-  struct RefitPlan* refit = nullptr;   // vxrt_accel_refit: built at the first refit
-  uint32_t blas_status = 0;        // STATUS_FMA_DECODE_DIFFERS of the BLAS region as its last re-layout found it (build or GEOMETRY refit)
-  bool stale = false;              // a refit failed after it had started writing: every render / trace refuses until a refit succeeds
-};
-
-// The refit plan (vxrt_accel_refit): every tree's leaves and its internal nodes by level, taken once from the topology, which a refit
-// never changes.  Items of level L lie in [lv[L], lv[L + 1]) of the items array: (node, index of its child 0).
-struct RefitPlan {
-  uint32_t* blas_leaves = nullptr; uint32_t n_blas_leaves = 0;
-  uint2* blas_items = nullptr; std::vector<uint32_t> blas_lv;
-  uint32_t* tlas_leaves = nullptr; uint32_t n_tlas_leaves = 0;
-  uint2* tlas_items = nullptr; std::vector<uint32_t> tlas_lv;
-  float* fbox_bvh = nullptr; float* fbox_tlas = nullptr;   // one float box per node (scratch)
-  uint32_t* ranges = nullptr; uint32_t nb = 0;             // sorted BLAS node ranges for accel_nodes_kernel: bases, then ends
-  uint32_t* res = nullptr;                                 // REFIT_RES_WORDS
-  float* xf = nullptr; uint32_t xf_cap = 0;                // set_transforms: 32 floats per record
-};
-static void refit_plan_free(RefitPlan* p) {
-  if (!p) return;
-  (void)hipFree(p->blas_leaves); (void)hipFree(p->blas_items); (void)hipFree(p->tlas_leaves); (void)hipFree(p->tlas_items);
-  (void)hipFree(p->fbox_bvh); (void)hipFree(p->fbox_tlas); (void)hipFree(p->ranges); (void)hipFree(p->res); (void)hipFree(p->xf);
-  delete p;
-}
-
-static void accel_free(vxrt_accel* a) {
-  if (!a) return;
-  (void)hipDeviceSynchronize();
-  (void)hipFree(a->nodes_c); (void)hipFree(a->tri_w); (void)hipFree(a->blas_root);
-  (void)hipFree(a->top_img); (void)hipFree(a->top_roots);
-  refit_plan_free(a->refit);
-  (void)hipFree(a->uvtab); (void)hipFree(a->apriori);
-  for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) (void)hipFree(a->batch_order[k]);
-  for (FrameCtx& c : a->ctx) {
-    (void)hipFree(c.hitbuf); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
-    for (FrameCtx::Lpt& l : c.lpt) { (void)hipFree(l.cost); (void)hipFree(l.order); }
-    (void)hipFree(c.ao_geo); (void)hipFree(c.ao_nrm); (void)hipFree(c.ao_col); (void)hipFree(c.ao_cnt); (void)hipFree(c.ao_rays); (void)hipFree(c.ao_tmax); (void)hipFree(c.ao_hits); (void)hipFree(c.ao_list); (void)hipFree(c.ao_hdr);
-    (void)hipFree(c.bin_hist); (void)hipFree(c.bin_keys); (void)hipFree(c.bin_order);
-    for (FrameCtx::Level& l : c.lv) {
-      (void)hipFree(l.rays); (void)hipFree(l.hits); (void)hipFree(l.parent); (void)hipFree(l.term); (void)hipFree(l.col);
-      (void)hipFree(l.srays); (void)hipFree(l.stmax); (void)hipFree(l.shits);
-    }
-    (void)hipFree(c.pbatch); (void)hipFree(c.pool_spill); (void)hipFree(c.cam);
-    if (c.side) (void)hipStreamDestroy(c.side);
-    if (c.ev_in) (void)hipEventDestroy(c.ev_in);
-    if (c.ev_side) (void)hipEventDestroy(c.ev_side);
-    if (c.ev_done) (void)hipEventDestroy(c.ev_done);
-  }
-  delete a;
 }
 
 // next frame context, ordered on `s` behind its previous use
@@ -3348,348 +2160,11 @@ extern "C" int vxrt_internal_lpt_sort(const uint32_t* cost, uint32_t* order, uin
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+#include "rt_trace_experiments.inc"   // rt_pool_trace_kernel, rt_pair_trace_kernel, trace_experiment (VXRT_POOL=1|2)
+
 extern "C" {
 
 const char* vxrt_version(void) { return "vortex-rt-mi355x 0.3 (gfx950, compact 64-byte nodes, persistent wavefronts)"; }
-
-int vxrt_accel_build(const vxrt_scene_t* s, void* stream, vxrt_accel_t** out) {
-  if (!s || !out || !s->tlas || !s->blas || !s->bvh || !s->tri) return -1;
-  if (s->n_tlas_nodes == 0 || s->n_blas == 0 || s->n_bvh_nodes == 0 || s->n_tris == 0) return -1;
-  if ((uint64_t)s->n_tlas_nodes + s->n_bvh_nodes > PAYLOAD_MASK || s->n_tris >= 0x7fffffffu) return -1;   // one compact index space
-  hipStream_t st = (hipStream_t)stream;
-  // instance node ranges (host side, n_blas is small): sorted unique bvh_offsets
-  std::vector<uint32_t> recs((size_t)s->n_blas * (RT_BLAS_STRIDE / 4));
-  if (hipStreamSynchronize(st) != hipSuccess) return -1;
-  if (hipMemcpy(recs.data(), s->blas, recs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  std::vector<uint32_t> bases;
-  float max_refl = 0.0f;
-  for (uint32_t j = 0; j < s->n_blas; ++j) {
-    const uint32_t off = recs[(size_t)j * (RT_BLAS_STRIDE / 4)];
-    if (off >= s->n_bvh_nodes) return -1;
-    bases.push_back(off);
-    float refl;
-    memcpy(&refl, &recs[(size_t)j * (RT_BLAS_STRIDE / 4) + 38], sizeof(float));   // blas_node_t::reflectivity @152
-    if (refl > max_refl) max_refl = refl;
-  }
-  std::sort(bases.begin(), bases.end());
-  bases.erase(std::unique(bases.begin(), bases.end()), bases.end());
-  std::vector<uint32_t> ends(bases.size());
-  for (size_t j = 0; j < bases.size(); ++j) ends[j] = j + 1 < bases.size() ? bases[j + 1] : s->n_bvh_nodes;
-
-  auto a = new (std::nothrow) vxrt_accel();
-  if (!a) return -1;
-  a->ref = *s;
-  a->max_reflectivity = max_refl;
-  (void)hipGetDevice(&a->device);
-  uint32_t* d_ranges = nullptr;
-  uint32_t* d_status = nullptr;
-  uint32_t* d_troot = nullptr;
-  constexpr uint32_t TOP_CAP = RT_TOP_NODES;
-  // slot descriptors use bit 29 of the payload: only scenes whose compact index space stays below it are staged
-  const bool stage_top = TOP_CAP > 0 && (uint64_t)s->n_tlas_nodes + s->n_bvh_nodes < DESC_TOP_FLAG;
-  bool ok = hipMalloc(&a->nodes_c, ((size_t)s->n_tlas_nodes + s->n_bvh_nodes) * CNODE_VEC4 * 16) == hipSuccess &&
-            (!stage_top || (hipMalloc(&a->top_img, (size_t)TOP_CAP * CNODE_VEC4 * 16) == hipSuccess &&
-                            hipMalloc((void**)&a->top_roots, ((size_t)s->n_blas + 2) * sizeof(uint32_t)) == hipSuccess)) &&
-            hipMalloc(&a->tri_w, (size_t)s->n_tris * WTRI_FLOATS * 4) == hipSuccess &&
-            hipMalloc(&a->blas_root, (size_t)s->n_blas * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc((void**)&d_ranges, bases.size() * 8) == hipSuccess &&
-            hipMalloc((void**)&d_status, 8) == hipSuccess && hipMalloc((void**)&d_troot, 4) == hipSuccess;
-  uint32_t hstatus = 0, troot = DESC_DONE, hstatus2[2] = {0, 0};   // [1]: what the BLAS re-layout found (kept for the refit)
-  if (ok) {
-    ok = hipMemcpy(d_ranges, bases.data(), bases.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d_ranges + bases.size(), ends.data(), ends.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(d_status, 0, 8) == hipSuccess;
-  }
-  if (ok) {
-    const uint32_t nb = (uint32_t)bases.size();
-    hipLaunchKernelGGL(accel_nodes_kernel, dim3((s->n_tlas_nodes + 255) / 256), dim3(256), 0, st, (const uint32_t*)s->tlas, s->n_tlas_nodes,
-                       (uint4*)a->nodes_c, 1, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, s->n_tris, s->n_blas, 0u, d_status);
-    hipLaunchKernelGGL(accel_nodes_kernel, dim3((s->n_bvh_nodes + 255) / 256), dim3(256), 0, st, (const uint32_t*)s->bvh, s->n_bvh_nodes,
-                       (uint4*)a->nodes_c + (size_t)s->n_tlas_nodes * CNODE_VEC4, 0, d_ranges, d_ranges + nb, nb, s->n_tris, s->n_blas, s->n_tlas_nodes, d_status + 1);
-    hipLaunchKernelGGL(accel_tris_kernel, dim3((s->n_tris + 255) / 256), dim3(256), 0, st, (const float*)s->tri, s->n_tris, (float4*)a->tri_w);
-    hipLaunchKernelGGL(accel_roots_kernel, dim3((s->n_blas + 1 + 255) / 256), dim3(256), 0, st, (const uint32_t*)s->tlas, (const uint32_t*)s->bvh,
-                       (const uint32_t*)s->blas, s->n_tlas_nodes, s->n_bvh_nodes, s->n_blas, s->n_tris, d_troot, (uint32_t*)a->blas_root, d_status);
-    if (s->triEx && s->mat && s->n_mats) {
-      const uint32_t nchk = std::max(s->n_tris, s->n_mats);
-      hipLaunchKernelGGL(accel_check_shading_kernel, dim3((nchk + 255) / 256), dim3(256), 0, st, (const rt_triex_t*)s->triEx, s->n_tris,
-                         (const rt_material_t*)s->mat, s->n_mats, (uint64_t)s->tex_bytes, s->tex ? 1 : 0, d_status);
-    }
-    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
-         hipMemcpy(hstatus2, d_status, 8, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(&troot, d_troot, 4, hipMemcpyDeviceToHost) == hipSuccess;
-    hstatus = hstatus2[0] | hstatus2[1];
-    a->blas_status = hstatus2[1] & STATUS_FMA_DECODE_DIFFERS;
-  }
-  uint32_t n_top = 0, troot_top = troot;
-  if (ok && stage_top && (hstatus & (STATUS_BAD_SCENE | STATUS_FMA_DECODE_DIFFERS)) == 0) {
-    ok = hipMemsetAsync(a->top_img, 0, (size_t)TOP_CAP * CNODE_VEC4 * 16, st) == hipSuccess;
-    hipLaunchKernelGGL(accel_top_kernel, dim3(1), dim3(64), 0, st, (const uint4*)a->nodes_c, troot, (const uint32_t*)a->blas_root, s->n_blas, TOP_CAP,
-                       (uint4*)a->top_img, a->top_roots, a->top_roots + 1, a->top_roots + 2);
-    uint32_t hdr[2] = {0, DESC_DONE};
-    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
-         hipMemcpy(hdr, a->top_roots, sizeof hdr, hipMemcpyDeviceToHost) == hipSuccess;
-    n_top = hdr[0]; troot_top = hdr[1];
-  }
-  // depth class of the scene (see accel_depth_kernel): RT_SHALLOW_LEVELS + 1 passes, no host round trip in between -- a scene that still
-  // reaches new nodes in the last one is deeper than the class
-  uint32_t levels = 0;
-  if (ok && (hstatus & STATUS_BAD_SCENE) == 0) {
-    const uint32_t nc = s->n_tlas_nodes + s->n_bvh_nodes;
-    uint32_t* d_depth = nullptr;
-    ok = hipMalloc((void**)&d_depth, ((size_t)nc + 1) * 4) == hipSuccess && hipMemsetAsync(d_depth, 0, ((size_t)nc + 1) * 4, st) == hipSuccess;
-    if (ok) {
-      for (uint32_t level = 1; level <= RT_SHALLOW_LEVELS + 1u; ++level)
-        hipLaunchKernelGGL(accel_depth_kernel, dim3(level == 1u ? 1u : (nc + 255) / 256), dim3(256), 0, st, (const uint4*)a->nodes_c, nc, troot,
-                           (const uint32_t*)a->blas_root, level, d_depth, d_depth + nc);
-      ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
-           hipMemcpy(&levels, d_depth + nc, 4, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    (void)hipFree(d_depth);
-  }
-  (void)hipFree(d_ranges); (void)hipFree(d_status); (void)hipFree(d_troot);
-  if (!ok || (hstatus & STATUS_BAD_SCENE) != 0) { accel_free(a); return -1; }   // malformed tree: rejected before any traversal
-  static const int shallow_env = [] { const char* e = getenv("VXRT_SHALLOW"); return e ? atoi(e) : -1; }();   // (measurement knob: 0 = full-size stacks for every scene)
-  a->levels = levels;
-  a->shallow = levels <= RT_SHALLOW_LEVELS && shallow_env != 0;
-  a->dev.nodes_c = (const uint4*)a->nodes_c; a->dev.ref_tlas = (const uint32_t*)s->tlas; a->dev.n_tlas = s->n_tlas_nodes; a->dev.tri_w = (const float4*)a->tri_w;
-  a->dev.blas_root = (const uint32_t*)a->blas_root; a->dev.tlas_root = troot;
-  a->dev.ident_root = 0u;
-  if (troot >= 0xC0000000u && troot < DESC_IDLE) {   // (an instance descriptor) a single instance under the TLAS root: is its inverse transform (dwords 1-12 of the record) the identity?
-    float m[12];
-    static const bool ident_off = [] { const char* e = getenv("VXRT_IDENT_ROOT"); return e && e[0] == '0'; }();
-    if (!ident_off && hipMemcpy(m, (const uint32_t*)s->blas + (size_t)(troot & PAYLOAD_MASK) * (RT_BLAS_STRIDE / 4) + 1, sizeof m, hipMemcpyDeviceToHost) == hipSuccess) {
-      bool id = true;
-      for (int i = 0; i < 12; ++i) id = id && m[i] == ((i % 5 == 0) ? 1.0f : 0.0f);     // (m[0], m[5], m[10] on the diagonal; -0 == 0)
-      a->dev.ident_root = id ? 1u : 0u;
-    }
-  }
-  a->dev.exact_decode = (hstatus & STATUS_FMA_DECODE_DIFFERS) ? 1u : 0u;
-  a->dev.ref_bvh = (const uint32_t*)s->bvh;
-  a->dev.blas = (const uint32_t*)s->blas; a->dev.triEx = (const rt_triex_t*)s->triEx;
-  a->dev.mat = (const rt_material_t*)s->mat; a->dev.tex = (const uint8_t*)s->tex;
-  a->dev.top_img = (const uint4*)a->top_img; a->dev.n_top = n_top; a->dev.tlas_root_top = troot_top;
-  a->dev.blas_root_top = n_top ? a->top_roots + 2 : (const uint32_t*)a->blas_root;
-  if (getenv("VXRT_DEBUG")) fprintf(stderr, "[vxrt] accel: %u top-of-tree nodes staged for LDS (cap %u)\n", n_top, TOP_CAP);
-  *out = a;
-  return 0;
-}
-
-int vxrt_accel_destroy(vxrt_accel_t* a) {
-  if (!a) return 0;
-  accel_free(a);
-  return 0;
-}
-
-uint64_t vxrt_accel_bytes(const vxrt_accel_t* a) {
-  if (!a) return 0;
-  return (uint64_t)a->ref.n_tlas_nodes * CNODE_VEC4 * 16 + (uint64_t)a->ref.n_bvh_nodes * CNODE_VEC4 * 16 +
-         (uint64_t)a->ref.n_tris * WTRI_FLOATS * 4 + (uint64_t)a->ref.n_blas * 4;
-}
-
-int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
-  if (!a || !value) return -1;
-  switch (which) {
-  case 0: *value = a->levels; return 0;            // internal levels on the longest root-to-leaf path, counted up to RT_SHALLOW_LEVELS + 1
-  case 1: *value = a->shallow ? 1u : 0u; return 0; // the timed launches take the SHALLOW instantiations (48-entry stacks)
-  case 2: *value = a->dev.ident_root; return 0;    // the TLAS root is one identity instance (rays keep their world coordinates)
-  case 3: *value = a->dev.exact_decode; return 0;  // the scene takes the ldexp decode / generic slab form
-  }
-  return -1;
-}
-
-int vxrt_accel_frames_in_flight(vxrt_accel_t* a, uint32_t n) {
-  if (!a || n < 1 || n > MAX_FRAMES_IN_FLIGHT) return -1;
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  a->n_ctx = n; a->next_ctx = 0;
-  return 0;
-}
-
-// The refit plan, built on the host from the reference nodes (the topology never changes, so this runs once per accel): breadth-first
-// from the TLAS root and from every distinct BLAS root (sorted unique bvh_offsets, as the build takes them; a BLAS shared by several
-// instances is one tree), each node's level within its own tree; internal nodes are bucketed by level (count, scan, scatter).
-// a refit that fails reports where with VXRT_DEBUG set, and leaves no HIP error behind for the caller's next launch to trip over
-static int refit_fail(const char* where) {
-  const hipError_t e = hipGetLastError();
-  if (getenv("VXRT_DEBUG")) fprintf(stderr, "[vxrt] refit failed: %s (%s)\n", where, hipGetErrorString(e));
-  return -1;
-}
-
-static RefitPlan* refit_plan_build(vxrt_accel* a, hipStream_t st) {
-  const vxrt_scene_t& s = a->ref;
-  std::vector<uint32_t> tl((size_t)s.n_tlas_nodes * RT_NODE_DWORDS), bv((size_t)s.n_bvh_nodes * RT_NODE_DWORDS), recs((size_t)s.n_blas * (RT_BLAS_STRIDE / 4));
-  if (hipStreamSynchronize(st) != hipSuccess ||
-      hipMemcpy(tl.data(), s.tlas, tl.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(bv.data(), s.bvh, bv.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(recs.data(), s.blas, recs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { refit_fail("plan: node copy"); return nullptr; }
-  std::vector<uint32_t> bases;
-  for (uint32_t j = 0; j < s.n_blas; ++j) bases.push_back(recs[(size_t)j * (RT_BLAS_STRIDE / 4)]);
-  std::sort(bases.begin(), bases.end());
-  bases.erase(std::unique(bases.begin(), bases.end()), bases.end());
-  std::vector<uint32_t> ends(bases.size());
-  for (size_t j = 0; j < bases.size(); ++j) ends[j] = j + 1 < bases.size() ? bases[j + 1] : s.n_bvh_nodes;
-  // one tree: leaves out, internal nodes (node, child 0) with their level; false on an index the build would have rejected
-  auto walk = [](const std::vector<uint32_t>& w, uint32_t root, uint32_t base, uint32_t end, bool tlas, std::vector<uint32_t>& leaves,
-                 std::vector<std::pair<uint32_t, uint2>>& items) -> bool {
-    std::vector<std::pair<uint32_t, uint32_t>> q{{root, 0u}};
-    for (size_t h = 0; h < q.size(); ++h) {
-      const uint32_t i = q[h].first, L = q[h].second;
-      const uint32_t* n = w.data() + (size_t)i * RT_NODE_DWORDS;
-      if (tlas ? n[5] != 0xffffffffu : n[5] != 0u) { leaves.push_back(i); continue; }
-      const uint64_t c0 = (uint64_t)base + n[4];
-      items.push_back({L, make_uint2(i, (uint32_t)c0)});
-      const uint8_t* b = (const uint8_t*)n;
-      bool any = false;
-      for (uint32_t k = 0; k < 4; ++k) {
-        if (b[24 + 7 * k] == 0) continue;
-        if (c0 + k >= end || c0 + k <= i) return false;
-        q.push_back({(uint32_t)(c0 + k), L + 1u});
-        any = true;
-      }
-      if (!any) return false;   // an internal node without a child has no box to refit from: refused before anything is written
-    }
-    return true;
-  };
-  std::vector<uint32_t> bl, tlv;
-  std::vector<std::pair<uint32_t, uint2>> bi, ti;
-  for (size_t j = 0; j < bases.size(); ++j)
-    if (!walk(bv, bases[j], bases[j], ends[j], false, bl, bi)) { refit_fail("plan: BLAS walk"); return nullptr; }
-  if (!walk(tl, 0u, 0u, s.n_tlas_nodes, true, tlv, ti)) { refit_fail("plan: TLAS walk"); return nullptr; }
-  for (uint32_t i : tlv) if (tl[(size_t)i * RT_NODE_DWORDS + 5] >= s.n_blas) { refit_fail("plan: instance index"); return nullptr; }
-  auto bucket = [](const std::vector<std::pair<uint32_t, uint2>>& it, std::vector<uint2>& out, std::vector<uint32_t>& lv) {
-    uint32_t depth = 0;
-    for (const auto& x : it) depth = std::max(depth, x.first + 1u);
-    lv.assign(depth + 1u, 0u);
-    for (const auto& x : it) ++lv[x.first + 1u];
-    for (uint32_t L = 0; L < depth; ++L) lv[L + 1u] += lv[L];
-    std::vector<uint32_t> pos(lv.begin(), lv.end() - 1);
-    out.resize(it.size());
-    for (const auto& x : it) out[pos[x.first]++] = x.second;
-  };
-  std::vector<uint32_t> ranges(bases);   // bases, then ends
-  ranges.insert(ranges.end(), ends.begin(), ends.end());
-  std::vector<uint2> bitems, titems;
-  auto p = new (std::nothrow) RefitPlan();
-  if (!p) return nullptr;
-  bucket(bi, bitems, p->blas_lv);
-  bucket(ti, titems, p->tlas_lv);
-  p->n_blas_leaves = (uint32_t)bl.size(); p->n_tlas_leaves = (uint32_t)tlv.size(); p->nb = (uint32_t)bases.size();
-  auto up = [](void** d, const void* h, size_t bytes) {
-    return hipMalloc(d, std::max<size_t>(bytes, 16)) == hipSuccess && (bytes == 0 || hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess);
-  };
-  const bool ok = up((void**)&p->blas_leaves, bl.data(), bl.size() * 4) && up((void**)&p->blas_items, bitems.data(), bitems.size() * 8) &&
-                  up((void**)&p->tlas_leaves, tlv.data(), tlv.size() * 4) && up((void**)&p->tlas_items, titems.data(), titems.size() * 8) &&
-                  up((void**)&p->ranges, ranges.data(), ranges.size() * 4) &&
-                  hipMalloc((void**)&p->fbox_bvh, (size_t)s.n_bvh_nodes * 24) == hipSuccess &&
-                  hipMalloc((void**)&p->fbox_tlas, (size_t)s.n_tlas_nodes * 24) == hipSuccess &&
-                  hipMalloc((void**)&p->res, REFIT_RES_WORDS * 4) == hipSuccess;
-  if (!ok) { refit_fail("plan: upload"); refit_plan_free(p); return nullptr; }
-  return p;
-}
-
-// Everything of one refit after the plan exists: the box passes, the re-layout, one host synchronisation, the flags.  `xf_first` /
-// `xf_count`: set_transforms' records (its two kernels run first, on the same stream); xf_count == 0 for a plain refit.
-static int refit_run(vxrt_accel* a, uint32_t what, hipStream_t st, const float* xf_in, uint32_t xf_first, uint32_t xf_count) {
-  RefitPlan* p = a->refit;
-  const vxrt_scene_t& s = a->ref;
-  // ordered after every call already issued on this accel, on any stream
-  for (uint32_t k = 0; k < MAX_FRAMES_IN_FLIGHT; ++k) {
-    FrameCtx& c = a->ctx[k];
-    if (!c.busy || c.last_stream == st) continue;
-    if (c.done_recorded) { if (hipStreamWaitEvent(st, c.ev_done, 0) != hipSuccess) return refit_fail("ordering"); }
-    else if (hipDeviceSynchronize() != hipSuccess) return refit_fail("ordering");
-  }
-  const bool geom = (what & VXRT_REFIT_GEOMETRY) != 0u;
-  auto grid = [](uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); };
-  bool ok = hipMemsetAsync(p->res, 0, REFIT_RES_WORDS * 4, st) == hipSuccess;
-  if (ok && xf_count) {
-    hipLaunchKernelGGL(refit_xform_kernel, grid(xf_count), dim3(256), 0, st, xf_in, xf_count, p->xf, p->res);
-    hipLaunchKernelGGL(refit_xform_commit_kernel, grid((uint64_t)xf_count * 32u), dim3(256), 0, st, (const float*)p->xf, xf_first, xf_count,
-                       (uint32_t*)s.blas, (const uint32_t*)p->res);
-  }
-  if (ok && geom) {
-    if (p->n_blas_leaves)
-      hipLaunchKernelGGL(refit_blas_leaf_kernel, grid(p->n_blas_leaves), dim3(256), 0, st, (uint32_t*)s.bvh, (const float*)s.tri, p->blas_leaves,
-                         p->n_blas_leaves, p->fbox_bvh, p->res);
-    for (size_t L = p->blas_lv.size() - 1; L-- > 0;) {
-      const uint32_t n = p->blas_lv[L + 1] - p->blas_lv[L];
-      if (n) hipLaunchKernelGGL(refit_level_kernel, grid(n), dim3(256), 0, st, (uint32_t*)s.bvh, p->blas_items + p->blas_lv[L], n, p->fbox_bvh, p->res);
-    }
-  }
-  if (ok) {
-    if (p->n_tlas_leaves)
-      hipLaunchKernelGGL(refit_instance_kernel, grid(p->n_tlas_leaves), dim3(256), 0, st, (uint32_t*)s.tlas, p->tlas_leaves, p->n_tlas_leaves,
-                         (const uint32_t*)s.blas, (const uint32_t*)s.bvh, (const float*)s.tri, geom ? (const float*)p->fbox_bvh : (const float*)nullptr,
-                         p->fbox_tlas, p->res);
-    for (size_t L = p->tlas_lv.size() - 1; L-- > 0;) {
-      const uint32_t n = p->tlas_lv[L + 1] - p->tlas_lv[L];
-      if (n) hipLaunchKernelGGL(refit_level_kernel, grid(n), dim3(256), 0, st, (uint32_t*)s.tlas, p->tlas_items + p->tlas_lv[L], n, p->fbox_tlas, p->res);
-    }
-    // the re-layout of vxrt_accel_build over what moved
-    hipLaunchKernelGGL(accel_nodes_kernel, grid(s.n_tlas_nodes), dim3(256), 0, st, (const uint32_t*)s.tlas, s.n_tlas_nodes,
-                       (uint4*)a->nodes_c, 1, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, s.n_tris, s.n_blas, 0u, p->res);
-    if (geom) {
-      hipLaunchKernelGGL(accel_nodes_kernel, grid(s.n_bvh_nodes), dim3(256), 0, st, (const uint32_t*)s.bvh, s.n_bvh_nodes,
-                         (uint4*)a->nodes_c + (size_t)s.n_tlas_nodes * CNODE_VEC4, 0, p->ranges, p->ranges + p->nb, p->nb, s.n_tris, s.n_blas, s.n_tlas_nodes,
-                         p->res + 5);
-      hipLaunchKernelGGL(accel_tris_kernel, grid(s.n_tris), dim3(256), 0, st, (const float*)s.tri, s.n_tris, (float4*)a->tri_w);
-    }
-    if (a->top_img) {   // re-staged whatever the flags say; used only if the scene keeps the fma decode (as the build decides)
-      ok = hipMemsetAsync(a->top_img, 0, (size_t)RT_TOP_NODES * CNODE_VEC4 * 16, st) == hipSuccess;
-      hipLaunchKernelGGL(accel_top_kernel, dim3(1), dim3(64), 0, st, (const uint4*)a->nodes_c, a->dev.tlas_root, (const uint32_t*)a->blas_root, s.n_blas,
-                         (uint32_t)RT_TOP_NODES, (uint4*)a->top_img, a->top_roots, a->top_roots + 1, a->top_roots + 2);
-    }
-    hipLaunchKernelGGL(refit_finish_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)s.blas, a->dev.tlas_root, (const uint32_t*)a->top_roots, p->res);
-  }
-  uint32_t res[REFIT_RES_WORDS] = {0};
-  ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
-       hipMemcpy(res, p->res, sizeof res, hipMemcpyDeviceToHost) == hipSuccess;
-  // (from here on the boxes in the scene's buffers and the layout are the refit's: either it all holds, or the accel is stale)
-  if (!ok || res[1] != 0u || ((res[0] | res[5]) & STATUS_BAD_SCENE) != 0u) {
-    a->stale = true;
-    if (getenv("VXRT_DEBUG")) fprintf(stderr, "[vxrt] refit: ok %d, errors %u, status %u / %u\n", (int)ok, res[1], res[0], res[5]);
-    return refit_fail("boxes");
-  }
-  if (geom) a->blas_status = res[5] & STATUS_FMA_DECODE_DIFFERS;
-  const uint32_t st_all = (res[0] & STATUS_FMA_DECODE_DIFFERS) | a->blas_status;
-  a->dev.exact_decode = st_all ? 1u : 0u;
-  static const bool ident_off = [] { const char* e = getenv("VXRT_IDENT_ROOT"); return e && e[0] == '0'; }();
-  a->dev.ident_root = ident_off ? 0u : res[2];
-  if (a->top_img && !st_all) {
-    a->dev.n_top = res[3]; a->dev.tlas_root_top = res[4]; a->dev.blas_root_top = a->top_roots + 2;
-  } else {
-    a->dev.n_top = 0; a->dev.tlas_root_top = a->dev.tlas_root; a->dev.blas_root_top = (const uint32_t*)a->blas_root;
-  }
-  a->stale = false;
-  return res[6] != 0u ? -1 : 0;   // set_transforms: a matrix was refused, the records are unchanged (and the refit of them holds)
-}
-
-static int refit_prepare(vxrt_accel* a, uint32_t what, hipStream_t st) {
-  if (!a || (what & ~(uint32_t)(VXRT_REFIT_INSTANCES | VXRT_REFIT_GEOMETRY)) != 0u) return -1;
-  if (!a->refit && !(a->refit = refit_plan_build(a, st))) return -1;
-  return 0;
-}
-
-int vxrt_accel_refit(vxrt_accel_t* a, uint32_t what, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (refit_prepare(a, what, st) != 0) return -1;
-  if (what == 0u) return a->stale ? -1 : 0;
-  if (a->stale) what |= VXRT_REFIT_GEOMETRY;   // (the BLAS boxes of a failed GEOMETRY refit are not trusted: redo them)
-  return refit_run(a, what, st, nullptr, 0, 0);
-}
-
-int vxrt_accel_set_transforms(vxrt_accel_t* a, uint32_t first, uint32_t count, const float* transforms, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (!a || (count && !transforms) || (uint64_t)first + count > a->ref.n_blas) return -1;
-  if (refit_prepare(a, VXRT_REFIT_INSTANCES, st) != 0) return -1;
-  RefitPlan* p = a->refit;
-  if (count > p->xf_cap) {
-    if (hipStreamSynchronize(st) != hipSuccess) return refit_fail("scratch");
-    (void)hipFree(p->xf); p->xf = nullptr; p->xf_cap = 0;
-    if (hipMalloc((void**)&p->xf, (size_t)count * 32 * sizeof(float)) != hipSuccess) return refit_fail("scratch");
-    p->xf_cap = count;
-  }
-  return refit_run(a, a->stale ? (VXRT_REFIT_INSTANCES | VXRT_REFIT_GEOMETRY) : VXRT_REFIT_INSTANCES, st, transforms, first, count);
-}
 
 static int ensure_defer(FrameCtx* c, uint64_t jobs, hipStream_t s) {
   if (c->defer_cap >= jobs) return 0;
@@ -3733,34 +2208,9 @@ static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_
   X.total_dev = nullptr;   // the EXACT launch takes its count from the deferral list
   X.order = nullptr;
   ShadeParams p{};
-  // incoherent rays: the ray-pool kernel (rt_pool_trace_kernel; VXRT_POOL=0/1 forces the choice), timed builds only
+  // incoherent rays: the ray-pool kernel (1) or two rays per lane (2) instead of the persistent kernel, timed builds only
   static const int pool_env = [] { const char* e = getenv("VXRT_POOL"); return e ? atoi(e) : 0; }();
-  if (pool_env == 2 && !stats_counters) {     // two rays per lane (rt_pair_trace_kernel)
-#define LAUNCH_PAIR(LD, SH) do { \
-      hipLaunchKernelGGL((rt_pair_trace_kernel<LD, SH>), dim3(persistent_grid(rt_pair_trace_kernel<LD, SH>, n / 2, 64)), dim3(64), 0, s, a->dev, A); \
-      hipLaunchKernelGGL((rt_persistent_kernel<JOB_TRACE, 0, LD, true>), dim3(std::max<uint32_t>(EXACT_GRID, persistent_grid(rt_persistent_kernel<JOB_TRACE, 0, LD, true>, n / 8, 256))), dim3(256), 0, s, a->dev, p, X); } while (0)
-    if (a->shallow) { if (a->dev.exact_decode) LAUNCH_PAIR(true, true); else LAUNCH_PAIR(false, true); }
-    else            { if (a->dev.exact_decode) LAUNCH_PAIR(true, false); else LAUNCH_PAIR(false, false); }
-#undef LAUNCH_PAIR
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  if (pool_env == 1 && !stats_counters) {
-#define LAUNCH_POOL(LD, SH) do { \
-      const uint32_t g = persistent_grid(rt_pool_trace_kernel<LD, SH>, n, 64); \
-      const uint64_t need = (uint64_t)g * RT_POOL_SLOTS * ((SH ? 3 * RT_SHALLOW_LEVELS : 3 * RT_MAX_LEVELS + RT_POOL_LSTK) - RT_POOL_LSTK) * sizeof(uint2); \
-      if (c->pool_spill_bytes < need) { \
-        if (hipStreamSynchronize(s) != hipSuccess) return -1; \
-        (void)hipFree(c->pool_spill); c->pool_spill = nullptr; c->pool_spill_bytes = 0; \
-        if (hipMalloc(&c->pool_spill, need) != hipSuccess) return -1; \
-        c->pool_spill_bytes = need; \
-      } \
-      hipLaunchKernelGGL((rt_pool_trace_kernel<LD, SH>), dim3(g), dim3(64), 0, s, a->dev, A, (uint2*)c->pool_spill); \
-      hipLaunchKernelGGL((rt_persistent_kernel<JOB_TRACE, 0, LD, true>), dim3(std::max<uint32_t>(EXACT_GRID, persistent_grid(rt_persistent_kernel<JOB_TRACE, 0, LD, true>, n / 8, 256))), dim3(256), 0, s, a->dev, p, X); } while (0)
-    if (a->shallow) { if (a->dev.exact_decode) LAUNCH_POOL(true, true); else LAUNCH_POOL(false, true); }
-    else            { if (a->dev.exact_decode) LAUNCH_POOL(true, false); else LAUNCH_POOL(false, false); }
-#undef LAUNCH_POOL
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
+  if ((pool_env == 1 || pool_env == 2) && !stats_counters) return trace_experiment(pool_env, a, c, n, s, p, A, X);
 #define LAUNCH_TJ(J, ST, LD, SH) do { \
     hipLaunchKernelGGL((rt_persistent_kernel<J, ST, LD, false, false, SH>), dim3(persistent_grid(rt_persistent_kernel<J, ST, LD, false, false, SH>, n)), dim3(RT_WG_THREADS), 0, s, a->dev, p, A); \
     hipLaunchKernelGGL((rt_persistent_kernel<JOB_TRACE, ST, LD, true>), dim3(std::max<uint32_t>(EXACT_GRID, persistent_grid(rt_persistent_kernel<JOB_TRACE, ST, LD, true>, n / 8, 256))), dim3(256), 0, s, a->dev, p, X); } while (0)

@@ -60,3 +60,39 @@ struct rt_material_t {         // common.h:20-36
   uint64_t tex_offset;
 };
 static_assert(sizeof(rt_material_t) == RT_MAT_BYTES, "material layout");
+
+// ---------------------------------------------------------------------------------------------
+// Compact device layout derived from the buffers above (built by rt_accel.hip, traversed by rt_kernels.hip; the layout
+// itself is described in rt_internal.h).  Here, and not in rt_internal.h, because every value below is compiled into the
+// timed kernels: this header is part of the kernels' source id.
+// ---------------------------------------------------------------------------------------------
+#define DK_TLAS 0u
+#define DK_BLAS 1u
+#define DK_LEAF 2u
+#define DK_INST 3u
+#define DESC(kind, payload) (((kind) << 30) | (payload))
+#define DESC_DONE 0xFFFFFFFEu   // traversal of the lane's ray has ended
+#define DESC_IDLE 0xFFFFFFFDu   // lane has no ray
+#define DESC_NONE 0xFFFFFFFFu   // compact node: empty child slot
+#define PAYLOAD_MASK 0x3FFFFFFFu
+#define DESC_TOP_FLAG 0x20000000u   // node descriptor: payload = slot of the LDS-staged top-of-tree image (kernels with USE_TOP only)
+#define DESC_TOP_SLOT 0x0000FFFFu
+#define LEAF_FIRST_BITS 26
+#define LEAF_FIRST_MASK 0x03FFFFFFu
+#define LEAF_MAX_INLINE 15u
+#define CNODE_VEC4 4
+#define WTRI_FLOATS 12
+#ifndef RT_SHALLOW_LEVELS
+#define RT_SHALLOW_LEVELS 16  // internal levels (TLAS + BLAS) up to which a scene takes the SHALLOW instantiations: 48 stack entries instead of 96 + the LDS levels
+#endif
+#ifndef RT_TOP_NODES
+#define RT_TOP_NODES 0      // internal nodes of the top of the tree staged in LDS per workgroup (64 B each); 0 = off
+#endif
+#define RT_TOP_MAX 1024
+static_assert(RT_TOP_NODES <= RT_TOP_MAX, "top-of-tree image");
+#ifdef __HIPCC__   // what kind of work a descriptor names (device code of both units)
+__device__ __forceinline__ bool is_node_desc(uint32_t d) { return d < 0x80000000u; }
+__device__ __forceinline__ bool is_leaf_desc(uint32_t d) { return (d >> 30) == DK_LEAF; }
+__device__ __forceinline__ bool is_inst_desc(uint32_t d) { return d >= 0xC0000000u && d < DESC_IDLE; }
+__device__ __forceinline__ bool is_work_desc(uint32_t d) { return d < DESC_IDLE; }
+#endif
