@@ -480,7 +480,16 @@ int vxrt_trace(vxrt_accel_t* accel, const float* rays, uint64_t n, const float* 
 
 /* Closest-hit / miss shader over n (ray, hit record) pairs -- the hit records vxrt_trace wrote for those rays: f32 colour (3 per
  * ray, optional) and packed RGB8 (optional) as closest.cpp:57-127 (no secondary ray) / miss.cpp:9-14 / common.h:149-154 compute
- * them.  The records must come from this accel (their blasIdx / triIdx are followed unchecked). */
+ * them.  The records must come from this accel (their blasIdx / triIdx are followed unchecked).
+ *
+ * Conversions C leaves undefined.  The reference's shader casts floats that need not fit: uint32_t(u * width) in texSample
+ * (rtx_shading.h:7-8) and int(min(c, 1) * 255) in RGB32FtoRGB8 (common.h:149-154).  Every finite or non-finite scene value and shade
+ * parameter is accepted, and this shader -- here and in every frame entry point -- returns what the reference's x86-64 build returns,
+ * stated as a rule that neither the kernels nor the oracle leave to a cast:
+ *   uint32_t(f) = the truncated value modulo 2^32 for -2^63 <= f < 2^63 (negative uv wraps), 0 for NaN and every other f
+ *   int(f)      = the truncated value for -2^31 <= f < 2^31, INT_MIN (0x80000000) for NaN and every other f
+ * and the pack adds (r << 16) + (g << 8) + b modulo 2^32: an all-NaN colour packs to 0x80000000, a NaN in r or g alone adds nothing.
+ * tests/test_shading_cpu.py pins the values, tests/test_gpu_shading_fuzz.py holds the kernels to them. */
 int vxrt_shade_rays(vxrt_accel_t* accel, const float* rays, const vxrt_hit_t* hits, uint64_t n, const vxrt_shade_params_t* params,
                     float* colors, uint32_t* rgb8, void* stream);
 

@@ -456,9 +456,13 @@ static f3 rgb8_to_f3(uint32_t c) {
   return f3_make(r * s, g * s, b * s);
 }
 
-/* x86-64 g++ lowers uint32_t(float) to cvttss2si r64 + truncation; this is that behaviour made
- * explicit (negative uv wraps instead of being UB: SURVEY.md a16). */
-static inline uint32_t f2u_x86(float f) { return (uint32_t)(int64_t)f; }
+/* x86-64 g++ lowers uint32_t(float) to cvttss2si r64 + truncation and int(float) to cvttss2si r32; this is that behaviour
+ * made explicit (negative uv wraps instead of being UB: SURVEY.md a16), as a range test, so that no cast here is out of range
+ * (the rule of include/vortex_hip.h, vxrt_shade_rays; the kernel's f2u_x86 / f2i_x86 are the same two lines):
+ *   uint32_t(f): the truncated value mod 2^32 for -2^63 <= f < 2^63, 0 for NaN and everything else
+ *   int(f):      the truncated value for -2^31 <= f < 2^31, INT_MIN (0x80000000) for NaN and everything else */
+static inline uint32_t f2u_x86(float f) { return (f >= -0x1p63f && f < 0x1p63f) ? (uint32_t)(int64_t)f : 0u; }
+static inline uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int32_t)f : 0x80000000u; }
 
 /* rtx_shading.h:5-18 texSample */
 static f3 tex_sample(float u, float v, const uint32_t* pixels, uint32_t width, uint32_t height) {
@@ -603,10 +607,10 @@ static f3 radiance_of(const orc_node_t* tlas, const orc_blas_t* blas, const orc_
 
 /* common.h:149-154 RGB32FtoRGB8 */
 uint32_t orc_pack_rgb8(const float c[3]) {
-  int r = (int)(std_min(c[0], 1.f) * 255);
-  int g = (int)(std_min(c[1], 1.f) * 255);
-  int b = (int)(std_min(c[2], 1.f) * 255);
-  return (uint32_t)((r << 16) + (g << 8) + b);
+  uint32_t r = f2i_x86(std_min(c[0], 1.f) * 255);   /* (the int's bits: shifts and sums mod 2^32, as the 32-bit registers hold them) */
+  uint32_t g = f2i_x86(std_min(c[1], 1.f) * 255);
+  uint32_t b = f2i_x86(std_min(c[2], 1.f) * 255);
+  return (r << 16) + (g << 8) + b;
 }
 
 int orc_render(uint32_t w, uint32_t h, uint32_t y0, uint32_t y1,

@@ -178,7 +178,13 @@ struct Fetches { unsigned node = 0, inst = 0, tri = 0; };
 // ---------------------------------------------------------------------------------------------
 // shading (closest.cpp:57-127 / miss.cpp:9-14)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t f2u_x86(float f) { return (uint32_t)(long long)f; } // rtx_shading.h:7-8 as x86-64 g++ lowers it
+// rtx_shading.h:7-8 and common.h:149-154 convert floats that C leaves undefined (NaN, a value outside the target type).  The rule
+// (include/vortex_hip.h, vxrt_shade_rays) is what x86-64 g++ makes of them, written as a range test so that neither
+// this file nor oracle/rt_oracle.c depends on an out-of-range cast:
+//   uint32_t(f) = cvttss2si r64, low half: the truncated value mod 2^32 for -2^63 <= f < 2^63, 0 for NaN and everything else
+//   int(f)      = cvttss2si r32: the truncated value for -2^31 <= f < 2^31, INT_MIN (0x80000000) for NaN and everything else
+__device__ __forceinline__ uint32_t f2u_x86(float f) { return (f >= -0x1p63f && f < 0x1p63f) ? (uint32_t)(long long)f : 0u; }
+__device__ __forceinline__ uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int)f : 0x80000000u; }
 
 // Occlusion ray of the shadow extension (no reference counterpart): from the hit point toward the
 // light, origin pushed 1e-3 along L like the reference's mirror bounce (closest.cpp:104), tmax = |L|.
@@ -293,10 +299,10 @@ __device__ __forceinline__ void mirror_ray(float dx, float dy, float dz, float I
 }
 
 __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // common.h:149-154
-  int ir = (int)(std_min(r, 1.f) * 255);
-  int ig = (int)(std_min(g, 1.f) * 255);
-  int ib = (int)(std_min(b, 1.f) * 255);
-  return (uint32_t)((ir << 16) + (ig << 8) + ib);
+  const uint32_t ir = f2i_x86(std_min(r, 1.f) * 255);   // (shifts and sums of the int's bits, mod 2^32: what the 32-bit registers hold)
+  const uint32_t ig = f2i_x86(std_min(g, 1.f) * 255);
+  const uint32_t ib = f2i_x86(std_min(b, 1.f) * 255);
+  return (ir << 16) + (ig << 8) + ib;
 }
 
 // kernel.cpp:28-39.  u = (x*2.0 - W)/H and v = (y*2.0 - H)/H are evaluated in double and rounded to
