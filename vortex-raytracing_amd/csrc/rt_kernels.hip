@@ -18,6 +18,9 @@
 // What is not timed lives elsewhere: the acceleration-layout build and the refit in rt_accel.hip, the two ray-compaction
 // experiments (VXRT_POOL) in rt_trace_experiments.inc; SceneDev, HitRec, ShadeParams, FrameCtx and vxrt_accel in rt_internal.h,
 // the constants of the compact layout in rt_types.h.
+// Host half (behind the kernels): an entry point describes its frame in a RenderRequest; render_common checks it, prepares the frame
+// context's resources, makes a LaunchPlan and launches -- no launch macros: the template arguments are picked by launch_traversal /
+// launch_trace and with_decode_and_depth.  Environment knobs are read once, into HostKnobs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rt_internal.h"
@@ -419,12 +422,6 @@ __device__ __forceinline__ void ao_sample_ray(uint32_t x, uint32_t y, uint32_t W
 #endif                      // through LDS"): leaves of up to RT_TRI_LDS triangles, when at least RT_TRI_LDS_MIN lanes hold the same one.  Measured, off: DESIGN.md s5
 #ifndef RT_TRI_LDS_MIN
 #define RT_TRI_LDS_MIN 8
-#endif
-#ifndef RT_OCCLUSION_ORDER
-#define RT_OCCLUSION_ORDER 0      // 0: slot order (the default); 1 / 2: measurement variants (profiles/r05_g_gpu_reinsertion.txt, section 7)
-#endif
-#ifndef RT_OCCLUSION_SLOT_ORDER
-#define RT_OCCLUSION_SLOT_ORDER 0
 #endif
 #ifndef RT_UNORDERED_OCCLUSION
 #define RT_UNORDERED_OCCLUSION 1
@@ -1042,63 +1039,18 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
           // ordering network and the path_m bookkeeping are skipped (vxrt_trace's MODE_ANY, which
           // returns the reference's FIRST accepted candidate, keeps the ordered path)
           const bool v0 = c[0].d < __builtin_inff(), v1 = c[1].d < __builtin_inff(), v2 = c[2].d < __builtin_inff(), v3 = c[3].d < __builtin_inff();
-#if RT_OCCLUSION_ORDER == 1
-          // measurement variant: the child the ray enters LAST first (an occlusion ray starts on a surface: the boxes around its origin hold
-          // that surface's own neighbourhood, which cannot block it), the others in slot order
-          if (v0 || v1 || v2 || v3) {
-            bool more = true;
-            if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-            const float ninf = -__builtin_inff();
-            const float e0 = v0 ? c[0].d : ninf, e1 = v1 ? c[1].d : ninf, e2 = v2 ? c[2].d : ninf, e3 = v3 ? c[3].d : ninf;
-            const float m = fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
-            const int pick = e0 == m ? 0 : (e1 == m ? 1 : (e2 == m ? 2 : 3));
-            cur = pick == 0 ? c[0].desc : (pick == 1 ? c[1].desc : (pick == 2 ? c[2].desc : c[3].desc));
-            if (more) {
-              if (v0 && pick != 0) push(c[0].desc, c[0].d);
-              if (v1 && pick != 1) push(c[1].desc, c[1].d);
-              if (v2 && pick != 2) push(c[2].desc, c[2].d);
-              if (v3 && pick != 3) push(c[3].desc, c[3].d);
-            }
-          } else {
-            pop_next();
-          }
-#elif RT_OCCLUSION_ORDER == 2
-          // measurement variant: all children by descending entry distance
-          if (v0 || v1 || v2 || v3) {
-            bool more = true;
-            if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-            order_children(c);      // valid first, nearest in c[0]
-            const int nv = (int)v0 + (int)v1 + (int)v2 + (int)v3;
-            cur = nv == 1 ? c[0].desc : (nv == 2 ? c[1].desc : (nv == 3 ? c[2].desc : c[3].desc));
-            if (more) {
-              if (nv > 1) push(c[0].desc, c[0].d);
-              if (nv > 2) push(c[1].desc, c[1].d);
-              if (nv > 3) push(c[2].desc, c[2].d);
-            }
-          } else {
-            pop_next();
-          }
-#else
           if (v0 || v1 || v2 || v3) {
             bool more = true;
             if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
             cur = v0 ? c[0].desc : (v1 ? c[1].desc : (v2 ? c[2].desc : c[3].desc));
             if (more) {
-#if RT_OCCLUSION_SLOT_ORDER
-              // pushed last = visited next: the children are visited in slot order, which a builder may choose (largest surface area first)
-              if (v3 && (v0 || v1 || v2)) push(c[3].desc, c[3].d);
-              if (v2 && (v0 || v1)) push(c[2].desc, c[2].d);
-              if (v1 && v0) push(c[1].desc, c[1].d);
-#else
               if (v1 && v0) push(c[1].desc, c[1].d);
               if (v2 && (v0 || v1)) push(c[2].desc, c[2].d);
               if (v3 && (v0 || v1 || v2)) push(c[3].desc, c[3].d);
-#endif
             }
           } else {
             pop_next();
           }
-#endif
         } else {
           order_children(c);   // valid children first (d < inf), nearest in c[0]
           // (path_m and the candidates' distances are never NaN -- a filtered child carries +inf -- so the maxima need no
@@ -2044,8 +1996,10 @@ __global__ void add_counter_kernel(unsigned long long* c, unsigned long long v) 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -2067,6 +2021,37 @@ static uint32_t* status_word() {
 #define EXACT_GRID 128   // workgroups of the EXACT launch (it sees a fraction of a percent of the rays)
 #endif
 
+// Measurement knobs of the render and trace path (docs/KNOBS.md), read from the environment once per process: on the first call
+// that asks for one.  Each keeps the parsing it always had (atoi, atoll, or "first character is 0").
+struct HostKnobs {
+  uint32_t shard_rot, lpt_batch_max;
+  bool lpt, lpt_batch;                  // on unless the value begins with '0'
+  bool unordered_any_off, debug;        // VXRT_UNORDERED_ANY is 0; VXRT_DEBUG is set at all
+  int lpt_batch_alone, side_reserve, packed, packed_batch, grid_div, pool, wgs_per_cu;   // side_reserve, packed: -1 = unset
+};
+static const HostKnobs& host_knobs() {
+  static const HostKnobs knobs = [] {
+    const auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    const auto not_off = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+    HostKnobs k;
+    k.shard_rot = (uint32_t)num("VXRT_SHARD_ROT", 0);
+    k.lpt = not_off("VXRT_LPT");
+    k.lpt_batch = not_off("VXRT_LPT_BATCH");
+    { const char* e = getenv("VXRT_LPT_BATCH_MAX"); k.lpt_batch_max = e ? (uint32_t)atoll(e) : LPT_BATCH_MAX_TILES; }
+    k.lpt_batch_alone = num("VXRT_LPT_BATCH_ALONE", 1);
+    k.side_reserve = num("VXRT_SIDE_RESERVE", -1);
+    k.packed = num("VXRT_PACKED", -1);
+    k.packed_batch = num("VXRT_PACKED_BATCH", 0);
+    k.grid_div = num("VXRT_GRID_DIV", 0);
+    k.pool = num("VXRT_POOL", 0);
+    { const char* e = getenv("VXRT_UNORDERED_ANY"); k.unordered_any_off = e && atoi(e) == 0; }
+    k.wgs_per_cu = num("VXRT_WGS_PER_CU", 0);
+    k.debug = getenv("VXRT_DEBUG") != nullptr;
+    return k;
+  }();
+  return knobs;
+}
+
 // grid of a persistent launch: what the device holds at once (occupancy x CUs, queried once per kernel
 // and device), capped by the job count
 template <class K>
@@ -2086,9 +2071,9 @@ static uint32_t persistent_grid(K kernel, uint64_t jobs, int wg_threads = RT_WG_
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, wg_threads, 0) != hipSuccess || per_cu < 1) per_cu = 4;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
     // measurement knob (tools/occupancy_sweep.sh): fewer resident workgroups per CU than the kernel allows
-    if (const char* e = getenv("VXRT_WGS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < per_cu) per_cu = v; }
+    if (const int v = host_knobs().wgs_per_cu; v >= 1 && v < per_cu) per_cu = v;
     g = (uint64_t)per_cu * (uint64_t)cus;
-    if (getenv("VXRT_DEBUG")) fprintf(stderr, "[vxrt] persistent grid: %d blocks/CU x %d CUs\n", per_cu, cus);
+    if (host_knobs().debug) fprintf(stderr, "[vxrt] persistent grid: %d blocks/CU x %d CUs\n", per_cu, cus);
     std::lock_guard<std::mutex> lk(mu);
     cache[{(const void*)kernel, dev}] = g;
   }
@@ -2168,18 +2153,60 @@ extern "C" int vxrt_internal_lpt_sort(const uint32_t* cost, uint32_t* order, uin
 
 #include "rt_trace_experiments.inc"   // rt_pool_trace_kernel, rt_pair_trace_kernel, trace_experiment (VXRT_POOL=1|2)
 
-extern "C" {
+// What has to finish before a buffer that grows is freed.  Each caller passes its own rule, and the rules are correctness, not taste:
+// a context's buffers are only read by work on the caller's stream (STREAM), an accel's tables by frames in flight on any stream (DEVICE).
+enum class GrowSync { NONE, STREAM, DEVICE };
+struct DevBuf { void** ptr; size_t bytes_per_entry; };
+// Grow the device buffers that share the capacity *cap (in entries) to `need` entries.  Nothing happens when they hold that many; else
+// the wait `sync` names, every old buffer freed, every new one allocated (contents are not kept).  false: a HIP call failed -- the
+// buffers are then missing and *cap is 0, unless it was the wait that failed (nothing touched).
+template <class C>
+static bool grow_device(std::initializer_list<DevBuf> bufs, C* cap, uint64_t need, GrowSync sync, hipStream_t s) {
+  if (*cap >= need) return true;
+  if (sync == GrowSync::STREAM && hipStreamSynchronize(s) != hipSuccess) return false;
+  if (sync == GrowSync::DEVICE && hipDeviceSynchronize() != hipSuccess) return false;
+  for (const DevBuf& b : bufs) { (void)hipFree(*b.ptr); *b.ptr = nullptr; }
+  *cap = 0;
+  for (const DevBuf& b : bufs) if (hipMalloc(b.ptr, (size_t)need * b.bytes_per_entry) != hipSuccess) return false;
+  *cap = (C)need;
+  return true;
+}
 
-const char* vxrt_version(void) { return "vortex-rt-mi355x 0.3 (gfx950, compact 64-byte nodes, persistent wavefronts)"; }
+static ShadeParams shade_params(const vxrt_shade_params_t& in) {
+  ShadeParams p;
+  for (int i = 0; i < 3; ++i) {
+    p.amb[i] = in.ambient[i]; p.lcol[i] = in.light_color[i];
+    p.lpos[i] = in.light_pos[i]; p.bg[i] = in.background[i];
+  }
+  p.max_depth = in.max_depth;
+  return p;
+}
 
-static int ensure_defer(FrameCtx* c, uint64_t jobs, hipStream_t s) {
-  if (c->defer_cap >= jobs) return 0;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  (void)hipFree(c->defer);
-  c->defer = nullptr; c->defer_cap = 0;
-  if (hipMalloc((void**)&c->defer, jobs * sizeof(uint32_t)) != hipSuccess) return -1;
-  c->defer_cap = jobs;
-  return 0;
+// The two run-time bits of a scene that select a traversal instantiation -- the ldexp decode (dev.exact_decode) and the depth class
+// (shallow: the size of the scratch part of the stack) -- as the template arguments LDEXP and SHALLOW: calls
+// f(std::bool_constant<LDEXP>, std::bool_constant<SHALLOW>).  Counting builds have no SHALLOW form: with ALLOW_SHALLOW = false it is
+// not instantiated.
+template <bool ALLOW_SHALLOW, class F>
+static void with_decode_and_depth(const vxrt_accel* a, F&& f) {
+  if constexpr (ALLOW_SHALLOW) {
+    if (a->shallow) { if (a->dev.exact_decode) f(std::true_type{}, std::true_type{}); else f(std::false_type{}, std::true_type{}); return; }
+  }
+  if (a->dev.exact_decode) f(std::true_type{}, std::false_type{}); else f(std::false_type{}, std::false_type{});
+}
+
+// The two launches of a ray buffer: JOB over every ray, then the EXACT form over the rays it deferred (JOB_TRACE for the unordered
+// job too: the EXACT launch keeps the ordered form, a boolean either way).
+// (the EXACT launch's grid grows with the ray buffer -- a workgroup per 2,048 rays, up to the machine: how many rays were deferred
+// is known on the device only, and a buffer of axis-parallel rays defers all of them; with nothing deferred its wavefronts find
+// every shard empty without an atomic and exit)
+template <int JOB, int STATS>
+static void launch_trace(const vxrt_accel* a, const ShadeParams& p, const PersistArgs& A, const PersistArgs& X, uint64_t n, hipStream_t s) {
+  with_decode_and_depth<STATS == 0>(a, [&](auto ld, auto sh) {
+    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, false, decltype(sh)::value>;
+    const auto k_exact = rt_persistent_kernel<JOB_TRACE, STATS, decltype(ld)::value, true>;
+    hipLaunchKernelGGL(k_main, dim3(persistent_grid(k_main, n)), dim3(RT_WG_THREADS), 0, s, a->dev, p, A);
+    hipLaunchKernelGGL(k_exact, dim3(std::max<uint32_t>(EXACT_GRID, persistent_grid(k_exact, n / 8, 256))), dim3(256), 0, s, a->dev, p, X);
+  });
 }
 
 // internal mode of trace_on_ctx: any-hit rays whose hit records are only read as "blocked or not" (JOB_TRACE_UNORDERED)
@@ -2200,7 +2227,7 @@ static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_
   A.wave_log = stats_counters ? a->trace_wave_log : nullptr;
   A.status = st;
   A.per_shard = ((A.total + QUEUE_SHARDS - 1) / QUEUE_SHARDS + 63u) & ~63u;
-  if (ensure_defer(c, A.total, s) != 0) return -1;
+  if (!grow_device({{(void**)&c->defer, sizeof(uint32_t)}}, &c->defer_cap, A.total, GrowSync::STREAM, s)) return -1;
   if (c->ctl_dirty) {
     if (hipMemsetAsync(c->ctl, 0, CTL_DWORDS * sizeof(uint32_t), s) != hipSuccess) return -1;
   }
@@ -2215,35 +2242,19 @@ static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_
   X.order = nullptr;
   ShadeParams p{};
   // incoherent rays: the ray-pool kernel (1) or two rays per lane (2) instead of the persistent kernel, timed builds only
-  static const int pool_env = [] { const char* e = getenv("VXRT_POOL"); return e ? atoi(e) : 0; }();
-  if ((pool_env == 1 || pool_env == 2) && !stats_counters) return trace_experiment(pool_env, a, c, n, s, p, A, X);
-#define LAUNCH_TJ(J, ST, LD, SH) do { \
-    hipLaunchKernelGGL((rt_persistent_kernel<J, ST, LD, false, false, SH>), dim3(persistent_grid(rt_persistent_kernel<J, ST, LD, false, false, SH>, n)), dim3(RT_WG_THREADS), 0, s, a->dev, p, A); \
-    hipLaunchKernelGGL((rt_persistent_kernel<JOB_TRACE, ST, LD, true>), dim3(std::max<uint32_t>(EXACT_GRID, persistent_grid(rt_persistent_kernel<JOB_TRACE, ST, LD, true>, n / 8, 256))), dim3(256), 0, s, a->dev, p, X); } while (0)
-#define LAUNCH_T(ST, LD, SH) LAUNCH_TJ(JOB_TRACE, ST, LD, SH)
-  // any-hit rays whose caller only wants "blocked or not": children in slot order (the EXACT launch keeps the ordered form: a boolean either way)
-  static const bool unordered_off = [] { const char* e = getenv("VXRT_UNORDERED_ANY"); return e && atoi(e) == 0; }();
-  if (unordered && !unordered_off && !stats_counters) {
-    if (a->shallow) { if (a->dev.exact_decode) LAUNCH_TJ(JOB_TRACE_UNORDERED, 0, true, true); else LAUNCH_TJ(JOB_TRACE_UNORDERED, 0, false, true); }
-    else            { if (a->dev.exact_decode) LAUNCH_TJ(JOB_TRACE_UNORDERED, 0, true, false); else LAUNCH_TJ(JOB_TRACE_UNORDERED, 0, false, false); }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  // (the EXACT launch's grid grows with the ray buffer -- a workgroup per 2,048 rays, up to the machine: how many rays were deferred
-  // is known on the device only, and a buffer of axis-parallel rays defers all of them; with nothing deferred its wavefronts find
-  // every shard empty without an atomic and exit)
-  if (stats_counters)  { if (a->dev.exact_decode) LAUNCH_T(1, true, false); else LAUNCH_T(1, false, false); }
-  else if (a->shallow) { if (a->dev.exact_decode) LAUNCH_T(0, true, true); else LAUNCH_T(0, false, true); }
-  else                 { if (a->dev.exact_decode) LAUNCH_T(0, true, false); else LAUNCH_T(0, false, false); }
-#undef LAUNCH_T
-#undef LAUNCH_TJ
+  const int pool = host_knobs().pool;
+  if ((pool == 1 || pool == 2) && !stats_counters) return trace_experiment(pool, a, c, n, s, p, A, X);
+  // any-hit rays whose caller only wants "blocked or not": children in slot order
+  if (stats_counters) launch_trace<JOB_TRACE, 1>(a, p, A, X, n, s);
+  else if (unordered && !host_knobs().unordered_any_off) launch_trace<JOB_TRACE_UNORDERED, 0>(a, p, A, X, n, s);
+  else launch_trace<JOB_TRACE, 0>(a, p, A, X, n, s);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// (a buffer that is missing is allocated whatever the capacity its level or pass shares says)
 static bool grow_buf(void** ptr, uint64_t have, uint64_t need, size_t bytes_per_entry) {
-  if (have >= need && *ptr) return true;
-  (void)hipFree(*ptr);
-  *ptr = nullptr;
-  return hipMalloc(ptr, (size_t)need * bytes_per_entry) == hipSuccess;
+  uint64_t cap = *ptr ? have : 0;
+  return grow_device({{ptr, bytes_per_entry}}, &cap, need, GrowSync::NONE, nullptr);
 }
 
 static bool level_reserve(FrameCtx::Level& l, uint64_t n, bool shadow, bool only_term) {
@@ -2260,26 +2271,52 @@ static bool level_reserve(FrameCtx::Level& l, uint64_t n, bool shadow, bool only
   return ok;
 }
 
+// Which build of the kernels a frame runs; the value is their STATS template argument (see rt_persistent_kernel)
+enum class Counting { TIMED = 0, REFERENCE_ORDER = 1, TIMED_TRAVERSAL = 2 };
+
+// One frame, or one set of frames, as the vxrt_render* entry points ask for it.  Every field defaults to "absent": an entry point
+// sets the ones it means.
+struct RenderRequest {
+  uint32_t width = 0, height = 0, y0 = 0, y1 = 0;   // rows [y0, y1) of a width x height frame ...
+  uint32_t stride = 1;                              // ... of which every stride-th tile row (8 rows), starting with the one at y0
+  const vxrt_shade_params_t* params = nullptr;      // `batch` entries
+  uint32_t batch = 1;                               // frames in this set of launches
+  int shadow = 0;
+  uint32_t* dst = nullptr; uint64_t dst_frame_stride = 0;   // frame f goes to dst + f * dst_frame_stride
+  vxrt_hit_t* hits = nullptr; float* colors = nullptr;      // optional outputs, single frames
+  unsigned long long* counters = nullptr;           // [0] rays traced; the counting builds: all of them
+  uint32_t* unoccluded = nullptr;                   // ambient occlusion, optional
+  unsigned long long* wave_log = nullptr;           // diagnostic, TIMED_TRAVERSAL only
+  const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
+  const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
+  void* stream = nullptr;
+  Counting counting = Counting::TIMED;
+};
+
 // Tail of a frame with reflective instances (replaces the plain shading pass): shade level 0, then per
 // bounce level trace -> (occlusion rays ->) shade, then fold the colours back.  The level sizes come back
 // to the host between levels, so this path synchronises the stream (it is not the benchmarked one).
-static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p, uint32_t width, uint32_t y0, uint32_t y1,
-                              int shadow, const float* utab, const float* vtab, uint32_t* dst, HitRec* hits, float* colors,
-                              unsigned long long* rays_traced, hipStream_t s, uint32_t height = 0, const float* cam = nullptr) {
+// (utab / vtab: the tables the traversal used; a camera frame's utab is its camera block)
+static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
   const SceneDev& sc = a->dev;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  const bool shadow = r.shadow != 0;
+  uint32_t* dst = r.dst; float* colors = r.colors;
+  unsigned long long* rays_traced = r.counters;
+  hipStream_t s = (hipStream_t)r.stream;
   const uint64_t npix = (uint64_t)width * (y1 - y0);          // entries of level 0 (addressed by pixel index)
   const uint64_t pix_span = (uint64_t)width * y1;              // term[] of level 0 is indexed by x + y*W
   if (npix > 0x7fffffffull) return -1;
   if (!c->bcount && hipMalloc((void**)&c->bcount, sizeof(uint32_t)) != hipSuccess) return -1;
   if (c->lv.size() < 2) c->lv.resize(2);
   if (!level_reserve(c->lv[0], pix_span, false, true)) return -1;
-  if (!level_reserve(c->lv[1], npix, shadow != 0, false)) return -1;
+  if (!level_reserve(c->lv[1], npix, shadow, false)) return -1;
   dim3 block(256);
   if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
-  if (cam) hipLaunchKernelGGL(rt_shade_bounce_camera_kernel, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, npix, width, height, y0, cam,
-                              (const HitRec*)c->hitbuf, c->lv[0].term, dst, hits, colors, c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
+  if (r.cams) hipLaunchKernelGGL(rt_shade_bounce_camera_kernel, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, npix, width, r.height, y0, utab,
+                                 (const HitRec*)c->hitbuf, c->lv[0].term, dst, (HitRec*)r.hits, colors, c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
   else hipLaunchKernelGGL(rt_shade_bounce_kernel<true>, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, 0u, npix, width, y0, utab, vtab,
-                          (const HitRec*)c->hitbuf, (const float*)nullptr, (const HitRec*)nullptr, c->lv[0].term, (float*)nullptr, dst, hits, colors,
+                          (const HitRec*)c->hitbuf, (const float*)nullptr, (const HitRec*)nullptr, c->lv[0].term, (float*)nullptr, dst, (HitRec*)r.hits, colors,
                           c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
   if (hipGetLastError() != hipSuccess) return -1;
   c->ctl_dirty = false;
@@ -2302,7 +2339,7 @@ static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p
     if (c->lv.size() < (size_t)k + 2) c->lv.resize((size_t)k + 2);
     FrameCtx::Level& Nx = c->lv[k + 1];
     const bool more = k + 1 < p.max_depth;
-    if (more && !level_reserve(Nx, n, shadow != 0, false)) return -1;
+    if (more && !level_reserve(Nx, n, shadow, false)) return -1;
     FrameCtx::Level& Lk = c->lv[k];   // (resize may have moved the vector)
     if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
     hipLaunchKernelGGL(rt_shade_bounce_kernel<false>, grid, block, 0, s, sc, p, k, (uint64_t)n, width, y0, utab, vtab,
@@ -2326,10 +2363,11 @@ static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p
 // batch is one any-hit launch whose job count stays in device memory.  No host synchronisation.
 #define AO_BATCH_RAYS (32ull << 20)
 #define VXRT_AO_MODE_DIFFUSE_BOUNCE 1u   // internal: vxrt_ao_params_t::reserved
-static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p, uint32_t width, uint32_t y0, uint32_t y1,
-                          const vxrt_ao_params_t* ao, const float* utab, const float* vtab, uint32_t* dst, float* colors,
-                          uint32_t* unoccluded, unsigned long long* rays_traced, hipStream_t s) {
+static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
   const SceneDev& sc = a->dev;
+  const vxrt_ao_params_t* ao = r.ao;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  hipStream_t s = (hipStream_t)r.stream;
   const uint64_t n = (uint64_t)width * (y1 - y0);
   if (ao->reserved == VXRT_AO_MODE_DIFFUSE_BOUNCE) return -1;    // (the diffuse-bounce frame is JOB_RENDER_GI: it has no tail)
   if (n > 0x7fffffffull || ao->spp == 0) return -1;
@@ -2384,322 +2422,391 @@ static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const ShadeParams& p, ui
                        (const HitRec*)c->ao_hits, c->ao_cnt);
   }
   hipLaunchKernelGGL(rt_ao_final_kernel, grid, block, 0, s, n, width, y0, (const float4*)c->ao_geo, (const float4*)c->ao_col, (const uint32_t*)c->ao_cnt,
-                     ao->spp, dst, colors, unoccluded, rays_traced);
+                     ao->spp, r.dst, r.colors, r.unoccluded, r.counters);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-static int render_common(vxrt_accel_t* a, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                         const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits, float* colors,
-                         unsigned long long* counters, int stats, void* stream, unsigned long long* wave_log = nullptr,
-                         const vxrt_ao_params_t* ao = nullptr, uint32_t* unoccluded = nullptr, uint32_t stride = 1,
-                         uint32_t batch = 1, uint64_t dst_frame_stride = 0, const vxrt_camera_t* cams = nullptr) {
-  if (!a || a->stale || !params || !dst) return -1;
+// ---------------------------------------------------------------------------------------------
+// render_common, step by step: refusals, frame resources, launch plan, traversal launches, shading launch
+// ---------------------------------------------------------------------------------------------
+
+// tile rows of the window: every stride-th tile row of [y0, y1) starting with the one at y0
+struct Tiles {
+  uint32_t x, y;        // tiles per row, tile rows
+  uint32_t row_step;    // frame rows between two consecutive tile rows
+  uint32_t per_frame;
+  uint64_t total;       // of the whole batch
+};
+static Tiles window_tiles(const RenderRequest& r) {
+  Tiles t;
+  t.x = (r.width + 7) / 8; t.y = ((r.y1 - r.y0 + 7) / 8 + r.stride - 1) / r.stride;
+  t.row_step = 8u * r.stride;
+  t.per_frame = t.x * t.y;
+  t.total = (uint64_t)t.x * t.y * r.batch;
+  return t;
+}
+
+static bool mirror_frame(const vxrt_accel* a, const vxrt_shade_params_t& params) { return params.max_depth > 1 && a->max_reflectivity > 0.0f; }
+static bool gi_fused_frame(const RenderRequest& r) { return r.ao && r.ao->reserved == VXRT_AO_MODE_DIFFUSE_BOUNCE; }
+
+// Every refusal that depends on the arguments alone.  It comes BEFORE a frame context is taken (a context taken and not released
+// would leave its next user unordered behind whatever this call had already enqueued).  -1: refused; 0: an empty window, nothing
+// to do; 1: render.
+static int check_request(const vxrt_accel* a, const RenderRequest& r) {
+  const bool stats = r.counting != Counting::TIMED;
+  if (!a || a->stale || !r.params || !r.dst) return -1;
   // camera frames (cams[f] per frame of the batch): plain and shadow frames, whole rows, the timed build only
-  if (cams && (stride != 1 || ao || stats || wave_log || unoccluded)) return -1;
+  if (r.cams && (r.stride != 1 || r.ao || stats || r.wave_log || r.unoccluded)) return -1;
   // batch > 1: `params` is an array of `batch` entries, frame f goes to dst + f * dst_frame_stride; plain frames without optional outputs
-  if (batch == 0 || batch > VXRT_MAX_BATCH || (batch > 1 && (hits || colors || ao || ((stats || wave_log) && !(stats == 2 && wave_log))))) return -1;   // (a batch with the wave log: diagnostic, traversal only -- its shading launch is the single-frame one)
-  if (ao && (stats || shadow)) return -1;
-  if (stride == 0 || (stride > 1 && ((y0 & 7u) != 0 || ao))) return -1;   // interleaved tile rows: tile-aligned start, plain frames only
+  // (a batch with the wave log: diagnostic, traversal only -- its shading launch is the single-frame one)
+  if (r.batch == 0 || r.batch > VXRT_MAX_BATCH) return -1;
+  if (r.batch > 1 && (r.hits || r.colors || r.ao || ((stats || r.wave_log) && !(r.counting == Counting::TIMED_TRAVERSAL && r.wave_log)))) return -1;
+  if (r.ao && (stats || r.shadow)) return -1;
+  if (r.stride == 0 || (r.stride > 1 && ((r.y0 & 7u) != 0 || r.ao))) return -1;   // interleaved tile rows: tile-aligned start, plain frames only
   if (!a->ref.triEx || !a->ref.mat || a->ref.n_mats == 0) return -1;  // shading needs them (closest.cpp:52-55)
-  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
-  if (stats && !counters) return -1;
-  if (y0 == y1) return 0;
-  uint32_t* st = status_word();
-  if (!st) return -1;
-  ShadeParams p;
-  for (int i = 0; i < 3; ++i) {
-    p.amb[i] = params->ambient[i]; p.lcol[i] = params->light_color[i];
-    p.lpos[i] = params->light_pos[i]; p.bg[i] = params->background[i];
-  }
-  p.max_depth = params->max_depth;
-  // tile rows of the window: every stride-th tile row of [y0, y1) starting with the one at y0
-  const uint32_t tiles_x = (width + 7) / 8, tiles_y = ((y1 - y0 + 7) / 8 + stride - 1) / stride;
-  const uint32_t row_step = 8u * stride;
-  const uint64_t n_tiles64 = (uint64_t)tiles_x * tiles_y * batch;
-  if (n_tiles64 > 0x1ffffffull) return -1;
-  const uint32_t n_tiles = (uint32_t)n_tiles64;            // of the whole batch
-  const uint32_t frame_tiles = tiles_x * tiles_y;
-  dim3 block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const SceneDev& sc = a->dev;
-  // every refusal that depends on the arguments alone comes BEFORE a frame context is taken (a context taken and not released
-  // would leave its next user unordered behind whatever this call had already enqueued)
-  const bool mirror = p.max_depth > 1 && a->max_reflectivity > 0.0f;
-  if (mirror && (stats || stride > 1 || batch > 1)) return -1;   // the mirror-bounce path: whole single frames, timed build only
-  if (batch > 1)
-    for (uint32_t f = 0; f < batch; ++f)
-      if (params[f].max_depth > 1 && a->max_reflectivity > 0.0f) return -1;
-  FrameCtx* c = acquire_ctx(a, s);
-  if (!c) return -1;
-  // from here on a failure releases the context the way a success does: its event is recorded behind whatever was enqueued, the
-  // context is marked busy on this stream and its control block is cleared before the next use
-  auto fail = [&]() -> int { c->ctl_dirty = true; (void)release_ctx(a, c, s); return -1; };
-  // hit-record buffer between the two passes (one per frame in flight)
-  const uint64_t pixels = batch > 1 ? (uint64_t)n_tiles * 64u : (uint64_t)tiles_x * ((height + 7) / 8 + 1) * 64u;   // tile-major records of any row window of the frame
-  if (c->hitbuf_pixels < pixels) {
-    if (hipStreamSynchronize(s) != hipSuccess) return fail();
-    (void)hipFree(c->hitbuf);
-    c->hitbuf = nullptr; c->hitbuf_pixels = 0;
-    if (hipMalloc(&c->hitbuf, pixels * sizeof(HitRec)) != hipSuccess) return fail();
-    c->hitbuf_pixels = pixels;
-  }
-  if (!cams && (a->uv_w != width || a->uv_h != height)) {
-    // kernel.cpp:32-33 evaluated on the host in double, once per column and row
-    std::vector<float> tab((size_t)width + height);
-    for (uint32_t x = 0; x < width; ++x) tab[x] = (float)(((double)x * 2.0 - (double)width) / (double)height);
-    for (uint32_t y = 0; y < height; ++y) tab[width + y] = (float)(((double)y * 2.0 - (double)height) / (double)height);
-    if (hipDeviceSynchronize() != hipSuccess) return fail();   // frames in flight on other streams read the old table
-    (void)hipFree(a->uvtab);
-    a->uvtab = nullptr; a->uv_w = a->uv_h = 0;
-    if (hipMalloc((void**)&a->uvtab, tab.size() * sizeof(float)) != hipSuccess) return fail();
-    if (hipMemcpy(a->uvtab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail();
-    a->uv_w = width; a->uv_h = height;
-  }
-  PersistArgs A{};
-  A.W = width; A.H = height; A.y0 = y0; A.y1 = y1; A.tiles_x = tiles_x; A.row_step = row_step; A.total = n_tiles * 64u;
-  A.div_tiles_x = fast_div_make(tiles_x); A.div_frame_tiles = fast_div_make(frame_tiles); A.frame_tiles = frame_tiles;
-  A.hits = (HitRec*)c->hitbuf; A.counters = counters; A.status = st; A.wave_log = wave_log; A.end_log = a->end_log;
-  A.utab = a->uvtab; A.vtab = a->uvtab + width;
-  if (cams) {
-    // the camera block lives in the frame context and is written on the frame's stream: the fixed camera's tables and a-priori
-    // list stay untouched, and frames in flight on other contexts keep their own cameras
-    const uint64_t need = CAM_TAB + (uint64_t)batch * (width + height);
-    if (c->cam_floats < need) {
-      if (hipStreamSynchronize(s) != hipSuccess) return fail();
-      (void)hipFree(c->cam);
-      c->cam = nullptr; c->cam_floats = 0;
-      if (hipMalloc((void**)&c->cam, need * sizeof(float)) != hipSuccess) return fail();
-      c->cam_floats = need;
-    }
-    CamBatch cb;
-    for (uint32_t f = 0; f < VXRT_MAX_BATCH; ++f) cb.c[f] = cams[f < batch ? f : 0];
-    const uint32_t g = (uint32_t)std::min<uint64_t>((need + 255) / 256, 1024);
-    hipLaunchKernelGGL(rt_camera_prep_kernel, dim3(g), dim3(256), 0, s, cb, batch, width, height, c->cam);
-    if (hipGetLastError() != hipSuccess) return fail();
-    A.utab = c->cam; A.vtab = c->cam + CAM_TAB;
-  }
-  if (batch > 1) {
-    if (!c->pbatch && hipMalloc((void**)&c->pbatch, VXRT_MAX_BATCH * sizeof(ShadeParams)) != hipSuccess) return fail();
-    ShadeParams pb[VXRT_MAX_BATCH];
-    for (uint32_t f = 0; f < batch; ++f) {
-      for (int i = 0; i < 3; ++i) {
-        pb[f].amb[i] = params[f].ambient[i]; pb[f].lcol[i] = params[f].light_color[i];
-        pb[f].lpos[i] = params[f].light_pos[i]; pb[f].bg[i] = params[f].background[i];
-      }
-      pb[f].max_depth = params[f].max_depth;
-    }
-    // (by value through the kernel arguments: captured when the launch is enqueued, whatever the caller does with `params` next)
-    ShadeBatch sb;
-    for (uint32_t f = 0; f < VXRT_MAX_BATCH; ++f) sb.p[f] = pb[f < batch ? f : 0];
-    hipLaunchKernelGGL(set_batch_params_kernel, dim3(1), dim3(64), 0, s, sb, batch, c->pbatch);
-    A.pbatch = c->pbatch; A.frame_tiles = frame_tiles;
-    // tile order of a batch: band-major -- queue shard s (= the XCD that works on it) gets band s of EVERY frame, so that an
-    // XCD's L2 keeps holding one band's part of the BVH, as it does for a single frame; frame-major order would hand each XCD
-    // whole frames (measured at 8 frames per batch: slower than no batch at all)
-    if (a->bo_tiles != frame_tiles) {   // another window: drop the orders of the old one
-      if (hipDeviceSynchronize() != hipSuccess) return fail();
-      for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) { (void)hipFree(a->batch_order[k]); a->batch_order[k] = nullptr; }
-      a->bo_tiles = frame_tiles;
-    }
-    if (!a->batch_order[batch]) {
-      std::vector<uint32_t> ord;
-      ord.reserve(n_tiles);
-      const uint32_t band = (frame_tiles + QUEUE_SHARDS - 1) / QUEUE_SHARDS;
-      for (uint32_t sh = 0; sh < QUEUE_SHARDS; ++sh)
-        for (uint32_t f = 0; f < batch; ++f)
-          for (uint32_t t = sh * band; t < std::min(frame_tiles, (sh + 1) * band); ++t) ord.push_back(f * frame_tiles + t);
-      if (hipMalloc((void**)&a->batch_order[batch], ord.size() * sizeof(uint32_t)) != hipSuccess) return fail();
-      if (hipMemcpy(a->batch_order[batch], ord.data(), ord.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return fail();
-    }
-    A.tile_order = a->batch_order[batch];
-  }
-  if (ensure_defer(c, A.total, s) != 0) return fail();
-  A.defer_count = c->ctl; A.defer_list = c->defer; A.defer_cap = A.total;
-  A.queue = c->ctl + 32;
-  A.per_shard = ((A.total + QUEUE_SHARDS - 1) / QUEUE_SHARDS + 63u) & ~63u;
-  static const uint32_t shard_rot_env = [] { const char* e = getenv("VXRT_SHARD_ROT"); return e ? (uint32_t)atoi(e) : 0u; }();
-  A.shard_rot = shard_rot_env;
-  // longest tile first, learned from this context's previous frame of the same window (VXRT_LPT=0 disables).  Only
-  // with one frame in flight: overlapped frames fill each other's tails already
-  static const bool lpt_on = [] { const char* e = getenv("VXRT_LPT"); return !(e && e[0] == '0'); }();
-  // and only for frames of more than LPT_MIN_TILES tiles: below, the sort launch costs more than the shorter tail saves
+  if (r.width == 0 || r.height == 0 || r.y0 > r.y1 || r.y1 > r.height) return -1;
+  if (stats && !r.counters) return -1;
+  if (r.y0 == r.y1) return 0;
+  if (window_tiles(r).total > 0x1ffffffull) return -1;   // (tile indices stay below 2^25: see FastDiv)
+  // the mirror-bounce path: whole single frames, timed build only
+  if (mirror_frame(a, r.params[0]) && (stats || r.stride > 1 || r.batch > 1)) return -1;
+  if (r.batch > 1)
+    for (uint32_t f = 0; f < r.batch; ++f)
+      if (mirror_frame(a, r.params[f])) return -1;
+  // one diffuse bounce: a plain frame of the timed build
+  if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
+  return 1;
+}
+
+// Longest tile first, learned from this context's previous frame of the same window?
+static bool lpt_wanted(const vxrt_accel* a, const RenderRequest& r, uint32_t n_tiles) {
+  const HostKnobs& k = host_knobs();
+  if (!k.lpt || !(r.counting == Counting::TIMED || r.wave_log)) return false;   // (VXRT_LPT=0 disables)
+  // only for frames of more than LPT_MIN_TILES tiles: below, the sort launch costs more than the shorter tail saves
   // (1024x1024, 86 % background: -5 %; 1920x1080: +9 %; 3840x2160: +4 %; the sort on a side stream instead: worse, the
   // two extra event hops cost more than the kernel)
-  // Single frames in flight on several streams: no difference, measured (round 2).  BATCHES of frames: a rank's share of a frame split
+  if (n_tiles < LPT_MIN_TILES) return false;
+  // Only with one frame in flight: overlapped frames fill each other's tails already.
+  // Single frames in flight on several streams: no difference, measured (round 2).
+  if (r.batch == 1) return a->n_ctx == 1;
+  // BATCHES of frames: a rank's share of a frame split
   // over GPUs makes short launches -- at 8 ranks a 20-step run is two launches of ~5 tiles per wavefront, whose tails nothing
   // fills -- and the batches of a frame loop repeat: the order is learned from the context's previous batch of the same size
   // (VXRT_LPT_BATCH=0 disables; profiles/r03_h_lpt_batch.txt).
-  static const bool lpt_batch_on = [] { const char* e = getenv("VXRT_LPT_BATCH"); return !(e && e[0] == '0'); }();
+  if (!k.lpt_batch) return false;
   // ... for batches of at most LPT_BATCH_MAX_TILES tiles (about a dozen per resident wavefront): measured on one box, driver-sized
   // runs, rank 0's pipeline of 8 / 4 / 2 ranks (40.8 K / 81.6 K / 162 K tiles per batch): +5.5 % / +2 % / 0; one GPU's batches of
   // five whole frames (162 K tiles, sets overlapping on two streams): -5 % -- sorted by cost, a band's tiles are no longer
-  // traced next to their screen neighbours, and there the tails are filled anyway.
-  static const uint32_t lpt_batch_max = [] { const char* e = getenv("VXRT_LPT_BATCH_MAX"); return e ? (uint32_t)atoll(e) : LPT_BATCH_MAX_TILES; }();   // (measurement knob)
+  // traced next to their screen neighbours, and there the tails are filled anyway.  (VXRT_LPT_BATCH_MAX: measurement knob)
+  if (n_tiles <= k.lpt_batch_max) return true;
   // (a set issued on its own -- one frame context: the samples of one vx_start -- has nothing behind it to fill its tail, whatever its size)
   // (longest tile first also in a large set then: the samples of `rt_host -s 5`, 162 K tiles, 2.25 -> 2.00 ms per vx_start; VXRT_LPT_BATCH_ALONE=0: off)
-  static const int lpt_alone_env = [] { const char* e = getenv("VXRT_LPT_BATCH_ALONE"); return e ? atoi(e) : 1; }();
-  const bool lpt = lpt_on && (!stats || wave_log) && n_tiles >= LPT_MIN_TILES &&
-                   (batch == 1 ? a->n_ctx == 1 : (lpt_batch_on && (n_tiles <= lpt_batch_max || (lpt_alone_env && a->n_ctx == 1))));
-  FrameCtx::Lpt& L = c->lpt[batch];
-  if (lpt) {
-    if (L.cap < n_tiles) {
-      if (hipStreamSynchronize(s) != hipSuccess) return fail();
-      (void)hipFree(L.cost); (void)hipFree(L.order);
-      L.cost = L.order = nullptr; L.cap = 0; L.valid = false;
-      // (cost: n entries + n start clocks + n durations + n steal distances behind them, the latter three written by the wave-log build only)
-      if (hipMalloc((void**)&L.cost, (size_t)n_tiles * 4 * 4) != hipSuccess || hipMalloc((void**)&L.order, (size_t)n_tiles * 4) != hipSuccess) return fail();
-      L.cap = n_tiles;
-    }
-    // (camera frames learn their own order: they do not share the fixed camera's tiles' costs)
-    const uint32_t key[6] = {width, height, y0, y1, (uint32_t)shadow | (stride << 1), (ao ? 1u : 0u) | (batch << 1) | (cams ? 0x80000000u : 0u)};
-    if (memcmp(key, L.key, sizeof key) != 0) { L.valid = false; memcpy(L.key, key, sizeof key); }
-    if (!L.cost || !L.order) return fail();   // (whatever happened above: no launch with a missing table)
-    A.tile_cost = L.cost;
-    if (L.valid) A.tile_order = L.order;      // else: the static order (identity, or the batch's band-major order set above)
-    else if (batch == 1) A.tile_order = nullptr;
+  return k.lpt_batch_alone && a->n_ctx == 1;
+}
+
+// camera tables of the fixed camera (u per column, v per row), rebuilt when the frame size changes
+static bool ensure_uv_tables(vxrt_accel* a, uint32_t width, uint32_t height, hipStream_t s) {
+  if (a->uv_w == width && a->uv_h == height) return true;
+  // kernel.cpp:32-33 evaluated on the host in double, once per column and row
+  std::vector<float> tab((size_t)width + height);
+  for (uint32_t x = 0; x < width; ++x) tab[x] = (float)(((double)x * 2.0 - (double)width) / (double)height);
+  for (uint32_t y = 0; y < height; ++y) tab[width + y] = (float)(((double)y * 2.0 - (double)height) / (double)height);
+  a->uv_w = a->uv_h = 0;
+  uint64_t none = 0;   // (always replaced.)  DEVICE: frames in flight on other streams read the old table
+  if (!grow_device({{(void**)&a->uvtab, sizeof(float)}}, &none, tab.size(), GrowSync::DEVICE, s)) return false;
+  if (hipMemcpy(a->uvtab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return false;
+  a->uv_w = width; a->uv_h = height;
+  return true;
+}
+
+// the camera block lives in the frame context and is written on the frame's stream: the fixed camera's tables and a-priori
+// list stay untouched, and frames in flight on other contexts keep their own cameras
+static bool upload_cameras(FrameCtx* c, const RenderRequest& r, hipStream_t s) {
+  const uint64_t need = CAM_TAB + (uint64_t)r.batch * (r.width + r.height);
+  if (!grow_device({{(void**)&c->cam, sizeof(float)}}, &c->cam_floats, need, GrowSync::STREAM, s)) return false;
+  CamBatch cb;
+  for (uint32_t f = 0; f < VXRT_MAX_BATCH; ++f) cb.c[f] = r.cams[f < r.batch ? f : 0];
+  const uint32_t g = (uint32_t)std::min<uint64_t>((need + 255) / 256, 1024);
+  hipLaunchKernelGGL(rt_camera_prep_kernel, dim3(g), dim3(256), 0, s, cb, r.batch, r.width, r.height, c->cam);
+  return hipGetLastError() == hipSuccess;
+}
+
+// a batch's per-frame shading parameters (into the context) and its band-major tile order (kept by the accel per batch size)
+static bool upload_batch(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, const Tiles& t, hipStream_t s) {
+  if (!c->pbatch && hipMalloc((void**)&c->pbatch, VXRT_MAX_BATCH * sizeof(ShadeParams)) != hipSuccess) return false;
+  // (by value through the kernel arguments: captured when the launch is enqueued, whatever the caller does with `params` next)
+  ShadeBatch sb;
+  for (uint32_t f = 0; f < VXRT_MAX_BATCH; ++f) sb.p[f] = shade_params(r.params[f < r.batch ? f : 0]);
+  hipLaunchKernelGGL(set_batch_params_kernel, dim3(1), dim3(64), 0, s, sb, r.batch, c->pbatch);
+  // tile order of a batch: band-major -- queue shard s (= the XCD that works on it) gets band s of EVERY frame, so that an
+  // XCD's L2 keeps holding one band's part of the BVH, as it does for a single frame; frame-major order would hand each XCD
+  // whole frames (measured at 8 frames per batch: slower than no batch at all)
+  if (a->bo_tiles != t.per_frame) {   // another window: drop the orders of the old one
+    if (hipDeviceSynchronize() != hipSuccess) return false;
+    for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) { (void)hipFree(a->batch_order[k]); a->batch_order[k] = nullptr; }
+    a->bo_tiles = t.per_frame;
   }
-  // a-priori EXACT list (camera rays with u == 0 or v == 0), rebuilt only when the window changes.  The list of a batch is the
-  // frames' lists one after the other, so a list built for F frames serves every batch <= F: the launch takes a prefix.
-  // (camera frames have none: their primary rays outside the fast domain are deferred to the EXACT launch behind the main one)
-  if (!cams && (a->ap_key[0] != width || a->ap_key[1] != height || a->ap_key[2] != y0 || a->ap_key[3] != y1 || a->ap_key[4] != stride || a->ap_key[5] < batch || !a->apriori)) {
-    std::vector<uint32_t> list(1, 0u);
-    for (uint32_t t = 0; t < frame_tiles; ++t)
-      for (uint32_t l = 0; l < 64; ++l) {
-        const uint32_t x = (t % tiles_x) * 8u + (l & 7u), y = y0 + (t / tiles_x) * row_step + (l >> 3);
-        if (x >= width || y >= y1) continue;
-        const float u = (float)(((double)x * 2.0 - (double)width) / (double)height);
-        const float v = (float)(((double)y * 2.0 - (double)height) / (double)height);
-        if (u == 0.0f || v == 0.0f) list.push_back(t * 64u + l);
-      }
-    const size_t per_frame = list.size() - 1;
-    for (uint32_t f = 1; f < batch; ++f)
-      for (size_t i = 0; i < per_frame; ++i) list.push_back(list[1 + i] + f * frame_tiles * 64u);
-    list[0] = (uint32_t)(list.size() - 1);
-    if (hipDeviceSynchronize() != hipSuccess) return fail();
-    if (a->ap_cap < list.size()) {
-      (void)hipFree(a->apriori);
-      a->apriori = nullptr; a->ap_cap = 0;
-      if (hipMalloc((void**)&a->apriori, list.size() * sizeof(uint32_t)) != hipSuccess) return fail();
-      a->ap_cap = list.size();
-    }
-    if (hipMemcpy(a->apriori, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return fail();
-    a->ap_count = (uint32_t)per_frame;      // per frame
-    a->ap_key[0] = width; a->ap_key[1] = height; a->ap_key[2] = y0; a->ap_key[3] = y1; a->ap_key[4] = stride; a->ap_key[5] = batch;
+  if (!a->batch_order[r.batch]) {
+    std::vector<uint32_t> ord;
+    ord.reserve(t.total);
+    const uint32_t band = (t.per_frame + QUEUE_SHARDS - 1) / QUEUE_SHARDS;
+    for (uint32_t sh = 0; sh < QUEUE_SHARDS; ++sh)
+      for (uint32_t f = 0; f < r.batch; ++f)
+        for (uint32_t k = sh * band; k < std::min(t.per_frame, (sh + 1) * band); ++k) ord.push_back(f * t.per_frame + k);
+    if (hipMalloc((void**)&a->batch_order[r.batch], ord.size() * sizeof(uint32_t)) != hipSuccess) return false;
+    if (hipMemcpy(a->batch_order[r.batch], ord.data(), ord.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return false;
   }
-  const uint32_t ap_count = cams ? 0u : a->ap_count * batch;   // of this launch: the first `batch` frames of the list
-  // EXACT launch over the a-priori list on the side stream (ordered after everything already queued on
-  // `s`: it writes hit records the previous frame's shading pass may still be reading), concurrent with
-  // the main launch; then the main launch and the EXACT launch over whatever the main one deferred
-  PersistArgs X = A, X0 = A;
-  X.queue = c->ctl + 32 + CTL_QUEUE_DWORDS;
-  c->ctl_dirty = true;   // until the shading pass that zeroes the block again is enqueued
-  const bool side_launch = ap_count != 0;
+  return true;
+}
+
+// the context's cost and order tables for sets of `batch` frames; A gets the cost table and, once a frame of this window has been
+// sorted, the learned order
+static bool ensure_lpt_tables(FrameCtx* c, const RenderRequest& r, uint32_t n_tiles, PersistArgs& A, hipStream_t s) {
+  FrameCtx::Lpt& L = c->lpt[r.batch];
+  const bool grows = L.cap < n_tiles;
+  // (cost: n entries + n start clocks + n durations + n steal distances behind them, the latter three written by the wave-log build only)
+  if (!grow_device({{(void**)&L.cost, 4 * 4}, {(void**)&L.order, 4}}, &L.cap, n_tiles, GrowSync::STREAM, s)) return false;
+  if (grows) L.valid = false;
+  // (camera frames learn their own order: they do not share the fixed camera's tiles' costs)
+  const uint32_t key[6] = {r.width, r.height, r.y0, r.y1, (uint32_t)r.shadow | (r.stride << 1), (r.ao ? 1u : 0u) | (r.batch << 1) | (r.cams ? 0x80000000u : 0u)};
+  if (memcmp(key, L.key, sizeof key) != 0) { L.valid = false; memcpy(L.key, key, sizeof key); }
+  if (!L.cost || !L.order) return false;   // (whatever happened above: no launch with a missing table)
+  A.tile_cost = L.cost;
+  if (L.valid) A.tile_order = L.order;      // else: the static order (identity, or the batch's band-major order)
+  else if (r.batch == 1) A.tile_order = nullptr;
+  return true;
+}
+
+// a-priori EXACT list (camera rays with u == 0 or v == 0), rebuilt only when the window changes.  The list of a batch is the
+// frames' lists one after the other, so a list built for F frames serves every batch <= F: the launch takes a prefix.
+static bool ensure_apriori(vxrt_accel* a, const RenderRequest& r, const Tiles& t, hipStream_t s) {
+  if (a->ap_key[0] == r.width && a->ap_key[1] == r.height && a->ap_key[2] == r.y0 && a->ap_key[3] == r.y1 && a->ap_key[4] == r.stride && a->ap_key[5] >= r.batch && a->apriori) return true;
+  std::vector<uint32_t> list(1, 0u);
+  for (uint32_t k = 0; k < t.per_frame; ++k)
+    for (uint32_t l = 0; l < 64; ++l) {
+      const uint32_t x = (k % t.x) * 8u + (l & 7u), y = r.y0 + (k / t.x) * t.row_step + (l >> 3);
+      if (x >= r.width || y >= r.y1) continue;
+      const float u = (float)(((double)x * 2.0 - (double)r.width) / (double)r.height);
+      const float v = (float)(((double)y * 2.0 - (double)r.height) / (double)r.height);
+      if (u == 0.0f || v == 0.0f) list.push_back(k * 64u + l);
+    }
+  const size_t per_frame = list.size() - 1;
+  for (uint32_t f = 1; f < r.batch; ++f)
+    for (size_t i = 0; i < per_frame; ++i) list.push_back(list[1 + i] + f * t.per_frame * 64u);
+  list[0] = (uint32_t)(list.size() - 1);
+  if (hipDeviceSynchronize() != hipSuccess) return false;   // (whether or not the list grows: frames in flight read the one it overwrites)
+  if (!grow_device({{(void**)&a->apriori, sizeof(uint32_t)}}, &a->ap_cap, list.size(), GrowSync::NONE, s)) return false;
+  if (hipMemcpy(a->apriori, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return false;
+  a->ap_count = (uint32_t)per_frame;      // per frame
+  a->ap_key[0] = r.width; a->ap_key[1] = r.height; a->ap_key[2] = r.y0; a->ap_key[3] = r.y1; a->ap_key[4] = r.stride; a->ap_key[5] = r.batch;
+  return true;
+}
+
+// Everything the frame's launches read, grown or rebuilt where the request needs it, and the argument block A of the main launch
+static bool frame_resources(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, const Tiles& t, bool lpt, PersistArgs& A, hipStream_t s) {
+  const uint32_t n_tiles = (uint32_t)t.total;
+  // hit-record buffer between the two passes (one per frame in flight)
+  const uint64_t pixels = r.batch > 1 ? (uint64_t)n_tiles * 64u : (uint64_t)t.x * ((r.height + 7) / 8 + 1) * 64u;   // tile-major records of any row window of the frame
+  if (!grow_device({{&c->hitbuf, sizeof(HitRec)}}, &c->hitbuf_pixels, pixels, GrowSync::STREAM, s)) return false;
+  if (!r.cams && !ensure_uv_tables(a, r.width, r.height, s)) return false;
+  A.W = r.width; A.H = r.height; A.y0 = r.y0; A.y1 = r.y1; A.tiles_x = t.x; A.row_step = t.row_step; A.total = n_tiles * 64u;
+  A.div_tiles_x = fast_div_make(t.x); A.div_frame_tiles = fast_div_make(t.per_frame); A.frame_tiles = t.per_frame;
+  A.hits = (HitRec*)c->hitbuf; A.counters = r.counters; A.wave_log = r.wave_log; A.end_log = a->end_log;
+  A.utab = a->uvtab; A.vtab = a->uvtab + r.width;
+  if (r.cams) {
+    if (!upload_cameras(c, r, s)) return false;
+    A.utab = c->cam; A.vtab = c->cam + CAM_TAB;
+  }
+  if (r.batch > 1) {
+    if (!upload_batch(a, c, r, t, s)) return false;
+    A.pbatch = c->pbatch; A.tile_order = a->batch_order[r.batch];
+  }
+  if (!grow_device({{(void**)&c->defer, sizeof(uint32_t)}}, &c->defer_cap, A.total, GrowSync::STREAM, s)) return false;
+  A.defer_count = c->ctl; A.defer_list = c->defer; A.defer_cap = A.total;
+  A.queue = c->ctl + 32;
+  A.per_shard = ((A.total + QUEUE_SHARDS - 1) / QUEUE_SHARDS + 63u) & ~63u;
+  A.shard_rot = host_knobs().shard_rot;
+  if (lpt && !ensure_lpt_tables(c, r, n_tiles, A, s)) return false;
+  // (camera frames have no a-priori list: their primary rays outside the fast domain are deferred to the EXACT launch behind the main one)
+  return r.cams || ensure_apriori(a, r, t, s);
+}
+
+// How the frame's traversal is launched
+struct LaunchPlan {
+  bool lpt;             // longest tile first (see lpt_wanted); the shading launch then sorts the tiles for the context's next frame
+  // frames packed in overlapping sets: the 8-wavefront instantiation (see rt_persistent_kernel); VXRT_PACKED=0/1 forces it
+  // (VXRT_PACKED_BATCH, a measurement knob: sets of frames take it even with one frame context)
+  bool packed;
+  bool side_launch;     // an EXACT launch over the a-priori list on the side stream, concurrent with the main launch
   // the a-priori EXACT launch needs a few workgroups (3,000 rays of a 1080p frame = 12); the main launch leaves that many slots
   // free: a persistent grid that fills every CU (LDS) would otherwise keep them waiting until its first workgroups retire, and
   // the frame would end on them (measured: 33 us after the main launch, profiles/r02_d_exact_timeline.txt)
-  const uint32_t side_wgs = side_launch ? std::min<uint32_t>(EXACT_GRID, (ap_count + 255u) / 256u) : 0u;
+  uint32_t side_wgs;
   // ... on a serial frame.  With sets of frames overlapping on several streams the a-priori launch cannot get those slots anyway --
   // an EXACT workgroup needs more registers than one retired main workgroup frees, so it only finds room in a tail (measured:
   // it ends when its own main launch begins to drain, profiles/r03_a_pipeline_timeline.txt) -- and nothing waits for it before
   // the other stream's tail: the main launch takes the whole machine then, +1 % (serial: -7 %).  VXRT_SIDE_RESERVE=0/1 forces it.
-  static const int side_reserve_env = [] { const char* e = getenv("VXRT_SIDE_RESERVE"); return e ? atoi(e) : -1; }();
-  const bool side_reserve = side_reserve_env >= 0 ? side_reserve_env != 0 : a->n_ctx == 1;
-  // frames packed in overlapping sets: the 8-wavefront instantiation (see rt_persistent_kernel); VXRT_PACKED=0/1 forces it
-  static const int packed_env = [] { const char* e = getenv("VXRT_PACKED"); return e ? atoi(e) : -1; }();
-  static const int packed_batch_env = [] { const char* e = getenv("VXRT_PACKED_BATCH"); return e ? atoi(e) : 0; }();   // (measurement knob: sets of frames take it even with one frame context)
-  const bool packed = packed_env >= 0 ? packed_env != 0 : ((a->n_ctx > 1 || (packed_batch_env && batch > 1)) && n_tiles >= LPT_MIN_TILES);
-  hipStream_t side = c->side;
-  if (side_launch) {
-    // the side stream starts behind what is queued on `s` (the previous frame's shading pass reads the hit records this launch writes) --
-    // unless nothing is: a caller that waits for every frame before it starts the next (the vx_* sequence: vx_ready_wait, then vx_start)
-    // finds the stream drained, and the fork's event record -- a barrier packet in front of the main launch, ~12 us -- is not needed
-    const bool drained = hipStreamQuery(s) == hipSuccess;
-    if (!drained && (hipEventRecord(c->ev_in, s) != hipSuccess || hipStreamWaitEvent(side, c->ev_in, 0) != hipSuccess)) return fail();
-    X0.queue = c->ctl + 32 + 2 * CTL_QUEUE_DWORDS;
-    X0.defer_count = a->apriori; X0.defer_list = a->apriori + 1; X0.defer_cap = ap_count;
-  }
+  bool side_reserve;
   // A window that is small against the machine (one rank's share of a frame split N ways: at 1080p / 8 GPUs 4,080 tiles for 6,096
   // resident wavefronts) makes one launch a single round of tiles -- as long as its slowest tile, about half a full frame -- and a
   // second frame's launch only gets the slots the first one leaves.  With several frames in flight each launch therefore takes
   // its share of the machine (capacity / frames in flight): the frames run side by side, each wavefront working through several
   // tiles, and the machine stays full.  (A full frame, many tiles per wavefront, keeps the whole grid: measured better.)
-  static const int grid_div_env = [] { const char* e = getenv("VXRT_GRID_DIV"); return e ? atoi(e) : 0; }();
-#define MAIN_GRID(K) [&]() -> uint32_t { \
-    const uint32_t side_wgs_r = side_reserve ? side_wgs : 0u; \
-    uint32_t g = persistent_grid(K, A.total + (uint64_t)side_wgs_r * RT_WG_THREADS); \
-    const uint32_t cap = persistent_grid(K, ~0ull >> 8); \
-    uint32_t div = grid_div_env > 0 ? (uint32_t)grid_div_env : ((grid_div_env == 0 && a->n_ctx > 1 && (uint64_t)A.total < 2ull * 64ull * RT_WG_WAVES * cap) ? a->n_ctx : 1u); \
-    if (div > 1u) g = std::min<uint32_t>(g, std::max<uint32_t>(cap / div, 1u)); \
-    return std::max<uint32_t>(1u, g > side_wgs_r ? g - side_wgs_r : 1u); }()
-#define LAUNCH_P(J, ST, LD, PK, SH) do { \
-    if (side_launch) hipLaunchKernelGGL((rt_persistent_kernel<J, ST, LD, true>), dim3(side_wgs), block, 0, side, sc, p, X0); \
-    hipLaunchKernelGGL((rt_persistent_kernel<J, ST, LD, false, PK, SH>), dim3(MAIN_GRID((rt_persistent_kernel<J, ST, LD, false, PK, SH>))), dim3(RT_WG_THREADS), 0, s, sc, p, A); \
-    hipLaunchKernelGGL((rt_persistent_kernel<J, ST, LD, true>), dim3(EXACT_GRID), block, 0, s, sc, p, X); } while (0)
-#define LAUNCH_PD(J, ST, PK) do { if (sc.exact_decode) LAUNCH_P(J, ST, true, PK, false); else LAUNCH_P(J, ST, false, PK, false); } while (0)
-  // (timed builds: the scene's depth class picks the size of the scratch part of the stack)
-#define LAUNCH_PDS(J, PK) do { if (a->shallow) { if (sc.exact_decode) LAUNCH_P(J, 0, true, PK, true); else LAUNCH_P(J, 0, false, PK, true); } else LAUNCH_PD(J, 0, PK); } while (0)
-  // one diffuse bounce: the whole frame in the persistent launches (JOB_RENDER_GI).  (The multi-pass form it replaced -- list the hit
-  // pixels, generate the rays, a 2 M-ray trace launch, accumulate, final -- took the same 1.18 ms: profiles/r03_f_gi_fused_ab.txt)
-  const bool gi_fused = ao && ao->reserved == VXRT_AO_MODE_DIFFUSE_BOUNCE;
-  if (gi_fused && (stats || shadow || unoccluded)) return fail();
-  if (gi_fused) {
-    A.dst = dst; A.colors = colors; A.gi_seed = ao->seed;
-    X.dst = dst; X.colors = colors; X.gi_seed = ao->seed;
-    X0.dst = dst; X0.colors = colors; X0.gi_seed = ao->seed;
-    LAUNCH_PDS(JOB_RENDER_GI, false);
-  } else
-  if (stats == 2)  { if (shadow) LAUNCH_PD(JOB_RENDER_SHADOW, 2, false); else LAUNCH_PD(JOB_RENDER, 2, false); }
-  else if (stats)  { if (shadow) LAUNCH_PD(JOB_RENDER_SHADOW, 1, false); else LAUNCH_PD(JOB_RENDER, 1, false); }
-  else if (cams)   { if (shadow) LAUNCH_PDS(JOB_RENDER_SHADOW | JOB_CAM, false); else LAUNCH_PDS(JOB_RENDER | JOB_CAM, false); }
-  else if (packed) { if (shadow) LAUNCH_PDS(JOB_RENDER_SHADOW, true); else LAUNCH_PDS(JOB_RENDER, true); }
-  else             { if (shadow) LAUNCH_PDS(JOB_RENDER_SHADOW, false); else LAUNCH_PDS(JOB_RENDER, false); }
-#undef LAUNCH_PDS
-#undef LAUNCH_PD
-#undef LAUNCH_P
-#undef MAIN_GRID
-  // (the tile sort for the next frame rides in the shading launch; the AO / bounce tails have no such launch and skip it)
-  const bool lpt_sort = lpt && !ao && !(p.max_depth > 1 && a->max_reflectivity > 0.0f);
-  if (lpt && !lpt_sort) L.valid = false;
-  if (side_launch) {
-    if (hipEventRecord(c->ev_side, side) != hipSuccess || hipStreamWaitEvent(s, c->ev_side, 0) != hipSuccess) return fail();
+  // VXRT_GRID_DIV=n forces the divisor for every window; a negative value switches it off.
+  uint32_t grid_div;    // the main launch takes at most capacity / grid_div workgroups ...
+  bool grid_div_small;  // ... only if its window is small against the machine (see main_grid)
+};
+static LaunchPlan launch_plan(const vxrt_accel* a, const RenderRequest& r, uint32_t n_tiles, bool lpt, uint32_t ap_count) {
+  const HostKnobs& k = host_knobs();
+  LaunchPlan plan;
+  plan.lpt = lpt;
+  plan.packed = k.packed >= 0 ? k.packed != 0 : ((a->n_ctx > 1 || (k.packed_batch && r.batch > 1)) && n_tiles >= LPT_MIN_TILES);
+  plan.side_launch = ap_count != 0;
+  plan.side_wgs = plan.side_launch ? std::min<uint32_t>(EXACT_GRID, (ap_count + 255u) / 256u) : 0u;
+  plan.side_reserve = k.side_reserve >= 0 ? k.side_reserve != 0 : a->n_ctx == 1;
+  plan.grid_div = k.grid_div > 0 ? (uint32_t)k.grid_div : ((k.grid_div == 0 && a->n_ctx > 1) ? a->n_ctx : 1u);
+  plan.grid_div_small = k.grid_div == 0;
+  return plan;
+}
+
+// grid of the main launch: what the machine holds of `kernel`, less the slots reserved for the side launch, divided as the plan says
+template <class K>
+static uint32_t main_grid(K kernel, const LaunchPlan& plan, uint32_t total) {
+  const uint32_t side_wgs_r = plan.side_reserve ? plan.side_wgs : 0u;
+  uint32_t g = persistent_grid(kernel, total + (uint64_t)side_wgs_r * RT_WG_THREADS);
+  const uint32_t cap = persistent_grid(kernel, ~0ull >> 8);
+  const uint32_t div = (plan.grid_div_small && (uint64_t)total >= 2ull * 64ull * RT_WG_WAVES * cap) ? 1u : plan.grid_div;
+  if (div > 1u) g = std::min<uint32_t>(g, std::max<uint32_t>(cap / div, 1u));
+  return std::max<uint32_t>(1u, g > side_wgs_r ? g - side_wgs_r : 1u);
+}
+
+// what the three traversal launches of a frame share
+struct FrameLaunch {
+  const vxrt_accel* a; FrameCtx* c; const LaunchPlan& plan; const ShadeParams& p; hipStream_t s;
+  PersistArgs A, X, X0;   // argument blocks of the main launch, of the EXACT launch over what it defers, of the a-priori EXACT launch
+};
+
+// EXACT launch over the a-priori list on the side stream, concurrent with the main launch; then the main launch and the EXACT
+// launch over whatever the main one deferred.  (The EXACT form knows neither PACKED nor SHALLOW.)
+template <int JOB, int STATS, bool PACKED>
+static void launch_traversal(const FrameLaunch& l) {
+  static_assert(!(PACKED && (JOB == JOB_RENDER_GI || STATS != 0)), "only the timed render jobs have a packed form");
+  with_decode_and_depth<STATS == 0>(l.a, [&](auto ld, auto sh) {
+    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, PACKED, decltype(sh)::value>;
+    const auto k_exact = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, true>;
+    if (l.plan.side_launch) hipLaunchKernelGGL(k_exact, dim3(l.plan.side_wgs), dim3(256), 0, l.c->side, l.a->dev, l.p, l.X0);
+    hipLaunchKernelGGL(k_main, dim3(main_grid(k_main, l.plan, l.A.total)), dim3(RT_WG_THREADS), 0, l.s, l.a->dev, l.p, l.A);
+    hipLaunchKernelGGL(k_exact, dim3(EXACT_GRID), dim3(256), 0, l.s, l.a->dev, l.p, l.X);
+  });
+}
+template <int STATS, bool PACKED, int CAM = 0>
+static void launch_render(bool shadow, const FrameLaunch& l) {
+  if (shadow) launch_traversal<JOB_RENDER_SHADOW | CAM, STATS, PACKED>(l); else launch_traversal<JOB_RENDER | CAM, STATS, PACKED>(l);
+}
+
+// The traversal of the frame: fork the side stream, the three launches, join.  false: a HIP call failed.
+static bool traverse_frame(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, const LaunchPlan& plan, const ShadeParams& p, const PersistArgs& A, hipStream_t s) {
+  FrameLaunch l{a, c, plan, p, s, A, A, A};
+  l.X.queue = c->ctl + 32 + CTL_QUEUE_DWORDS;
+  c->ctl_dirty = true;   // until the shading pass that zeroes the block again is enqueued
+  if (plan.side_launch) {
+    // the side stream starts behind what is queued on `s` (the previous frame's shading pass reads the hit records this launch writes) --
+    // unless nothing is: a caller that waits for every frame before it starts the next (the vx_* sequence: vx_ready_wait, then vx_start)
+    // finds the stream drained, and the fork's event record -- a barrier packet in front of the main launch, ~12 us -- is not needed
+    const bool drained = hipStreamQuery(s) == hipSuccess;
+    if (!drained && (hipEventRecord(c->ev_in, s) != hipSuccess || hipStreamWaitEvent(c->side, c->ev_in, 0) != hipSuccess)) return false;
+    const uint32_t ap_count = a->ap_count * r.batch;   // the first `batch` frames of the list
+    l.X0.queue = c->ctl + 32 + 2 * CTL_QUEUE_DWORDS;
+    l.X0.defer_count = a->apriori; l.X0.defer_list = a->apriori + 1; l.X0.defer_cap = ap_count;
   }
-  if (gi_fused) {
+  if (gi_fused_frame(r)) {
+    // one diffuse bounce: the whole frame in the persistent launches (JOB_RENDER_GI).  (The multi-pass form it replaced -- list the hit
+    // pixels, generate the rays, a 2 M-ray trace launch, accumulate, final -- took the same 1.18 ms: profiles/r03_f_gi_fused_ab.txt)
+    for (PersistArgs* g : {&l.A, &l.X, &l.X0}) { g->dst = r.dst; g->colors = r.colors; g->gi_seed = r.ao->seed; }
+    launch_traversal<JOB_RENDER_GI, 0, false>(l);
+  }
+  else if (r.counting == Counting::TIMED_TRAVERSAL) launch_render<2, false>(r.shadow != 0, l);
+  else if (r.counting == Counting::REFERENCE_ORDER) launch_render<1, false>(r.shadow != 0, l);
+  else if (r.cams)      launch_render<0, false, JOB_CAM>(r.shadow != 0, l);
+  else if (plan.packed) launch_render<0, true>(r.shadow != 0, l);
+  else                  launch_render<0, false>(r.shadow != 0, l);
+  return !plan.side_launch || (hipEventRecord(c->ev_side, c->side) == hipSuccess && hipStreamWaitEvent(s, c->ev_side, 0) == hipSuccess);
+}
+
+// The shading launch of a plain frame; with lpt_sort its first workgroups sort the tiles for the context's next frame
+static bool shade_frame(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, const Tiles& t, bool lpt_sort, const ShadeParams& p, const PersistArgs& A, hipStream_t s) {
+  const FrameCtx::Lpt& L = c->lpt[r.batch];
+  const uint32_t n_tiles = (uint32_t)t.total, n_rows = t.y * 8u;
+  const uint64_t npx = (uint64_t)r.width * n_rows * r.batch;
+  const uint32_t lpt_blocks = lpt_sort ? QUEUE_SHARDS : 0u;
+  const dim3 sgrid((uint32_t)((npx + 255) / 256) + lpt_blocks), block(256);
+  const uint32_t* base_order = r.batch > 1 ? (const uint32_t*)a->batch_order[r.batch] : (const uint32_t*)nullptr;
+  // (the camera kernels take the camera block for the two tables and have no counters: a launch per signature)
+  if (r.cams) {
+    hipLaunchKernelGGL(r.batch > 1 ? rt_shade_camera_kernel<true> : rt_shade_camera_kernel<false>, sgrid, block, 0, s, a->dev, p, r.width, r.height, r.y0, r.y1, t.row_step,
+                       n_rows, (const float*)A.utab, (const HitRec*)c->hitbuf, r.dst, (HitRec*)r.hits, r.colors, c->ctl, lpt_blocks, (const uint32_t*)L.cost,
+                       L.order, n_tiles, A.per_shard >> 6, r.batch, (const ShadeParams*)c->pbatch, r.dst_frame_stride, base_order);
+  } else {
+    // (the counting build shades single frames only: the one set of frames it sees, the wave-log diagnostic, is traversal only)
+    const bool stats = r.counting != Counting::TIMED;
+    hipLaunchKernelGGL(stats ? rt_shade_kernel<true> : rt_shade_kernel<false>, sgrid, block, 0, s, a->dev, p, r.width, r.height, r.y0, r.y1, t.row_step,
+                       n_rows, A.utab, A.vtab, (const HitRec*)c->hitbuf, r.dst, (HitRec*)r.hits, r.colors, r.counters, c->ctl, lpt_blocks, (const uint32_t*)L.cost,
+                       L.order, n_tiles, A.per_shard >> 6, stats ? 1u : r.batch, stats ? (const ShadeParams*)nullptr : (const ShadeParams*)c->pbatch,
+                       stats ? (uint64_t)0 : r.dst_frame_stride, base_order);
+  }
+  return hipGetLastError() == hipSuccess;
+}
+
+static int render_common(vxrt_accel_t* a, const RenderRequest& r) {
+  const int go = check_request(a, r);
+  if (go <= 0) return go;
+  uint32_t* st = status_word();
+  if (!st) return -1;
+  const ShadeParams p = shade_params(r.params[0]);
+  const Tiles t = window_tiles(r);
+  hipStream_t s = (hipStream_t)r.stream;
+  FrameCtx* c = acquire_ctx(a, s);
+  if (!c) return -1;
+  // from here on a failure releases the context the way a success does: its event is recorded behind whatever was enqueued, the
+  // context is marked busy on this stream and its control block is cleared before the next use
+  auto fail = [&]() -> int { c->ctl_dirty = true; (void)release_ctx(a, c, s); return -1; };
+  const bool lpt = lpt_wanted(a, r, (uint32_t)t.total);
+  PersistArgs A{};
+  A.status = st;
+  if (!frame_resources(a, c, r, t, lpt, A, s)) return fail();
+  const LaunchPlan plan = launch_plan(a, r, (uint32_t)t.total, lpt, r.cams ? 0u : a->ap_count * r.batch);
+  if (!traverse_frame(a, c, r, plan, p, A, s)) return fail();
+  // (the tile sort for the next frame rides in the shading launch; the AO / bounce tails have no such launch and skip it)
+  const bool mirror = mirror_frame(a, r.params[0]);
+  const bool lpt_sort = plan.lpt && !r.ao && !mirror;
+  if (plan.lpt && !lpt_sort) c->lpt[r.batch].valid = false;
+  if (gi_fused_frame(r)) {
     // nothing follows: the pixels are written.  The control block stays as the launches left it; the context's next call clears it.
     if (hipGetLastError() != hipSuccess) return fail();
-    return release_ctx(a, c, s);
-  }
-  if (ao) {
-    if (render_ao_tail(a, c, p, width, y0, y1, ao, A.utab, A.vtab, dst, colors, unoccluded, counters, s) != 0) return fail();
-    return release_ctx(a, c, s);
-  }
-  if (p.max_depth > 1 && a->max_reflectivity > 0.0f) {
+  } else if (r.ao) {
+    if (render_ao_tail(a, c, r, p, A.utab, A.vtab) != 0) return fail();
+  } else if (mirror) {
     // reflective instances: the shading pass becomes the level-0 step of the mirror-bounce wavefront
-    if (render_bounce_tail(a, c, p, width, y0, y1, shadow, A.utab, A.vtab, dst, (HitRec*)hits, colors, counters, s, height, cams ? A.utab : nullptr) != 0) return fail();
-    return release_ctx(a, c, s);
+    if (render_bounce_tail(a, c, r, p, A.utab, A.vtab) != 0) return fail();
+  } else {
+    if (!shade_frame(a, c, r, t, lpt_sort, p, A, s)) return fail();
+    if (lpt_sort) c->lpt[r.batch].valid = true;
+    c->ctl_dirty = false;
   }
-  const uint64_t npx = (uint64_t)width * tiles_y * 8u * batch;
-  const uint32_t lpt_blocks = lpt_sort ? QUEUE_SHARDS : 0u;
-  dim3 sgrid((uint32_t)((npx + 255) / 256) + lpt_blocks);
-  if (cams) hipLaunchKernelGGL(batch > 1 ? rt_shade_camera_kernel<true> : rt_shade_camera_kernel<false>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step,
-                               tiles_y * 8u, (const float*)A.utab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, c->ctl, lpt_blocks, (const uint32_t*)L.cost,
-                               L.order, n_tiles, A.per_shard >> 6, batch, (const ShadeParams*)c->pbatch, dst_frame_stride,
-                               batch > 1 ? (const uint32_t*)a->batch_order[batch] : (const uint32_t*)nullptr);
-  else if (stats) hipLaunchKernelGGL(rt_shade_kernel<true>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step, tiles_y * 8u, A.utab, A.vtab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, counters, c->ctl,
-                                lpt_blocks, (const uint32_t*)L.cost, L.order, n_tiles, A.per_shard >> 6, 1u, (const ShadeParams*)nullptr, (uint64_t)0,
-                                batch > 1 ? (const uint32_t*)a->batch_order[batch] : (const uint32_t*)nullptr);
-  else       hipLaunchKernelGGL(rt_shade_kernel<false>, sgrid, block, 0, s, sc, p, width, height, y0, y1, row_step, tiles_y * 8u, A.utab, A.vtab, (const HitRec*)c->hitbuf, dst, (HitRec*)hits, colors, counters, c->ctl,
-                                lpt_blocks, (const uint32_t*)L.cost, L.order, n_tiles, A.per_shard >> 6, batch, (const ShadeParams*)c->pbatch, dst_frame_stride,
-                                batch > 1 ? (const uint32_t*)a->batch_order[batch] : (const uint32_t*)nullptr);
-  if (hipGetLastError() != hipSuccess) return fail();
-  if (lpt_sort) L.valid = true;
-  c->ctl_dirty = false;
   return release_ctx(a, c, s);
 }
+
+extern "C" {
+
+const char* vxrt_version(void) { return "vortex-rt-mi355x 0.3 (gfx950, compact 64-byte nodes, persistent wavefronts)"; }
 
 int vxrt_render(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                 const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits,
                 float* colors, unsigned long long* rays_traced, void* stream) {
-  return render_common(accel, width, height, y0, y1, params, shadow, dst, hits, colors, rays_traced, false, stream);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow;
+  r.dst = dst; r.hits = hits; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // Tile rows phase, phase + stride, phase + 2 stride, ... of the frame (8 rows each): what rank `phase` of `stride` ranks renders when one
@@ -2710,7 +2817,10 @@ int vxrt_render_interleaved(vxrt_accel_t* accel, uint32_t width, uint32_t height
                             float* colors, unsigned long long* rays_traced, void* stream) {
   if (stride == 0 || phase >= stride) return -1;
   if ((uint64_t)phase * 8u >= height) return 0;   // more ranks than tile rows: nothing for this one
-  return render_common(accel, width, height, phase * 8u, height, params, shadow, dst, hits, colors, rays_traced, false, stream, nullptr, nullptr, nullptr, stride);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = phase * 8u; r.y1 = height; r.stride = stride; r.params = params; r.shadow = shadow;
+  r.dst = dst; r.hits = hits; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // n_frames frames of the same window in ONE set of launches: frame f is lit and shaded with params[f] and written to dst + f *
@@ -2721,8 +2831,10 @@ int vxrt_render_interleaved_batch(vxrt_accel_t* accel, uint32_t width, uint32_t 
                                   unsigned long long* rays_traced, void* stream) {
   if (stride == 0 || phase >= stride || n_frames == 0) return -1;
   if ((uint64_t)phase * 8u >= height) return 0;
-  return render_common(accel, width, height, phase * 8u, height, params, shadow, dst, nullptr, nullptr, rays_traced, false, stream, nullptr, nullptr, nullptr, stride,
-                       n_frames, dst_frame_stride);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = phase * 8u; r.y1 = height; r.stride = stride; r.params = params; r.batch = n_frames; r.shadow = shadow;
+  r.dst = dst; r.dst_frame_stride = dst_frame_stride; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // n_frames frames of the row window [y0, y1) in one set of launches: what a rank renders when the frame is split into contiguous
@@ -2733,8 +2845,10 @@ int vxrt_render_rows_batch(vxrt_accel_t* accel, uint32_t width, uint32_t height,
                            const vxrt_shade_params_t* params, int shadow, uint32_t* dst, uint64_t dst_frame_stride,
                            unsigned long long* rays_traced, void* stream) {
   if (n_frames == 0) return -1;
-  return render_common(accel, width, height, y0, y1, params, shadow, dst, nullptr, nullptr, rays_traced, false, stream, nullptr, nullptr, nullptr, 1,
-                       n_frames, dst_frame_stride);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.batch = n_frames; r.shadow = shadow;
+  r.dst = dst; r.dst_frame_stride = dst_frame_stride; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // diagnostic: vxrt_render_interleaved_batch's traversal launch with the per-wavefront log of vxrt_render_wave_log (counting build of the
@@ -2743,8 +2857,11 @@ int vxrt_render_interleaved_batch_wave_log(vxrt_accel_t* accel, uint32_t width, 
                                            const vxrt_shade_params_t* params, int shadow, uint32_t* dst, uint64_t dst_frame_stride,
                                            unsigned long long* counters, unsigned long long* wave_log, void* stream) {
   if (stride == 0 || phase >= stride || n_frames == 0 || !wave_log || !counters) return -1;
-  return render_common(accel, width, height, phase * 8u, height, params, shadow, dst, nullptr, nullptr, counters, 2, stream, wave_log, nullptr, nullptr, stride,
-                       n_frames, dst_frame_stride);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = phase * 8u; r.y1 = height; r.stride = stride; r.params = params; r.batch = n_frames; r.shadow = shadow;
+  r.dst = dst; r.dst_frame_stride = dst_frame_stride; r.counters = counters; r.wave_log = wave_log; r.stream = stream;
+  r.counting = Counting::TIMED_TRAVERSAL;
+  return render_common(accel, r);
 }
 
 // n_frames whole frames in one set of launches (vxrt_render_interleaved_batch with a single rank)
@@ -2766,7 +2883,10 @@ int vxrt_render_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t w
                        const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits, float* colors,
                        unsigned long long* rays_traced, void* stream) {
   if (!camera_ok(cam)) return -1;
-  return render_common(accel, width, height, y0, y1, params, shadow, dst, hits, colors, rays_traced, false, stream, nullptr, nullptr, nullptr, 1, 1, 0, cam);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow; r.cams = cam;
+  r.dst = dst; r.hits = hits; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // vxrt_render_batch with cams[f] per frame (see the header)
@@ -2777,8 +2897,10 @@ int vxrt_render_batch_camera(vxrt_accel_t* accel, uint32_t width, uint32_t heigh
   for (uint32_t f = 0; f < n_frames; ++f) if (!camera_ok(cams + f)) return -1;
   if (!accel || accel->stale || !params || !dst) return -1;
   if (height == 0) return 0;   // (as vxrt_render_batch: no tile row to render)
-  return render_common(accel, width, height, 0, height, params, shadow, dst, nullptr, nullptr, rays_traced, false, stream, nullptr, nullptr, nullptr, 1,
-                       n_frames, dst_frame_stride, cams);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = 0; r.y1 = height; r.params = params; r.batch = n_frames; r.shadow = shadow; r.cams = cams;
+  r.dst = dst; r.dst_frame_stride = dst_frame_stride; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // Same launches as vxrt_render with the fetch counters compiled in (slower; never the timed path).
@@ -2787,7 +2909,10 @@ int vxrt_render_batch_camera(vxrt_accel_t* accel, uint32_t width, uint32_t heigh
 int vxrt_render_stats(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                       const vxrt_shade_params_t* params, int shadow, uint32_t* dst,
                       unsigned long long* counters, void* stream) {
-  return render_common(accel, width, height, y0, y1, params, shadow, dst, nullptr, nullptr, counters, true, stream);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow;
+  r.dst = dst; r.counters = counters; r.stream = stream; r.counting = Counting::REFERENCE_ORDER;
+  return render_common(accel, r);
 }
 
 // vxrt_render_stats for the traversal the TIMED kernel performs: occlusion rays of a frame visit children in slot order (the
@@ -2796,7 +2921,10 @@ int vxrt_render_stats(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint
 int vxrt_render_stats_timed(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                             const vxrt_shade_params_t* params, int shadow, uint32_t* dst,
                             unsigned long long* counters, void* stream) {
-  return render_common(accel, width, height, y0, y1, params, shadow, dst, nullptr, nullptr, counters, 2, stream);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow;
+  r.dst = dst; r.counters = counters; r.stream = stream; r.counting = Counting::TIMED_TRAVERSAL;
+  return render_common(accel, r);
 }
 
 // diagnostic: vxrt_render_stats that also logs, per wavefront of the main traversal launch, the first
@@ -2805,7 +2933,10 @@ int vxrt_render_stats_timed(vxrt_accel_t* accel, uint32_t width, uint32_t height
 int vxrt_render_wave_log(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                          const vxrt_shade_params_t* params, int shadow, uint32_t* dst,
                          unsigned long long* counters, unsigned long long* wave_log, void* stream) {
-  return render_common(accel, width, height, y0, y1, params, shadow, dst, nullptr, nullptr, counters, 2, stream, wave_log);   // the timed traversal
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow;
+  r.dst = dst; r.counters = counters; r.wave_log = wave_log; r.stream = stream; r.counting = Counting::TIMED_TRAVERSAL;
+  return render_common(accel, r);
 }
 
 int vxrt_render_diffuse_bounce(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
@@ -2813,14 +2944,20 @@ int vxrt_render_diffuse_bounce(vxrt_accel_t* accel, uint32_t width, uint32_t hei
                                unsigned long long* rays_traced, void* stream) {
   vxrt_ao_params_t gi{};
   gi.spp = 1; gi.radius = RT_LARGE_FLOAT; gi.seed = seed; gi.reserved = VXRT_AO_MODE_DIFFUSE_BOUNCE;
-  return render_common(accel, width, height, y0, y1, params, 0, dst, nullptr, colors, rays_traced, false, stream, nullptr, &gi, nullptr);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = &gi;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 int vxrt_render_ao(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                    const vxrt_shade_params_t* params, const vxrt_ao_params_t* ao, uint32_t* dst, float* colors,
                    uint32_t* unoccluded, unsigned long long* rays_traced, void* stream) {
   if (!ao || ao->spp == 0 || ao->spp > 4096 || !(ao->radius > 0.0f) || ao->reserved != 0) return -1;
-  return render_common(accel, width, height, y0, y1, params, 0, dst, nullptr, colors, rays_traced, false, stream, nullptr, ao, unoccluded);
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = ao;
+  r.dst = dst; r.colors = colors; r.unoccluded = unoccluded; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
 }
 
 // vxrt_trace with the fetch counters compiled in (slower; never the timed path): counters = device u64[8],
@@ -2895,11 +3032,7 @@ int vxrt_shade_rays(vxrt_accel_t* a, const float* rays, const vxrt_hit_t* hits, 
   if (n == 0) return 0;
   if (n > 0x7fffffffull) return -1;
   // a hit record names a triangle and an instance: both must exist (records a caller made up are not trusted)
-  ShadeParams p;
-  for (int i = 0; i < 3; ++i) {
-    p.amb[i] = params->ambient[i]; p.lcol[i] = params->light_color[i];
-    p.lpos[i] = params->light_pos[i]; p.bg[i] = params->background[i];
-  }
+  ShadeParams p = shade_params(*params);
   p.max_depth = 1;
   hipLaunchKernelGGL(rt_shade_rays_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->dev, p, n, rays, (const HitRec*)hits, colors, rgb8);
   return hipGetLastError() == hipSuccess ? 0 : -1;
