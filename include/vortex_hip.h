@@ -412,6 +412,17 @@ int vxrt_render_ao(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_
                    const vxrt_shade_params_t* params, const vxrt_ao_params_t* ao, uint32_t* dst, float* colors,
                    uint32_t* unoccluded, unsigned long long* rays_traced, void* stream);
 
+/* vxrt_render_ao seen from `cam` (see vxrt_camera_t): orc_render_ao with the pinhole ray of pixel (x, y) in place of the fixed
+ * GenerateRay and everything else unchanged -- the seed WangHash((x + y * W) * spp + s + 1 + seed * 0x9E3779B9), the view
+ * direction (that ray's direction) the normal is turned against, the 1e-3 push along the facing normal, tmax = radius, any-hit,
+ * pixel = Lambert colour of the primary hit x unoccluded / spp, rays_traced = primary + occlusion rays.  `cam` is a host pointer
+ * read during the call; no host synchronisation is added to what vxrt_render_ao does.  Returns -1 before anything is launched
+ * (dst untouched) for a null camera, a camera field that is not finite, a stale accel, and whatever vxrt_render_ao refuses.  There
+ * is no batch form, no interleaved form and no counting build. */
+int vxrt_render_ao_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                          const vxrt_shade_params_t* params, const vxrt_ao_params_t* ao, uint32_t* dst, float* colors /* optional */,
+                          uint32_t* unoccluded /* optional */, unsigned long long* rays_traced /* optional */, void* stream);
+
 /* One diffuse bounce (extension for BASELINE config 3, "1 bounce diffuse"; absent from the reference): per pixel with
  * a primary hit one cosine-weighted ray about the shading normal -- the vxrt_render_ao recipe with spp = 1, sample 0,
  * no tmax -- traced for its closest hit; pixel = Lambert colour of the primary hit + albedo * (Lambert colour of the
@@ -419,6 +430,14 @@ int vxrt_render_ao(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_
 int vxrt_render_diffuse_bounce(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                                const vxrt_shade_params_t* params, uint32_t seed, uint32_t* dst, float* colors,
                                unsigned long long* rays_traced, void* stream);
+
+/* vxrt_render_diffuse_bounce seen from `cam`: orc_render_gi with the pinhole ray of pixel (x, y) in place of the fixed GenerateRay
+ * (primary ray and view direction of the bounce recipe); the bounce ray is traced for its closest hit, pixel = Lambert colour of
+ * the primary hit + albedo * (Lambert colour of the bounce hit | background), rays_traced = primary + bounce rays.  Contract and
+ * refusals as for vxrt_render_ao_camera, with what vxrt_render_diffuse_bounce refuses. */
+int vxrt_render_diffuse_bounce_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                      const vxrt_shade_params_t* params, uint32_t seed, uint32_t* dst, float* colors /* optional */,
+                                      unsigned long long* rays_traced /* optional */, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

@@ -496,7 +496,8 @@ __device__ __forceinline__ void ao_sample_ray(uint32_t x, uint32_t y, uint32_t W
 enum { JOB_RENDER = 0, JOB_RENDER_SHADOW = 1, JOB_TRACE = 2, JOB_RENDER_GI = 3, JOB_TRACE_UNORDERED = 4 };
 __host__ __device__ constexpr bool is_trace_job(int job) { return job == JOB_TRACE || job == JOB_TRACE_UNORDERED; }
 // JOB_CAM: a render job seen from a caller-supplied pinhole camera (vxrt_render_camera) instead of the fixed GenerateRay: its own
-// instantiations, so the fixed-camera kernels do not change.  JOB_RENDER | JOB_CAM and JOB_RENDER_SHADOW | JOB_CAM only.
+// instantiations, so the fixed-camera kernels do not change.  JOB_RENDER | JOB_CAM, JOB_RENDER_SHADOW | JOB_CAM and
+// JOB_RENDER_GI | JOB_CAM (vxrt_render_diffuse_bounce_camera); job_base() names the job without the bit.
 enum { JOB_CAM = 8 };
 __host__ __device__ constexpr int job_base(int job) { return job & ~JOB_CAM; }
 __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) != 0; }
@@ -624,12 +625,12 @@ __device__ __forceinline__ float vmax_nonan(float a, float b) { float r; asm("v_
 // scratch is sized for that instead of for the reference's 32 levels: 344 instead of 768 bytes per lane for the 8-wavefront instantiation.
 // (The 1,048,576-triangle atrium is 13 levels deep, the 10 M-triangle hairball 15.)  Timed builds only; deeper scenes take the full-size form.
 template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false>
-__global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (JOB == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
+__global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
   // stack levels in LDS: what the instantiation's occupancy leaves room for (160 KB per CU)
-  constexpr int LSTK = EXACT ? LDS_STACK : (is_trace_job(JOB) ? RT_LDS_STACK_TRACE : (JOB == JOB_RENDER_GI ? RT_LDS_STACK_GI : (PACKED ? RT_LDS_STACK_RENDER_PACKED : RT_LDS_STACK_RENDER)));
+  constexpr int LSTK = EXACT ? LDS_STACK : (is_trace_job(JOB) ? RT_LDS_STACK_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_LDS_STACK_GI : (PACKED ? RT_LDS_STACK_RENDER_PACKED : RT_LDS_STACK_RENDER)));
   constexpr int WG_WAVES = EXACT ? 4 : RT_WG_WAVES;
   constexpr bool USE_TOP = RT_TOP_NODES > 0 && !EXACT && !LDEXP;   // (the ldexp decode reads exponents from the reference node by index)
-  constexpr uint32_t DEAD_MAX = is_trace_job(JOB) ? RT_TRACE_DEAD_MAX : (JOB == JOB_RENDER_GI ? RT_GI_DEAD_MAX : RT_DEAD_MAX);
+  constexpr uint32_t DEAD_MAX = is_trace_job(JOB) ? RT_TRACE_DEAD_MAX : (job_base(JOB) == JOB_RENDER_GI ? RT_GI_DEAD_MAX : RT_DEAD_MAX);
   // render-with-shadow jobs: retire finished primary rays (their lanes continue with the occlusion ray
   // of the same pixel - same traversal code, so no phase mixing) before the whole tile is done
   constexpr uint32_t FINISH_MIN = job_base(JOB) == JOB_RENDER_SHADOW ? RT_SHADOW_FINISH_MIN : 65u;
@@ -749,7 +750,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       uint32_t x, y;
       pixel_of(job, x, y);
       pixel_ray(x, y, ox, oy, oz, dx, dy, dz);
-      if (JOB == JOB_RENDER_GI && (flags & F_SHADOW)) {   // bounce phase: the ray drawn when the primary ray finished
+      if (job_base(JOB) == JOB_RENDER_GI && (flags & F_SHADOW)) {   // bounce phase: the ray drawn when the primary ray finished
         ox = g_ray[0]; oy = g_ray[1]; oz = g_ray[2]; dx = g_ray[3]; dy = g_ray[4]; dz = g_ray[5];
       }
       if (job_base(JOB) == JOB_RENDER_SHADOW && (flags & F_SHADOW)) {
@@ -768,8 +769,8 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     const uint32_t slot = atomicAdd(A.defer_count, 1u);
     // (JOB_RENDER_GI: a bounce ray outside the fast domain sends the whole PIXEL to the EXACT launch, which traces its primary ray again
     // -- same hit by construction -- and goes on from there; the primary ray this launch counted is taken back)
-    if (JOB == JOB_RENDER_GI && (flags & F_SHADOW)) nrays--;
-    if (slot < A.defer_cap) A.defer_list[slot] = job | ((flags & F_SHADOW) && JOB != JOB_RENDER_GI ? 0x80000000u : 0u);
+    if (job_base(JOB) == JOB_RENDER_GI && (flags & F_SHADOW)) nrays--;
+    if (slot < A.defer_cap) A.defer_list[slot] = job | ((flags & F_SHADOW) && job_base(JOB) != JOB_RENDER_GI ? 0x80000000u : 0u);
     if (job_base(JOB) == JOB_RENDER_SHADOW && (flags & F_SHADOW)) {
       // the EXACT launch resumes this pixel's occlusion ray from the primary hit record in memory
       HitRec h;
@@ -1182,7 +1183,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
           __builtin_nontemporal_store(h.blasIdx, hp + 4); __builtin_nontemporal_store(h.triIdx, hp + 5);
         } else *hit_slot() = h;
         cur = DESC_IDLE;
-      } else if (JOB == JOB_RENDER_GI) {
+      } else if (job_base(JOB) == JOB_RENDER_GI) {
         // one diffuse bounce, in the lane (see JOB_RENDER_GI above).  Every step is the code of the pass it replaces:
         // rt_ao_prepare_kernel (colour / albedo / hit point / normal of the primary hit), rt_ao_rays_kernel (the bounce ray) and, for the rest,
         // what the multi-pass form did after its trace launch: shade the bounce hit, colour += albedo * that, pack (orc_render_gi).
@@ -1197,7 +1198,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
         }
         if (!(flags & F_SHADOW)) {
           float ox, oy, oz, dx, dy, dz;
-          generate_ray(A.utab[x], A.vtab[y], ox, oy, oz, dx, dy, dz);
+          pixel_ray(x, y, ox, oy, oz, dx, dy, dz);
           if (!found) {
             cr = p.bg[0]; cg = p.bg[1]; cb = p.bg[2];   // miss.cpp:9-14; no bounce
             write = true;
@@ -1589,8 +1590,10 @@ __global__ __launch_bounds__(256) void rt_bounce_unwind_kernel(uint32_t n, const
 // per pixel of rows [y0,y1): Lambert colour of the primary hit (else arm of closest.cpp), hit point and
 // shading normal for the occlusion rays; geo[t] = (I, hit?), nrm[t] = (N, 0), col[t] = (rgb, 0), cnt[t] = 0;
 // pixels with a hit are appended to list[] (count in hdr[0]; the order is arbitrary, nothing depends on it)
+// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
 #define AO_PREP_CHUNKS 4   // pixels per thread of rt_ao_prepare_kernel: one list-append atomic per 1,024 pixels
-__global__ __launch_bounds__(256) void rt_ao_prepare_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
+template <bool CAM>
+__device__ __forceinline__ void ao_prepare_pass(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
     const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
     float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
     uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float4* __restrict__ alb /* optional: albedo of the hit */) {
@@ -1611,7 +1614,8 @@ __global__ __launch_bounds__(256) void rt_ao_prepare_kernel(SceneDev sc, ShadePa
       HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
       h.blasIdx &= 0x7fffffffu;
       float ox, oy, oz, dx, dy, dz;
-      generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
+      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
       float r, g, b;
       if (h.dist == RT_LARGE_FLOAT) {
         r = p.bg[0]; g = p.bg[1]; b = p.bg[2];
@@ -1648,9 +1652,24 @@ __global__ __launch_bounds__(256) void rt_ao_prepare_kernel(SceneDev sc, ShadePa
   for (int c = 0; c < AO_PREP_CHUNKS; ++c)
     if (hit_c[c]) list[s_base + s_cnt[c][wv] + off_c[c]] = (uint32_t)(((uint64_t)blockIdx.x * AO_PREP_CHUNKS + c) * 256u + threadIdx.x);
 }
+__global__ __launch_bounds__(256) void rt_ao_prepare_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float4* __restrict__ alb) {
+  ao_prepare_pass<false>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, col, cnt, list, hdr, ctl_reset, alb);
+}
+// the same pass of a camera frame (vxrt_render_ao_camera): cam = the frame context's camera block, whose head every lane reads at the
+// same address -- scalar loads, the camera stays in SGPRs
+__global__ __launch_bounds__(256) void rt_ao_prepare_camera_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ cam, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
+  ao_prepare_pass<true>(sc, p, n, W, y0, cam, cam + CAM_TAB, hb, geo, nrm, col, cnt, list, hdr, ctl_reset, nullptr);
+}
 
 // samples [s0, s0 + ns) of every listed pixel: ray i = (pixel list[i / ns], sample s0 + i % ns); hdr[1] = number of rays
-__global__ __launch_bounds__(256) void rt_ao_rays_kernel(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
+template <bool CAM>
+__device__ __forceinline__ void ao_rays_pass(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
     const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
     uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
   const uint64_t total = (uint64_t)hdr[0] * ns;
@@ -1662,13 +1681,25 @@ __global__ __launch_bounds__(256) void rt_ao_rays_kernel(uint64_t cap, uint32_t 
   const float4 gI = geo[t];
   const uint32_t x = t % W, y = y0 + t / W;
   float ox, oy, oz, vdx, vdy, vdz;
-  generate_ray(utab[x], vtab[y], ox, oy, oz, vdx, vdy, vdz);
+  if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, vdx, vdy, vdz);
+  else generate_ray(utab[x], vtab[y], ox, oy, oz, vdx, vdy, vdz);
   const float4 gN = nrm[t];
   float r6[6];
   ao_sample_ray(x, y, W, spp, smp, user_seed, gI.x, gI.y, gI.z, gN.x, gN.y, gN.z, vdx, vdy, vdz, r6);
 #pragma unroll
   for (int k = 0; k < 6; ++k) o[k] = r6[k];
   tmax[i] = radius;
+}
+__global__ __launch_bounds__(256) void rt_ao_rays_kernel(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
+    uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
+  ao_rays_pass<false>(cap, W, y0, utab, vtab, geo, nrm, list, hdr, spp, s0, ns, user_seed, radius, rays, tmax);
+}
+// (camera frames: see rt_ao_prepare_camera_kernel)
+__global__ __launch_bounds__(256) void rt_ao_rays_camera_kernel(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ cam,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
+    uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
+  ao_rays_pass<true>(cap, W, y0, cam, cam + CAM_TAB, geo, nrm, list, hdr, spp, s0, ns, user_seed, radius, rays, tmax);
 }
 
 __global__ __launch_bounds__(256) void rt_ao_accumulate_kernel(uint64_t cap, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
@@ -2409,14 +2440,20 @@ static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, 
     return c->bin_order;
   };
   if (hipMemsetAsync(c->ao_hdr, 0, 8, s) != hipSuccess) return -1;
-  hipLaunchKernelGGL(rt_ao_prepare_kernel, dim3((uint32_t)((n + 256u * AO_PREP_CHUNKS - 1u) / (256u * AO_PREP_CHUNKS))), block, 0, s, sc, p, n, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
-                     c->ao_geo, c->ao_nrm, c->ao_col, c->ao_cnt, c->ao_list, c->ao_hdr, c->ctl, (float4*)nullptr);
+  const dim3 pgrid((uint32_t)((n + 256u * AO_PREP_CHUNKS - 1u) / (256u * AO_PREP_CHUNKS)));
+  // (a camera frame's utab is its camera block: the camera forms of the two passes that derive the primary ray again)
+  if (r.cams) hipLaunchKernelGGL(rt_ao_prepare_camera_kernel, pgrid, block, 0, s, sc, p, n, width, y0, utab, (const HitRec*)c->hitbuf,
+                                 c->ao_geo, c->ao_nrm, c->ao_col, c->ao_cnt, c->ao_list, c->ao_hdr, c->ctl);
+  else hipLaunchKernelGGL(rt_ao_prepare_kernel, pgrid, block, 0, s, sc, p, n, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
+                          c->ao_geo, c->ao_nrm, c->ao_col, c->ao_cnt, c->ao_list, c->ao_hdr, c->ctl, (float4*)nullptr);
   if (hipGetLastError() != hipSuccess) return -1;
   c->ctl_dirty = false;
   for (uint32_t s0 = 0; s0 < ao->spp; s0 += ns) {
     const uint32_t k = std::min(ns, ao->spp - s0);
-    hipLaunchKernelGGL(rt_ao_rays_kernel, rgrid, block, 0, s, ray_cap, width, y0, utab, vtab, (const float4*)c->ao_geo, (const float4*)c->ao_nrm,
-                       (const uint32_t*)c->ao_list, c->ao_hdr, ao->spp, s0, k, ao->seed, ao->radius, c->ao_rays, c->ao_tmax);
+    if (r.cams) hipLaunchKernelGGL(rt_ao_rays_camera_kernel, rgrid, block, 0, s, ray_cap, width, y0, utab, (const float4*)c->ao_geo, (const float4*)c->ao_nrm,
+                                   (const uint32_t*)c->ao_list, c->ao_hdr, ao->spp, s0, k, ao->seed, ao->radius, c->ao_rays, c->ao_tmax);
+    else hipLaunchKernelGGL(rt_ao_rays_kernel, rgrid, block, 0, s, ray_cap, width, y0, utab, vtab, (const float4*)c->ao_geo, (const float4*)c->ao_nrm,
+                            (const uint32_t*)c->ao_list, c->ao_hdr, ao->spp, s0, k, ao->seed, ao->radius, c->ao_rays, c->ao_tmax);
     if (trace_on_ctx(a, c, c->ao_rays, n * k, c->ao_tmax, c->ao_hits, MODE_ANY_UNORDERED, s, c->ao_hdr + 1, nullptr, bin_rays(k)) != 0) return -1;
     hipLaunchKernelGGL(rt_ao_accumulate_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_list, (const uint32_t*)c->ao_hdr, k,
                        (const HitRec*)c->ao_hits, c->ao_cnt);
@@ -2455,8 +2492,9 @@ static bool gi_fused_frame(const RenderRequest& r) { return r.ao && r.ao->reserv
 static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   const bool stats = r.counting != Counting::TIMED;
   if (!a || a->stale || !r.params || !r.dst) return -1;
-  // camera frames (cams[f] per frame of the batch): plain and shadow frames, whole rows, the timed build only
-  if (r.cams && (r.stride != 1 || r.ao || stats || r.wave_log || r.unoccluded)) return -1;
+  // camera frames (cams[f] per frame of the batch): whole rows, the timed build only; plain and shadow frames, and single
+  // ambient-occlusion / diffuse-bounce frames (`unoccluded` is an output of the ambient-occlusion frame alone)
+  if (r.cams && (r.stride != 1 || stats || r.wave_log || (r.unoccluded && !r.ao))) return -1;
   // batch > 1: `params` is an array of `batch` entries, frame f goes to dst + f * dst_frame_stride; plain frames without optional outputs
   // (a batch with the wave log: diagnostic, traversal only -- its shading launch is the single-frame one)
   if (r.batch == 0 || r.batch > VXRT_MAX_BATCH) return -1;
@@ -2690,7 +2728,7 @@ struct FrameLaunch {
 // launch over whatever the main one deferred.  (The EXACT form knows neither PACKED nor SHALLOW.)
 template <int JOB, int STATS, bool PACKED>
 static void launch_traversal(const FrameLaunch& l) {
-  static_assert(!(PACKED && (JOB == JOB_RENDER_GI || STATS != 0)), "only the timed render jobs have a packed form");
+  static_assert(!(PACKED && (job_base(JOB) == JOB_RENDER_GI || STATS != 0)), "only the timed render jobs have a packed form");
   with_decode_and_depth<STATS == 0>(l.a, [&](auto ld, auto sh) {
     const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, PACKED, decltype(sh)::value>;
     const auto k_exact = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, true>;
@@ -2723,7 +2761,8 @@ static bool traverse_frame(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, c
     // one diffuse bounce: the whole frame in the persistent launches (JOB_RENDER_GI).  (The multi-pass form it replaced -- list the hit
     // pixels, generate the rays, a 2 M-ray trace launch, accumulate, final -- took the same 1.18 ms: profiles/r03_f_gi_fused_ab.txt)
     for (PersistArgs* g : {&l.A, &l.X, &l.X0}) { g->dst = r.dst; g->colors = r.colors; g->gi_seed = r.ao->seed; }
-    launch_traversal<JOB_RENDER_GI, 0, false>(l);
+    // (a camera frame has no a-priori list -- plan.side_launch is false: its primary rays outside the fast domain are deferred)
+    if (r.cams) launch_traversal<JOB_RENDER_GI | JOB_CAM, 0, false>(l); else launch_traversal<JOB_RENDER_GI, 0, false>(l);
   }
   else if (r.counting == Counting::TIMED_TRAVERSAL) launch_render<2, false>(r.shadow != 0, l);
   else if (r.counting == Counting::REFERENCE_ORDER) launch_render<1, false>(r.shadow != 0, l);
@@ -2956,6 +2995,30 @@ int vxrt_render_ao(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_
   if (!ao || ao->spp == 0 || ao->spp > 4096 || !(ao->radius > 0.0f) || ao->reserved != 0) return -1;
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = ao;
+  r.dst = dst; r.colors = colors; r.unoccluded = unoccluded; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+// vxrt_render_diffuse_bounce / vxrt_render_ao from a caller-supplied pinhole camera (see the header)
+int vxrt_render_diffuse_bounce_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                      const vxrt_shade_params_t* params, uint32_t seed, uint32_t* dst, float* colors,
+                                      unsigned long long* rays_traced, void* stream) {
+  if (!camera_ok(cam)) return -1;
+  vxrt_ao_params_t gi{};
+  gi.spp = 1; gi.radius = RT_LARGE_FLOAT; gi.seed = seed; gi.reserved = VXRT_AO_MODE_DIFFUSE_BOUNCE;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = &gi; r.cams = cam;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+int vxrt_render_ao_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                          const vxrt_shade_params_t* params, const vxrt_ao_params_t* ao, uint32_t* dst, float* colors,
+                          uint32_t* unoccluded, unsigned long long* rays_traced, void* stream) {
+  if (!camera_ok(cam)) return -1;
+  if (!ao || ao->spp == 0 || ao->spp > 4096 || !(ao->radius > 0.0f) || ao->reserved != 0) return -1;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = ao; r.cams = cam;
   r.dst = dst; r.colors = colors; r.unoccluded = unoccluded; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }

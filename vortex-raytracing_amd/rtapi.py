@@ -471,3 +471,25 @@ def pinhole_rays(cam, width, height, y0, y1, rays_ptr, stream=None):
     L.vxrt_pinhole_rays.restype = C.c_int
     L.vxrt_pinhole_rays.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     check(L.vxrt_pinhole_rays(C.byref(_camera(cam)), width, height, y0, y1, rays_ptr, stream), "vxrt_pinhole_rays")
+
+
+def render_ao_camera(accel, cam, width, height, y0, y1, params, spp, radius, dst_ptr, seed=0, colors_ptr=None, unoccluded_ptr=None,
+                     rays_ptr=None, stream=None):
+    """vxrt_render_ao_camera: vxrt_render_ao seen from pinhole camera `cam` (a Camera or 14 floats)."""
+    L = _lib()
+    L.vxrt_render_ao_camera.restype = C.c_int
+    L.vxrt_render_ao_camera.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
+                                        C.POINTER(AoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    ao = AoParams(int(spp), float(radius), int(seed), 0)
+    check(L.vxrt_render_ao_camera(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(ao), dst_ptr, colors_ptr,
+                                  unoccluded_ptr, rays_ptr, stream), "vxrt_render_ao_camera")
+
+
+def render_diffuse_bounce_camera(accel, cam, width, height, y0, y1, params, dst_ptr, seed=0, colors_ptr=None, rays_ptr=None, stream=None):
+    """vxrt_render_diffuse_bounce_camera: vxrt_render_diffuse_bounce seen from pinhole camera `cam` (a Camera or 14 floats)."""
+    L = _lib()
+    L.vxrt_render_diffuse_bounce_camera.restype = C.c_int
+    L.vxrt_render_diffuse_bounce_camera.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(ShadeParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.vxrt_render_diffuse_bounce_camera(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), int(seed), dst_ptr,
+                                              colors_ptr, rays_ptr, stream), "vxrt_render_diffuse_bounce_camera")
