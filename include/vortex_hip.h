@@ -209,7 +209,7 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* accel);
 /* What the build found (diagnostic): which = 0 -> internal levels on the longest root-to-leaf path, TLAS and BLAS together, counted up
  * to 17; 1 -> 1 if the scene is at most 16 levels deep and its timed launches keep 48-entry traversal stacks (deeper scenes: the
  * reference's 32 levels, 96 entries + the LDS part); 2 -> 1 if the TLAS root is a single identity instance; 3 -> 1 if the scene
- * takes the ldexp decode / generic slab form. */
+ * takes the ldexp decode / generic slab form; 4 -> 1 while a non-zero alpha table is set (vxrt_accel_set_alpha_test). */
 int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
 
 /* Refit: new boxes for a scene whose instances or vertices moved, in place, without a rebuild (extension; the reference has no refit,
@@ -241,6 +241,32 @@ int vxrt_accel_refit(vxrt_accel_t* accel, uint32_t what, void* stream);
  * non-finite matrix or a singular one (det == 0, for which the reference would silently keep the identity); the matrices are
  * checked before any record is written, so then every record is left as it was. */
 int vxrt_accel_set_transforms(vxrt_accel_t* accel, uint32_t first, uint32_t count, const float* transforms, void* stream);
+
+/* Alpha test: cutout textures reject candidates inside the traversal (extension; the reference's any-hit shader holds the test,
+ * anyhit.cpp:24-35, with alpha hard-wired to 1, and its COMMIT_CONT path cannot serve as the definition: DESIGN.md s2, "Alpha test").
+ * thresholds: HOST, n_mats bytes, one per material.  0 = the material is opaque (no test, no fetch); T in 1..255 = a candidate -- a
+ * triangle test that returns d < hit.dist -- on a triangle of that material is REJECTED when the texel the closest-hit shader would
+ * sample for it has a top byte below T: texels are 0xAARRGGBB, AA is read by this test alone (shading keeps masking it off), the texel
+ * index is computed exactly as vxrt_shade_rays computes it (u, v from uv0..2 and the candidate's barycentrics without contraction,
+ * uint32_t(u * (float)tex_width) % tex_width by the conversion rule written there: negative uv wraps, NaN gives 0).  T = 128 is the
+ * reference's `alpha < 0.5f` for an 8-bit alpha.  A rejected candidate is treated in every respect as if the triangle test had
+ * missed: hit.dist and the record stay, no abandon test, an any-hit ray does not stop, the leaf's next triangle follows.
+ * NULL (n_mats is then ignored) or all zeros switches the test off: the accel launches exactly the kernels it launches without it.
+ * The thresholds are copied to storage the accel owns, together with each triangle's texId as the scene holds it at this call.  Ordered
+ * after every call already issued on this accel, on any stream; synchronous with respect to `stream`, like vxrt_accel_refit.  The table
+ * survives vxrt_accel_refit and vxrt_accel_set_transforms.  vxrt_accel_info(accel, 4) is 1 while a non-zero table is set.
+ * Returns -1, with nothing changed, for a null or stale accel, n_mats different from the scene's, or a non-zero threshold for a
+ * material without a texture (diffuse_tex_id < 0).  vxrt_accel_build has validated every textured material's texel range.
+ * While a non-zero table is set:
+ *   vxrt_trace (both modes, the rays traced by its EXACT launch included), vxrt_render and vxrt_render_camera (primary rays, the
+ *   occlusion rays of shadow != 0 -- light passes through holes -- and the mirror-bounce rays up to max_depth) honour it for every
+ *   ray they trace; their optional outputs are as without it;
+ *   EVERY OTHER entry point that traces rays returns -1 before it launches anything -- vxrt_render_interleaved, the *_batch and
+ *   rows forms, vxrt_render_stats / _stats_timed / _wave_log, vxrt_trace_stats, vxrt_render_ao / _diffuse_bounce and their camera
+ *   forms: none of them silently ignores the table;
+ *   vxrt_shade_rays and the ray generators trace nothing and are unaffected.  The vx_* boundary has no access to the table. */
+int vxrt_accel_set_alpha_test(vxrt_accel_t* accel, const uint8_t* thresholds /* HOST, n_mats entries, or NULL */, uint32_t n_mats,
+                              void* stream);
 
 /* Number of frames (vxrt_render / vxrt_trace calls) this accel keeps in flight, 1..8, default 1.
  * Each in-flight frame has its own hit-record buffer, deferred-ray list and side stream; calls take

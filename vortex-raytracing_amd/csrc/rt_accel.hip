@@ -458,6 +458,7 @@ static void accel_free(vxrt_accel* a) {
   (void)hipFree(a->top_img); (void)hipFree(a->top_roots);
   refit_plan_free(a->refit);
   (void)hipFree(a->uvtab); (void)hipFree(a->apriori);
+  (void)hipFree(a->alpha_mat); (void)hipFree(a->alpha_tri);
   for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) (void)hipFree(a->batch_order[k]);
   for (FrameCtx& c : a->ctx) {
     (void)hipFree(c.hitbuf); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
@@ -620,8 +621,56 @@ int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
   case 1: *value = a->shallow ? 1u : 0u; return 0; // the timed launches take the SHALLOW instantiations (48-entry stacks)
   case 2: *value = a->dev.ident_root; return 0;    // the TLAS root is one identity instance (rays keep their world coordinates)
   case 3: *value = a->dev.exact_decode; return 0;  // the scene takes the ldexp decode / generic slab form
+  case 4: *value = a->alpha_on ? 1u : 0u; return 0; // a non-zero alpha table is set (vxrt_accel_set_alpha_test)
   }
   return -1;
+}
+
+// alpha_tri[t] = threshold of triangle t's material (texId < n_mats: checked by the build)
+__global__ __launch_bounds__(256) void accel_alpha_tri_kernel(const rt_triex_t* __restrict__ triEx, uint32_t n_tris, const uint8_t* __restrict__ thr, uint32_t n_mats,
+                                                             uint8_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_tris) return;
+  const uint32_t m = triEx[t].texId;
+  out[t] = m < n_mats ? thr[m] : (uint8_t)0;
+}
+
+// The alpha table (see the header).  Every refusal comes before anything is written; then, behind everything already issued on the accel,
+// the thresholds go to the accel's own storage and the per-triangle table the traversal reads is derived from them.
+int vxrt_accel_set_alpha_test(vxrt_accel_t* a, const uint8_t* thresholds, uint32_t n_mats, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!a || a->stale) return -1;
+  const vxrt_scene_t& s = a->ref;
+  bool any = false;
+  if (thresholds) {
+    if (n_mats != s.n_mats) return -1;
+    for (uint32_t m = 0; m < n_mats; ++m) any = any || thresholds[m] != 0;
+  }
+  if (any) {
+    if (!s.triEx || !s.mat || !s.tex) return -1;
+    std::vector<rt_material_t> mats(n_mats);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(mats.data(), s.mat, (size_t)n_mats * sizeof(rt_material_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (uint32_t m = 0; m < n_mats; ++m)
+      if (thresholds[m] != 0 && mats[m].diffuse_tex_id < 0) return -1;   // a cutout needs a texture (whose texel range the build has checked)
+    if (!a->alpha_mat && hipMalloc((void**)&a->alpha_mat, std::max<size_t>(s.n_mats, 16)) != hipSuccess) return -1;
+    if (!a->alpha_tri && hipMalloc((void**)&a->alpha_tri, std::max<size_t>(s.n_tris, 16)) != hipSuccess) return -1;
+  }
+  // ordered after every call already issued on this accel, on any stream (frames in flight read the table this call rewrites)
+  for (uint32_t k = 0; k < MAX_FRAMES_IN_FLIGHT; ++k) {
+    FrameCtx& c = a->ctx[k];
+    if (!c.busy || c.last_stream == st) continue;
+    if (c.done_recorded) { if (hipStreamWaitEvent(st, c.ev_done, 0) != hipSuccess) return -1; }
+    else if (hipDeviceSynchronize() != hipSuccess) return -1;
+  }
+  if (any) {
+    if (hipMemcpyAsync(a->alpha_mat, thresholds, n_mats, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    hipLaunchKernelGGL(accel_alpha_tri_kernel, dim3((s.n_tris + 255) / 256), dim3(256), 0, st, (const rt_triex_t*)s.triEx, s.n_tris,
+                       (const uint8_t*)a->alpha_mat, n_mats, a->alpha_tri);
+    if (hipGetLastError() != hipSuccess) { a->alpha_on = false; (void)hipStreamSynchronize(st); return -1; }
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) { a->alpha_on = false; return -1; }
+  a->alpha_on = any;
+  return 0;
 }
 
 int vxrt_accel_frames_in_flight(vxrt_accel_t* a, uint32_t n) {

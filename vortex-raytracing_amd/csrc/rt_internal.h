@@ -126,4 +126,8 @@ struct vxrt_accel {
   struct RefitPlan* refit = nullptr;   // vxrt_accel_refit: built at the first refit
   uint32_t blas_status = 0;        // STATUS_FMA_DECODE_DIFFERS of the BLAS region as its last re-layout found it (build or GEOMETRY refit)
   bool stale = false;              // a refit failed after it had started writing: every render / trace refuses until a refit succeeds
+  // alpha test (vxrt_accel_set_alpha_test): the caller's per-material thresholds and, derived from them, one byte per triangle
+  // (alpha_tri[t] = alpha_mat[triEx[t].texId]: what the traversal reads).  alpha_on: some threshold is non-zero.
+  uint8_t* alpha_mat = nullptr; uint8_t* alpha_tri = nullptr;
+  bool alpha_on = false;
 };

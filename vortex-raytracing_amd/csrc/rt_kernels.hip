@@ -387,6 +387,27 @@ __device__ __forceinline__ void ao_sample_ray(uint32_t x, uint32_t y, uint32_t W
   o6[5] = tz * u + bz * v + nz * z;
 }
 
+// Alpha test of a candidate (ALPHA instantiations; the rule is in DESIGN.md s2, "Alpha test"): true = the candidate on triangle triIdx with
+// barycentrics (bx, by, bz) is rejected -- its material has a threshold T > 0 and the texel shade_terms would sample there has a top byte
+// below T.  u, v, the conversions and the texel address are shade_terms', operation for operation.
+// What it loads, in this order: one byte of the per-triangle threshold table (an opaque triangle ends here); then the seven words uv0 .. texId
+// of the triangle's tri_ex_t (not its normals), the material's four texture fields (not its colours) and the texel.
+__device__ __forceinline__ bool alpha_rejects(const SceneDev& sc, const uint8_t* __restrict__ alpha_tri, uint32_t triIdx, float bx, float by, float bz) {
+  const uint32_t T = alpha_tri[triIdx];
+  if (T == 0u) return false;
+  const rt_triex_t* te = sc.triEx + triIdx;
+  const float u0 = te->uv0[0], v0 = te->uv0[1], u1 = te->uv1[0], v1 = te->uv1[1], u2 = te->uv2[0], v2 = te->uv2[1];
+  const rt_material_t* mat = sc.mat + te->texId;
+  const uint32_t tw = mat->tex_width, th = mat->tex_height;
+  const uint64_t off = mat->tex_offset;
+  const float u = u1 * bx + u2 * by + u0 * bz;
+  const float v = v1 * bx + v2 * by + v0 * bz;
+  uint32_t iu = f2u_x86(u * (float)tw), iv = f2u_x86(v * (float)th);
+  iu %= tw; iv %= th;
+  const uint32_t texel = ((const uint32_t*)(sc.tex + off))[iu + iv * tw];
+  return (texel >> 24) < T;
+}
+
 #ifndef RT_TRI_PREFETCH
 #define RT_TRI_PREFETCH 1
 #endif
@@ -584,6 +605,8 @@ struct PersistArgs {
   const ShadeParams* pbatch; uint32_t frame_tiles;
   // JOB_RENDER_GI: the frame itself (pixel (x, y) at dst[x + y * W]), optional f32 colours, seed of the bounce rays
   uint32_t* dst; float* colors; uint32_t gi_seed;
+  // ALPHA instantiations only (vxrt_accel_set_alpha_test): per triangle, the threshold of its material (0 = opaque)
+  const uint8_t* alpha_tri;
 };
 
 // Domain of the fast (non-EXACT) traversal: every component of 1/d finite, non-zero and at most 2^64 in magnitude, every origin
@@ -624,8 +647,11 @@ __device__ __forceinline__ float vmax_nonan(float a, float b) { float r; asm("v_
 // accel build, accel_depth_kernel), so a lane's stack never holds more than 3 x RT_SHALLOW_LEVELS entries and the part of it that lives in
 // scratch is sized for that instead of for the reference's 32 levels: 344 instead of 768 bytes per lane for the 8-wavefront instantiation.
 // (The 1,048,576-triangle atrium is 13 levels deep, the 10 M-triangle hairball 15.)  Timed builds only; deeper scenes take the full-size form.
-template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false>
+// ALPHA: candidates pass the alpha test before they are accepted (vxrt_accel_set_alpha_test; A.alpha_tri).  Timed builds of the ray-buffer
+// and plain / shadow frame jobs only, one value of the speed-only axes (PACKED and SHALLOW false).  With ALPHA false nothing of it is compiled.
+template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false, bool ALPHA = false>
 __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
+  static_assert(!ALPHA || (STATS == 0 && !PACKED && !SHALLOW && job_base(JOB) != JOB_RENDER_GI), "alpha instantiations: see ALPHA above");
   // stack levels in LDS: what the instantiation's occupancy leaves room for (160 KB per CU)
   constexpr int LSTK = EXACT ? LDS_STACK : (is_trace_job(JOB) ? RT_LDS_STACK_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_LDS_STACK_GI : (PACKED ? RT_LDS_STACK_RENDER_PACKED : RT_LDS_STACK_RENDER)));
   constexpr int WG_WAVES = EXACT ? 4 : RT_WG_WAVES;
@@ -1138,6 +1164,8 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
               float bx, by, bz;
               const float d = ray_tri(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz);
               if (d < hitd) {
+                // a rejected candidate is a triangle the ray missed: no record, no abandon test, no stop, on to the leaf's next triangle
+                if constexpr (ALPHA) { if (alpha_rejects(sc, A.alpha_tri, triIdx, bx, by, bz)) continue; }
                 hitd = d;
                 flags |= F_FOUND;
                 // (a frame's occlusion ray only feeds a boolean; slots 3-7 keep the pixel's primary hit meanwhile)
@@ -2230,11 +2258,12 @@ static void with_decode_and_depth(const vxrt_accel* a, F&& f) {
 // (the EXACT launch's grid grows with the ray buffer -- a workgroup per 2,048 rays, up to the machine: how many rays were deferred
 // is known on the device only, and a buffer of axis-parallel rays defers all of them; with nothing deferred its wavefronts find
 // every shard empty without an atomic and exit)
-template <int JOB, int STATS>
+// (ALPHA: the alpha-tested forms, which have no SHALLOW instantiation)
+template <int JOB, int STATS, bool ALPHA = false>
 static void launch_trace(const vxrt_accel* a, const ShadeParams& p, const PersistArgs& A, const PersistArgs& X, uint64_t n, hipStream_t s) {
-  with_decode_and_depth<STATS == 0>(a, [&](auto ld, auto sh) {
-    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, false, decltype(sh)::value>;
-    const auto k_exact = rt_persistent_kernel<JOB_TRACE, STATS, decltype(ld)::value, true>;
+  with_decode_and_depth<STATS == 0 && !ALPHA>(a, [&](auto ld, auto sh) {
+    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, false, decltype(sh)::value, ALPHA>;
+    const auto k_exact = rt_persistent_kernel<JOB_TRACE, STATS, decltype(ld)::value, true, false, false, ALPHA>;
     hipLaunchKernelGGL(k_main, dim3(persistent_grid(k_main, n)), dim3(RT_WG_THREADS), 0, s, a->dev, p, A);
     hipLaunchKernelGGL(k_exact, dim3(std::max<uint32_t>(EXACT_GRID, persistent_grid(k_exact, n / 8, 256))), dim3(256), 0, s, a->dev, p, X);
   });
@@ -2248,7 +2277,11 @@ static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_
                         unsigned long long* stats_counters = nullptr, const uint32_t* order = nullptr) {
   uint32_t* st = status_word();
   if (!st) return -1;
+  // a non-zero alpha table: the alpha-tested launches, timed build only (callers that cannot honour the table have refused already)
+  const bool alpha = a->alpha_on;
+  if (alpha && stats_counters) return -1;
   PersistArgs A{};
+  A.alpha_tri = alpha ? a->alpha_tri : nullptr;
   const bool unordered = mode == MODE_ANY_UNORDERED;
   A.total = (uint32_t)n; A.hits = hits; A.rays = rays; A.tmax = tmax; A.any_hit = mode == VXRT_MODE_ANY || unordered;
   A.total_dev = n_dev;
@@ -2274,9 +2307,11 @@ static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_
   ShadeParams p{};
   // incoherent rays: the ray-pool kernel (1) or two rays per lane (2) instead of the persistent kernel, timed builds only
   const int pool = host_knobs().pool;
-  if ((pool == 1 || pool == 2) && !stats_counters) return trace_experiment(pool, a, c, n, s, p, A, X);
+  if ((pool == 1 || pool == 2) && !stats_counters && !alpha) return trace_experiment(pool, a, c, n, s, p, A, X);
   // any-hit rays whose caller only wants "blocked or not": children in slot order
-  if (stats_counters) launch_trace<JOB_TRACE, 1>(a, p, A, X, n, s);
+  // (alpha-tested: one form for both -- the ordered one, whose answer to "blocked or not" is the same)
+  if (alpha) launch_trace<JOB_TRACE, 0, true>(a, p, A, X, n, s);
+  else if (stats_counters) launch_trace<JOB_TRACE, 1>(a, p, A, X, n, s);
   else if (unordered && !host_knobs().unordered_any_off) launch_trace<JOB_TRACE_UNORDERED, 0>(a, p, A, X, n, s);
   else launch_trace<JOB_TRACE, 0>(a, p, A, X, n, s);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -2322,6 +2357,7 @@ struct RenderRequest {
   const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
   void* stream = nullptr;
   Counting counting = Counting::TIMED;
+  bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set
 };
 
 // Tail of a frame with reflective instances (replaces the plain shading pass): shade level 0, then per
@@ -2492,6 +2528,8 @@ static bool gi_fused_frame(const RenderRequest& r) { return r.ao && r.ao->reserv
 static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   const bool stats = r.counting != Counting::TIMED;
   if (!a || a->stale || !r.params || !r.dst) return -1;
+  // a non-zero alpha table (vxrt_accel_set_alpha_test): only the entry points that honour it render -- plain single frames, timed build
+  if (a->alpha_on && (!r.honours_alpha || stats || r.wave_log || r.ao || r.batch != 1 || r.stride != 1)) return -1;
   // camera frames (cams[f] per frame of the batch): whole rows, the timed build only; plain and shadow frames, and single
   // ambient-occlusion / diffuse-bounce frames (`unoccluded` is an output of the ambient-occlusion frame alone)
   if (r.cams && (r.stride != 1 || stats || r.wave_log || (r.unoccluded && !r.ao))) return -1;
@@ -2664,6 +2702,7 @@ static bool frame_resources(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, 
   A.queue = c->ctl + 32;
   A.per_shard = ((A.total + QUEUE_SHARDS - 1) / QUEUE_SHARDS + 63u) & ~63u;
   A.shard_rot = host_knobs().shard_rot;
+  A.alpha_tri = a->alpha_on ? a->alpha_tri : nullptr;   // (check_request has refused every request that cannot honour it)
   if (lpt && !ensure_lpt_tables(c, r, n_tiles, A, s)) return false;
   // (camera frames have no a-priori list: their primary rays outside the fast domain are deferred to the EXACT launch behind the main one)
   return r.cams || ensure_apriori(a, r, t, s);
@@ -2726,20 +2765,21 @@ struct FrameLaunch {
 
 // EXACT launch over the a-priori list on the side stream, concurrent with the main launch; then the main launch and the EXACT
 // launch over whatever the main one deferred.  (The EXACT form knows neither PACKED nor SHALLOW.)
-template <int JOB, int STATS, bool PACKED>
+// (ALPHA: the alpha-tested forms -- timed, neither PACKED nor SHALLOW)
+template <int JOB, int STATS, bool PACKED, bool ALPHA = false>
 static void launch_traversal(const FrameLaunch& l) {
   static_assert(!(PACKED && (job_base(JOB) == JOB_RENDER_GI || STATS != 0)), "only the timed render jobs have a packed form");
-  with_decode_and_depth<STATS == 0>(l.a, [&](auto ld, auto sh) {
-    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, PACKED, decltype(sh)::value>;
-    const auto k_exact = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, true>;
+  with_decode_and_depth<STATS == 0 && !ALPHA>(l.a, [&](auto ld, auto sh) {
+    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, PACKED, decltype(sh)::value, ALPHA>;
+    const auto k_exact = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, true, false, false, ALPHA>;
     if (l.plan.side_launch) hipLaunchKernelGGL(k_exact, dim3(l.plan.side_wgs), dim3(256), 0, l.c->side, l.a->dev, l.p, l.X0);
     hipLaunchKernelGGL(k_main, dim3(main_grid(k_main, l.plan, l.A.total)), dim3(RT_WG_THREADS), 0, l.s, l.a->dev, l.p, l.A);
     hipLaunchKernelGGL(k_exact, dim3(EXACT_GRID), dim3(256), 0, l.s, l.a->dev, l.p, l.X);
   });
 }
-template <int STATS, bool PACKED, int CAM = 0>
+template <int STATS, bool PACKED, int CAM = 0, bool ALPHA = false>
 static void launch_render(bool shadow, const FrameLaunch& l) {
-  if (shadow) launch_traversal<JOB_RENDER_SHADOW | CAM, STATS, PACKED>(l); else launch_traversal<JOB_RENDER | CAM, STATS, PACKED>(l);
+  if (shadow) launch_traversal<JOB_RENDER_SHADOW | CAM, STATS, PACKED, ALPHA>(l); else launch_traversal<JOB_RENDER | CAM, STATS, PACKED, ALPHA>(l);
 }
 
 // The traversal of the frame: fork the side stream, the three launches, join.  false: a HIP call failed.
@@ -2764,6 +2804,7 @@ static bool traverse_frame(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, c
     // (a camera frame has no a-priori list -- plan.side_launch is false: its primary rays outside the fast domain are deferred)
     if (r.cams) launch_traversal<JOB_RENDER_GI | JOB_CAM, 0, false>(l); else launch_traversal<JOB_RENDER_GI, 0, false>(l);
   }
+  else if (l.A.alpha_tri) { if (r.cams) launch_render<0, false, JOB_CAM, true>(r.shadow != 0, l); else launch_render<0, false, 0, true>(r.shadow != 0, l); }
   else if (r.counting == Counting::TIMED_TRAVERSAL) launch_render<2, false>(r.shadow != 0, l);
   else if (r.counting == Counting::REFERENCE_ORDER) launch_render<1, false>(r.shadow != 0, l);
   else if (r.cams)      launch_render<0, false, JOB_CAM>(r.shadow != 0, l);
@@ -2845,6 +2886,7 @@ int vxrt_render(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t y
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow;
   r.dst = dst; r.hits = hits; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  r.honours_alpha = true;
   return render_common(accel, r);
 }
 
@@ -2855,6 +2897,7 @@ int vxrt_render_interleaved(vxrt_accel_t* accel, uint32_t width, uint32_t height
                             const vxrt_shade_params_t* params, int shadow, uint32_t* dst, vxrt_hit_t* hits,
                             float* colors, unsigned long long* rays_traced, void* stream) {
   if (stride == 0 || phase >= stride) return -1;
+  if (accel && accel->alpha_on) return -1;        // (this form does not honour an alpha table: see check_request)
   if ((uint64_t)phase * 8u >= height) return 0;   // more ranks than tile rows: nothing for this one
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = phase * 8u; r.y1 = height; r.stride = stride; r.params = params; r.shadow = shadow;
@@ -2869,6 +2912,7 @@ int vxrt_render_interleaved_batch(vxrt_accel_t* accel, uint32_t width, uint32_t 
                                   const vxrt_shade_params_t* params, int shadow, uint32_t* dst, uint64_t dst_frame_stride,
                                   unsigned long long* rays_traced, void* stream) {
   if (stride == 0 || phase >= stride || n_frames == 0) return -1;
+  if (accel && accel->alpha_on) return -1;
   if ((uint64_t)phase * 8u >= height) return 0;
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = phase * 8u; r.y1 = height; r.stride = stride; r.params = params; r.batch = n_frames; r.shadow = shadow;
@@ -2925,6 +2969,7 @@ int vxrt_render_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t w
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = shadow; r.cams = cam;
   r.dst = dst; r.hits = hits; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  r.honours_alpha = true;
   return render_common(accel, r);
 }
 
@@ -2934,7 +2979,7 @@ int vxrt_render_batch_camera(vxrt_accel_t* accel, uint32_t width, uint32_t heigh
                              unsigned long long* rays_traced, void* stream) {
   if (!cams || n_frames == 0 || n_frames > VXRT_MAX_BATCH) return -1;
   for (uint32_t f = 0; f < n_frames; ++f) if (!camera_ok(cams + f)) return -1;
-  if (!accel || accel->stale || !params || !dst) return -1;
+  if (!accel || accel->stale || accel->alpha_on || !params || !dst) return -1;
   if (height == 0) return 0;   // (as vxrt_render_batch: no tile row to render)
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = 0; r.y1 = height; r.params = params; r.batch = n_frames; r.shadow = shadow; r.cams = cams;
@@ -3028,6 +3073,7 @@ int vxrt_render_ao_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_
 int vxrt_trace_stats(vxrt_accel_t* a, const float* rays, uint64_t n, const float* tmax,
                      vxrt_hit_t* hits, int mode, unsigned long long* counters, void* stream) {
   if (!a || a->stale || !counters || (n && (!rays || !hits))) return -1;
+  if (a->alpha_on) return -1;   // (the counting build has no alpha-tested form)
   if (mode != VXRT_MODE_CLOSEST && mode != VXRT_MODE_ANY) return -1;
   if (n == 0) return 0;
   if (n > 0x7fffffffull) return -1;

@@ -127,6 +127,22 @@ def accel_set_transforms(accel, first, count, ptr, stream=None):
     check(L.vxrt_accel_set_transforms(accel, int(first), int(count), ptr, stream), "vxrt_accel_set_transforms")
 
 
+def accel_set_alpha_test(accel, thresholds, stream=None):
+    """vxrt_accel_set_alpha_test: one threshold byte per material (0 = opaque; T in 1..255 rejects candidates whose texel's top byte is
+    below T); None switches the test off.  Raises on a refusal (nothing is changed then)."""
+    L = _lib()
+    L.vxrt_accel_set_alpha_test.restype = C.c_int
+    L.vxrt_accel_set_alpha_test.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    if thresholds is None:
+        check(L.vxrt_accel_set_alpha_test(accel, None, 0, stream), "vxrt_accel_set_alpha_test")
+        return
+    t = [int(v) for v in thresholds]
+    if any(v < 0 or v > 255 for v in t):
+        raise ValueError("alpha thresholds are bytes")
+    buf = (C.c_uint8 * max(len(t), 1))(*t)
+    check(L.vxrt_accel_set_alpha_test(accel, buf, len(t), stream), "vxrt_accel_set_alpha_test")
+
+
 def accel_destroy(accel):
     if accel:
         check(_lib().vxrt_accel_destroy(accel), "vxrt_accel_destroy")
@@ -255,7 +271,7 @@ def wire_unpack(wire_all_ptr, wire_stride_bytes, width, tile_rows_per_rank, worl
 
 def accel_info(accel, which):
     """vxrt_accel_info: 0 -> internal levels of the deepest path (counted up to 17), 1 -> 48-entry stacks (depth class <= 16),
-    2 -> single identity instance under the TLAS root, 3 -> ldexp decode."""
+    2 -> single identity instance under the TLAS root, 3 -> ldexp decode, 4 -> a non-zero alpha table is set."""
     L = _lib()
     L.vxrt_accel_info.restype = C.c_int
     L.vxrt_accel_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]

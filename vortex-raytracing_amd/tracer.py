@@ -212,6 +212,15 @@ class DeviceScene:
         with torch.cuda.device(dev):
             rtapi.accel_refit(self.accel, rtapi.REFIT_GEOMETRY if geometry else rtapi.REFIT_INSTANCES, torch.cuda.current_stream().cuda_stream)
 
+    def set_alpha_test(self, thresholds):
+        """Cutout textures: one threshold byte per material (0 = opaque); a candidate whose texel has a top byte below its material's
+        threshold is rejected inside the traversal (vxrt_accel_set_alpha_test).  None switches the test off.  Survives set_transforms
+        and refit; trace / render / render_camera honour it, every other tracing entry point refuses while it is set."""
+        import torch
+        dev = self.t["blas"].device
+        with torch.cuda.device(dev):
+            rtapi.accel_set_alpha_test(self.accel, thresholds, torch.cuda.current_stream().cuda_stream)
+
     def to_host(self):
         """The scene buffers as a scene.Scene (numpy), e.g. to hand a GPU-built tree to the oracle."""
         from .scene import Scene
