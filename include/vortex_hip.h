@@ -209,7 +209,8 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* accel);
 /* What the build found (diagnostic): which = 0 -> internal levels on the longest root-to-leaf path, TLAS and BLAS together, counted up
  * to 17; 1 -> 1 if the scene is at most 16 levels deep and its timed launches keep 48-entry traversal stacks (deeper scenes: the
  * reference's 32 levels, 96 entries + the LDS part); 2 -> 1 if the TLAS root is a single identity instance; 3 -> 1 if the scene
- * takes the ldexp decode / generic slab form; 4 -> 1 while a non-zero alpha table is set (vxrt_accel_set_alpha_test). */
+ * takes the ldexp decode / generic slab form; 4 -> 1 while a non-zero alpha table is set (vxrt_accel_set_alpha_test); 5 -> 1 if the
+ * timed plain / shadow frames take the identity-root kernels (2 holds, 1 holds, 3 and 4 do not). */
 int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
 
 /* Refit: new boxes for a scene whose instances or vertices moved, in place, without a rebuild (extension; the reference has no refit,

@@ -622,6 +622,7 @@ int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
   case 2: *value = a->dev.ident_root; return 0;    // the TLAS root is one identity instance (rays keep their world coordinates)
   case 3: *value = a->dev.exact_decode; return 0;  // the scene takes the ldexp decode / generic slab form
   case 4: *value = a->alpha_on ? 1u : 0u; return 0; // a non-zero alpha table is set (vxrt_accel_set_alpha_test)
+  case 5: *value = ident_root_form(a) ? 1u : 0u; return 0; // timed plain / shadow frames take the identity-root kernels (no TLAS level in the loop)
   }
   return -1;
 }

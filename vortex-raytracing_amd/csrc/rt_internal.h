@@ -131,3 +131,13 @@ struct vxrt_accel {
   uint8_t* alpha_mat = nullptr; uint8_t* alpha_tri = nullptr;
   bool alpha_on = false;
 };
+
+// RT_IDENT_ROOT_KERNEL: accels whose TLAS root is one identity instance take frame kernels that compile the TLAS level out of the
+// traversal loop (the IDENT template argument of rt_persistent_kernel).  0 = no such instantiations (the A/B: docs/KNOBS.md).
+#ifndef RT_IDENT_ROOT_KERNEL
+#define RT_IDENT_ROOT_KERNEL 1
+#endif
+// the accel's timed plain / shadow frames take the IDENT instantiations (as the accel is now: a refit may change ident_root and the decode)
+static inline bool ident_root_form(const vxrt_accel* a) {
+  return RT_IDENT_ROOT_KERNEL && a->dev.ident_root != 0u && a->shallow && !a->dev.exact_decode && !a->alpha_on;
+}

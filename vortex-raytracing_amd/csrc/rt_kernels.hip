@@ -538,8 +538,16 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #define RT_GI_DEAD_MAX 64    // (lanes refilled one by one: 16 -> 1.50 ms, 32 -> 1.45, 8 -> 1.72 against 1.18 with whole tiles: profiles/r03_f_gi_fused_ab.txt)
 #endif
 
+// RT_BATCH_PUSH: the children a node step leaves pending go onto the lane's stack in ONE operation (push_pending: one count, one
+// LDS-or-scratch decision, sp and the register top set once) instead of one push() per child; pop_next() refills the register top outside
+// its re-filter loop; the loop's exit test takes one ballot in the common case.  0 = the per-child form (the A/B: docs/KNOBS.md).
+#ifndef RT_BATCH_PUSH
+#define RT_BATCH_PUSH 1
+#endif
+// (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
+
 // -DRT_ISA_MARKS: comment-only markers in the listing (hipcc -S) that delimit the regions of the traversal loop for
-// tools/isa_regions.py; never set for a build that is run
+// tools/isa_regions.py and tools/isa_sections.py; never set for a build that is run
 #ifdef RT_ISA_MARKS
 #define RT_MARK(name) asm volatile("; RTMARK " name)
 #else
@@ -649,9 +657,15 @@ __device__ __forceinline__ float vmax_nonan(float a, float b) { float r; asm("v_
 // (The 1,048,576-triangle atrium is 13 levels deep, the 10 M-triangle hairball 15.)  Timed builds only; deeper scenes take the full-size form.
 // ALPHA: candidates pass the alpha test before they are accepted (vxrt_accel_set_alpha_test; A.alpha_tri).  Timed builds of the ray-buffer
 // and plain / shadow frame jobs only, one value of the speed-only axes (PACKED and SHALLOW false).  With ALPHA false nothing of it is compiled.
-template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false, bool ALPHA = false>
+// IDENT: the accel's TLAS root is one instance whose inverse transform is the identity (sc.ident_root, checked by the accel build and by every
+// refit).  start_ray then puts every ray at BLAS level -- at the BLAS root with its world coordinates, or, for an origin component that is -0,
+// through enter_instance -- and nothing ever brings a lane back: no lane holds a TLAS node or an instance descriptor inside the loop, whose
+// instance step, "back at TLAS level" test and the ballots that go with them are not compiled.  Timed plain / shadow frame jobs of shallow
+// scenes with the fma decode only (launch_traversal); every other scene keeps the general kernels.
+template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false, bool ALPHA = false, bool IDENT = false>
 __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
   static_assert(!ALPHA || (STATS == 0 && !PACKED && !SHALLOW && job_base(JOB) != JOB_RENDER_GI), "alpha instantiations: see ALPHA above");
+  static_assert(!IDENT || (STATS == 0 && !ALPHA && !EXACT && !LDEXP && SHALLOW && (job_base(JOB) == JOB_RENDER || job_base(JOB) == JOB_RENDER_SHADOW)), "identity-root instantiations: see IDENT above");
   // stack levels in LDS: what the instantiation's occupancy leaves room for (160 KB per CU)
   constexpr int LSTK = EXACT ? LDS_STACK : (is_trace_job(JOB) ? RT_LDS_STACK_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_LDS_STACK_GI : (PACKED ? RT_LDS_STACK_RENDER_PACKED : RT_LDS_STACK_RENDER)));
   constexpr int WG_WAVES = EXACT ? 4 : RT_WG_WAVES;
@@ -878,9 +892,70 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     }
     tos_d = d; tos_m = m;
   };
+  // The pending children of one node step, pushed at once: (d0, m0) if p0, then (d1, m1) if p1, then (d2, m2) if p2 -- the stack ends up
+  // exactly as after those push() calls.  What goes to memory is the old register top (if there is one) followed by the pushed entries
+  // but the last, at consecutive slots from sp on; the last one becomes the register top.  The slots are counted once, sp and the top are
+  // set once, and a lane decides once where its slots lie: all in LDS, all in scratch, or (the step that crosses the boundary) entry by
+  // entry as push() does.  The three arms are per-lane branches: the compiler keeps them apart in this listing (an arm no lane takes is
+  // jumped over with EXEC empty), but nothing in the source forces that -- tools/isa_sections.py shows what a compiler made of it.
+  auto push_pending = [&](bool p0, uint32_t d0, float m0, bool p1, uint32_t d1, float m1, bool p2, uint32_t d2, float m2) {
+    if (!RT_BATCH_PUSH) {
+      if (p0) push(d0, m0);
+      if (p1) push(d1, m1);
+      if (p2) push(d2, m2);
+      return;
+    }
+    if (!(p0 || p1 || p2)) return;
+    const bool w_top = tos_d != DESC_DONE;          // the old top goes to slot sp
+    const bool w0 = p0 && (p1 || p2), w1 = p1 && p2;   // (d2 is never stored: if it is pushed, it is the new top)
+    const int q0 = sp + (w_top ? 1 : 0), q1 = q0 + (w0 ? 1 : 0), end = q1 + (w1 ? 1 : 0);   // slots of d0, of d1; the new sp
+    if (end <= LSTK) {
+      if (w_top) lstk[sp * 64] = make_uint2(tos_d, __float_as_uint(tos_m));
+      if (w0) lstk[q0 * 64] = make_uint2(d0, __float_as_uint(m0));
+      if (w1) lstk[q1 * 64] = make_uint2(d1, __float_as_uint(m1));
+    } else if (sp >= LSTK) {
+      if (w_top) { ovf_d[sp - LSTK] = tos_d; ovf_m[sp - LSTK] = tos_m; }
+      if (w0) { ovf_d[q0 - LSTK] = d0; ovf_m[q0 - LSTK] = m0; }
+      if (w1) { ovf_d[q1 - LSTK] = d1; ovf_m[q1 - LSTK] = m1; }
+    } else {
+      auto put = [&](int q, uint32_t d, float m) {
+        if (q < LSTK) lstk[q * 64] = make_uint2(d, __float_as_uint(m));
+        else { ovf_d[q - LSTK] = d; ovf_m[q - LSTK] = m; }
+      };
+      if (w_top) put(sp, tos_d, tos_m);
+      if (w0) put(q0, d0, m0);
+      if (w1) put(q1, d1, m1);
+    }
+    sp = end;
+    tos_d = p2 ? d2 : (p1 ? d1 : d0);
+    tos_m = p2 ? m2 : (p1 ? m1 : m0);
+  };
+  // entry `i` of the stack's memory part (LDS, then scratch)
+  auto stack_load = [&](int i, uint32_t& d, float& m) {
+    // (LDS-typed pointer: through two plain pointers the compiler merges the arms into flat loads of a selected address)
+    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) const u32x2_t lds_u32x2_t;
+    if (i < LSTK) { const u32x2_t e = ((lds_u32x2_t*)lstk)[i * 64]; d = e.x; m = __uint_as_float(e.y); }
+    else { d = ovf_d[i - LSTK]; m = ovf_m[i - LSTK]; }
+  };
   // next pending work item of this lane (m < hit.dist: the reference's re-filtering),
   // or DESC_DONE when its stack is exhausted.  The refill of the register top from LDS is not waited for.
   auto pop_next = [&]() {
+    if (RT_BATCH_PUSH) {
+      // the candidates are the register top, then the memory part from sp - 1 down.  Entries that the shrunken hit distance filters (rare)
+      // are skipped first, reading memory directly; the register top is then refilled ONCE, behind the entry that was taken.
+      uint32_t d = tos_d; float m = tos_m;
+      while (d != DESC_DONE && !(m < hitd)) {
+        if (sp > 0) { --sp; stack_load(sp, d, m); } else d = DESC_DONE;
+      }
+      cur = d;
+      tos_d = DESC_DONE;
+      if (d != DESC_DONE) {
+        path_m = m;
+        if (sp > 0) { --sp; stack_load(sp, tos_d, tos_m); }
+      }
+      return;
+    }
     cur = DESC_DONE;
     while (tos_d != DESC_DONE) {
       const uint32_t d = tos_d;
@@ -1032,7 +1107,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       RT_MARK("node");
       if (is_node_desc(cur)) {
         // ---- internal node: 4 box tests, order, push the far ones, continue with the nearest ----
-        const bool top = (cur >> 30) == DK_TLAS;
+        const bool top = !IDENT && (cur >> 30) == DK_TLAS;   // (IDENT: no lane is at TLAS level inside the loop)
         if (top && !(flags & F_WORLD)) {   // back at TLAS level after an instance (multi-instance scenes only)
           float ox, oy, oz, dx, dy, dz, tm;
           world_ray(ox, oy, oz, dx, dy, dz, tm);
@@ -1060,6 +1135,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
         if (STATS) fx.node++;
         Cand c[4];
         eval_children<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
+        RT_MARK("stack");
         if (((job_base(JOB) == JOB_RENDER_SHADOW && RT_UNORDERED_OCCLUSION) || JOB == JOB_TRACE_UNORDERED) && STATS != 1 && __all((flags & F_ANYHIT) != 0u)) {   // STATS keeps the reference's order, hence its fetch counts
           // occlusion rays of a frame only feed a boolean (is anything hit before the light?): the set
           // of triangles an any-hit traversal can reach does not depend on the visiting order, so the
@@ -1070,11 +1146,8 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
             bool more = true;
             if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
             cur = v0 ? c[0].desc : (v1 ? c[1].desc : (v2 ? c[2].desc : c[3].desc));
-            if (more) {
-              if (v1 && v0) push(c[1].desc, c[1].d);
-              if (v2 && (v0 || v1)) push(c[2].desc, c[2].d);
-              if (v3 && (v0 || v1 || v2)) push(c[3].desc, c[3].d);
-            }
+            // (slot order: the first valid child is visited, the others are pushed as they come)
+            push_pending(more && v1 && v0, c[1].desc, c[1].d, more && v2 && (v0 || v1), c[2].desc, c[2].d, more && v3 && (v0 || v1 || v2), c[3].desc, c[3].d);
           } else {
             pop_next();
           }
@@ -1086,9 +1159,8 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
             bool more = true;
             if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
             // far first so that the nearest pending sibling is on top (:98-103)
-            if (more && c[3].d < __builtin_inff()) push(c[3].desc, vmax_nonan(path_m, c[3].d));
-            if (more && c[2].d < __builtin_inff()) push(c[2].desc, vmax_nonan(path_m, c[2].d));
-            if (more && c[1].d < __builtin_inff()) push(c[1].desc, vmax_nonan(path_m, c[1].d));
+            push_pending(more && c[3].d < __builtin_inff(), c[3].desc, vmax_nonan(path_m, c[3].d), more && c[2].d < __builtin_inff(), c[2].desc, vmax_nonan(path_m, c[2].d),
+                         more && c[1].d < __builtin_inff(), c[1].desc, vmax_nonan(path_m, c[1].d));
             cur = c[0].desc;
             path_m = vmax_nonan(path_m, c[0].d);
           } else {
@@ -1098,7 +1170,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       }
       if (STATS && A.wave_log) { const unsigned long long t1 = __builtin_readcyclecounter(); wl_tn += t1 - wl_t0; wl_t0 = t1; }
       RT_MARK("inst");
-      if (__any(is_inst_desc(cur))) {
+      if (!IDENT && __any(is_inst_desc(cur))) {
         if (is_inst_desc(cur)) {
           float ox, oy, oz, dx, dy, dz, tm;
           world_ray(ox, oy, oz, dx, dy, dz, tm);
@@ -1109,7 +1181,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       // body then runs for many lanes at once instead of once per iteration for a few
       RT_MARK("leaf");
       const unsigned long long leafm = __ballot(is_leaf_desc(cur));
-      if (leafm != 0ull && ((uint32_t)__popcll(leafm) >= (is_trace_job(JOB) ? RT_TRACE_LEAF_MIN : RT_LEAF_MIN) || __ballot(is_node_desc(cur) || is_inst_desc(cur)) == 0ull)) {
+      if (leafm != 0ull && ((uint32_t)__popcll(leafm) >= (is_trace_job(JOB) ? RT_TRACE_LEAF_MIN : RT_LEAF_MIN) || __ballot(is_node_desc(cur) || (!IDENT && is_inst_desc(cur))) == 0ull)) {
         // ---- BLAS leaf (:123-161): triangles in index order, strict '<' ----
         if (STATS && A.wave_log) { ++wl_leaf_x; wl_leaf_l += (unsigned)__popcll(leafm); }
         if (!is_trace_job(JOB) && !EXACT) lpt_work += 2u;   // (a leaf-body run costs about 2.5 node-body runs: tools/wave_balance.py)
@@ -1187,6 +1259,9 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       // revive them (finished rays to retire, or idle lanes while jobs remain)
       const unsigned long long work = __ballot(is_work_desc(cur));
       if (work == 0ull) break;
+      // (every lane that holds no work is finished or idle: while those are fewer than the smaller of the two bounds, neither test below
+      // can hold, and the one ballot above has decided)
+      if (RT_BATCH_PUSH && 64u - (uint32_t)__popcll(work) < (DEAD_MAX < FINISH_MIN ? DEAD_MAX : FINISH_MIN)) continue;
       const unsigned long long done = __ballot(cur == DESC_DONE);
       const uint32_t n_done = (uint32_t)__popcll(done);
       const uint32_t n_idle = queue_empty && loc_next == loc_end ? 0u : 64u - (uint32_t)__popcll(work | done);
@@ -2766,15 +2841,25 @@ struct FrameLaunch {
 // EXACT launch over the a-priori list on the side stream, concurrent with the main launch; then the main launch and the EXACT
 // launch over whatever the main one deferred.  (The EXACT form knows neither PACKED nor SHALLOW.)
 // (ALPHA: the alpha-tested forms -- timed, neither PACKED nor SHALLOW)
+// (IDENT: timed plain / shadow frames of an accel whose root is one identity instance -- ident_root_form, rt_internal.h -- take the
+// main kernel without the TLAS level; their EXACT launches are the general ones)
 template <int JOB, int STATS, bool PACKED, bool ALPHA = false>
 static void launch_traversal(const FrameLaunch& l) {
   static_assert(!(PACKED && (job_base(JOB) == JOB_RENDER_GI || STATS != 0)), "only the timed render jobs have a packed form");
-  with_decode_and_depth<STATS == 0 && !ALPHA>(l.a, [&](auto ld, auto sh) {
-    const auto k_main = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, PACKED, decltype(sh)::value, ALPHA>;
-    const auto k_exact = rt_persistent_kernel<JOB, STATS, decltype(ld)::value, true, false, false, ALPHA>;
+  const auto launch = [&](auto k_main, auto k_exact) {
     if (l.plan.side_launch) hipLaunchKernelGGL(k_exact, dim3(l.plan.side_wgs), dim3(256), 0, l.c->side, l.a->dev, l.p, l.X0);
     hipLaunchKernelGGL(k_main, dim3(main_grid(k_main, l.plan, l.A.total)), dim3(RT_WG_THREADS), 0, l.s, l.a->dev, l.p, l.A);
     hipLaunchKernelGGL(k_exact, dim3(EXACT_GRID), dim3(256), 0, l.s, l.a->dev, l.p, l.X);
+  };
+  if constexpr (RT_IDENT_ROOT_KERNEL && STATS == 0 && !ALPHA && job_base(JOB) != JOB_RENDER_GI) {
+    if (ident_root_form(l.a)) {
+      launch(rt_persistent_kernel<JOB, 0, false, false, PACKED, true, false, true>, rt_persistent_kernel<JOB, 0, false, true, false, false, false>);
+      return;
+    }
+  }
+  with_decode_and_depth<STATS == 0 && !ALPHA>(l.a, [&](auto ld, auto sh) {
+    launch(rt_persistent_kernel<JOB, STATS, decltype(ld)::value, false, PACKED, decltype(sh)::value, ALPHA>,
+           rt_persistent_kernel<JOB, STATS, decltype(ld)::value, true, false, false, ALPHA>);
   });
 }
 template <int STATS, bool PACKED, int CAM = 0, bool ALPHA = false>
