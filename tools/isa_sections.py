@@ -4,7 +4,9 @@
 Compiles rt_kernels.hip for gfx950 with the flags of build.py plus -DRT_ISA_MARKS, which turns every RT_MARK("name") of
 rt_persistent_kernel into a `; RTMARK name` comment in the listing, and counts what lies between consecutive marks of ONE
 instantiation: instructions, and among them the classes told apart by prefix -- v_ (VALU), s_cbranch (branches), ds_ (LDS),
-global_ and scratch_ (vector memory).  Nothing else is classified.
+global_ and scratch_ (vector memory), s_ other than branches, s_waitcnt and s_nop (scalar ALU: the exec-mask bookkeeping of per-lane
+control flow lands here), and the s_waitcnt that name vmcnt (waits for vector memory: one per dependent round trip).  Nothing else is
+classified.
 
 The listing is in layout order, not execution order: a block the compiler sinks out of line is counted in the section it lands in.
 The numbers say how large a section is, not how long it runs.
@@ -67,6 +69,10 @@ def sections(body):
         for cls, prefix in CLASSES:
             if op.startswith(prefix):
                 c[cls] += 1
+        if op.startswith("s_") and not op.startswith(("s_cbranch", "s_branch", "s_waitcnt", "s_nop")):
+            c["salu"] += 1
+        if op.startswith("s_waitcnt") and "vmcnt" in t:
+            c["vmwait"] += 1
     return counts
 
 
@@ -100,7 +106,7 @@ def main():
     if name is None:
         raise SystemExit("no instantiation matches %s (see --list)" % (subs,))
     counts = sections(ks[name])
-    cols = ("insts",) + tuple(c for c, _ in CLASSES)
+    cols = ("insts",) + tuple(c for c, _ in CLASSES) + ("salu", "vmwait")
     print("# %s" % (label or "rt_kernels.hip"))
     print("# flags: %s" % " ".join(extra or ["(none)"]))
     print("# kernel: %s" % name)
@@ -110,7 +116,7 @@ def main():
         print("%-10s" % sec + "".join("%9d" % c[k] for k in cols))
         total.update(c)
     loop = collections.Counter()
-    for sec in ("loop_top", "node", "stack", "inst", "leaf", "loop_exit"):
+    for sec in ("loop_top", "node", "stack", "inst", "leaf", "leaf_tris", "leaf_pop", "loop_exit"):
         loop.update(counts.get(sec, {}))
     print("%-10s" % "loop" + "".join("%9d" % loop[k] for k in cols))
     print("%-10s" % "kernel" + "".join("%9d" % total[k] for k in cols))

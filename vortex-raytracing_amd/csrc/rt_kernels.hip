@@ -87,6 +87,34 @@ __device__ __forceinline__ float ray_tri(float ox, float oy, float oz, float dx,
   return tf;
 }
 
+// ray_tri without control flow: the same operations in the same order (the build contracts nothing), the four rejections evaluated as
+// predicates in the polarity of the returns above -- a comparison with a NaN is false in both forms -- and one select at the end.  1 / a
+// of a rejected lane may be inf or NaN; nothing that depends on it survives the select.  With no return between the loads of a
+// triangle's three words and their uses, the loads issue together and the test waits for memory once.
+__device__ __forceinline__ float ray_tri_flat(float ox, float oy, float oz, float dx, float dy, float dz,
+                                              float4 t0, float4 t1, float4 t2, float& bx, float& by, float& bz) {
+  const float v0x = t0.x, v0y = t0.y, v0z = t0.z;
+  const float e1x = t0.w, e1y = t1.x, e1z = t1.y;
+  const float e2x = t1.z, e2y = t1.w, e2z = t2.x;
+  float hx = dy * e2z - dz * e2y;
+  float hy = dz * e2x - dx * e2z;
+  float hz = dx * e2y - dy * e2x;
+  float a = e1x * hx + e1y * hy + e1z * hz;
+  float f = 1 / a;
+  float sx = ox - v0x, sy = oy - v0y, sz = oz - v0z;
+  float w1 = f * (sx * hx + sy * hy + sz * hz);
+  float qx = sy * e1z - sz * e1y;
+  float qy = sz * e1x - sx * e1z;
+  float qz = sx * e1y - sy * e1x;
+  float w2 = f * (dx * qx + dy * qy + dz * qz);
+  float tf = f * (e2x * qx + e2y * qy + e2z * qz);
+  const bool rejected = (fabsf(a) < RT_EPSILON) | (w1 < 0 || w1 > 1) | (w2 < 0 || w1 + w2 > 1) | (tf <= RT_EPSILON);
+  bx = w1;
+  by = w2;
+  bz = 1 - w1 - w2;
+  return rejected ? RT_LARGE_FLOAT : tf;
+}
+
 struct Cand { float d; uint32_t desc; };
 // visit order: nearer first; equal distance -> higher child index first (stable far->near sort of
 // rt_traversal.cpp:76-78 read from the back).  Filtered children carry d = +inf.
@@ -543,6 +571,14 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 // its re-filter loop; the loop's exit test takes one ballot in the common case.  0 = the per-child form (the A/B: docs/KNOBS.md).
 #ifndef RT_BATCH_PUSH
 #define RT_BATCH_PUSH 1
+#endif
+// RT_LEAF_FLAT: the triangle test of the plain / shadow frame jobs in its straight-line form (ray_tri_flat: the triangle's 48 bytes arrive
+// in one memory round trip instead of two, the four early returns are one select): +1.1 % on the headline frame.  0 = ray_tri (the A/B:
+// docs/KNOBS.md).  Ray buffers, the diffuse-bounce job, the EXACT launch and the alpha-tested instantiations keep ray_tri whatever the
+// value.  (The triangle LOOP without per-lane control flow -- the leaf lanes of a wavefront walking their leaves in step, a lane that is
+// through re-reading its first triangle -- was built on top of it and lost 3 % against this form: DESIGN.md s5, rejected.)
+#ifndef RT_LEAF_FLAT
+#define RT_LEAF_FLAT 1
 #endif
 // (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
 
@@ -1214,6 +1250,9 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
             constexpr bool PREFETCH = is_trace_job(JOB) && RT_TRI_PREFETCH;
             float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, n2 = n0;
             if (PREFETCH) { const float4* tp0 = sc.tri_w + (size_t)leftFirst * 3; n0 = tp0[0]; n1 = tp0[1]; n2 = tp0[2]; }
+            // the plain / shadow frame jobs (RT_LEAF_FLAT above); the others keep the two-trip triangle test
+            constexpr bool FLAT_TEST = RT_LEAF_FLAT >= 1 && !EXACT && !ALPHA && (job_base(JOB) == JOB_RENDER || job_base(JOB) == JOB_RENDER_SHADOW);
+            RT_MARK("leaf_tris");
             for (uint32_t i = 0; i < triCount; ++i) {
               const uint32_t triIdx = leftFirst + i;
               float4 t0, t1, t2;
@@ -1234,7 +1273,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
               }
               if (STATS) fx.tri++;
               float bx, by, bz;
-              const float d = ray_tri(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz);
+              const float d = FLAT_TEST ? ray_tri_flat(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz) : ray_tri(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz);
               if (d < hitd) {
                 // a rejected candidate is a triangle the ray missed: no record, no abandon test, no stop, on to the leaf's next triangle
                 if constexpr (ALPHA) { if (alpha_rejects(sc, A.alpha_tri, triIdx, bx, by, bz)) continue; }
@@ -1248,6 +1287,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
                 if (!(path_m < hitd)) break;
               }
             }
+            RT_MARK("leaf_pop");
             if (stop) { sp = 0; tos_d = DESC_DONE; cur = DESC_DONE; }
             else pop_next();
           }
