@@ -503,7 +503,15 @@ int vxrc_render_accel(vxrc_accel_t* accel, uint32_t width, uint32_t height, uint
  * Rows [y0,y1) of the frame kernel.cpp:9-33 renders: GenerateRay (render.h:192-211) -> Trace (:213-275) summed
  * over the samples -> RGB32FtoRGB8 -> dst[x + y*W].  colors (optional): f32 rgb per pixel before packing.
  * A malformed BVH fails the call (-1); a TLAS / instance index or texture extent outside its buffer, a stack deeper than the
- * reference's BVH_STACK_SIZE (64, undefined behaviour there) or a runaway TLAS walk sets vxrt_status bits 2 / 0 / 1. */
+ * reference's BVH_STACK_SIZE (64, undefined behaviour there) or a runaway TLAS walk sets vxrt_status bits 2 / 0 / 1.
+ *
+ * Conversions C leaves undefined.  The twin's Trace casts floats that need not fit, as the RTU shader does: uint32_t(uv * size) in
+ * texSample (render.h:10-11) and int(min(c, 1) * 255) in RGB32FtoRGB8 (common.h:106-108).  Every uv, light, ambient, background and
+ * reflectivity value is accepted, finite or not, and the frame is what the reference's x86-64 build renders -- by the rule written at
+ * vxrt_shade_rays, which the kernel (csrc/rc_kernels.hip: f2u_x86, f2i_x86) and the restatement (oracle/rc_oracle.c) state as range tests
+ * instead of casts: u * w at or above 2^63, +-inf and NaN read texel column 0, negative uv wrap, a NaN channel packs as INT_MIN (the
+ * bare cast gave 0 on gfx950: an all-NaN colour packed as 0 instead of 0x80000000).  The reference's object code agrees for every class
+ * tried; tests/test_rc_hostile_cpu.py pins the values, tests/test_gpu_rc_hostile.py holds the kernel to them. */
 int vxrc_render(const vxrc_scene_t* scene, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                 const vxrc_params_t* params, uint32_t* dst, float* colors, void* stream);
 

@@ -157,7 +157,15 @@ void rc_generate_ray(const rc_args_t* a, uint32_t x, uint32_t y, float out6[6]) 
   out6[0] = pos.x; out6[1] = pos.y; out6[2] = pos.z; out6[3] = d.x; out6[4] = d.y; out6[5] = d.z;
 }
 
-static inline uint32_t f2u_x86(float f) { return (uint32_t)(int64_t)f; }   /* uint32_t(float) as x86-64 g++ lowers it */
+/* The two conversions of the reference that C leaves undefined when the value does not fit: uint32_t(uv * size) in texSample (render.h:10-11)
+ * and int(min(c, 1) * 255) in RGB32FtoRGB8 (common.h:106-108).  x86-64 g++ lowers them to cvttss2si r64 + truncation and cvttss2si r32; this
+ * is that behaviour as a range test, so that no cast here is out of range -- the rule of include/vortex_hip.h (vxrt_shade_rays, vxrc_render),
+ * the same two lines as in rt_oracle.c and in the kernels.  The reference's object code agrees for every class of
+ * tests/test_rc_hostile_cpu.py (uv negative, around 2^31 / 2^32 / +-2^63, huge, +-inf, NaN; colours negative, below -2^31 / 255, +-inf, NaN):
+ *   uint32_t(f): the truncated value mod 2^32 for -2^63 <= f < 2^63, 0 for NaN and everything else
+ *   int(f):      the truncated value for -2^31 <= f < 2^31, INT_MIN (0x80000000) for NaN and everything else */
+static inline uint32_t f2u_x86(float f) { return (f >= -0x1p63f && f < 0x1p63f) ? (uint32_t)(int64_t)f : 0u; }
+static inline uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int32_t)f : 0x80000000u; }
 
 /* render.h:213-275 Trace */
 int rc_radiance(const rc_args_t* a, const float ray6[6], float out3[3]) {
@@ -226,8 +234,9 @@ int rc_render(const rc_args_t* a, uint32_t y0, uint32_t y1, uint32_t* out_pixels
         color = add(color, v3m(c[0], c[1], c[2]));
       }
       uint32_t idx = x + y * a->dst_width;
-      int r = (int)(std_min(color.x, 1.f) * 255), g = (int)(std_min(color.y, 1.f) * 255), b = (int)(std_min(color.z, 1.f) * 255);   /* common.h:107-112 */
-      out_pixels[idx] = (uint32_t)((r << 16) + (g << 8) + b);
+      /* common.h:106-112; shifts and sums of the ints' bits, mod 2^32: what the 32-bit registers hold */
+      uint32_t r = f2i_x86(std_min(color.x, 1.f) * 255), g = f2i_x86(std_min(color.y, 1.f) * 255), b = f2i_x86(std_min(color.z, 1.f) * 255);
+      out_pixels[idx] = (r << 16) + (g << 8) + b;
       if (out_color) { out_color[3 * idx] = color.x; out_color[3 * idx + 1] = color.y; out_color[3 * idx + 2] = color.z; }
     }
   }

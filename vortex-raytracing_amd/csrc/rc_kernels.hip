@@ -136,7 +136,11 @@ __device__ __forceinline__ bool ray_tri(float ox, float oy, float oz, float dx, 
   return true;
 }
 
-__device__ __forceinline__ uint32_t f2u_x86(float f) { return (uint32_t)(long long)f; }   // uint32_t(float) as x86-64 g++ lowers it
+// uint32_t(float) and int(float) as x86-64 g++ lowers them (cvttss2si r64 + truncation; cvttss2si r32), as range tests: a bare cast of a value that
+// does not fit is undefined in C; on gfx950 the bare casts returned the x86 value for every u * w tried, +-inf and >= 2^63 included, but packed
+// a NaN channel as 0 where x86 gives INT_MIN.  The rule of include/vortex_hip.h (vxrt_shade_rays, vxrc_render); same lines as rt_kernels.hip.
+__device__ __forceinline__ uint32_t f2u_x86(float f) { return (f >= -0x1p63f && f < 0x1p63f) ? (uint32_t)(long long)f : 0u; }
+__device__ __forceinline__ uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int)f : 0x80000000u; }
 
 // ---------------------------------------------------------------------------------------------
 // acceleration-layout build (validates every index the BVH walk follows; a malformed scene fails on the host)
@@ -667,8 +671,9 @@ __global__ __launch_bounds__(256, RC_WAVES) void rc_persistent_kernel(RcDev sc, 
         if (++smp < p.spp) primary_ray();
         else {
           const size_t idx = (size_t)px + (size_t)py * A.W;
-          const int ir = (int)(std_min(cr, 1.f) * 255), ig = (int)(std_min(cg, 1.f) * 255), ib = (int)(std_min(cb, 1.f) * 255);   // common.h:107-112
-          A.dst[idx] = (uint32_t)((ir << 16) + (ig << 8) + ib);
+          // common.h:106-112 (shifts and sums of the ints' bits, mod 2^32: what the 32-bit registers hold)
+          const uint32_t ir = f2i_x86(std_min(cr, 1.f) * 255), ig = f2i_x86(std_min(cg, 1.f) * 255), ib = f2i_x86(std_min(cb, 1.f) * 255);
+          A.dst[idx] = (ir << 16) + (ig << 8) + ib;
           if (A.colors) { A.colors[3 * idx] = cr; A.colors[3 * idx + 1] = cg; A.colors[3 * idx + 2] = cb; }
           cur = RC_CUR_IDLE;
         }
