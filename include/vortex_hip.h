@@ -264,7 +264,7 @@ int vxrt_accel_set_transforms(vxrt_accel_t* accel, uint32_t first, uint32_t coun
  *   ray they trace; their optional outputs are as without it;
  *   EVERY OTHER entry point that traces rays returns -1 before it launches anything -- vxrt_render_interleaved, the *_batch and
  *   rows forms, vxrt_render_stats / _stats_timed / _wave_log, vxrt_trace_stats, vxrt_render_ao / _diffuse_bounce and their camera
- *   forms: none of them silently ignores the table;
+ *   forms, vxrt_render_path: none of them silently ignores the table;
  *   vxrt_shade_rays and the ray generators trace nothing and are unaffected.  The vx_* boundary has no access to the table. */
 int vxrt_accel_set_alpha_test(vxrt_accel_t* accel, const uint8_t* thresholds /* HOST, n_mats entries, or NULL */, uint32_t n_mats,
                               void* stream);
@@ -465,6 +465,48 @@ int vxrt_render_diffuse_bounce(vxrt_accel_t* accel, uint32_t width, uint32_t hei
 int vxrt_render_diffuse_bounce_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                                       const vxrt_shade_params_t* params, uint32_t seed, uint32_t* dst, float* colors /* optional */,
                                       unsigned long long* rays_traced /* optional */, void* stream);
+
+/* Path-traced frame (extension; absent from the reference): several diffuse bounces, several samples per pixel, the light sampled at
+ * every vertex of the path.  vxrt_render_ao's sampling recipe, vxrt_render's occlusion ray and the shading of vxrt_shade_rays, joined
+ * by per-path state.  Every + and * below is an fp32 operation without contraction, in the order written, so the frame is
+ * reproducible bit for bit (tests/path_ref.py restates it).  cam == NULL: the RTU test's fixed GenerateRay, as vxrt_render uses it;
+ * else the pinhole ray of vxrt_camera_t.  params->max_depth is ignored (as vxrt_render_ao and vxrt_render_diffuse_bounce ignore it):
+ * the mirror arm is never followed.  For pixel (x, y) of rows [y0, y1):
+ *   r_0 = the camera ray, h_0 = its closest hit; on a miss the pixel is the background and no further ray is traced.
+ *   Lit(r, h) = the Lambert colour of the hit as vxrt_shade_rays computes it (term + background * reflectivity, the else arm of
+ *     closest.cpp); with shadow != 0 the occlusion ray of vxrt_render is traced first (origin pushed 1e-3 along L, tmax = |L|,
+ *     any-hit) and a blocked hit takes the same expression with NdotL forced to 0.   Alb(h) = texColor of the hit (closest.cpp:72-77).
+ *   For sample s = 0 .. spp-1:  Lc = Lit(r_0, h_0), thr = Alb(h_0), r = r_0, h = h_0; then for k = 0 .. bounces-1:
+ *     r' = the vxrt_render_ao ray of (x, y, W, spp, s) with user seed (seed + k) mod 2^32, leaving the hit point I(r, h) along the shading
+ *          normal N(r, h) turned against dir(r); traced for its closest hit, no tmax.
+ *     miss:   Lc = Lc + thr * background, and the path ends.
+ *     hit h': Lc = Lc + thr * Lit(r', h'), then thr = thr * Alb(h'), r = r', h = h'.
+ *     (the primary hit, its Lit and its Alb are computed once per pixel and shared by all samples)
+ *   acc = the first sample's Lc; each later sample's Lc is added in ascending s (not from zero: 0 + (-0) would change a sign bit);
+ *   colour = acc / (float)spp; pixel = the RGB8 pack of colour.
+ *   rays_traced increases by the primary rays of the window + one per occlusion ray of a real hit + one per bounce ray of a live path.
+ * Two identities follow: bounces = 1, spp = 1, shadow = 0 is vxrt_render_diffuse_bounce[_camera] bit for bit (colours, pixels, rays
+ * traced); bounces = 0 is vxrt_render[_camera] with the same shadow on a frame rendered with max_depth = 1, for every spp whose
+ * sum and division are exact (the powers of two; x + x + x divided by 3 is not always x in fp32).
+ * dst, colors (optional, 3 floats per pixel of the full frame) and rays_traced (optional) as for vxrt_render.  Asynchronous on `stream`:
+ * the primary pass is vxrt_render's launch, the rest runs from per-path state in the frame context's own storage (frames in flight on
+ * several streams do not see each other's) in batches of whole samples (host knob VXRT_PATH_BATCH, docs/KNOBS.md); every ray count stays
+ * on the device, and the host synchronises the stream only when that storage has to grow.
+ * Returns -1 before anything is launched (dst untouched) for a null `path`, spp = 0 or > 4096, bounces > VXRT_PATH_MAX_BOUNCES,
+ * shadow > 1, a camera field that is not finite, a stale accel, a non-zero alpha table, and whatever vxrt_render refuses for the
+ * window; 0 for an empty window.  There is no batch form, no interleaved form and no counting build. */
+#define VXRT_PATH_MAX_BOUNCES 16
+typedef struct vxrt_path_params {
+  uint32_t spp;      /* samples per pixel, 1..4096 */
+  uint32_t bounces;  /* diffuse bounces after the primary hit, 0..VXRT_PATH_MAX_BOUNCES */
+  uint32_t seed;     /* user seed of bounce 0; bounce k takes seed + k */
+  uint32_t shadow;   /* 0 / 1: sample the light with an occlusion ray at every vertex */
+} vxrt_path_params_t;
+int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
+                     uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                     const vxrt_shade_params_t* params, const vxrt_path_params_t* path,
+                     uint32_t* dst, float* colors /* optional */,
+                     unsigned long long* rays_traced /* optional */, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

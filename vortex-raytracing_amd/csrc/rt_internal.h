@@ -94,7 +94,16 @@ struct FrameCtx {
   uint32_t* ao_list = nullptr; uint32_t* ao_hdr = nullptr;   // pixels with a hit; [0] their number, [1] rays of the current batch
   float* ao_rays = nullptr; float* ao_tmax = nullptr; HitRec* ao_hits = nullptr; uint64_t ao_cap = 0, ao_ray_cap = 0;
   uint32_t* bin_hist = nullptr; uint32_t* bin_keys = nullptr; uint32_t* bin_order = nullptr; uint64_t bin_cap = 0, bin_ray_cap = 0;   // secondary-ray binning
-  void* pool_spill = nullptr; uint64_t pool_spill_bytes = 0;   // ray-pool trace kernel: the part of the slots' stacks that does not fit LDS
+  // path frames (vxrt_render_path; allocated on first use).  Per pixel of the window: hit point (w = hit?), shading normal, primary
+  // direction, Lit, Alb of the primary hit and the accumulator over samples; the pixels with a hit ([0] of pt_hdr their number, [1] / [2]
+  // the live paths of even / odd depths).  Per path of a batch: I, N, dir of its last vertex, Lc, thr; the two lists of live paths;
+  // the bounce rays and their hit records; with light sampling the occlusion rays, their tmax and hit records.
+  float4* pt_geo = nullptr; float4* pt_nrm = nullptr; float4* pt_dir = nullptr; float4* pt_lit = nullptr; float4* pt_alb = nullptr; float4* pt_acc = nullptr;
+  uint32_t* pt_list = nullptr; uint32_t* pt_hdr = nullptr; uint64_t pt_cap = 0;
+  float4* pt_I = nullptr; float4* pt_N = nullptr; float4* pt_D = nullptr; float4* pt_L = nullptr; float4* pt_T = nullptr;
+  uint32_t* pt_live[2] = {nullptr, nullptr}; float* pt_rays = nullptr; HitRec* pt_hits = nullptr; uint64_t pt_path_cap = 0;
+  float* pt_srays = nullptr; float* pt_stmax = nullptr; HitRec* pt_shits = nullptr; uint64_t pt_shadow_cap = 0;
+  void* pool_spill = nullptr; uint64_t pool_spill_bytes = 0;  // ray-pool trace kernel: the part of the slots' stacks that does not fit LDS
   hipStream_t side = nullptr;
   hipEvent_t ev_in = nullptr, ev_side = nullptr, ev_done = nullptr;
   bool busy = false, inited = false, done_recorded = false;

@@ -1889,6 +1889,240 @@ __global__ __launch_bounds__(256) void rt_ao_final_kernel(uint64_t n, uint32_t W
 }
 
 // ---------------------------------------------------------------------------------------------
+// Path frames (vxrt_render_path; the definition is in include/vortex_hip.h, the launch sequence in render_path_tail and DESIGN.md s2,
+// "Path frames").  The kernels around the ray-buffer launches: per-pixel state of the primary hit, per-path state that survives from
+// bounce to bounce, the scatter step and the accumulation over samples.  Every arithmetic step is an existing __device__ function
+// (shade_terms, ao_sample_ray, shadow_ray, pack_rgb8, camera_ray / generate_ray).
+// Path slot i of a batch of ns samples starting at s0 = (pixel list[i / ns], sample s0 + i % ns); a path's state stays in its slot,
+// and the rays of a depth are those of the slots still listed as live (ray q belongs to slot live[q]).
+// ---------------------------------------------------------------------------------------------
+// Append value[c] of every thread with flag[c] to list[] (its length in *counter; the order is arbitrary): the workgroup counts in LDS
+// and does one atomic (see ao_prepare_pass).  Every thread of the workgroup calls it.
+template <int C>
+__device__ __forceinline__ void wg_append(const bool (&flag)[C], const uint32_t (&value)[C], uint32_t* __restrict__ list, uint32_t* counter) {
+  __shared__ uint32_t s_cnt[C][4];
+  __shared__ uint32_t s_base;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t off[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const unsigned long long m = __ballot(flag[c]);
+    off[c] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[c][wv] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int c = 0; c < C; ++c) for (int w = 0; w < 4; ++w) { const uint32_t v = s_cnt[c][w]; s_cnt[c][w] = tot; tot += v; }
+    s_base = tot ? atomicAdd(counter, tot) : 0u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+    if (flag[c]) list[s_base + s_cnt[c][wv] + off[c]] = value[c];
+}
+
+// per pixel t of rows [y0,y1): geo[t] = (I, hit?), nrm[t] = (N, 0), dir[t] = (direction of the primary ray, 0), lit[t] = (Lit of the
+// primary hit with the occlusion bit the shadow frame launch left in its record | background, 0), alb[t] = (Alb, 0); pixels with a hit
+// are appended to list[] (count in hdr[0])
+// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
+#define PATH_PREP_CHUNKS 4   // pixels per thread, as AO_PREP_CHUNKS
+template <bool CAM>
+__device__ __forceinline__ void path_prepare_pass(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
+  if (ctl_reset && blockIdx.x == 0)
+    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
+  bool hit_c[PATH_PREP_CHUNKS];
+  uint32_t t_c[PATH_PREP_CHUNKS];
+#pragma unroll
+  for (int c = 0; c < PATH_PREP_CHUNKS; ++c) {
+    const uint64_t t64 = ((uint64_t)blockIdx.x * PATH_PREP_CHUNKS + c) * 256u + threadIdx.x;
+    const uint32_t t = (uint32_t)t64;
+    bool hit = false;
+    if (t64 < n) {
+      const uint32_t x = t % W, y = y0 + t / W;
+      HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
+      const bool occ = (h.blasIdx & 0x80000000u) != 0u;
+      h.blasIdx &= 0x7fffffffu;
+      float ox, oy, oz, dx, dy, dz;
+      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
+      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+      if (h.dist == RT_LARGE_FLOAT) {
+        geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        lit[t] = make_float4(p.bg[0], p.bg[1], p.bg[2], 0.f);
+      } else {
+        float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
+        shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
+        float thr = 1.0f;
+        thr *= refl;
+        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+        geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
+        nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
+        dir[t] = make_float4(dx, dy, dz, 0.f);
+        lit[t] = make_float4(r, g, b, 0.f);
+        alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
+        hit = true;
+      }
+    }
+    hit_c[c] = hit; t_c[c] = t;
+  }
+  wg_append<PATH_PREP_CHUNKS>(hit_c, t_c, list, hdr);
+}
+__global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
+  path_prepare_pass<false>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset);
+}
+// the same pass of a camera frame: cam = the frame context's camera block, whose head every lane reads at the same address (see
+// rt_ao_prepare_camera_kernel)
+__global__ __launch_bounds__(256) void rt_path_prepare_camera_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ cam, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
+  path_prepare_pass<true>(sc, p, n, W, y0, cam, cam + CAM_TAB, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset);
+}
+
+// start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
+__global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, uint32_t* __restrict__ live) {
+  const uint64_t want = (uint64_t)hdr[0] * ns;
+  const uint32_t total = want < cap ? (uint32_t)want : cap;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i == 0) hdr[1] = total;
+  if (i >= total) return;
+  const uint32_t t = list[i / ns];
+  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
+  live[i] = i;
+}
+
+// the bounce rays of one depth: ray q leaves the last vertex of slot live[q] (user seed = seed + depth); zeroes the next depth's count
+__global__ __launch_bounds__(256) void rt_path_bounce_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, unsigned long long* rays_traced) {
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q == 0) {
+    *n_next = 0u;
+    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one)
+  }
+  if (q >= total) return;
+  const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
+  const uint32_t x = t % W, y = y0 + t / W;
+  const float4 I = pI[slot], N = pN[slot], D = pD[slot];
+  float r6[6];
+  ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
+  float* o = rays + (size_t)q * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = r6[k];
+}
+
+// the occlusion rays of one depth (light sampling): one per bounce ray that hit; a miss gets a ray nothing can hit, which is not
+// counted (see rt_bounce_shadow_rays_kernel).  One atomic per workgroup on the ray counter.
+__global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams p, uint32_t cap, const uint32_t* n_live, const float* __restrict__ rays,
+    const HitRec* __restrict__ hits, float* __restrict__ srays, float* __restrict__ stmax, unsigned long long* rays_traced) {
+  __shared__ uint32_t s_real;
+  if (threadIdx.x == 0) s_real = 0u;
+  __syncthreads();
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  bool real = false;
+  if (q < total) {
+    const float* rp = rays + (size_t)q * 6;
+    float* sp = srays + (size_t)q * 6;
+    const float d = hits[q].dist;
+    if (d == RT_LARGE_FLOAT) {
+      sp[0] = 0.f; sp[1] = 0.f; sp[2] = 0.f; sp[3] = 1.f; sp[4] = 1.f; sp[5] = 1.f;
+      stmax[q] = -1.0f;
+    } else {
+      float sdist;
+      shadow_ray(p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], d, sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sdist);
+      stmax[q] = sdist;
+      real = true;
+    }
+  }
+  const unsigned long long m = __ballot(real);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
+  __syncthreads();
+  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
+}
+
+// the scatter step of one depth.  Miss: Lc = Lc + thr * background, the path ends.  Hit: Lc = Lc + thr * Lit (occluded iff shits[q]
+// hit), then thr = thr * Alb and the hit becomes the slot's last vertex; with `next` the slot is appended to the next depth's live list.
+__global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next) {
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  bool go[1] = {false};
+  uint32_t val[1] = {0u};
+  if (q < total) {
+    const uint32_t slot = live[q];
+    const float* rp = rays + (size_t)q * 6;
+    HitRec h = hits[q];
+    h.blasIdx &= 0x7fffffffu;
+    float4 L = pL[slot];
+    const float4 T = pT[slot];
+    if (h.dist == RT_LARGE_FLOAT) {
+      L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
+    } else {
+      const bool occ = shits != nullptr && shits[q].dist != RT_LARGE_FLOAT;
+      float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
+      shade_terms<false>(sc, p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
+      float thr = 1.0f;
+      thr *= refl;
+      r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+      L.x = L.x + T.x * r; L.y = L.y + T.y * g; L.z = L.z + T.z * b;
+      if (next) {
+        pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
+        pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
+        pN[slot] = make_float4(Nx, Ny, Nz, 0.f);
+        pD[slot] = make_float4(rp[3], rp[4], rp[5], 0.f);
+        go[0] = true; val[0] = slot;
+      }
+    }
+    pL[slot] = L;
+  }
+  if (next) wg_append<1>(go, val, next, n_next);   // (uniform over the launch)
+}
+
+// after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
+// starts it); one thread per listed pixel
+__global__ __launch_bounds__(256) void rt_path_accumulate_kernel(uint32_t n, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
+    uint32_t first, const float4* __restrict__ pL, float4* __restrict__ acc) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= min(hdr[0], n)) return;
+  const uint32_t t = list[j];
+  const float4* L = pL + (size_t)j * ns;
+  float4 a = first ? L[0] : acc[t];
+  for (uint32_t s = first ? 1u : 0u; s < ns; ++s) { const float4 c = L[s]; a.x = a.x + c.x; a.y = a.y + c.y; a.z = a.z + c.z; }
+  acc[t] = a;
+}
+
+// colour = acc / spp, pack, write.  flat (bounces = 0): every sample's Lc is the pixel's Lit, summed here the same way.
+__global__ __launch_bounds__(256) void rt_path_final_kernel(uint32_t n, uint32_t W, uint32_t y0, const float4* __restrict__ geo, const float4* __restrict__ lit,
+    const float4* __restrict__ acc, uint32_t spp, uint32_t flat, uint32_t* __restrict__ dst, float* __restrict__ colors_out) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t x = t % W, y = y0 + t / W;
+  const size_t e = (size_t)x + (size_t)y * W;
+  const float4 c = lit[t];
+  float r = c.x, g = c.y, b = c.z;   // (a miss: the background)
+  if (geo[t].w != 0.f) {
+    if (flat) { for (uint32_t s = 1; s < spp; ++s) { r = r + c.x; g = g + c.y; b = b + c.z; } }
+    else { const float4 a = acc[t]; r = a.x; g = a.y; b = a.z; }
+    const float f = (float)spp;
+    r = r / f; g = g / f; b = b / f;
+  }
+  dst[e] = pack_rgb8(r, g, b);
+  if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Secondary rays re-sorted before they are traced (north_star: "ray packets re-sorted ... to tame divergence").
 // The rays of a bounce / AO pass leave the compaction in pixel order with directions spread over a hemisphere: a wavefront of
 // 64 consecutive rays shares origins but not directions.  Counting sort by key = direction octant x origin cell (the 16x16-pixel
@@ -2190,6 +2424,11 @@ static uint32_t* status_word() {
 }
 
 #define LPT_MIN_TILES 20000u
+// Paths per batch of a path frame (VXRT_PATH_BATCH).  A path costs 136 bytes of frame-context storage -- 80 of state (I, N, dir, Lc, thr:
+// five float4), 24 + 24 of bounce ray and hit record, 2 x 4 of live-list entries -- and 52 more with light sampling (occlusion ray, tmax,
+// hit record): 4 Mi paths are 0.53 / 0.73 GiB per frame context, and at 1920x1080 two samples per batch, i.e. ray-buffer launches of up to
+// 4 M rays for a machine that holds 0.4 M lanes of the traversal kernel -- launch ramps and tails stay a small part of each.
+#define PATH_BATCH_PATHS (4ull << 20)
 #define LPT_BATCH_MAX_TILES 100000u
 #ifndef EXACT_GRID
 #define EXACT_GRID 128   // workgroups of the EXACT launch (it sees a fraction of a percent of the rays)
@@ -2202,6 +2441,7 @@ struct HostKnobs {
   bool lpt, lpt_batch;                  // on unless the value begins with '0'
   bool unordered_any_off, debug;        // VXRT_UNORDERED_ANY is 0; VXRT_DEBUG is set at all
   int lpt_batch_alone, side_reserve, packed, packed_batch, grid_div, pool, wgs_per_cu;   // side_reserve, packed: -1 = unset
+  uint64_t path_batch;                  // paths per batch of a path frame (see render_path_tail)
 };
 static const HostKnobs& host_knobs() {
   static const HostKnobs knobs = [] {
@@ -2221,6 +2461,7 @@ static const HostKnobs& host_knobs() {
     { const char* e = getenv("VXRT_UNORDERED_ANY"); k.unordered_any_off = e && atoi(e) == 0; }
     k.wgs_per_cu = num("VXRT_WGS_PER_CU", 0);
     k.debug = getenv("VXRT_DEBUG") != nullptr;
+    { const char* e = getenv("VXRT_PATH_BATCH"); const long long v = e ? atoll(e) : 0; k.path_batch = v > 0 ? (uint64_t)v : PATH_BATCH_PATHS; }
     return k;
   }();
   return knobs;
@@ -2470,6 +2711,7 @@ struct RenderRequest {
   unsigned long long* wave_log = nullptr;           // diagnostic, TIMED_TRAVERSAL only
   const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
   const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
+  const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
   void* stream = nullptr;
   Counting counting = Counting::TIMED;
   bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set
@@ -2614,6 +2856,77 @@ static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, 
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
+// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
+// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
+// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
+// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
+// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
+static int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  const SceneDev& sc = a->dev;
+  const vxrt_path_params_t& pp = *r.path;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  hipStream_t s = (hipStream_t)r.stream;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull) return -1;
+  const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, host_knobs().path_batch / n));   // samples per batch
+  const uint64_t path_cap = pp.bounces ? n * ns : 0, shadow_cap = pp.shadow ? path_cap : 0;
+  if (path_cap > 0x7fffffffull) return -1;
+  if (c->pt_cap < n || c->pt_path_cap < path_cap || c->pt_shadow_cap < shadow_cap) {
+    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    const uint64_t have = c->pt_cap, phave = c->pt_path_cap, shave = c->pt_shadow_cap;
+    bool ok = grow_buf((void**)&c->pt_geo, have, n, 16) && grow_buf((void**)&c->pt_nrm, have, n, 16) && grow_buf((void**)&c->pt_dir, have, n, 16) &&
+              grow_buf((void**)&c->pt_lit, have, n, 16) && grow_buf((void**)&c->pt_alb, have, n, 16) && grow_buf((void**)&c->pt_acc, have, n, 16) &&
+              grow_buf((void**)&c->pt_list, have, n, 4) && grow_buf((void**)&c->pt_hdr, c->pt_hdr ? 1 : 0, 1, 16);
+    if (ok && path_cap)
+      ok = grow_buf((void**)&c->pt_I, phave, path_cap, 16) && grow_buf((void**)&c->pt_N, phave, path_cap, 16) && grow_buf((void**)&c->pt_D, phave, path_cap, 16) &&
+           grow_buf((void**)&c->pt_L, phave, path_cap, 16) && grow_buf((void**)&c->pt_T, phave, path_cap, 16) &&
+           grow_buf((void**)&c->pt_live[0], phave, path_cap, 4) && grow_buf((void**)&c->pt_live[1], phave, path_cap, 4) &&
+           grow_buf((void**)&c->pt_rays, phave, path_cap, 24) && grow_buf((void**)&c->pt_hits, phave, path_cap, sizeof(HitRec));
+    if (ok && shadow_cap)
+      ok = grow_buf((void**)&c->pt_srays, shave, shadow_cap, 24) && grow_buf((void**)&c->pt_stmax, shave, shadow_cap, 4) &&
+           grow_buf((void**)&c->pt_shits, shave, shadow_cap, sizeof(HitRec));
+    if (!ok) { c->pt_cap = c->pt_path_cap = c->pt_shadow_cap = 0; return -1; }   // (whatever is left is allocated again by the next frame)
+    c->pt_cap = std::max(have, n); c->pt_path_cap = std::max(phave, path_cap); c->pt_shadow_cap = std::max(shave, shadow_cap);
+  }
+  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
+  const dim3 block(256), grid((n32 + 255u) / 256u), pgrid((n32 + 256u * PATH_PREP_CHUNKS - 1u) / (256u * PATH_PREP_CHUNKS)), rgrid((cap + 255u) / 256u);
+  if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
+  if (r.cams) hipLaunchKernelGGL(rt_path_prepare_camera_kernel, pgrid, block, 0, s, sc, p, n32, width, y0, utab, (const HitRec*)c->hitbuf,
+                                 c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl);
+  else hipLaunchKernelGGL(rt_path_prepare_kernel, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
+                          c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl);
+  if (hipGetLastError() != hipSuccess) return -1;
+  c->ctl_dirty = false;
+  for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
+    const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
+    hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
+                       (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
+    for (uint32_t d = 0; d < pp.bounces; ++d) {
+      uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
+      uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
+      const uint32_t* live = c->pt_live[d & 1u];
+      const bool more = d + 1u < pp.bounces;
+      hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
+                         (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
+      if (trace_on_ctx(a, c, c->pt_rays, (uint64_t)n * k, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
+      if (pp.shadow) {
+        hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                           c->pt_srays, c->pt_stmax, r.counters);
+        if (trace_on_ctx(a, c, c->pt_srays, (uint64_t)n * k, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+      }
+      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                         pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T,
+                         more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr, n_next);
+    }
+    hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
+                       (const float4*)c->pt_L, c->pt_acc);
+  }
+  hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
+                     pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ---------------------------------------------------------------------------------------------
 // render_common, step by step: refusals, frame resources, launch plan, traversal launches, shading launch
 // ---------------------------------------------------------------------------------------------
@@ -2664,6 +2977,9 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if (r.batch > 1)
     for (uint32_t f = 0; f < r.batch; ++f)
       if (mirror_frame(a, r.params[f])) return -1;
+  // path frames: whole rows of single frames, the timed build only, colours the one optional output besides the ray count
+  if (r.path && (r.path->spp == 0 || r.path->spp > 4096 || r.path->bounces > VXRT_PATH_MAX_BOUNCES || r.path->shadow > 1 || stats || r.wave_log || r.ao ||
+                 r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
   return 1;
@@ -2759,7 +3075,7 @@ static bool ensure_lpt_tables(FrameCtx* c, const RenderRequest& r, uint32_t n_ti
   if (!grow_device({{(void**)&L.cost, 4 * 4}, {(void**)&L.order, 4}}, &L.cap, n_tiles, GrowSync::STREAM, s)) return false;
   if (grows) L.valid = false;
   // (camera frames learn their own order: they do not share the fixed camera's tiles' costs)
-  const uint32_t key[6] = {r.width, r.height, r.y0, r.y1, (uint32_t)r.shadow | (r.stride << 1), (r.ao ? 1u : 0u) | (r.batch << 1) | (r.cams ? 0x80000000u : 0u)};
+  const uint32_t key[6] = {r.width, r.height, r.y0, r.y1, (uint32_t)r.shadow | (r.stride << 1), (r.ao || r.path ? 1u : 0u) | (r.batch << 1) | (r.cams ? 0x80000000u : 0u)};
   if (memcmp(key, L.key, sizeof key) != 0) { L.valid = false; memcpy(L.key, key, sizeof key); }
   if (!L.cost || !L.order) return false;   // (whatever happened above: no launch with a missing table)
   A.tile_cost = L.cost;
@@ -2982,14 +3298,16 @@ static int render_common(vxrt_accel_t* a, const RenderRequest& r) {
   const LaunchPlan plan = launch_plan(a, r, (uint32_t)t.total, lpt, r.cams ? 0u : a->ap_count * r.batch);
   if (!traverse_frame(a, c, r, plan, p, A, s)) return fail();
   // (the tile sort for the next frame rides in the shading launch; the AO / bounce tails have no such launch and skip it)
-  const bool mirror = mirror_frame(a, r.params[0]);
-  const bool lpt_sort = plan.lpt && !r.ao && !mirror;
+  const bool mirror = !r.path && mirror_frame(a, r.params[0]);   // (a path frame ignores max_depth)
+  const bool lpt_sort = plan.lpt && !r.ao && !r.path && !mirror;
   if (plan.lpt && !lpt_sort) c->lpt[r.batch].valid = false;
   if (gi_fused_frame(r)) {
     // nothing follows: the pixels are written.  The control block stays as the launches left it; the context's next call clears it.
     if (hipGetLastError() != hipSuccess) return fail();
   } else if (r.ao) {
     if (render_ao_tail(a, c, r, p, A.utab, A.vtab) != 0) return fail();
+  } else if (r.path) {
+    if (render_path_tail(a, c, r, p, A.utab, A.vtab) != 0) return fail();
   } else if (mirror) {
     // reflective instances: the shading pass becomes the level-0 step of the mirror-bounce wavefront
     if (render_bounce_tail(a, c, r, p, A.utab, A.vtab) != 0) return fail();
@@ -3190,6 +3508,18 @@ int vxrt_render_ao_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = ao; r.cams = cam;
   r.dst = dst; r.colors = colors; r.unoccluded = unoccluded; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+// Path-traced frame (see the header): the plain or shadow frame launch, then render_path_tail
+int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                     const vxrt_shade_params_t* params, const vxrt_path_params_t* path, uint32_t* dst, float* colors,
+                     unsigned long long* rays_traced, void* stream) {
+  if (!path) return -1;
+  if (cam && !camera_ok(cam)) return -1;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }
 

@@ -509,3 +509,22 @@ def render_diffuse_bounce_camera(accel, cam, width, height, y0, y1, params, dst_
                                                     C.POINTER(ShadeParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     check(L.vxrt_render_diffuse_bounce_camera(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), int(seed), dst_ptr,
                                               colors_ptr, rays_ptr, stream), "vxrt_render_diffuse_bounce_camera")
+
+
+PATH_MAX_BOUNCES = 16   # VXRT_PATH_MAX_BOUNCES
+
+
+class PathParams(C.Structure):   # vxrt_path_params_t
+    _fields_ = [("spp", C.c_uint32), ("bounces", C.c_uint32), ("seed", C.c_uint32), ("shadow", C.c_uint32)]
+
+
+def render_path(accel, cam, width, height, y0, y1, params, spp, bounces, dst_ptr, seed=0, shadow=0, colors_ptr=None, rays_ptr=None, stream=None):
+    """vxrt_render_path: `spp` paths per pixel of `bounces` diffuse bounces each, the light sampled at every vertex with shadow=1, seen
+    from pinhole camera `cam` (a Camera or 14 floats; None = the fixed camera of vxrt_render)."""
+    L = _lib()
+    L.vxrt_render_path.restype = C.c_int
+    L.vxrt_render_path.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
+                                   C.POINTER(PathParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(L.vxrt_render_path(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), dst_ptr,
+                             colors_ptr, rays_ptr, stream), "vxrt_render_path")
