@@ -264,7 +264,7 @@ int vxrt_accel_set_transforms(vxrt_accel_t* accel, uint32_t first, uint32_t coun
  *   ray they trace; their optional outputs are as without it;
  *   EVERY OTHER entry point that traces rays returns -1 before it launches anything -- vxrt_render_interleaved, the *_batch and
  *   rows forms, vxrt_render_stats / _stats_timed / _wave_log, vxrt_trace_stats, vxrt_render_ao / _diffuse_bounce and their camera
- *   forms, vxrt_render_path: none of them silently ignores the table;
+ *   forms, vxrt_render_path, vxrt_render_path_denoised: none of them silently ignores the table;
  *   vxrt_shade_rays and the ray generators trace nothing and are unaffected.  The vx_* boundary has no access to the table. */
 int vxrt_accel_set_alpha_test(vxrt_accel_t* accel, const uint8_t* thresholds /* HOST, n_mats entries, or NULL */, uint32_t n_mats,
                               void* stream);
@@ -507,6 +507,75 @@ int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fix
                      const vxrt_shade_params_t* params, const vxrt_path_params_t* path,
                      uint32_t* dst, float* colors /* optional */,
                      unsigned long long* rays_traced /* optional */, void* stream);
+
+/* Denoised path frame (extension; absent from the reference): vxrt_render_path at a few samples per pixel, its stochastic part passed
+ * through a guided a-trous filter, and the guide buffers of the primary hit as optional outputs.  Per pixel the path frame is
+ * Lc = Lit_0 + Alb_0 * (everything stochastic): Lit_0 is deterministic and Alb_0 carries the texture detail, so only the demodulated
+ * indirect term E is filtered.  Every + - * / below is one fp32 operation, in the order written, without contraction (`/` is the
+ * correctly rounded division; there is no exp, pow or reciprocal approximation), so the result is reproducible bit for bit
+ * (tests/denoise_ref.py restates it).
+ *
+ * THE FILTER  F = atrous(S, P, N, prm) over a window of rows x width pixels.  S = the signal, 3 floats per pixel; P = (Ix, Iy, Iz, hit),
+ * hit != 0 (a NaN included) meaning that the pixel has a primary hit; N = (Nx, Ny, Nz, ignored); prm = vxrt_denoise_params_t.
+ * For iteration i = 0 .. iterations-1, with step = 1 << i and sl = sigma_l * 2^-i (one multiplication by the exact power of two), `in`
+ * being S for i = 0 and the previous iteration's `out` after that, for every pixel p of the window:
+ *   p is not a hit: out[p] = in[p].
+ *   else sw = +0, sc = (+0, +0, +0); the taps are visited in the order dy = -2..2 (outer), dx = -2..2 (inner), q = p + step * (dx, dy).
+ *   A tap is skipped if q lies outside the window (columns [0, width), the rows of the window only) or q is not a hit; the centre is a
+ *   tap like any other.  For a tap that is not skipped:
+ *     h  = k[dy+2] * k[dx+2], k = {1/16, 1/4, 3/8, 1/4, 1/16} (the products are exact)
+ *     d  = dot(Np, Nq); dn = d > 0 ? d : +0 (so 0 for a NaN), then dn = dn * dn repeated normal_power times
+ *     t  = fabsf(dot(Np, Iq - Ip)) / sigma_z;  wz = 1 / (1 + t * t)
+ *     u  = fabsf(lum(in[p]) - lum(in[q])) / sl;  wc = 1 / (1 + u * u)
+ *     w  = ((h * dn) * wz) * wc;  if w > 0 (false for a NaN): sw = sw + w and sc = sc + w * in[q] per channel
+ *   with dot(a, b) = (ax * bx + ay * by) + az * bz and lum(c) = (0.2126f * r + 0.7152f * g) + 0.0722f * b.
+ *   out[p] = sw > 0 ? sc / sw (per channel) : in[p].
+ * sigma_z and sigma_l must be > 0; +inf is legal and switches the term off (x / inf = 0, weight 1).  Guide values that are not finite
+ * or normals that are not unit vectors are legal input: the result is whatever the IEEE operations above give.  iterations = 0: F = S.
+ *
+ * THE FRAME.  With c = the colour vxrt_render_path defines for the pixel (acc / spp), D = Lit(r_0, h_0), A = Alb(h_0):
+ *   demodulate   E_ch = A_ch > 0 ? (c_ch - D_ch) / A_ch : 0
+ *   guides       P = (I(r_0, h_0), 1), N = (N(r_0, h_0), 0) for a pixel with a primary hit; a miss has P = 0 (so P.w = 0) and N = 0
+ *   filter       F = atrous(E, P, N, dn) over the rows [y0, y1) that are rendered.  A ROW WINDOW IS ITS OWN IMAGE: taps never reach
+ *                outside it, so a frame rendered in bands is not the frame rendered whole.
+ *   remodulate   colour_ch = D_ch + A_ch * F_ch; a miss is the background; pixel = the RGB8 pack of colour.
+ * iterations = 0 is vxrt_render_path bit for bit (no demodulation round trip).  rays_traced as for vxrt_render_path.
+ * aov (optional, any member may be NULL): full-frame addressing like `colors`, rows [y0, y1) written.
+ * Asynchronous on `stream` like vxrt_render_path (the host synchronises only when the frame context's storage has to grow); the two
+ * signal buffers of the iterations live in the frame context, so frames in flight on several streams do not see each other's.
+ * Launches after the path tail: one that demodulates and writes the guides (it takes the place of the pack), one per iteration, the
+ * last of which remodulates and packs.
+ * Returns -1 before anything is launched (dst untouched) for a null `dn`, iterations > VXRT_DENOISE_MAX_ITERATIONS, normal_power > 7,
+ * a sigma that is <= 0 or NaN, a non-zero alpha table, and everything vxrt_render_path refuses; 0 for an empty window. */
+#define VXRT_DENOISE_MAX_ITERATIONS 6
+typedef struct vxrt_denoise_params {
+  uint32_t iterations;    /* a-trous passes, 0..VXRT_DENOISE_MAX_ITERATIONS; pass i has stride 2^i */
+  uint32_t normal_power;  /* the normal weight is max(0, dot)^(2^normal_power), 0..7 */
+  float sigma_z;          /* scale of the distance of a tap's hit point from the centre's tangent plane, > 0 */
+  float sigma_l;          /* scale of the luminance difference in the first pass (halved every pass), > 0 */
+} vxrt_denoise_params_t;
+typedef struct vxrt_path_aov {
+  float* noisy;     /* 3 / pixel: vxrt_render_path's colour */
+  float* direct;    /* 3 / pixel: Lit_0 | background */
+  float* albedo;    /* 3 / pixel: Alb_0 | 0 */
+  float* position;  /* 4 / pixel: I, hit flag (1 | 0) */
+  float* normal;    /* 4 / pixel: N, 0 */
+} vxrt_path_aov_t;
+int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
+                              uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                              uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
+                              unsigned long long* rays_traced /* optional */, void* stream);
+
+/* The filter alone, F = atrous(signal, position, normal, dn), on caller-owned DEVICE buffers holding a window of `rows` rows of `width`
+ * pixels: signal and out 3 floats per pixel, position and normal 4 floats per pixel and 16-byte aligned.  out must not alias signal.
+ * scratch: device memory of at least vxrt_denoise_scratch_bytes(width, rows) bytes, 16-byte aligned (the two (r, g, b, lum) buffers the
+ * iterations alternate between; unused and may be NULL with iterations = 0).  Asynchronous on `stream`, no host synchronisation.
+ * Returns -1 before anything is launched (out untouched) for a null `dn` or parameters vxrt_render_path_denoised refuses, a window of
+ * 2^31 pixels or more, a null or misaligned buffer, and scratch that is too small; 0 for an empty window (width or rows = 0). */
+uint64_t vxrt_denoise_scratch_bytes(uint32_t width, uint32_t rows);
+int vxrt_denoise(uint32_t width, uint32_t rows, const float* signal, const float* position, const float* normal,
+                 const vxrt_denoise_params_t* dn, float* out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

@@ -1,6 +1,6 @@
 // Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
-// level-2 entry points) and rt_accel.hip (acceleration-layout build, refit) share.  The constants of the compact layout are in
-// rt_types.h.
+// level-2 entry points), rt_accel.hip (acceleration-layout build, refit) and rt_denoise.hip (the a-trous filter of denoised path
+// frames) share.  The constants of the compact layout are in rt_types.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,6 +103,9 @@ struct FrameCtx {
   float4* pt_I = nullptr; float4* pt_N = nullptr; float4* pt_D = nullptr; float4* pt_L = nullptr; float4* pt_T = nullptr;
   uint32_t* pt_live[2] = {nullptr, nullptr}; float* pt_rays = nullptr; HitRec* pt_hits = nullptr; uint64_t pt_path_cap = 0;
   float* pt_srays = nullptr; float* pt_stmax = nullptr; HitRec* pt_shits = nullptr; uint64_t pt_shadow_cap = 0;
+  // denoised path frames (vxrt_render_path_denoised; allocated on first use): the two signal buffers the a-trous iterations ping-pong
+  // between, one float4 (E, lum(E)) per pixel of the window; the guides are pt_geo and pt_nrm
+  float4* dn_sig[2] = {nullptr, nullptr}; uint64_t dn_cap = 0;
   void* pool_spill = nullptr; uint64_t pool_spill_bytes = 0;  // ray-pool trace kernel: the part of the slots' stacks that does not fit LDS
   hipStream_t side = nullptr;
   hipEvent_t ev_in = nullptr, ev_side = nullptr, ev_done = nullptr;
@@ -150,3 +153,31 @@ struct vxrt_accel {
 static inline bool ident_root_form(const vxrt_accel* a) {
   return RT_IDENT_ROOT_KERNEL && a->dev.ident_root != 0u && a->shallow && !a->dev.exact_decode && !a->alpha_on;
 }
+
+// ---------------------------------------------------------------------------------------------
+// shared device arithmetic: the RGB8 pack of every frame (rt_kernels.hip, rt_denoise.hip)
+// ---------------------------------------------------------------------------------------------
+// libstdc++ std::min (NaN behaviour is part of parity; std_max is in rt_kernels.hip)
+__device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
+// int(f) as x86-64 converts it (the rule of include/vortex_hip.h, vxrt_shade_rays; f2u_x86 is in rt_kernels.hip)
+__device__ __forceinline__ uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int)f : 0x80000000u; }
+__device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // common.h:149-154
+  const uint32_t ir = f2i_x86(std_min(r, 1.f) * 255);   // (shifts and sums of the int's bits, mod 2^32: what the 32-bit registers hold)
+  const uint32_t ig = f2i_x86(std_min(g, 1.f) * 255);
+  const uint32_t ib = f2i_x86(std_min(b, 1.f) * 255);
+  return (ir << 16) + (ig << 8) + ib;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rt_denoise.hip: the launches of a denoised path frame's tail (render_path_tail in rt_kernels.hip calls them; all asynchronous on `s`)
+// ---------------------------------------------------------------------------------------------
+// the checks of vxrt_denoise_params_t both entry points share
+bool dn_params_ok(const vxrt_denoise_params_t* dn);
+// per pixel t of the window: c = the path frame's colour (acc / spp | the flat sum of Lit_0 | the background), the optional guide
+// outputs, and with `sig` the demodulated signal (E, lum(E)) the filter starts from
+int dn_launch_demodulate(hipStream_t s, uint32_t n, uint32_t W, uint32_t y0, const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
+                         const float4* acc, uint32_t spp, uint32_t flat, float4* sig, const vxrt_path_aov_t* aov);
+// dn->iterations (>= 1) a-trous passes over sig[0] (ping-pong with sig[1]); the last one remodulates with lit / alb, packs and writes
+// dst / colors (full-frame addressing, rows from y0)
+int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn, float4* const sig[2], const float4* geo,
+                          const float4* nrm, const float4* lit, const float4* alb, uint32_t* dst, float* colors);

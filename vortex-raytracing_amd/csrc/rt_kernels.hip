@@ -26,8 +26,7 @@
 #include "rt_internal.h"
 #include "pinhole.h"
 
-// libstdc++ std::min / std::max (rt_traversal.cpp:327-337 use them; NaN behaviour is part of parity)
-__device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
+// libstdc++ std::min / std::max (rt_traversal.cpp:327-337 use them; NaN behaviour is part of parity; std_min is in rt_internal.h)
 __device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }
 
 // rt_traversal.cpp:318-339 with idir hoisted (1.0f/rd is recomputed per child there; same value).
@@ -214,8 +213,8 @@ struct Fetches { unsigned node = 0, inst = 0, tri = 0; };
 // this file nor oracle/rt_oracle.c depends on an out-of-range cast:
 //   uint32_t(f) = cvttss2si r64, low half: the truncated value mod 2^32 for -2^63 <= f < 2^63, 0 for NaN and everything else
 //   int(f)      = cvttss2si r32: the truncated value for -2^31 <= f < 2^31, INT_MIN (0x80000000) for NaN and everything else
+// (f2i_x86 and pack_rgb8, which rt_denoise.hip packs with as well, are in rt_internal.h)
 __device__ __forceinline__ uint32_t f2u_x86(float f) { return (f >= -0x1p63f && f < 0x1p63f) ? (uint32_t)(long long)f : 0u; }
-__device__ __forceinline__ uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int)f : 0x80000000u; }
 
 // Occlusion ray of the shadow extension (no reference counterpart): from the hit point toward the
 // light, origin pushed 1e-3 along L like the reference's mirror bounce (closest.cpp:104), tmax = |L|.
@@ -327,13 +326,6 @@ __device__ __forceinline__ void mirror_ray(float dx, float dy, float dz, float I
   const float Rx = vx * inv, Ry = vy * inv, Rz = vz * inv;
   out6[0] = Ix + Rx * 0.001f; out6[1] = Iy + Ry * 0.001f; out6[2] = Iz + Rz * 0.001f;
   out6[3] = Rx; out6[4] = Ry; out6[5] = Rz;
-}
-
-__device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // common.h:149-154
-  const uint32_t ir = f2i_x86(std_min(r, 1.f) * 255);   // (shifts and sums of the int's bits, mod 2^32: what the 32-bit registers hold)
-  const uint32_t ig = f2i_x86(std_min(g, 1.f) * 255);
-  const uint32_t ib = f2i_x86(std_min(b, 1.f) * 255);
-  return (ir << 16) + (ig << 8) + ib;
 }
 
 // kernel.cpp:28-39.  u = (x*2.0 - W)/H and v = (y*2.0 - H)/H are evaluated in double and rounded to
@@ -2712,6 +2704,8 @@ struct RenderRequest {
   const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
   const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
   const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
+  const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
+  const vxrt_path_aov_t* aov = nullptr;
   void* stream = nullptr;
   Counting counting = Counting::TIMED;
   bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set
@@ -2862,6 +2856,22 @@ static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, 
 // occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
 // batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
 // device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
+// End of a denoised path frame's tail in place of rt_path_final_kernel (the kernels and their launches are in rt_denoise.hip): demodulate
+// the pixels' accumulators into the context's first signal buffer and write the guide outputs, then one launch per a-trous iteration,
+// ping-pong between the two signal buffers, the last of which remodulates, packs and writes.  n = pixels of the window.
+static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
+  hipStream_t s = (hipStream_t)r.stream;
+  if (c->dn_cap < n) {
+    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    const uint64_t have = c->dn_cap;
+    if (!(grow_buf((void**)&c->dn_sig[0], have, n, 16) && grow_buf((void**)&c->dn_sig[1], have, n, 16))) { c->dn_cap = 0; return -1; }
+    c->dn_cap = n;
+  }
+  if (dn_launch_demodulate(s, n, r.width, r.y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, r.path->spp, r.path->bounces == 0 ? 1u : 0u,
+                           c->dn_sig[0], r.aov) != 0) return -1;
+  return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);
+}
+
 static int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
   const SceneDev& sc = a->dev;
   const vxrt_path_params_t& pp = *r.path;
@@ -2922,6 +2932,9 @@ static int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r
     hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
                        (const float4*)c->pt_L, c->pt_acc);
   }
+  if (r.denoise && r.denoise->iterations) return render_denoise_tail(c, r, n32);
+  if (r.denoise && r.aov && dn_launch_demodulate(s, n32, width, y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, pp.spp, pp.bounces == 0 ? 1u : 0u,
+                                                 nullptr, r.aov) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
   hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
                      pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -2980,6 +2993,8 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   // path frames: whole rows of single frames, the timed build only, colours the one optional output besides the ray count
   if (r.path && (r.path->spp == 0 || r.path->spp > 4096 || r.path->bounces > VXRT_PATH_MAX_BOUNCES || r.path->shadow > 1 || stats || r.wave_log || r.ao ||
                  r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
+  // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
+  if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
   return 1;
@@ -3519,6 +3534,19 @@ int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t wid
   if (cam && !camera_ok(cam)) return -1;
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+// Denoised path frame (see the header): vxrt_render_path whose tail ends in the a-trous filter of rt_denoise.hip
+int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn, uint32_t* dst, float* colors,
+                              const vxrt_path_aov_t* aov, unsigned long long* rays_traced, void* stream) {
+  if (!path || !dn) return -1;
+  if (cam && !camera_ok(cam)) return -1;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.denoise = dn; r.aov = aov;
   r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }

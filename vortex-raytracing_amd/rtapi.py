@@ -528,3 +528,49 @@ def render_path(accel, cam, width, height, y0, y1, params, spp, bounces, dst_ptr
     pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
     check(L.vxrt_render_path(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), dst_ptr,
                              colors_ptr, rays_ptr, stream), "vxrt_render_path")
+
+
+DENOISE_MAX_ITERATIONS = 6   # VXRT_DENOISE_MAX_ITERATIONS
+
+
+class DenoiseParams(C.Structure):   # vxrt_denoise_params_t
+    _fields_ = [("iterations", C.c_uint32), ("normal_power", C.c_uint32), ("sigma_z", C.c_float), ("sigma_l", C.c_float)]
+
+
+class PathAov(C.Structure):   # vxrt_path_aov_t: device pointers, any of them None
+    _fields_ = [("noisy", C.c_void_p), ("direct", C.c_void_p), ("albedo", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p)]
+
+
+def _denoise_lib():
+    L = _lib()
+    L.vxrt_render_path_denoised.restype = C.c_int
+    L.vxrt_render_path_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
+                                            C.POINTER(PathParams), C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(PathAov), C.c_void_p,
+                                            C.c_void_p]
+    L.vxrt_denoise_scratch_bytes.restype = C.c_uint64
+    L.vxrt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    L.vxrt_denoise.restype = C.c_int
+    L.vxrt_denoise.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_uint64,
+                               C.c_void_p]
+    return L
+
+
+def render_path_denoised(accel, cam, width, height, y0, y1, params, spp, bounces, denoise, dst_ptr, seed=0, shadow=0, colors_ptr=None, aov=None,
+                         rays_ptr=None, stream=None):
+    """vxrt_render_path_denoised: render_path whose demodulated indirect term goes through `denoise.iterations` passes of the guided a-trous
+    filter (`denoise`: a DenoiseParams); `aov` (a PathAov of device pointers, optional) receives the guide buffers of the primary hit."""
+    L = _denoise_lib()
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(L.vxrt_render_path_denoised(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+                                      C.byref(denoise), dst_ptr, colors_ptr, None if aov is None else C.byref(aov), rays_ptr, stream),
+          "vxrt_render_path_denoised")
+
+
+def denoise_scratch_bytes(width, rows):
+    return int(_denoise_lib().vxrt_denoise_scratch_bytes(width, rows))
+
+
+def denoise(width, rows, signal_ptr, position_ptr, normal_ptr, denoise, out_ptr, scratch_ptr, scratch_bytes, stream=None):
+    """vxrt_denoise: the a-trous filter alone over a window of rows x width pixels (signal / out: 3 floats per pixel; position / normal: 4)."""
+    check(_denoise_lib().vxrt_denoise(width, rows, signal_ptr, position_ptr, normal_ptr, C.byref(denoise), out_ptr, scratch_ptr, scratch_bytes, stream),
+          "vxrt_denoise")
