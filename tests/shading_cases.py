@@ -1,4 +1,4 @@
-"""Randomised SHADING inputs for the closest-hit / miss shader (shade_terms, shade_eval, pack_rgb8 of csrc/rt_kernels.hip and their
+"""Randomised SHADING inputs for the closest-hit / miss shader (shade_terms, shade_eval of csrc/rt_shading.h, pack_rgb8 of csrc/rt_internal.h and their
 restatement in oracle/rt_oracle.c), shared by tests/test_shading_cpu.py and tests/test_gpu_shading_fuzz.py.  TEST INFRASTRUCTURE ONLY.
 
 geometry(seed)   the triangle soups and transforms of tests/test_gpu_fuzz.py (1-4 instances, rotations x non-uniform scales)

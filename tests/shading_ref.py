@@ -2,7 +2,7 @@
 the RGB8 pack (common.h:149-154), in the manner of tests/camera_ref.py.  TEST INFRASTRUCTURE ONLY.
 
 Written from the reference's shader text and the conversion rule of include/vortex_hip.h (vxrt_shade_rays), independently of
-oracle/rt_oracle.c and csrc/rt_kernels.hip: one fp32 operation per line, no einsum, no contraction (numpy float32 arithmetic rounds
+oracle/rt_oracle.c and csrc/rt_shading.h: one fp32 operation per line, no einsum, no contraction (numpy float32 arithmetic rounds
 every operation).  tests/test_shading_cpu.py holds it bit-equal to pyoracle.shade; a misreading that the kernel and rt_oracle.c
 shared would show there.  shade() also returns the intermediate values the liveness checks count."""
 import numpy as np

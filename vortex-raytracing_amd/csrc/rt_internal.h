@@ -1,9 +1,12 @@
 // Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
-// level-2 entry points), rt_accel.hip (acceleration-layout build, refit) and rt_denoise.hip (the a-trous filter of denoised path
-// frames) share.  The constants of the compact layout are in rt_types.h.
+// level-2 entry points), rt_accel.hip (acceleration-layout build, refit), rt_secondary.hip (the tails of mirror-bounce,
+// ambient-occlusion and path frames) and rt_denoise.hip (the a-trous filter of denoised path frames) share: the types, and the
+// few host functions one unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of
+// shading, which rt_kernels.hip and rt_secondary.hip share, is in rt_shading.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include <vector>
 #include "rt_types.h"
 #include "../../include/vortex_hip.h"
@@ -79,9 +82,10 @@ struct FrameCtx {
   bool ctl_dirty = false;      // a call failed after touching it: clear before the next use
   // mirror-bounce levels (allocated on first use; level 0 only holds `term`, one entry per pixel)
   struct Level {
-    float* rays = nullptr; HitRec* hits = nullptr; uint32_t* parent = nullptr; float4* term = nullptr; float* col = nullptr;
-    float* srays = nullptr; float* stmax = nullptr; HitRec* shits = nullptr;
-    uint64_t cap = 0; uint32_t n = 0;
+    float4* term = nullptr; uint64_t cap = 0;
+    float* rays = nullptr; HitRec* hits = nullptr; uint32_t* parent = nullptr; float* col = nullptr; uint64_t ray_cap = 0;
+    float* srays = nullptr; float* stmax = nullptr; HitRec* shits = nullptr; uint64_t shadow_cap = 0;   // (frames with the shadow extension)
+    uint32_t n = 0;
   };
   std::vector<Level> lv;
   uint32_t* bcount = nullptr;  // device: rays appended to the level being built
@@ -155,11 +159,11 @@ static inline bool ident_root_form(const vxrt_accel* a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// shared device arithmetic: the RGB8 pack of every frame (rt_kernels.hip, rt_denoise.hip)
+// shared device arithmetic: the RGB8 pack of every frame (rt_kernels.hip, rt_secondary.hip, rt_denoise.hip)
 // ---------------------------------------------------------------------------------------------
-// libstdc++ std::min (NaN behaviour is part of parity; std_max is in rt_kernels.hip)
+// libstdc++ std::min (NaN behaviour is part of parity; std_max is in rt_shading.h)
 __device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
-// int(f) as x86-64 converts it (the rule of include/vortex_hip.h, vxrt_shade_rays; f2u_x86 is in rt_kernels.hip)
+// int(f) as x86-64 converts it (the rule of include/vortex_hip.h, vxrt_shade_rays; f2u_x86 is in rt_shading.h)
 __device__ __forceinline__ uint32_t f2i_x86(float f) { return (f >= -0x1p31f && f < 0x1p31f) ? (uint32_t)(int)f : 0x80000000u; }
 __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // common.h:149-154
   const uint32_t ir = f2i_x86(std_min(r, 1.f) * 255);   // (shifts and sums of the int's bits, mod 2^32: what the 32-bit registers hold)
@@ -169,7 +173,7 @@ __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // c
 }
 
 // ---------------------------------------------------------------------------------------------
-// rt_denoise.hip: the launches of a denoised path frame's tail (render_path_tail in rt_kernels.hip calls them; all asynchronous on `s`)
+// rt_denoise.hip: the launches of a denoised path frame's tail (render_path_tail in rt_secondary.hip calls them; all asynchronous on `s`)
 // ---------------------------------------------------------------------------------------------
 // the checks of vxrt_denoise_params_t both entry points share
 bool dn_params_ok(const vxrt_denoise_params_t* dn);
@@ -181,3 +185,75 @@ int dn_launch_demodulate(hipStream_t s, uint32_t n, uint32_t W, uint32_t y0, con
 // dst / colors (full-frame addressing, rows from y0)
 int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn, float4* const sig[2], const float4* geo,
                           const float4* nrm, const float4* lit, const float4* alb, uint32_t* dst, float* colors);
+
+// ---------------------------------------------------------------------------------------------
+// rt_kernels.hip <-> rt_secondary.hip: a frame as an entry point asks for it, the per-frame control block, growing device buffers,
+// the ray-buffer launch the secondary tails trace with and the three tails render_common ends such a frame with
+// ---------------------------------------------------------------------------------------------
+#ifndef QUEUE_SHARDS
+#define QUEUE_SHARDS 8u     // one device-scope counter saturates near 90 dequeues/us
+#endif
+#define QUEUE_STRIDE 32u    // one 128-byte line per shard counter
+// per-frame control block: [0] deferral count (own 128-byte line), then the queue counters of the main
+// launch, of the EXACT launch over the deferred list and of the a-priori EXACT launch
+#define CTL_QUEUE_DWORDS (QUEUE_SHARDS * QUEUE_STRIDE)
+#define CTL_DWORDS (32u + 3u * CTL_QUEUE_DWORDS)
+
+// Which build of the kernels a frame runs; the value is their STATS template argument (see rt_persistent_kernel)
+enum class Counting { TIMED = 0, REFERENCE_ORDER = 1, TIMED_TRAVERSAL = 2 };
+
+// One frame, or one set of frames, as the vxrt_render* entry points ask for it.  Every field defaults to "absent": an entry point
+// sets the ones it means.
+struct RenderRequest {
+  uint32_t width = 0, height = 0, y0 = 0, y1 = 0;   // rows [y0, y1) of a width x height frame ...
+  uint32_t stride = 1;                              // ... of which every stride-th tile row (8 rows), starting with the one at y0
+  const vxrt_shade_params_t* params = nullptr;      // `batch` entries
+  uint32_t batch = 1;                               // frames in this set of launches
+  int shadow = 0;
+  uint32_t* dst = nullptr; uint64_t dst_frame_stride = 0;   // frame f goes to dst + f * dst_frame_stride
+  vxrt_hit_t* hits = nullptr; float* colors = nullptr;      // optional outputs, single frames
+  unsigned long long* counters = nullptr;           // [0] rays traced; the counting builds: all of them
+  uint32_t* unoccluded = nullptr;                   // ambient occlusion, optional
+  unsigned long long* wave_log = nullptr;           // diagnostic, TIMED_TRAVERSAL only
+  const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
+  const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
+  const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
+  const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
+  const vxrt_path_aov_t* aov = nullptr;
+  void* stream = nullptr;
+  Counting counting = Counting::TIMED;
+  bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set
+};
+#define VXRT_AO_MODE_DIFFUSE_BOUNCE 1u   // internal: vxrt_ao_params_t::reserved
+
+// What has to finish before a buffer that grows is freed.  Each caller passes its own rule, and the rules are correctness, not taste:
+// a context's buffers are only read by work on the caller's stream (STREAM), an accel's tables by frames in flight on any stream (DEVICE).
+enum class GrowSync { NONE, STREAM, DEVICE };
+struct DevBuf { void** ptr; size_t bytes_per_entry; };
+// Grow the device buffers that share the capacity *cap (in entries) to `need` entries.  Nothing happens when they hold that many; else
+// the wait `sync` names, every old buffer freed, every new one allocated (contents are not kept).  false: a HIP call failed -- the
+// buffers are then missing and *cap is 0, unless it was the wait that failed (nothing touched).
+template <class C>
+static bool grow_device(std::initializer_list<DevBuf> bufs, C* cap, uint64_t need, GrowSync sync, hipStream_t s) {
+  if (*cap >= need) return true;
+  if (sync == GrowSync::STREAM && hipStreamSynchronize(s) != hipSuccess) return false;
+  if (sync == GrowSync::DEVICE && hipDeviceSynchronize() != hipSuccess) return false;
+  for (const DevBuf& b : bufs) { (void)hipFree(*b.ptr); *b.ptr = nullptr; }
+  *cap = 0;
+  for (const DevBuf& b : bufs) if (hipMalloc(b.ptr, (size_t)need * b.bytes_per_entry) != hipSuccess) return false;
+  *cap = (C)need;
+  return true;
+}
+
+// internal mode of trace_on_ctx: any-hit rays whose hit records are only read as "blocked or not" (JOB_TRACE_UNORDERED)
+constexpr int MODE_ANY_UNORDERED = 0x100;
+// ray buffer -> hit records on frame context c (rt_kernels.hip)
+int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, const float* tmax, HitRec* hits, int mode, hipStream_t s,
+                 const uint32_t* n_dev = nullptr, unsigned long long* stats_counters = nullptr, const uint32_t* order = nullptr);
+
+// rt_secondary.hip: what replaces the plain shading pass of a frame with reflective instances / an ambient-occlusion frame / a path
+// frame (denoised or not).  utab / vtab: the tables the traversal used (a camera frame's: the head and the tables of its camera block).
+// Each zeroes the context's control block in its first launch.  0, or -1 when a HIP call failed.
+int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
+int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
+int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);

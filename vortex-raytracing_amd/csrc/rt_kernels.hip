@@ -15,19 +15,20 @@
 // The trail/short-stack/restart machinery of the simulator is replaced by one pass over a full
 // per-lane stack whose entries carry m = max(entry distance along the path); DESIGN.md s3 proves
 // this returns the same hit (index included) as the reference's accept-and-re-descend loop.
-// What is not timed lives elsewhere: the acceleration-layout build and the refit in rt_accel.hip, the two ray-compaction
-// experiments (VXRT_POOL) in rt_trace_experiments.inc; SceneDev, HitRec, ShadeParams, FrameCtx and vxrt_accel in rt_internal.h,
-// the constants of the compact layout in rt_types.h.
+// What is not timed lives elsewhere: the acceleration-layout build and the refit in rt_accel.hip; the tails of the frames that trace
+// secondary rays (mirror bounce, ambient occlusion, path frames) and their kernels in rt_secondary.hip, the a-trous filter in
+// rt_denoise.hip; the two ray-compaction experiments (VXRT_POOL) in rt_trace_experiments.inc.  The shading arithmetic the frame
+// kernels share with those tails (shade_terms, the camera rays, the sample rays) is in rt_shading.h; SceneDev, HitRec, ShadeParams,
+// FrameCtx, vxrt_accel, RenderRequest and the seam to the other units in rt_internal.h; the constants of the compact layout in
+// rt_types.h.
 // Host half (behind the kernels): an entry point describes its frame in a RenderRequest; render_common checks it, prepares the frame
 // context's resources, makes a LaunchPlan and launches -- no launch macros: the template arguments are picked by launch_traversal /
-// launch_trace and with_decode_and_depth.  Environment knobs are read once, into HostKnobs.
+// launch_trace and with_decode_and_depth.  This unit's environment knobs are read once, into HostKnobs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rt_internal.h"
 #include "pinhole.h"
-
-// libstdc++ std::min / std::max (rt_traversal.cpp:327-337 use them; NaN behaviour is part of parity; std_min is in rt_internal.h)
-__device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }
+#include "rt_shading.h"   // (up here for std_max, which the slab test below takes)
 
 // rt_traversal.cpp:318-339 with idir hoisted (1.0f/rd is recomputed per child there; same value).
 // EXACT selects the libstdc++ min/max forms; the fast form uses v_min/v_max, which differs only
@@ -205,228 +206,9 @@ struct Fetches { unsigned node = 0, inst = 0, tri = 0; };
 
 #define ITER_LIMIT (1u << 22)   // backstop; accepted trees are acyclic (children stored after parents)
 
-// ---------------------------------------------------------------------------------------------
-// shading (closest.cpp:57-127 / miss.cpp:9-14)
-// ---------------------------------------------------------------------------------------------
-// rtx_shading.h:7-8 and common.h:149-154 convert floats that C leaves undefined (NaN, a value outside the target type).  The rule
-// (include/vortex_hip.h, vxrt_shade_rays) is what x86-64 g++ makes of them, written as a range test so that neither
-// this file nor oracle/rt_oracle.c depends on an out-of-range cast:
-//   uint32_t(f) = cvttss2si r64, low half: the truncated value mod 2^32 for -2^63 <= f < 2^63, 0 for NaN and everything else
-//   int(f)      = cvttss2si r32: the truncated value for -2^31 <= f < 2^31, INT_MIN (0x80000000) for NaN and everything else
-// (f2i_x86 and pack_rgb8, which rt_denoise.hip packs with as well, are in rt_internal.h)
-__device__ __forceinline__ uint32_t f2u_x86(float f) { return (f >= -0x1p63f && f < 0x1p63f) ? (uint32_t)(long long)f : 0u; }
-
-// Occlusion ray of the shadow extension (no reference counterpart): from the hit point toward the
-// light, origin pushed 1e-3 along L like the reference's mirror bounce (closest.cpp:104), tmax = |L|.
-// I, L and dist are computed exactly as shade_eval computes them.
-__device__ __forceinline__ void shadow_ray(float lpx, float lpy, float lpz, float ox, float oy, float oz, float dx, float dy, float dz,
-                                           float hit_dist, float& sox, float& soy, float& soz, float& sdx, float& sdy, float& sdz, float& sdist) {
-  const float Ix = ox + dx * hit_dist, Iy = oy + dy * hit_dist, Iz = oz + dz * hit_dist;
-  float Lx = lpx - Ix, Ly = lpy - Iy, Lz = lpz - Iz;
-  const float dist = sqrtf(Lx * Lx + Ly * Ly + Lz * Lz);
-  const float il = 1.0f / dist;
-  Lx *= il; Ly *= il; Lz *= il;
-  sox = Ix + Lx * 0.001f; soy = Iy + Ly * 0.001f; soz = Iz + Lz * 0.001f;
-  sdx = Lx; sdy = Ly; sdz = Lz;
-  sdist = dist;
-}
-
-__device__ __forceinline__ void shadow_ray(const ShadeParams& p, float ox, float oy, float oz, float dx, float dy, float dz,
-                                           float hit_dist, float& sox, float& soy, float& soz, float& sdx, float& sdy, float& sdz, float& sdist) {
-  shadow_ray(p.lpos[0], p.lpos[1], p.lpos[2], ox, oy, oz, dx, dy, dz, hit_dist, sox, soy, soz, sdx, sdy, sdz, sdist);
-}
-
-// closest.cpp:57-90 for one hit: the non-reflected diffuse contribution `throughput * diffuse * (1 - reflectivity)`
-// with throughput = 1 (:87), the reflectivity (:84), the hit point I and the shading normal N.
-// occluded: result of the shadow extension (false = reference).
-template <bool STATS = false>
-__device__ void shade_terms(const SceneDev& sc, const ShadeParams& p, float ox, float oy, float oz,
-                            float dx, float dy, float dz, const HitRec& hit, bool occluded,
-                            float& r, float& g, float& b, float& refl_out,
-                            float& Ix_o, float& Iy_o, float& Iz_o, float& Nx_o, float& Ny_o, float& Nz_o,
-                            unsigned* textured = nullptr, float* albedo3 = nullptr) {
-  const uint32_t* bp = sc.blas + (size_t)hit.blasIdx * (RT_BLAS_STRIDE / 4);
-  const rt_triex_t te = sc.triEx[hit.triIdx];
-  const rt_material_t* mat = sc.mat + te.texId;
-  // I = orig + dir * dist (:61)
-  const float Ix = ox + dx * hit.dist, Iy = oy + dy * hit.dist, Iz = oz + dz * hit.dist;
-  // N = N1*bx + N2*by + N0*bz (:64)
-  float Nx = te.N1[0] * hit.bx + te.N2[0] * hit.by + te.N0[0] * hit.bz;
-  float Ny = te.N1[1] * hit.bx + te.N2[1] * hit.by + te.N0[1] * hit.bz;
-  float Nz = te.N1[2] * hit.bx + te.N2[2] * hit.by + te.N0[2] * hit.bz;
-  // transposed 3x3 of invTransform, TransformVector with w = 0 (:65-66, geometry.h:1141-1147,1280-1293)
-  const float m0 = __uint_as_float(bp[1]), m1 = __uint_as_float(bp[2]), m2 = __uint_as_float(bp[3]);
-  const float m4 = __uint_as_float(bp[5]), m5 = __uint_as_float(bp[6]), m6 = __uint_as_float(bp[7]);
-  const float m8 = __uint_as_float(bp[9]), m9 = __uint_as_float(bp[10]), m10 = __uint_as_float(bp[11]);
-  const float z0 = 0.0f * 0.0f;
-  float Tx = m0 * Nx + m4 * Ny + m8 * Nz + z0;
-  float Ty = m1 * Nx + m5 * Ny + m9 * Nz + z0;
-  float Tz = m2 * Nx + m6 * Ny + m10 * Nz + z0;
-  float inv = 1.0f / sqrtf(Tx * Tx + Ty * Ty + Tz * Tz);
-  Nx = Tx * inv; Ny = Ty * inv; Nz = Tz * inv;
-  // uv (:69)
-  const float u = te.uv1[0] * hit.bx + te.uv2[0] * hit.by + te.uv0[0] * hit.bz;
-  const float v = te.uv1[1] * hit.bx + te.uv2[1] * hit.by + te.uv0[1] * hit.bz;
-  float cr, cg, cb;
-  if (mat->diffuse_tex_id >= 0) {  // :72-77, texSample rtx_shading.h:5-18, RGB8toRGB32F common.h:156-162
-    if (STATS) *textured += 1;
-    const uint32_t tw = mat->tex_width, th = mat->tex_height;
-    uint32_t iu = f2u_x86(u * (float)tw), iv = f2u_x86(v * (float)th);
-    iu %= tw; iv %= th;
-    const uint32_t texel = ((const uint32_t*)(sc.tex + mat->tex_offset))[iu + iv * tw];
-    const float s = 1 / 256.0f;
-    cr = (float)(int)((texel >> 16) & 255) * s;
-    cg = (float)(int)((texel >> 8) & 255) * s;
-    cb = (float)(int)(texel & 255) * s;
-  } else {
-    cr = mat->diffuse[0]; cg = mat->diffuse[1]; cb = mat->diffuse[2];
-  }
-  // diffuseLighting (rtx_shading.h:55-67)
-  float Lx = p.lpos[0] - Ix, Ly = p.lpos[1] - Iy, Lz = p.lpos[2] - Iz;
-  const float dist = sqrtf(Lx * Lx + Ly * Ly + Lz * Lz);
-  const float il = 1.0f / dist;
-  Lx *= il; Ly *= il; Lz *= il;
-  const float att = 1.0f / (1.0f + dist * 0.1f);
-  float NdotL = std_max(0.0f, Nx * Lx + Ny * Ly + Nz * Lz);
-  if (occluded) NdotL = 0.0f;   // shadow extension: occluded -> no direct term
-  const float dr = cr * (p.amb[0] + att * p.lcol[0] * NdotL);
-  const float dg = cg * (p.amb[1] + att * p.lcol[1] * NdotL);
-  const float db = cb * (p.amb[2] + att * p.lcol[2] * NdotL);
-  const float refl = __uint_as_float(bp[38]);   // blas_node_t::reflectivity @152
-  const float thr = 1.0f;
-  r = 0.0f + thr * dr * (1 - refl);             // :87
-  g = 0.0f + thr * dg * (1 - refl);
-  b = 0.0f + thr * db * (1 - refl);
-  refl_out = refl;
-  Ix_o = Ix; Iy_o = Iy; Iz_o = Iz; Nx_o = Nx; Ny_o = Ny; Nz_o = Nz;
-  if (albedo3) { albedo3[0] = cr; albedo3[1] = cg; albedo3[2] = cb; }   // texColor (:72-77)
-}
-
-// closest.cpp:57-127 without a secondary ray (reflectivity <= 0 or bounce + 1 >= max_depth) / miss.cpp:9-14
-template <bool STATS = false>
-__device__ void shade_eval(const SceneDev& sc, const ShadeParams& p, float ox, float oy, float oz,
-                           float dx, float dy, float dz, const HitRec& hit, bool found, bool occluded,
-                           float& r, float& g, float& b, unsigned* textured = nullptr) {
-  if (!found) { r = p.bg[0]; g = p.bg[1]; b = p.bg[2]; return; }
-  float refl, Ix, Iy, Iz, Nx, Ny, Nz;
-  shade_terms<STATS>(sc, p, ox, oy, oz, dx, dy, dz, hit, occluded, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, textured);
-  float thr = 1.0f;
-  thr *= refl;                                  // :90
-  r = r + p.bg[0] * thr;                        // :123
-  g = g + p.bg[1] * thr;
-  b = b + p.bg[2] * thr;
-}
-
-// closest.cpp:96-99: the mirror ray leaving a hit.  R = normalize(dir - 2.0f * N * dot(N, dir)), origin I + R * 0.001f
-__device__ __forceinline__ void mirror_ray(float dx, float dy, float dz, float Ix, float Iy, float Iz, float Nx, float Ny, float Nz,
-                                           float* out6) {
-  const float nd = Nx * dx + Ny * dy + Nz * dz;
-  const float vx = dx - (2.0f * Nx) * nd, vy = dy - (2.0f * Ny) * nd, vz = dz - (2.0f * Nz) * nd;
-  const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
-  const float Rx = vx * inv, Ry = vy * inv, Rz = vz * inv;
-  out6[0] = Ix + Rx * 0.001f; out6[1] = Iy + Ry * 0.001f; out6[2] = Iz + Rz * 0.001f;
-  out6[3] = Rx; out6[4] = Ry; out6[5] = Rz;
-}
-
-// kernel.cpp:28-39.  u = (x*2.0 - W)/H and v = (y*2.0 - H)/H are evaluated in double and rounded to
-// f32 there; they depend on x (resp. y) only, so the host evaluates exactly that expression once per
-// column / row (IEEE double division is correctly rounded on both sides) and the kernels read the
-// two small tables instead of running an f64 divide per ray.
-__device__ __forceinline__ void generate_ray(float u, float v,
-                                             float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
-  // front=(1,0,0); right=cross(front,(0,1,0))=(0,0,1); up=cross(right,front)=(0,1,0)
-  const float rx = 0.0f * 0.0f - 0.0f * 1.0f, ry = 0.0f * 0.0f - 1.0f * 0.0f, rz = 1.0f * 1.0f - 0.0f * 0.0f;
-  const float ux = ry * 0.0f - rz * 0.0f, uy = rz * 1.0f - rx * 0.0f, uz = rx * 0.0f - ry * 1.0f;
-  const float FOV = 1.0f;
-  float vx = u * rx + v * ux + FOV * 1.0f;
-  float vy = u * ry + v * uy + FOV * 0.0f;
-  float vz = u * rz + v * uz + FOV * 0.0f;
-  const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
-  ox = 0.0f; oy = 100.0f; oz = 0.0f;
-  dx = vx * inv; dy = vy * inv; dz = vz * inv;
-}
-
-// Camera frames (JOB_CAM, vxrt_render_camera): the frame context's camera block, written on the stream by rt_camera_prep_kernel.  Its
-// head holds VXRT_MAX_BATCH cameras of CAM_HDR floats (pos, forward, right, up); behind it, frame f's x_vp[W] then y_vp[H] start at
-// CAM_TAB + f * (W + H) (see pinhole.h).  The kernels take the head as `utab` and the tables as `vtab`.
-#define CAM_HDR 12
-#define CAM_TAB (VXRT_MAX_BATCH * CAM_HDR)
-__device__ __forceinline__ void camera_ray(const float* c, const float* tab, uint32_t W, uint32_t x, uint32_t y,
-                                           float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
-  ox = c[0]; oy = c[1]; oz = c[2];
-  pinhole_dir(tab[x], tab[W + y], c, c + 3, c + 6, c + 9, dx, dy, dz);
-}
-// the primary ray of pixel (x, y) of frame `frame` (0 unless a batch): the fixed camera's tables, or the camera block
-template <bool CAM>
-__device__ __forceinline__ void frame_pixel_ray(const float* utab, const float* vtab, uint32_t W, uint32_t H, uint32_t frame, uint32_t x, uint32_t y,
-                                                float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
-  if constexpr (CAM) camera_ray(utab + frame * CAM_HDR, vtab + (size_t)frame * (W + H), W, x, y, ox, oy, oz, dx, dy, dz);
-  else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
-}
 // LDS copy of the camera block's head (camera traversal kernels only: the fixed-camera instantiations never reference it)
 template <int N>
 __device__ __forceinline__ float* cam_lds() { __shared__ float s[N]; return s; }
-
-__device__ __forceinline__ uint32_t wang_hash(uint32_t s) {   // common.h:129-135
-  s = (s ^ 61u) ^ (s >> 16);
-  s *= 9u; s = s ^ (s >> 4);
-  s *= 0x27d4eb2du;
-  s = s ^ (s >> 15);
-  return s;
-}
-__device__ __forceinline__ float random_float(uint32_t& s) {   // common.h:137-147
-  s ^= s << 13; s ^= s >> 17; s ^= s << 5;
-  return (float)s * 2.3283064365387e-10f;
-}
-
-// The occlusion / bounce ray of sample `smp` of pixel (x, y) leaving the hit point I with shading normal N (view direction vd), as
-// oracle/rt_oracle.c:orc_ao_ray defines it, operation by operation: o = I + N' * 1e-3, d = cosine-weighted about the normal N'
-// that faces the viewer (rejection-sampled disk, Duff et al. basis; only IEEE add / mul / div / sqrt).
-__device__ __forceinline__ void ao_sample_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t spp, uint32_t smp, uint32_t user_seed,
-                                              float Ix, float Iy, float Iz, float nx, float ny, float nz, float vdx, float vdy, float vdz, float* o6) {
-  uint32_t seed = wang_hash((x + y * W) * spp + smp + 1u + user_seed * 0x9E3779B9u);
-  if (seed == 0u) seed = 1u;
-  float u = 0.0f, v = 0.0f, r2 = 0.0f;
-  bool ok = false;
-  for (int k = 0; k < 8 && !ok; ++k) {
-    const float a = 2.0f * random_float(seed) - 1.0f;
-    const float b = 2.0f * random_float(seed) - 1.0f;
-    const float q = a * a + b * b;
-    if (q < 1.0f) { u = a; v = b; r2 = q; ok = true; }
-  }
-  const float z = sqrtf(1.0f - r2);
-  if (nx * vdx + ny * vdy + nz * vdz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
-  const float sign = nz >= 0.0f ? 1.0f : -1.0f;
-  const float a = -1.0f / (sign + nz);
-  const float b = nx * ny * a;
-  const float tx = 1.0f + sign * nx * nx * a, ty = sign * b, tz = -sign * nx;
-  const float bx = b, by = sign + ny * ny * a, bz = -ny;
-  o6[0] = Ix + nx * 0.001f; o6[1] = Iy + ny * 0.001f; o6[2] = Iz + nz * 0.001f;
-  o6[3] = tx * u + bx * v + nx * z;
-  o6[4] = ty * u + by * v + ny * z;
-  o6[5] = tz * u + bz * v + nz * z;
-}
-
-// Alpha test of a candidate (ALPHA instantiations; the rule is in DESIGN.md s2, "Alpha test"): true = the candidate on triangle triIdx with
-// barycentrics (bx, by, bz) is rejected -- its material has a threshold T > 0 and the texel shade_terms would sample there has a top byte
-// below T.  u, v, the conversions and the texel address are shade_terms', operation for operation.
-// What it loads, in this order: one byte of the per-triangle threshold table (an opaque triangle ends here); then the seven words uv0 .. texId
-// of the triangle's tri_ex_t (not its normals), the material's four texture fields (not its colours) and the texel.
-__device__ __forceinline__ bool alpha_rejects(const SceneDev& sc, const uint8_t* __restrict__ alpha_tri, uint32_t triIdx, float bx, float by, float bz) {
-  const uint32_t T = alpha_tri[triIdx];
-  if (T == 0u) return false;
-  const rt_triex_t* te = sc.triEx + triIdx;
-  const float u0 = te->uv0[0], v0 = te->uv0[1], u1 = te->uv1[0], v1 = te->uv1[1], u2 = te->uv2[0], v2 = te->uv2[1];
-  const rt_material_t* mat = sc.mat + te->texId;
-  const uint32_t tw = mat->tex_width, th = mat->tex_height;
-  const uint64_t off = mat->tex_offset;
-  const float u = u1 * bx + u2 * by + u0 * bz;
-  const float v = v1 * bx + v2 * by + v0 * bz;
-  uint32_t iu = f2u_x86(u * (float)tw), iv = f2u_x86(v * (float)th);
-  iu %= tw; iv %= th;
-  const uint32_t texel = ((const uint32_t*)(sc.tex + off))[iu + iv * tw];
-  return (texel >> 24) < T;
-}
 
 #ifndef RT_TRI_PREFETCH
 #define RT_TRI_PREFETCH 1
@@ -492,14 +274,7 @@ __device__ __forceinline__ bool alpha_rejects(const SceneDev& sc, const uint8_t*
 #define RT_STEAL_SPREAD 0     // order in which a wavefront visits the other shards once its home shard is handed out: +1, +2, ... (0) or bit-reversed distance (1:
                               // the helpers of a drained band spread over the remaining ones; measured -1.4 % serial, +-0 elsewhere: profiles/r04_m_steal_spread_ab.txt)
 #endif
-#ifndef QUEUE_SHARDS
-#define QUEUE_SHARDS 8u     // one device-scope counter saturates near 90 dequeues/us
-#endif
-#define QUEUE_STRIDE 32u    // one 128-byte line per shard counter
-// per-frame control block: [0] deferral count (own 128-byte line), then the queue counters of the main
-// launch, of the EXACT launch over the deferred list and of the a-priori EXACT launch
-#define CTL_QUEUE_DWORDS (QUEUE_SHARDS * QUEUE_STRIDE)
-#define CTL_DWORDS (32u + 3u * CTL_QUEUE_DWORDS)
+// (QUEUE_SHARDS and the layout of the per-frame control block: rt_internal.h)
 // Frames (camera tiles + their occlusion rays): 7 wavefronts per SIMD (72 VGPRs, 6 stack levels in LDS).  With frames traced in
 // batches -- many tiles per wavefront, so ramp and tail of a launch no longer decide -- occupancy pays: 7 / 8 wavefronts are +5.3 /
 // +5.6 % on the headline frame (one frame per launch: +-1 %, measured in round 2), 8 loses 3 % on serial frames, 7 gains 2 %
@@ -582,16 +357,7 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #define RT_MARK(name)
 #endif
 
-// Hit records of a frame window are kept TILE-MAJOR between the traversal and the shading pass: record of pixel (x, y) =
-// tile * 64 + lane of the 8x8 tile grid that starts at row y0, i.e. the job id of the traversal kernel.  A wavefront
-// therefore writes the 64 records of its tile as one contiguous, 128-byte aligned 1,536-byte block, once (the occlusion
-// result is folded into bit 31 of blasIdx before the record is written): no cache line is shared between wavefronts, so no
-// XCD writes a partial line back (round 1 wrote pixel-major records + an atomicOr per occluded pixel: 121 MB of HBM
-// writes per 1080p frame for 50 MB of records, profiles/r01_k_pmc.txt).
-// `lr` = local row of the window: rows are counted through the window's tile rows (8 each) in order.
-__device__ __forceinline__ size_t hit_index(uint32_t x, uint32_t lr, uint32_t tiles_x) {
-  return ((size_t)(lr >> 3) * tiles_x + (x >> 3)) * 64u + ((lr & 7u) << 3) + (x & 7u);
-}
+// (hit_index, rt_shading.h: hit records of a frame window are kept TILE-MAJOR between the traversal and the shading pass)
 // frame row of local row lr: the window's k-th tile row is frame rows y0 + k * row_step ... + 7 (row_step = 8 for a contiguous
 // window, 8 * stride for the interleaved tile rows of vxrt_render_interleaved)
 __device__ __forceinline__ uint32_t frame_row(uint32_t lr, uint32_t y0, uint32_t row_step) { return y0 + (lr >> 3) * row_step + (lr & 7u); }
@@ -1588,576 +1354,6 @@ __global__ __launch_bounds__(256) void rt_shade_rays_kernel(SceneDev sc, ShadePa
 }
 
 // ---------------------------------------------------------------------------------------------
-// Mirror bounce (closest.cpp:95-121) as a wavefront over depth levels.  The reference recurses inside
-// the closest-hit shader: C(ray) = term + (reflectivity > 0 && bounce + 1 < max_depth ? C(mirror ray)
-// : background) * reflectivity, C(miss) = background.  Here level k holds the rays of bounce k (level 0 =
-// the pixels); shading a level appends the next level's rays, and the colours are folded back from the
-// deepest level to the pixels in the reference's order of operations, so the result has the same bits.
-// Taken only when max_depth > 1 and some instance is reflective (the shipped scene builder has none).
-// ---------------------------------------------------------------------------------------------
-// Shade level `level`.  LEVEL0: entry = pixel of rows [y0,y1), hit record from the traversal (occlusion
-// in bit 31 of blasIdx); else entry i = ray rays[6i..] with hit hits[i] (occluded iff shits[i] hit).
-// Entries that bounce leave (term, reflectivity) in term[] and append a ray; the others are final.
-template <bool LEVEL0, bool CAM>
-__device__ __forceinline__ void shade_bounce_pass(SceneDev sc, ShadeParams p, uint32_t level, uint64_t n,
-    uint32_t W, uint32_t H, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
-    const HitRec* __restrict__ hb, const float* __restrict__ rays, const HitRec* __restrict__ shits,
-    float4* __restrict__ term, float* __restrict__ col, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
-    float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent,
-    uint32_t* __restrict__ ctl_reset) {
-  if (ctl_reset && blockIdx.x == 0)
-    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
-  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (t >= n) return;
-  size_t e = (size_t)t;
-  float ox, oy, oz, dx, dy, dz;
-  HitRec h;
-  bool occ;
-  if (LEVEL0) {
-    const uint32_t x = (uint32_t)(t % W), y = y0 + (uint32_t)(t / W);
-    e = (size_t)x + (size_t)y * W;
-    h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
-    occ = (h.blasIdx & 0x80000000u) != 0u;
-    if (hits_out) hits_out[e] = h;
-    h.blasIdx &= 0x7fffffffu;
-    frame_pixel_ray<CAM>(utab, vtab, W, H, 0u, x, y, ox, oy, oz, dx, dy, dz);
-  } else {
-    const float* rp = rays + e * 6;
-    ox = rp[0]; oy = rp[1]; oz = rp[2]; dx = rp[3]; dy = rp[4]; dz = rp[5];
-    h = hb[e];
-    occ = shits != nullptr && shits[e].dist != RT_LARGE_FLOAT;
-  }
-  float r, g, b;
-  bool final_ = true;
-  if (h.dist == RT_LARGE_FLOAT) {   // miss.cpp:9-14
-    r = p.bg[0]; g = p.bg[1]; b = p.bg[2];
-  } else {
-    float refl, Ix, Iy, Iz, Nx, Ny, Nz;
-    shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz);
-    if (refl > 0.0f && level + 1u < p.max_depth) {   // :95
-      final_ = false;
-      term[e] = make_float4(r, g, b, refl);
-      const uint32_t slot = atomicAdd(next_count, 1u);   // every level has room for one ray per entry of the level before
-      mirror_ray(dx, dy, dz, Ix, Iy, Iz, Nx, Ny, Nz, next_rays + (size_t)slot * 6);
-      next_parent[slot] = (uint32_t)e;
-    } else {
-      float thr = 1.0f;
-      thr *= refl;                    // :90
-      r = r + p.bg[0] * thr;          // :123
-      g = g + p.bg[1] * thr;
-      b = b + p.bg[2] * thr;
-    }
-  }
-  if (final_) {
-    if (LEVEL0) {
-      dst[e] = pack_rgb8(r, g, b);
-      if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
-    } else {
-      col[3 * e] = r; col[3 * e + 1] = g; col[3 * e + 2] = b;
-    }
-  }
-}
-template <bool LEVEL0>
-__global__ __launch_bounds__(256) void rt_shade_bounce_kernel(SceneDev sc, ShadeParams p, uint32_t level, uint64_t n,
-    uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
-    const HitRec* __restrict__ hb, const float* __restrict__ rays, const HitRec* __restrict__ shits,
-    float4* __restrict__ term, float* __restrict__ col, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
-    float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent,
-    uint32_t* __restrict__ ctl_reset) {
-  shade_bounce_pass<LEVEL0, false>(sc, p, level, n, W, 0u, y0, utab, vtab, hb, rays, shits, term, col, dst, hits_out, colors_out, next_count, next_rays,
-                                   next_parent, ctl_reset);
-}
-// level 0 of a camera frame's mirror bounce (the deeper levels hold ray buffers: rt_shade_bounce_kernel<false>)
-__global__ __launch_bounds__(256) void rt_shade_bounce_camera_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t H, uint32_t y0,
-    const float* __restrict__ cam, const HitRec* __restrict__ hb, float4* __restrict__ term, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
-    float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent, uint32_t* __restrict__ ctl_reset) {
-  shade_bounce_pass<true, true>(sc, p, 0u, n, W, H, y0, cam, cam + CAM_TAB, hb, nullptr, nullptr, term, nullptr, dst, hits_out, colors_out, next_count,
-                                next_rays, next_parent, ctl_reset);
-}
-
-// occlusion rays of a bounce level (shadow extension at every depth); a miss gets a ray nothing can hit
-__global__ __launch_bounds__(256) void rt_bounce_shadow_rays_kernel(ShadeParams p, uint32_t n, const float* __restrict__ rays,
-    const HitRec* __restrict__ hits, float* __restrict__ srays, float* __restrict__ stmax, unsigned long long* rays_traced) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  bool real = false;
-  if (i < n) {
-    const float* rp = rays + (size_t)i * 6;
-    float* sp = srays + (size_t)i * 6;
-    const float d = hits[i].dist;
-    if (d == RT_LARGE_FLOAT) {
-      sp[0] = 0.f; sp[1] = 0.f; sp[2] = 0.f; sp[3] = 1.f; sp[4] = 1.f; sp[5] = 1.f;
-      stmax[i] = -1.0f;
-    } else {
-      float sdist;
-      shadow_ray(p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], d, sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sdist);
-      stmax[i] = sdist;
-      real = true;
-    }
-  }
-  const unsigned long long m = __ballot(real);
-  if (rays_traced && (threadIdx.x & 63u) == 0u && m) atomicAdd(rays_traced, (unsigned long long)__popcll(m));
-}
-
-// fold level k into level k-1 (closest.cpp:117): C[parent] = term[parent] + C_k * (1 * reflectivity[parent])
-template <bool TO_PIXELS>
-__global__ __launch_bounds__(256) void rt_bounce_unwind_kernel(uint32_t n, const uint32_t* __restrict__ parent, const float* __restrict__ col_k,
-    const float4* __restrict__ term_prev, float* __restrict__ col_prev, uint32_t* __restrict__ dst, float* __restrict__ colors_out) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const size_t q = parent[i];
-  const float4 t = term_prev[q];
-  float thr = 1.0f;
-  thr *= t.w;
-  const float r = t.x + col_k[3 * (size_t)i] * thr, g = t.y + col_k[3 * (size_t)i + 1] * thr, b = t.z + col_k[3 * (size_t)i + 2] * thr;
-  if (TO_PIXELS) {
-    dst[q] = pack_rgb8(r, g, b);
-    if (colors_out) { colors_out[3 * q] = r; colors_out[3 * q + 1] = g; colors_out[3 * q + 2] = b; }
-  } else {
-    col_prev[3 * q] = r; col_prev[3 * q + 1] = g; col_prev[3 * q + 2] = b;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Ambient occlusion (extension, BASELINE config 5; recipe defined in oracle/rt_oracle.c:orc_ao_ray and
-// mirrored here operation by operation -- RNG of common.h:129-147, rejection-sampled disk, Duff basis:
-// only IEEE add/mul/div/sqrt, so host and device produce the same rays).
-// ---------------------------------------------------------------------------------------------
-// per pixel of rows [y0,y1): Lambert colour of the primary hit (else arm of closest.cpp), hit point and
-// shading normal for the occlusion rays; geo[t] = (I, hit?), nrm[t] = (N, 0), col[t] = (rgb, 0), cnt[t] = 0;
-// pixels with a hit are appended to list[] (count in hdr[0]; the order is arbitrary, nothing depends on it)
-// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
-#define AO_PREP_CHUNKS 4   // pixels per thread of rt_ao_prepare_kernel: one list-append atomic per 1,024 pixels
-template <bool CAM>
-__device__ __forceinline__ void ao_prepare_pass(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float4* __restrict__ alb /* optional: albedo of the hit */) {
-  if (ctl_reset && blockIdx.x == 0)
-    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
-  // The hit pixels are appended to one list.  One atomic per wavefront on the list's counter (32,400 for a 1080p frame, all on one
-  // address, ~10 ns apart) was 0.3 of the kernel's 0.37 ms: a workgroup now counts the hits of 1,024 pixels in LDS and appends once.
-  __shared__ uint32_t s_cnt[AO_PREP_CHUNKS][4];
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  bool hit_c[AO_PREP_CHUNKS];
-  uint32_t off_c[AO_PREP_CHUNKS];
-#pragma unroll
-  for (int c = 0; c < AO_PREP_CHUNKS; ++c) {
-    const uint64_t t = ((uint64_t)blockIdx.x * AO_PREP_CHUNKS + c) * 256u + threadIdx.x;
-    bool hit = false;
-    if (t < n) {
-      const uint32_t x = (uint32_t)(t % W), y = y0 + (uint32_t)(t / W);
-      HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
-      h.blasIdx &= 0x7fffffffu;
-      float ox, oy, oz, dx, dy, dz;
-      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
-      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
-      float r, g, b;
-      if (h.dist == RT_LARGE_FLOAT) {
-        r = p.bg[0]; g = p.bg[1]; b = p.bg[2];
-        geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        nrm[t] = make_float4(0.f, 0.f, 1.f, 0.f);
-      } else {
-        float refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
-        shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, false, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-        float thr = 1.0f;
-        thr *= refl;
-        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
-        geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
-        nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
-        if (alb) alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
-        hit = true;
-      }
-      col[t] = make_float4(r, g, b, 0.f);
-      cnt[t] = 0u;
-    }
-    const unsigned long long m = __ballot(hit);
-    hit_c[c] = hit;
-    off_c[c] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[c][wv] = (uint32_t)__popcll(m);
-  }
-  __syncthreads();
-  __shared__ uint32_t s_base;
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-    for (int c = 0; c < AO_PREP_CHUNKS; ++c) for (int w = 0; w < 4; ++w) { const uint32_t v = s_cnt[c][w]; s_cnt[c][w] = tot; tot += v; }
-    s_base = tot ? atomicAdd(hdr, tot) : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < AO_PREP_CHUNKS; ++c)
-    if (hit_c[c]) list[s_base + s_cnt[c][wv] + off_c[c]] = (uint32_t)(((uint64_t)blockIdx.x * AO_PREP_CHUNKS + c) * 256u + threadIdx.x);
-}
-__global__ __launch_bounds__(256) void rt_ao_prepare_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float4* __restrict__ alb) {
-  ao_prepare_pass<false>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, col, cnt, list, hdr, ctl_reset, alb);
-}
-// the same pass of a camera frame (vxrt_render_ao_camera): cam = the frame context's camera block, whose head every lane reads at the
-// same address -- scalar loads, the camera stays in SGPRs
-__global__ __launch_bounds__(256) void rt_ao_prepare_camera_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ cam, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
-  ao_prepare_pass<true>(sc, p, n, W, y0, cam, cam + CAM_TAB, hb, geo, nrm, col, cnt, list, hdr, ctl_reset, nullptr);
-}
-
-// samples [s0, s0 + ns) of every listed pixel: ray i = (pixel list[i / ns], sample s0 + i % ns); hdr[1] = number of rays
-template <bool CAM>
-__device__ __forceinline__ void ao_rays_pass(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
-    const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
-    uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
-  const uint64_t total = (uint64_t)hdr[0] * ns;
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i == 0) hdr[1] = (uint32_t)total;
-  if (i >= total || i >= cap) return;
-  const uint32_t t = list[i / ns], smp = s0 + (uint32_t)(i % ns);
-  float* o = rays + (size_t)i * 6;
-  const float4 gI = geo[t];
-  const uint32_t x = t % W, y = y0 + t / W;
-  float ox, oy, oz, vdx, vdy, vdz;
-  if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, vdx, vdy, vdz);
-  else generate_ray(utab[x], vtab[y], ox, oy, oz, vdx, vdy, vdz);
-  const float4 gN = nrm[t];
-  float r6[6];
-  ao_sample_ray(x, y, W, spp, smp, user_seed, gI.x, gI.y, gI.z, gN.x, gN.y, gN.z, vdx, vdy, vdz, r6);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[k] = r6[k];
-  tmax[i] = radius;
-}
-__global__ __launch_bounds__(256) void rt_ao_rays_kernel(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
-    const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
-    uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
-  ao_rays_pass<false>(cap, W, y0, utab, vtab, geo, nrm, list, hdr, spp, s0, ns, user_seed, radius, rays, tmax);
-}
-// (camera frames: see rt_ao_prepare_camera_kernel)
-__global__ __launch_bounds__(256) void rt_ao_rays_camera_kernel(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ cam,
-    const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
-    uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
-  ao_rays_pass<true>(cap, W, y0, cam, cam + CAM_TAB, geo, nrm, list, hdr, spp, s0, ns, user_seed, radius, rays, tmax);
-}
-
-__global__ __launch_bounds__(256) void rt_ao_accumulate_kernel(uint64_t cap, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
-    const HitRec* __restrict__ ohits, uint32_t* __restrict__ cnt) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  const bool live = i < hdr[1] && i < cap;
-  // the ns samples of a pixel sit next to each other: the lanes of a wavefront that belong to one pixel add up with a ballot and
-  // the first of them does the pixel's atomic (16 spp: 4 atomics per wavefront instead of up to 64)
-  const unsigned long long m = __ballot(live && ohits[live ? i : 0].dist == RT_LARGE_FLOAT);
-  if (!live) return;
-  const uint32_t lane = threadIdx.x & 63u, k = (uint32_t)(i % ns);
-  const uint32_t s0 = lane > k ? lane - k : 0u, e0 = min(63u, lane - k + ns - 1u);   // lanes of this pixel in this wavefront (lane - k may wrap: then s0 = 0)
-  const uint32_t e = lane >= k ? e0 : min(63u, lane + (ns - 1u - k));
-  if (lane == s0) {
-    const unsigned long long seg = (~0ull >> (63u - e)) & (~0ull << s0);
-    const uint32_t c = (uint32_t)__popcll(m & seg);
-    if (c) atomicAdd(cnt + list[i / ns], c);
-  }
-}
-
-__global__ __launch_bounds__(256) void rt_ao_final_kernel(uint64_t n, uint32_t W, uint32_t y0, const float4* __restrict__ geo, const float4* __restrict__ col,
-    const uint32_t* __restrict__ cnt, uint32_t spp, uint32_t* __restrict__ dst, float* __restrict__ colors_out, uint32_t* __restrict__ unoccluded,
-    unsigned long long* rays_traced) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  bool hit = false;
-  if (t < n) {
-    const uint32_t x = (uint32_t)(t % W), y = y0 + (uint32_t)(t / W);
-    const size_t e = (size_t)x + (size_t)y * W;
-    const float4 c = col[t];
-    float r = c.x, g = c.y, b = c.z;
-    uint32_t open = 0u;
-    if (geo[t].w != 0.f) {
-      hit = true;
-      open = cnt[t];
-      const float f = (float)open / (float)spp;
-      r *= f; g *= f; b *= f;
-    }
-    dst[e] = pack_rgb8(r, g, b);
-    if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
-    if (unoccluded) unoccluded[e] = open;
-  }
-  const unsigned long long m = __ballot(hit);
-  if (rays_traced && (threadIdx.x & 63u) == 0u && m) atomicAdd(rays_traced, (unsigned long long)__popcll(m) * spp);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Path frames (vxrt_render_path; the definition is in include/vortex_hip.h, the launch sequence in render_path_tail and DESIGN.md s2,
-// "Path frames").  The kernels around the ray-buffer launches: per-pixel state of the primary hit, per-path state that survives from
-// bounce to bounce, the scatter step and the accumulation over samples.  Every arithmetic step is an existing __device__ function
-// (shade_terms, ao_sample_ray, shadow_ray, pack_rgb8, camera_ray / generate_ray).
-// Path slot i of a batch of ns samples starting at s0 = (pixel list[i / ns], sample s0 + i % ns); a path's state stays in its slot,
-// and the rays of a depth are those of the slots still listed as live (ray q belongs to slot live[q]).
-// ---------------------------------------------------------------------------------------------
-// Append value[c] of every thread with flag[c] to list[] (its length in *counter; the order is arbitrary): the workgroup counts in LDS
-// and does one atomic (see ao_prepare_pass).  Every thread of the workgroup calls it.
-template <int C>
-__device__ __forceinline__ void wg_append(const bool (&flag)[C], const uint32_t (&value)[C], uint32_t* __restrict__ list, uint32_t* counter) {
-  __shared__ uint32_t s_cnt[C][4];
-  __shared__ uint32_t s_base;
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  uint32_t off[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const unsigned long long m = __ballot(flag[c]);
-    off[c] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[c][wv] = (uint32_t)__popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-    for (int c = 0; c < C; ++c) for (int w = 0; w < 4; ++w) { const uint32_t v = s_cnt[c][w]; s_cnt[c][w] = tot; tot += v; }
-    s_base = tot ? atomicAdd(counter, tot) : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-    if (flag[c]) list[s_base + s_cnt[c][wv] + off[c]] = value[c];
-}
-
-// per pixel t of rows [y0,y1): geo[t] = (I, hit?), nrm[t] = (N, 0), dir[t] = (direction of the primary ray, 0), lit[t] = (Lit of the
-// primary hit with the occlusion bit the shadow frame launch left in its record | background, 0), alb[t] = (Alb, 0); pixels with a hit
-// are appended to list[] (count in hdr[0])
-// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
-#define PATH_PREP_CHUNKS 4   // pixels per thread, as AO_PREP_CHUNKS
-template <bool CAM>
-__device__ __forceinline__ void path_prepare_pass(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
-  if (ctl_reset && blockIdx.x == 0)
-    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
-  bool hit_c[PATH_PREP_CHUNKS];
-  uint32_t t_c[PATH_PREP_CHUNKS];
-#pragma unroll
-  for (int c = 0; c < PATH_PREP_CHUNKS; ++c) {
-    const uint64_t t64 = ((uint64_t)blockIdx.x * PATH_PREP_CHUNKS + c) * 256u + threadIdx.x;
-    const uint32_t t = (uint32_t)t64;
-    bool hit = false;
-    if (t64 < n) {
-      const uint32_t x = t % W, y = y0 + t / W;
-      HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
-      const bool occ = (h.blasIdx & 0x80000000u) != 0u;
-      h.blasIdx &= 0x7fffffffu;
-      float ox, oy, oz, dx, dy, dz;
-      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
-      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
-      if (h.dist == RT_LARGE_FLOAT) {
-        geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        lit[t] = make_float4(p.bg[0], p.bg[1], p.bg[2], 0.f);
-      } else {
-        float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
-        shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-        float thr = 1.0f;
-        thr *= refl;
-        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
-        geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
-        nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
-        dir[t] = make_float4(dx, dy, dz, 0.f);
-        lit[t] = make_float4(r, g, b, 0.f);
-        alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
-        hit = true;
-      }
-    }
-    hit_c[c] = hit; t_c[c] = t;
-  }
-  wg_append<PATH_PREP_CHUNKS>(hit_c, t_c, list, hdr);
-}
-__global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
-  path_prepare_pass<false>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset);
-}
-// the same pass of a camera frame: cam = the frame context's camera block, whose head every lane reads at the same address (see
-// rt_ao_prepare_camera_kernel)
-__global__ __launch_bounds__(256) void rt_path_prepare_camera_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ cam, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
-  path_prepare_pass<true>(sc, p, n, W, y0, cam, cam + CAM_TAB, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset);
-}
-
-// start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
-__global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
-    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, uint32_t* __restrict__ live) {
-  const uint64_t want = (uint64_t)hdr[0] * ns;
-  const uint32_t total = want < cap ? (uint32_t)want : cap;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i == 0) hdr[1] = total;
-  if (i >= total) return;
-  const uint32_t t = list[i / ns];
-  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
-  live[i] = i;
-}
-
-// the bounce rays of one depth: ray q leaves the last vertex of slot live[q] (user seed = seed + depth); zeroes the next depth's count
-__global__ __launch_bounds__(256) void rt_path_bounce_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
-    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
-    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, unsigned long long* rays_traced) {
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  if (q == 0) {
-    *n_next = 0u;
-    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one)
-  }
-  if (q >= total) return;
-  const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
-  const uint32_t x = t % W, y = y0 + t / W;
-  const float4 I = pI[slot], N = pN[slot], D = pD[slot];
-  float r6[6];
-  ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
-  float* o = rays + (size_t)q * 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[k] = r6[k];
-}
-
-// the occlusion rays of one depth (light sampling): one per bounce ray that hit; a miss gets a ray nothing can hit, which is not
-// counted (see rt_bounce_shadow_rays_kernel).  One atomic per workgroup on the ray counter.
-__global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams p, uint32_t cap, const uint32_t* n_live, const float* __restrict__ rays,
-    const HitRec* __restrict__ hits, float* __restrict__ srays, float* __restrict__ stmax, unsigned long long* rays_traced) {
-  __shared__ uint32_t s_real;
-  if (threadIdx.x == 0) s_real = 0u;
-  __syncthreads();
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  bool real = false;
-  if (q < total) {
-    const float* rp = rays + (size_t)q * 6;
-    float* sp = srays + (size_t)q * 6;
-    const float d = hits[q].dist;
-    if (d == RT_LARGE_FLOAT) {
-      sp[0] = 0.f; sp[1] = 0.f; sp[2] = 0.f; sp[3] = 1.f; sp[4] = 1.f; sp[5] = 1.f;
-      stmax[q] = -1.0f;
-    } else {
-      float sdist;
-      shadow_ray(p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], d, sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sdist);
-      stmax[q] = sdist;
-      real = true;
-    }
-  }
-  const unsigned long long m = __ballot(real);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
-  __syncthreads();
-  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
-}
-
-// the scatter step of one depth.  Miss: Lc = Lc + thr * background, the path ends.  Hit: Lc = Lc + thr * Lit (occluded iff shits[q]
-// hit), then thr = thr * Alb and the hit becomes the slot's last vertex; with `next` the slot is appended to the next depth's live list.
-__global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
-    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next) {
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  bool go[1] = {false};
-  uint32_t val[1] = {0u};
-  if (q < total) {
-    const uint32_t slot = live[q];
-    const float* rp = rays + (size_t)q * 6;
-    HitRec h = hits[q];
-    h.blasIdx &= 0x7fffffffu;
-    float4 L = pL[slot];
-    const float4 T = pT[slot];
-    if (h.dist == RT_LARGE_FLOAT) {
-      L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
-    } else {
-      const bool occ = shits != nullptr && shits[q].dist != RT_LARGE_FLOAT;
-      float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
-      shade_terms<false>(sc, p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-      float thr = 1.0f;
-      thr *= refl;
-      r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
-      L.x = L.x + T.x * r; L.y = L.y + T.y * g; L.z = L.z + T.z * b;
-      if (next) {
-        pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
-        pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
-        pN[slot] = make_float4(Nx, Ny, Nz, 0.f);
-        pD[slot] = make_float4(rp[3], rp[4], rp[5], 0.f);
-        go[0] = true; val[0] = slot;
-      }
-    }
-    pL[slot] = L;
-  }
-  if (next) wg_append<1>(go, val, next, n_next);   // (uniform over the launch)
-}
-
-// after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
-// starts it); one thread per listed pixel
-__global__ __launch_bounds__(256) void rt_path_accumulate_kernel(uint32_t n, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
-    uint32_t first, const float4* __restrict__ pL, float4* __restrict__ acc) {
-  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= min(hdr[0], n)) return;
-  const uint32_t t = list[j];
-  const float4* L = pL + (size_t)j * ns;
-  float4 a = first ? L[0] : acc[t];
-  for (uint32_t s = first ? 1u : 0u; s < ns; ++s) { const float4 c = L[s]; a.x = a.x + c.x; a.y = a.y + c.y; a.z = a.z + c.z; }
-  acc[t] = a;
-}
-
-// colour = acc / spp, pack, write.  flat (bounces = 0): every sample's Lc is the pixel's Lit, summed here the same way.
-__global__ __launch_bounds__(256) void rt_path_final_kernel(uint32_t n, uint32_t W, uint32_t y0, const float4* __restrict__ geo, const float4* __restrict__ lit,
-    const float4* __restrict__ acc, uint32_t spp, uint32_t flat, uint32_t* __restrict__ dst, float* __restrict__ colors_out) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= n) return;
-  const uint32_t x = t % W, y = y0 + t / W;
-  const size_t e = (size_t)x + (size_t)y * W;
-  const float4 c = lit[t];
-  float r = c.x, g = c.y, b = c.z;   // (a miss: the background)
-  if (geo[t].w != 0.f) {
-    if (flat) { for (uint32_t s = 1; s < spp; ++s) { r = r + c.x; g = g + c.y; b = b + c.z; } }
-    else { const float4 a = acc[t]; r = a.x; g = a.y; b = a.z; }
-    const float f = (float)spp;
-    r = r / f; g = g / f; b = b / f;
-  }
-  dst[e] = pack_rgb8(r, g, b);
-  if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Secondary rays re-sorted before they are traced (north_star: "ray packets re-sorted ... to tame divergence").
-// The rays of a bounce / AO pass leave the compaction in pixel order with directions spread over a hemisphere: a wavefront of
-// 64 consecutive rays shares origins but not directions.  Counting sort by key = direction octant x origin cell (the 16x16-pixel
-// cell of the ray's pixel: hit points of neighbouring pixels are neighbours in space), so that 64 consecutive queue positions
-// hold rays that start in one small region AND point into the same octant.  Only the ORDER in which rays are traced changes:
-// the kernel reads ray order[q] and writes hit record order[q], so every result is bit-identical (tests compare them all).
-// ---------------------------------------------------------------------------------------------
-#define BIN_CELL_SHIFT 4u   // 16 x 16 pixels
-__global__ __launch_bounds__(256) void rt_bin_count_kernel(uint64_t cap, const uint32_t* __restrict__ hdr, const float* __restrict__ rays,
-    const uint32_t* __restrict__ list, uint32_t ns, uint32_t W, uint32_t cells_x, uint32_t n_cells, uint32_t* __restrict__ hist, uint32_t* __restrict__ keys) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= hdr[1] || i >= cap) return;
-  const uint32_t t = list[i / ns];
-  const uint32_t cell = ((t / W) >> BIN_CELL_SHIFT) * cells_x + ((t % W) >> BIN_CELL_SHIFT);
-  const float* r = rays + i * 6;
-  const uint32_t oct = (__float_as_uint(r[3]) >> 31) | ((__float_as_uint(r[4]) >> 31) << 1) | ((__float_as_uint(r[5]) >> 31) << 2);
-  const uint32_t key = oct * n_cells + cell;
-  keys[i] = key;
-  atomicAdd(&hist[key], 1u);
-}
-// exclusive scan of hist[0..n) in place, one workgroup of 1024 threads, `per` consecutive counters per thread
-__global__ __launch_bounds__(1024) void rt_bin_scan_kernel(uint32_t* __restrict__ hist, uint32_t n, uint32_t per) {
-  __shared__ uint32_t wsum[16];
-  const uint32_t lo = threadIdx.x * per, hi = min(lo + per, n);
-  uint32_t sum = 0;
-  for (uint32_t k = lo; k < hi; ++k) sum += hist[k];
-  uint32_t inc = sum;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
-  if (lane == 63u) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = inc - sum;
-  for (uint32_t w = 0; w < wave; ++w) base += wsum[w];
-  for (uint32_t k = lo; k < hi; ++k) { const uint32_t v = hist[k]; hist[k] = base; base += v; }
-}
-__global__ __launch_bounds__(256) void rt_bin_scatter_kernel(uint64_t cap, const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ keys,
-                                                            uint32_t* __restrict__ hist, uint32_t* __restrict__ order) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= hdr[1] || i >= cap) return;
-  order[atomicAdd(&hist[keys[i]], 1u)] = (uint32_t)i;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Reference-quirks traversal (opt-in; vxrt_trace_reference_quirks).  The kernels above implement the CANONICAL algorithm (DESIGN.md
 // s3), which returns what the reference's RTU returns wherever the reference addresses its own data.  The RTU does not always:
 // children of a TLAS internal node that is popped from the short stack are addressed relative to the LAST BLAS's base_ptr
@@ -2386,8 +1582,6 @@ __global__ __launch_bounds__(256) void wire_unpack_kernel(const uint32_t* __rest
   *(uint4*)(frames + (size_t)f * frame_stride + ((size_t)(j * world + r) * 8u + y) * (W4 * 4u) + (size_t)xq * 4u) = p;
 }
 
-__global__ void add_counter_kernel(unsigned long long* c, unsigned long long v) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(c, v); }
-
 // ---------------------------------------------------------------------------------------------
 // host entry points (C ABI, include/vortex_hip.h level 2)
 // ---------------------------------------------------------------------------------------------
@@ -2416,24 +1610,19 @@ static uint32_t* status_word() {
 }
 
 #define LPT_MIN_TILES 20000u
-// Paths per batch of a path frame (VXRT_PATH_BATCH).  A path costs 136 bytes of frame-context storage -- 80 of state (I, N, dir, Lc, thr:
-// five float4), 24 + 24 of bounce ray and hit record, 2 x 4 of live-list entries -- and 52 more with light sampling (occlusion ray, tmax,
-// hit record): 4 Mi paths are 0.53 / 0.73 GiB per frame context, and at 1920x1080 two samples per batch, i.e. ray-buffer launches of up to
-// 4 M rays for a machine that holds 0.4 M lanes of the traversal kernel -- launch ramps and tails stay a small part of each.
-#define PATH_BATCH_PATHS (4ull << 20)
 #define LPT_BATCH_MAX_TILES 100000u
 #ifndef EXACT_GRID
 #define EXACT_GRID 128   // workgroups of the EXACT launch (it sees a fraction of a percent of the rays)
 #endif
 
 // Measurement knobs of the render and trace path (docs/KNOBS.md), read from the environment once per process: on the first call
-// that asks for one.  Each keeps the parsing it always had (atoi, atoll, or "first character is 0").
+// that asks for one.  Each keeps the parsing it always had (atoi, atoll, or "first character is 0").  (The two of the secondary
+// tails, VXRT_PATH_BATCH and VXRT_SORT_SECONDARY, are read the same way in rt_secondary.hip.)
 struct HostKnobs {
   uint32_t shard_rot, lpt_batch_max;
   bool lpt, lpt_batch;                  // on unless the value begins with '0'
   bool unordered_any_off, debug;        // VXRT_UNORDERED_ANY is 0; VXRT_DEBUG is set at all
   int lpt_batch_alone, side_reserve, packed, packed_batch, grid_div, pool, wgs_per_cu;   // side_reserve, packed: -1 = unset
-  uint64_t path_batch;                  // paths per batch of a path frame (see render_path_tail)
 };
 static const HostKnobs& host_knobs() {
   static const HostKnobs knobs = [] {
@@ -2453,7 +1642,6 @@ static const HostKnobs& host_knobs() {
     { const char* e = getenv("VXRT_UNORDERED_ANY"); k.unordered_any_off = e && atoi(e) == 0; }
     k.wgs_per_cu = num("VXRT_WGS_PER_CU", 0);
     k.debug = getenv("VXRT_DEBUG") != nullptr;
-    { const char* e = getenv("VXRT_PATH_BATCH"); const long long v = e ? atoll(e) : 0; k.path_batch = v > 0 ? (uint64_t)v : PATH_BATCH_PATHS; }
     return k;
   }();
   return knobs;
@@ -2560,25 +1748,6 @@ extern "C" int vxrt_internal_lpt_sort(const uint32_t* cost, uint32_t* order, uin
 
 #include "rt_trace_experiments.inc"   // rt_pool_trace_kernel, rt_pair_trace_kernel, trace_experiment (VXRT_POOL=1|2)
 
-// What has to finish before a buffer that grows is freed.  Each caller passes its own rule, and the rules are correctness, not taste:
-// a context's buffers are only read by work on the caller's stream (STREAM), an accel's tables by frames in flight on any stream (DEVICE).
-enum class GrowSync { NONE, STREAM, DEVICE };
-struct DevBuf { void** ptr; size_t bytes_per_entry; };
-// Grow the device buffers that share the capacity *cap (in entries) to `need` entries.  Nothing happens when they hold that many; else
-// the wait `sync` names, every old buffer freed, every new one allocated (contents are not kept).  false: a HIP call failed -- the
-// buffers are then missing and *cap is 0, unless it was the wait that failed (nothing touched).
-template <class C>
-static bool grow_device(std::initializer_list<DevBuf> bufs, C* cap, uint64_t need, GrowSync sync, hipStream_t s) {
-  if (*cap >= need) return true;
-  if (sync == GrowSync::STREAM && hipStreamSynchronize(s) != hipSuccess) return false;
-  if (sync == GrowSync::DEVICE && hipDeviceSynchronize() != hipSuccess) return false;
-  for (const DevBuf& b : bufs) { (void)hipFree(*b.ptr); *b.ptr = nullptr; }
-  *cap = 0;
-  for (const DevBuf& b : bufs) if (hipMalloc(b.ptr, (size_t)need * b.bytes_per_entry) != hipSuccess) return false;
-  *cap = (C)need;
-  return true;
-}
-
 static ShadeParams shade_params(const vxrt_shade_params_t& in) {
   ShadeParams p;
   for (int i = 0; i < 3; ++i) {
@@ -2617,12 +1786,10 @@ static void launch_trace(const vxrt_accel* a, const ShadeParams& p, const Persis
   });
 }
 
-// internal mode of trace_on_ctx: any-hit rays whose hit records are only read as "blocked or not" (JOB_TRACE_UNORDERED)
-constexpr int MODE_ANY_UNORDERED = 0x100;
-// ray buffer -> hit records on frame context c (the body of vxrt_trace; also the bounce levels of vxrt_render)
-static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, const float* tmax,
-                        HitRec* hits, int mode, hipStream_t s, const uint32_t* n_dev = nullptr,
-                        unsigned long long* stats_counters = nullptr, const uint32_t* order = nullptr) {
+// ray buffer -> hit records on frame context c (the body of vxrt_trace; also the ray buffers of the secondary tails: declared in
+// rt_internal.h, with its default arguments and MODE_ANY_UNORDERED)
+int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, const float* tmax, HitRec* hits, int mode, hipStream_t s,
+                 const uint32_t* n_dev, unsigned long long* stats_counters, const uint32_t* order) {
   uint32_t* st = status_word();
   if (!st) return -1;
   // a non-zero alpha table: the alpha-tested launches, timed build only (callers that cannot honour the table have refused already)
@@ -2662,281 +1829,6 @@ static int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_
   else if (stats_counters) launch_trace<JOB_TRACE, 1>(a, p, A, X, n, s);
   else if (unordered && !host_knobs().unordered_any_off) launch_trace<JOB_TRACE_UNORDERED, 0>(a, p, A, X, n, s);
   else launch_trace<JOB_TRACE, 0>(a, p, A, X, n, s);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// (a buffer that is missing is allocated whatever the capacity its level or pass shares says)
-static bool grow_buf(void** ptr, uint64_t have, uint64_t need, size_t bytes_per_entry) {
-  uint64_t cap = *ptr ? have : 0;
-  return grow_device({{ptr, bytes_per_entry}}, &cap, need, GrowSync::NONE, nullptr);
-}
-
-static bool level_reserve(FrameCtx::Level& l, uint64_t n, bool shadow, bool only_term) {
-  if (l.cap >= n && l.term && (only_term || l.rays) && (!shadow || only_term || l.srays)) return true;
-  const uint64_t have = l.cap;
-  bool ok = grow_buf((void**)&l.term, have, n, 16);
-  if (!only_term) {
-    ok = ok && grow_buf((void**)&l.rays, have, n, 24) && grow_buf((void**)&l.hits, have, n, sizeof(HitRec)) &&
-         grow_buf((void**)&l.parent, have, n, 4) && grow_buf((void**)&l.col, have, n, 12);
-    if (shadow) ok = ok && grow_buf((void**)&l.srays, l.srays ? have : 0, n, 24) && grow_buf((void**)&l.stmax, l.stmax ? have : 0, n, 4) &&
-                     grow_buf((void**)&l.shits, l.shits ? have : 0, n, sizeof(HitRec));
-  }
-  if (ok && l.cap < n) l.cap = n;
-  return ok;
-}
-
-// Which build of the kernels a frame runs; the value is their STATS template argument (see rt_persistent_kernel)
-enum class Counting { TIMED = 0, REFERENCE_ORDER = 1, TIMED_TRAVERSAL = 2 };
-
-// One frame, or one set of frames, as the vxrt_render* entry points ask for it.  Every field defaults to "absent": an entry point
-// sets the ones it means.
-struct RenderRequest {
-  uint32_t width = 0, height = 0, y0 = 0, y1 = 0;   // rows [y0, y1) of a width x height frame ...
-  uint32_t stride = 1;                              // ... of which every stride-th tile row (8 rows), starting with the one at y0
-  const vxrt_shade_params_t* params = nullptr;      // `batch` entries
-  uint32_t batch = 1;                               // frames in this set of launches
-  int shadow = 0;
-  uint32_t* dst = nullptr; uint64_t dst_frame_stride = 0;   // frame f goes to dst + f * dst_frame_stride
-  vxrt_hit_t* hits = nullptr; float* colors = nullptr;      // optional outputs, single frames
-  unsigned long long* counters = nullptr;           // [0] rays traced; the counting builds: all of them
-  uint32_t* unoccluded = nullptr;                   // ambient occlusion, optional
-  unsigned long long* wave_log = nullptr;           // diagnostic, TIMED_TRAVERSAL only
-  const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
-  const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
-  const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
-  const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
-  const vxrt_path_aov_t* aov = nullptr;
-  void* stream = nullptr;
-  Counting counting = Counting::TIMED;
-  bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set
-};
-
-// Tail of a frame with reflective instances (replaces the plain shading pass): shade level 0, then per
-// bounce level trace -> (occlusion rays ->) shade, then fold the colours back.  The level sizes come back
-// to the host between levels, so this path synchronises the stream (it is not the benchmarked one).
-// (utab / vtab: the tables the traversal used; a camera frame's utab is its camera block)
-static int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
-  const SceneDev& sc = a->dev;
-  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
-  const bool shadow = r.shadow != 0;
-  uint32_t* dst = r.dst; float* colors = r.colors;
-  unsigned long long* rays_traced = r.counters;
-  hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t npix = (uint64_t)width * (y1 - y0);          // entries of level 0 (addressed by pixel index)
-  const uint64_t pix_span = (uint64_t)width * y1;              // term[] of level 0 is indexed by x + y*W
-  if (npix > 0x7fffffffull) return -1;
-  if (!c->bcount && hipMalloc((void**)&c->bcount, sizeof(uint32_t)) != hipSuccess) return -1;
-  if (c->lv.size() < 2) c->lv.resize(2);
-  if (!level_reserve(c->lv[0], pix_span, false, true)) return -1;
-  if (!level_reserve(c->lv[1], npix, shadow, false)) return -1;
-  dim3 block(256);
-  if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
-  if (r.cams) hipLaunchKernelGGL(rt_shade_bounce_camera_kernel, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, npix, width, r.height, y0, utab,
-                                 (const HitRec*)c->hitbuf, c->lv[0].term, dst, (HitRec*)r.hits, colors, c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
-  else hipLaunchKernelGGL(rt_shade_bounce_kernel<true>, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, 0u, npix, width, y0, utab, vtab,
-                          (const HitRec*)c->hitbuf, (const float*)nullptr, (const HitRec*)nullptr, c->lv[0].term, (float*)nullptr, dst, (HitRec*)r.hits, colors,
-                          c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
-  if (hipGetLastError() != hipSuccess) return -1;
-  c->ctl_dirty = false;
-  uint32_t depth = 0;   // deepest level that holds rays
-  for (uint32_t k = 1; k < p.max_depth; ++k) {
-    uint32_t n = 0;
-    if (hipMemcpyAsync(&n, c->bcount, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    if (n == 0) break;
-    FrameCtx::Level& L = c->lv[k];
-    L.n = n;
-    depth = k;
-    if (rays_traced) hipLaunchKernelGGL(add_counter_kernel, dim3(1), dim3(64), 0, s, rays_traced, (unsigned long long)n);
-    if (trace_on_ctx(a, c, L.rays, n, nullptr, L.hits, VXRT_MODE_CLOSEST, s) != 0) return -1;
-    const dim3 grid((n + 255u) / 256u);
-    if (shadow) {
-      hipLaunchKernelGGL(rt_bounce_shadow_rays_kernel, grid, block, 0, s, p, n, (const float*)L.rays, (const HitRec*)L.hits, L.srays, L.stmax, rays_traced);
-      if (trace_on_ctx(a, c, L.srays, n, L.stmax, L.shits, MODE_ANY_UNORDERED, s) != 0) return -1;
-    }
-    if (c->lv.size() < (size_t)k + 2) c->lv.resize((size_t)k + 2);
-    FrameCtx::Level& Nx = c->lv[k + 1];
-    const bool more = k + 1 < p.max_depth;
-    if (more && !level_reserve(Nx, n, shadow, false)) return -1;
-    FrameCtx::Level& Lk = c->lv[k];   // (resize may have moved the vector)
-    if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
-    hipLaunchKernelGGL(rt_shade_bounce_kernel<false>, grid, block, 0, s, sc, p, k, (uint64_t)n, width, y0, utab, vtab,
-                       (const HitRec*)Lk.hits, (const float*)Lk.rays, shadow ? (const HitRec*)Lk.shits : (const HitRec*)nullptr, Lk.term, Lk.col,
-                       (uint32_t*)nullptr, (HitRec*)nullptr, (float*)nullptr, c->bcount, more ? Nx.rays : (float*)nullptr, more ? Nx.parent : (uint32_t*)nullptr,
-                       (uint32_t*)nullptr);
-    if (hipGetLastError() != hipSuccess) return -1;
-    if (!more) break;
-  }
-  for (uint32_t k = depth; k >= 1; --k) {
-    FrameCtx::Level& L = c->lv[k];
-    const dim3 grid((L.n + 255u) / 256u);
-    if (k == 1) hipLaunchKernelGGL(rt_bounce_unwind_kernel<true>, grid, block, 0, s, L.n, (const uint32_t*)L.parent, (const float*)L.col, (const float4*)c->lv[0].term, (float*)nullptr, dst, colors);
-    else        hipLaunchKernelGGL(rt_bounce_unwind_kernel<false>, grid, block, 0, s, L.n, (const uint32_t*)L.parent, (const float*)L.col, (const float4*)c->lv[k - 1].term, c->lv[k - 1].col, (uint32_t*)nullptr, (float*)nullptr);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// Tail of an ambient-occlusion frame (replaces the plain shading pass): the pixels with a hit are listed on
-// the device, their occlusion rays are generated in batches of whole samples (<= AO_BATCH_RAYS rays) and each
-// batch is one any-hit launch whose job count stays in device memory.  No host synchronisation.
-#define AO_BATCH_RAYS (32ull << 20)
-#define VXRT_AO_MODE_DIFFUSE_BOUNCE 1u   // internal: vxrt_ao_params_t::reserved
-static int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
-  const SceneDev& sc = a->dev;
-  const vxrt_ao_params_t* ao = r.ao;
-  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
-  hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (ao->reserved == VXRT_AO_MODE_DIFFUSE_BOUNCE) return -1;    // (the diffuse-bounce frame is JOB_RENDER_GI: it has no tail)
-  if (n > 0x7fffffffull || ao->spp == 0) return -1;
-  uint32_t ns = (uint32_t)std::min<uint64_t>(ao->spp, std::max<uint64_t>(1, AO_BATCH_RAYS / n));   // samples per batch
-  const uint64_t ray_cap = n * ns;
-  if (ray_cap > 0x7fffffffull) return -1;
-  if (c->ao_cap < n || c->ao_ray_cap < ray_cap) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    const uint64_t have = c->ao_cap, rhave = c->ao_ray_cap;
-    bool ok = grow_buf((void**)&c->ao_geo, have, n, 16) && grow_buf((void**)&c->ao_nrm, have, n, 16) && grow_buf((void**)&c->ao_col, have, n, 16) &&
-              grow_buf((void**)&c->ao_cnt, have, n, 4) && grow_buf((void**)&c->ao_list, have, n, 4) && grow_buf((void**)&c->ao_hdr, c->ao_hdr ? 1 : 0, 1, 8) &&
-              grow_buf((void**)&c->ao_rays, rhave, ray_cap, 24) && grow_buf((void**)&c->ao_tmax, rhave, ray_cap, 4) &&
-              grow_buf((void**)&c->ao_hits, rhave, ray_cap, sizeof(HitRec));
-    if (!ok) return -1;
-    c->ao_cap = std::max(have, n); c->ao_ray_cap = std::max(rhave, ray_cap);
-  }
-  const dim3 block(256), grid((uint32_t)((n + 255) / 256)), rgrid((uint32_t)((ray_cap + 255) / 256));
-  // VXRT_SORT_SECONDARY=1: trace the secondary rays in (direction octant, origin cell) order instead of generation order.  OFF by
-  // default: measured SLOWER on both passes that use it (diffuse bounce 1.53 -> 1.95 ms, 10M-triangle hairball AO 9.2 -> 16.6 ms,
-  // profiles/r02_f_secondary_sort.txt).  The traversal is bound by per-lane VALU work, which coherence does not reduce, and the
-  // generation order already puts the 16 samples of one pixel (AO) / 64 neighbouring pixels (bounce) side by side.
-  static const bool sort_on = [] { const char* e = getenv("VXRT_SORT_SECONDARY"); return e && e[0] == '1'; }();
-  const uint32_t cells_x = (width + (1u << BIN_CELL_SHIFT) - 1) >> BIN_CELL_SHIFT, cells_y = (y1 - y0 + (1u << BIN_CELL_SHIFT) - 1) >> BIN_CELL_SHIFT;
-  const uint32_t n_cells = cells_x * cells_y, n_bins = 8u * n_cells;
-  if (sort_on && (c->bin_cap < n_bins || c->bin_ray_cap < ray_cap)) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    bool ok = grow_buf((void**)&c->bin_hist, c->bin_cap, n_bins, 4) && grow_buf((void**)&c->bin_keys, c->bin_ray_cap, ray_cap, 4) &&
-              grow_buf((void**)&c->bin_order, c->bin_ray_cap, ray_cap, 4);
-    if (!ok) return -1;
-    c->bin_cap = std::max<uint64_t>(c->bin_cap, n_bins); c->bin_ray_cap = std::max(c->bin_ray_cap, ray_cap);
-  }
-  auto bin_rays = [&](uint32_t ns_batch) -> const uint32_t* {   // ao_rays of the current batch -> bin_order
-    if (!sort_on) return nullptr;
-    if (hipMemsetAsync(c->bin_hist, 0, (size_t)n_bins * 4, s) != hipSuccess) return nullptr;
-    hipLaunchKernelGGL(rt_bin_count_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_hdr, (const float*)c->ao_rays, (const uint32_t*)c->ao_list, ns_batch,
-                       width, cells_x, n_cells, c->bin_hist, c->bin_keys);
-    hipLaunchKernelGGL(rt_bin_scan_kernel, dim3(1), dim3(1024), 0, s, c->bin_hist, n_bins, (n_bins + 1023u) / 1024u);
-    hipLaunchKernelGGL(rt_bin_scatter_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_hdr, (const uint32_t*)c->bin_keys, c->bin_hist, c->bin_order);
-    return c->bin_order;
-  };
-  if (hipMemsetAsync(c->ao_hdr, 0, 8, s) != hipSuccess) return -1;
-  const dim3 pgrid((uint32_t)((n + 256u * AO_PREP_CHUNKS - 1u) / (256u * AO_PREP_CHUNKS)));
-  // (a camera frame's utab is its camera block: the camera forms of the two passes that derive the primary ray again)
-  if (r.cams) hipLaunchKernelGGL(rt_ao_prepare_camera_kernel, pgrid, block, 0, s, sc, p, n, width, y0, utab, (const HitRec*)c->hitbuf,
-                                 c->ao_geo, c->ao_nrm, c->ao_col, c->ao_cnt, c->ao_list, c->ao_hdr, c->ctl);
-  else hipLaunchKernelGGL(rt_ao_prepare_kernel, pgrid, block, 0, s, sc, p, n, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
-                          c->ao_geo, c->ao_nrm, c->ao_col, c->ao_cnt, c->ao_list, c->ao_hdr, c->ctl, (float4*)nullptr);
-  if (hipGetLastError() != hipSuccess) return -1;
-  c->ctl_dirty = false;
-  for (uint32_t s0 = 0; s0 < ao->spp; s0 += ns) {
-    const uint32_t k = std::min(ns, ao->spp - s0);
-    if (r.cams) hipLaunchKernelGGL(rt_ao_rays_camera_kernel, rgrid, block, 0, s, ray_cap, width, y0, utab, (const float4*)c->ao_geo, (const float4*)c->ao_nrm,
-                                   (const uint32_t*)c->ao_list, c->ao_hdr, ao->spp, s0, k, ao->seed, ao->radius, c->ao_rays, c->ao_tmax);
-    else hipLaunchKernelGGL(rt_ao_rays_kernel, rgrid, block, 0, s, ray_cap, width, y0, utab, vtab, (const float4*)c->ao_geo, (const float4*)c->ao_nrm,
-                            (const uint32_t*)c->ao_list, c->ao_hdr, ao->spp, s0, k, ao->seed, ao->radius, c->ao_rays, c->ao_tmax);
-    if (trace_on_ctx(a, c, c->ao_rays, n * k, c->ao_tmax, c->ao_hits, MODE_ANY_UNORDERED, s, c->ao_hdr + 1, nullptr, bin_rays(k)) != 0) return -1;
-    hipLaunchKernelGGL(rt_ao_accumulate_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_list, (const uint32_t*)c->ao_hdr, k,
-                       (const HitRec*)c->ao_hits, c->ao_cnt);
-  }
-  hipLaunchKernelGGL(rt_ao_final_kernel, grid, block, 0, s, n, width, y0, (const float4*)c->ao_geo, (const float4*)c->ao_col, (const uint32_t*)c->ao_cnt,
-                     ao->spp, r.dst, r.colors, r.unoccluded, r.counters);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
-// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
-// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
-// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
-// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
-// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
-// End of a denoised path frame's tail in place of rt_path_final_kernel (the kernels and their launches are in rt_denoise.hip): demodulate
-// the pixels' accumulators into the context's first signal buffer and write the guide outputs, then one launch per a-trous iteration,
-// ping-pong between the two signal buffers, the last of which remodulates, packs and writes.  n = pixels of the window.
-static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
-  hipStream_t s = (hipStream_t)r.stream;
-  if (c->dn_cap < n) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    const uint64_t have = c->dn_cap;
-    if (!(grow_buf((void**)&c->dn_sig[0], have, n, 16) && grow_buf((void**)&c->dn_sig[1], have, n, 16))) { c->dn_cap = 0; return -1; }
-    c->dn_cap = n;
-  }
-  if (dn_launch_demodulate(s, n, r.width, r.y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, r.path->spp, r.path->bounces == 0 ? 1u : 0u,
-                           c->dn_sig[0], r.aov) != 0) return -1;
-  return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);
-}
-
-static int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
-  const SceneDev& sc = a->dev;
-  const vxrt_path_params_t& pp = *r.path;
-  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
-  hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull) return -1;
-  const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, host_knobs().path_batch / n));   // samples per batch
-  const uint64_t path_cap = pp.bounces ? n * ns : 0, shadow_cap = pp.shadow ? path_cap : 0;
-  if (path_cap > 0x7fffffffull) return -1;
-  if (c->pt_cap < n || c->pt_path_cap < path_cap || c->pt_shadow_cap < shadow_cap) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    const uint64_t have = c->pt_cap, phave = c->pt_path_cap, shave = c->pt_shadow_cap;
-    bool ok = grow_buf((void**)&c->pt_geo, have, n, 16) && grow_buf((void**)&c->pt_nrm, have, n, 16) && grow_buf((void**)&c->pt_dir, have, n, 16) &&
-              grow_buf((void**)&c->pt_lit, have, n, 16) && grow_buf((void**)&c->pt_alb, have, n, 16) && grow_buf((void**)&c->pt_acc, have, n, 16) &&
-              grow_buf((void**)&c->pt_list, have, n, 4) && grow_buf((void**)&c->pt_hdr, c->pt_hdr ? 1 : 0, 1, 16);
-    if (ok && path_cap)
-      ok = grow_buf((void**)&c->pt_I, phave, path_cap, 16) && grow_buf((void**)&c->pt_N, phave, path_cap, 16) && grow_buf((void**)&c->pt_D, phave, path_cap, 16) &&
-           grow_buf((void**)&c->pt_L, phave, path_cap, 16) && grow_buf((void**)&c->pt_T, phave, path_cap, 16) &&
-           grow_buf((void**)&c->pt_live[0], phave, path_cap, 4) && grow_buf((void**)&c->pt_live[1], phave, path_cap, 4) &&
-           grow_buf((void**)&c->pt_rays, phave, path_cap, 24) && grow_buf((void**)&c->pt_hits, phave, path_cap, sizeof(HitRec));
-    if (ok && shadow_cap)
-      ok = grow_buf((void**)&c->pt_srays, shave, shadow_cap, 24) && grow_buf((void**)&c->pt_stmax, shave, shadow_cap, 4) &&
-           grow_buf((void**)&c->pt_shits, shave, shadow_cap, sizeof(HitRec));
-    if (!ok) { c->pt_cap = c->pt_path_cap = c->pt_shadow_cap = 0; return -1; }   // (whatever is left is allocated again by the next frame)
-    c->pt_cap = std::max(have, n); c->pt_path_cap = std::max(phave, path_cap); c->pt_shadow_cap = std::max(shave, shadow_cap);
-  }
-  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
-  const dim3 block(256), grid((n32 + 255u) / 256u), pgrid((n32 + 256u * PATH_PREP_CHUNKS - 1u) / (256u * PATH_PREP_CHUNKS)), rgrid((cap + 255u) / 256u);
-  if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
-  if (r.cams) hipLaunchKernelGGL(rt_path_prepare_camera_kernel, pgrid, block, 0, s, sc, p, n32, width, y0, utab, (const HitRec*)c->hitbuf,
-                                 c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl);
-  else hipLaunchKernelGGL(rt_path_prepare_kernel, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
-                          c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl);
-  if (hipGetLastError() != hipSuccess) return -1;
-  c->ctl_dirty = false;
-  for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
-    const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
-    hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
-                       (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
-    for (uint32_t d = 0; d < pp.bounces; ++d) {
-      uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
-      uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
-      const uint32_t* live = c->pt_live[d & 1u];
-      const bool more = d + 1u < pp.bounces;
-      hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
-                         (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
-      if (trace_on_ctx(a, c, c->pt_rays, (uint64_t)n * k, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
-      if (pp.shadow) {
-        hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                           c->pt_srays, c->pt_stmax, r.counters);
-        if (trace_on_ctx(a, c, c->pt_srays, (uint64_t)n * k, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-      }
-      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                         pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T,
-                         more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr, n_next);
-    }
-    hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
-                       (const float4*)c->pt_L, c->pt_acc);
-  }
-  if (r.denoise && r.denoise->iterations) return render_denoise_tail(c, r, n32);
-  if (r.denoise && r.aov && dn_launch_demodulate(s, n32, width, y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, pp.spp, pp.bounces == 0 ? 1u : 0u,
-                                                 nullptr, r.aov) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
-  hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
-                     pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -1,0 +1,745 @@
+// Tails of the frames that trace secondary rays, and their kernels: what render_common (rt_kernels.hip) runs in place of the plain
+// shading pass of a frame with reflective instances (the mirror-bounce wavefront), of an ambient-occlusion frame and of a path frame
+// (whose denoised end is in rt_denoise.hip), and the binning of secondary rays.  None of it is timed by bench.py, and none of it can
+// reach the traversal kernel's unit: the seam is in rt_internal.h -- the ray buffers are traced through trace_on_ctx, buffers grow
+// through grow_device -- and the shading arithmetic is that of the frame kernels, rt_shading.h.  Same build flags (-ffp-contract=off).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "rt_internal.h"
+#include "rt_shading.h"
+
+__global__ void add_counter_kernel(unsigned long long* c, unsigned long long v) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(c, v); }
+
+// The hit pixels of a frame are appended to one list.  One atomic per wavefront on the list's counter (32,400 for a 1080p frame, all on
+// one address, ~10 ns apart) was 0.3 of the AO prepare kernel's 0.37 ms: a workgroup now counts the hits of 1,024 pixels in LDS and
+// appends once.
+#define PREP_CHUNKS 4   // pixels per thread of the two prepare kernels: one list-append atomic per 1,024 pixels
+// Append value[c] of every thread with flag[c] to list[] (its length in *counter; the order is arbitrary): the workgroup counts in LDS
+// and does one atomic.  Every thread of the workgroup calls it.
+template <int C>
+__device__ __forceinline__ void wg_append(const bool (&flag)[C], const uint32_t (&value)[C], uint32_t* __restrict__ list, uint32_t* counter) {
+  __shared__ uint32_t s_cnt[C][4];
+  __shared__ uint32_t s_base;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t off[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const unsigned long long m = __ballot(flag[c]);
+    off[c] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[c][wv] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int c = 0; c < C; ++c) for (int w = 0; w < 4; ++w) { const uint32_t v = s_cnt[c][w]; s_cnt[c][w] = tot; tot += v; }
+    s_base = tot ? atomicAdd(counter, tot) : 0u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+    if (flag[c]) list[s_base + s_cnt[c][wv] + off[c]] = value[c];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Mirror bounce (closest.cpp:95-121) as a wavefront over depth levels.  The reference recurses inside
+// the closest-hit shader: C(ray) = term + (reflectivity > 0 && bounce + 1 < max_depth ? C(mirror ray)
+// : background) * reflectivity, C(miss) = background.  Here level k holds the rays of bounce k (level 0 =
+// the pixels); shading a level appends the next level's rays, and the colours are folded back from the
+// deepest level to the pixels in the reference's order of operations, so the result has the same bits.
+// Taken only when max_depth > 1 and some instance is reflective (the shipped scene builder has none).
+// ---------------------------------------------------------------------------------------------
+// Shade level `level`.  LEVEL0: entry = pixel of rows [y0,y1), hit record from the traversal (occlusion
+// in bit 31 of blasIdx); else entry i = ray rays[6i..] with hit hits[i] (occluded iff shits[i] hit).
+// Entries that bounce leave (term, reflectivity) in term[] and append a ray; the others are final.
+// (CAM: camera frames -- utab / vtab are the head and the tables of the camera block, see CAM_HDR; only level 0 derives a primary ray)
+template <bool LEVEL0, bool CAM>
+__global__ __launch_bounds__(256) void rt_shade_bounce_kernel(SceneDev sc, ShadeParams p, uint32_t level, uint64_t n,
+    uint32_t W, uint32_t H, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
+    const HitRec* __restrict__ hb, const float* __restrict__ rays, const HitRec* __restrict__ shits,
+    float4* __restrict__ term, float* __restrict__ col, uint32_t* __restrict__ dst, HitRec* __restrict__ hits_out,
+    float* __restrict__ colors_out, uint32_t* next_count, float* __restrict__ next_rays, uint32_t* __restrict__ next_parent,
+    uint32_t* __restrict__ ctl_reset) {
+  if (ctl_reset && blockIdx.x == 0)
+    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  size_t e = (size_t)t;
+  float ox, oy, oz, dx, dy, dz;
+  HitRec h;
+  bool occ;
+  if (LEVEL0) {
+    const uint32_t x = (uint32_t)(t % W), y = y0 + (uint32_t)(t / W);
+    e = (size_t)x + (size_t)y * W;
+    h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
+    occ = (h.blasIdx & 0x80000000u) != 0u;
+    if (hits_out) hits_out[e] = h;
+    h.blasIdx &= 0x7fffffffu;
+    frame_pixel_ray<CAM>(utab, vtab, W, H, 0u, x, y, ox, oy, oz, dx, dy, dz);
+  } else {
+    const float* rp = rays + e * 6;
+    ox = rp[0]; oy = rp[1]; oz = rp[2]; dx = rp[3]; dy = rp[4]; dz = rp[5];
+    h = hb[e];
+    occ = shits != nullptr && shits[e].dist != RT_LARGE_FLOAT;
+  }
+  float r, g, b;
+  bool final_ = true;
+  if (h.dist == RT_LARGE_FLOAT) {   // miss.cpp:9-14
+    r = p.bg[0]; g = p.bg[1]; b = p.bg[2];
+  } else {
+    float refl, Ix, Iy, Iz, Nx, Ny, Nz;
+    shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz);
+    if (refl > 0.0f && level + 1u < p.max_depth) {   // :95
+      final_ = false;
+      term[e] = make_float4(r, g, b, refl);
+      const uint32_t slot = atomicAdd(next_count, 1u);   // every level has room for one ray per entry of the level before
+      mirror_ray(dx, dy, dz, Ix, Iy, Iz, Nx, Ny, Nz, next_rays + (size_t)slot * 6);
+      next_parent[slot] = (uint32_t)e;
+    } else {
+      float thr = 1.0f;
+      thr *= refl;                    // :90
+      r = r + p.bg[0] * thr;          // :123
+      g = g + p.bg[1] * thr;
+      b = b + p.bg[2] * thr;
+    }
+  }
+  if (final_) {
+    if (LEVEL0) {
+      dst[e] = pack_rgb8(r, g, b);
+      if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
+    } else {
+      col[3 * e] = r; col[3 * e + 1] = g; col[3 * e + 2] = b;
+    }
+  }
+}
+
+// occlusion rays of a bounce level (shadow extension at every depth); a miss gets a ray nothing can hit
+__global__ __launch_bounds__(256) void rt_bounce_shadow_rays_kernel(ShadeParams p, uint32_t n, const float* __restrict__ rays,
+    const HitRec* __restrict__ hits, float* __restrict__ srays, float* __restrict__ stmax, unsigned long long* rays_traced) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool real = false;
+  if (i < n) {
+    const float* rp = rays + (size_t)i * 6;
+    float* sp = srays + (size_t)i * 6;
+    const float d = hits[i].dist;
+    if (d == RT_LARGE_FLOAT) {
+      sp[0] = 0.f; sp[1] = 0.f; sp[2] = 0.f; sp[3] = 1.f; sp[4] = 1.f; sp[5] = 1.f;
+      stmax[i] = -1.0f;
+    } else {
+      float sdist;
+      shadow_ray(p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], d, sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sdist);
+      stmax[i] = sdist;
+      real = true;
+    }
+  }
+  const unsigned long long m = __ballot(real);
+  if (rays_traced && (threadIdx.x & 63u) == 0u && m) atomicAdd(rays_traced, (unsigned long long)__popcll(m));
+}
+
+// fold level k into level k-1 (closest.cpp:117): C[parent] = term[parent] + C_k * (1 * reflectivity[parent])
+template <bool TO_PIXELS>
+__global__ __launch_bounds__(256) void rt_bounce_unwind_kernel(uint32_t n, const uint32_t* __restrict__ parent, const float* __restrict__ col_k,
+    const float4* __restrict__ term_prev, float* __restrict__ col_prev, uint32_t* __restrict__ dst, float* __restrict__ colors_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const size_t q = parent[i];
+  const float4 t = term_prev[q];
+  float thr = 1.0f;
+  thr *= t.w;
+  const float r = t.x + col_k[3 * (size_t)i] * thr, g = t.y + col_k[3 * (size_t)i + 1] * thr, b = t.z + col_k[3 * (size_t)i + 2] * thr;
+  if (TO_PIXELS) {
+    dst[q] = pack_rgb8(r, g, b);
+    if (colors_out) { colors_out[3 * q] = r; colors_out[3 * q + 1] = g; colors_out[3 * q + 2] = b; }
+  } else {
+    col_prev[3 * q] = r; col_prev[3 * q + 1] = g; col_prev[3 * q + 2] = b;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ambient occlusion (extension, BASELINE config 5; recipe defined in oracle/rt_oracle.c:orc_ao_ray and
+// mirrored here operation by operation -- RNG of common.h:129-147, rejection-sampled disk, Duff basis:
+// only IEEE add/mul/div/sqrt, so host and device produce the same rays).
+// ---------------------------------------------------------------------------------------------
+// per pixel of rows [y0,y1): Lambert colour of the primary hit (else arm of closest.cpp), hit point and
+// shading normal for the occlusion rays; geo[t] = (I, hit?), nrm[t] = (N, 0), col[t] = (rgb, 0), cnt[t] = 0;
+// pixels with a hit are appended to list[] (count in hdr[0]; the order is arbitrary, nothing depends on it)
+// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
+template <bool CAM>
+__global__ __launch_bounds__(256) void rt_ao_prepare_kernel(SceneDev sc, ShadeParams p, uint64_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ col, uint32_t* __restrict__ cnt,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float4* __restrict__ alb /* optional: albedo of the hit */) {
+  if (ctl_reset && blockIdx.x == 0)
+    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
+  bool hit_c[PREP_CHUNKS];
+  uint32_t t_c[PREP_CHUNKS];
+#pragma unroll
+  for (int c = 0; c < PREP_CHUNKS; ++c) {
+    const uint64_t t = ((uint64_t)blockIdx.x * PREP_CHUNKS + c) * 256u + threadIdx.x;
+    bool hit = false;
+    if (t < n) {
+      const uint32_t x = (uint32_t)(t % W), y = y0 + (uint32_t)(t / W);
+      HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
+      h.blasIdx &= 0x7fffffffu;
+      float ox, oy, oz, dx, dy, dz;
+      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
+      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+      float r, g, b;
+      if (h.dist == RT_LARGE_FLOAT) {
+        r = p.bg[0]; g = p.bg[1]; b = p.bg[2];
+        geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        nrm[t] = make_float4(0.f, 0.f, 1.f, 0.f);
+      } else {
+        float refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
+        shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, false, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
+        float thr = 1.0f;
+        thr *= refl;
+        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+        geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
+        nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
+        if (alb) alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
+        hit = true;
+      }
+      col[t] = make_float4(r, g, b, 0.f);
+      cnt[t] = 0u;
+    }
+    hit_c[c] = hit; t_c[c] = (uint32_t)t;
+  }
+  wg_append<PREP_CHUNKS>(hit_c, t_c, list, hdr);
+}
+
+// samples [s0, s0 + ns) of every listed pixel: ray i = (pixel list[i / ns], sample s0 + i % ns); hdr[1] = number of rays
+template <bool CAM>
+__global__ __launch_bounds__(256) void rt_ao_rays_kernel(uint64_t cap, uint32_t W, uint32_t y0, const float* __restrict__ utab, const float* __restrict__ vtab,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const uint32_t* __restrict__ list, uint32_t* hdr,
+    uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed, float radius, float* __restrict__ rays, float* __restrict__ tmax) {
+  const uint64_t total = (uint64_t)hdr[0] * ns;
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i == 0) hdr[1] = (uint32_t)total;
+  if (i >= total || i >= cap) return;
+  const uint32_t t = list[i / ns], smp = s0 + (uint32_t)(i % ns);
+  float* o = rays + (size_t)i * 6;
+  const float4 gI = geo[t];
+  const uint32_t x = t % W, y = y0 + t / W;
+  float ox, oy, oz, vdx, vdy, vdz;
+  if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, vdx, vdy, vdz);
+  else generate_ray(utab[x], vtab[y], ox, oy, oz, vdx, vdy, vdz);
+  const float4 gN = nrm[t];
+  float r6[6];
+  ao_sample_ray(x, y, W, spp, smp, user_seed, gI.x, gI.y, gI.z, gN.x, gN.y, gN.z, vdx, vdy, vdz, r6);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = r6[k];
+  tmax[i] = radius;
+}
+
+__global__ __launch_bounds__(256) void rt_ao_accumulate_kernel(uint64_t cap, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
+    const HitRec* __restrict__ ohits, uint32_t* __restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const bool live = i < hdr[1] && i < cap;
+  // the ns samples of a pixel sit next to each other: the lanes of a wavefront that belong to one pixel add up with a ballot and
+  // the first of them does the pixel's atomic (16 spp: 4 atomics per wavefront instead of up to 64)
+  const unsigned long long m = __ballot(live && ohits[live ? i : 0].dist == RT_LARGE_FLOAT);
+  if (!live) return;
+  const uint32_t lane = threadIdx.x & 63u, k = (uint32_t)(i % ns);
+  const uint32_t s0 = lane > k ? lane - k : 0u, e0 = min(63u, lane - k + ns - 1u);   // lanes of this pixel in this wavefront (lane - k may wrap: then s0 = 0)
+  const uint32_t e = lane >= k ? e0 : min(63u, lane + (ns - 1u - k));
+  if (lane == s0) {
+    const unsigned long long seg = (~0ull >> (63u - e)) & (~0ull << s0);
+    const uint32_t c = (uint32_t)__popcll(m & seg);
+    if (c) atomicAdd(cnt + list[i / ns], c);
+  }
+}
+
+__global__ __launch_bounds__(256) void rt_ao_final_kernel(uint64_t n, uint32_t W, uint32_t y0, const float4* __restrict__ geo, const float4* __restrict__ col,
+    const uint32_t* __restrict__ cnt, uint32_t spp, uint32_t* __restrict__ dst, float* __restrict__ colors_out, uint32_t* __restrict__ unoccluded,
+    unsigned long long* rays_traced) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  bool hit = false;
+  if (t < n) {
+    const uint32_t x = (uint32_t)(t % W), y = y0 + (uint32_t)(t / W);
+    const size_t e = (size_t)x + (size_t)y * W;
+    const float4 c = col[t];
+    float r = c.x, g = c.y, b = c.z;
+    uint32_t open = 0u;
+    if (geo[t].w != 0.f) {
+      hit = true;
+      open = cnt[t];
+      const float f = (float)open / (float)spp;
+      r *= f; g *= f; b *= f;
+    }
+    dst[e] = pack_rgb8(r, g, b);
+    if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
+    if (unoccluded) unoccluded[e] = open;
+  }
+  const unsigned long long m = __ballot(hit);
+  if (rays_traced && (threadIdx.x & 63u) == 0u && m) atomicAdd(rays_traced, (unsigned long long)__popcll(m) * spp);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Path frames (vxrt_render_path; the definition is in include/vortex_hip.h, the launch sequence in render_path_tail and DESIGN.md s2,
+// "Path frames").  The kernels around the ray-buffer launches: per-pixel state of the primary hit, per-path state that survives from
+// bounce to bounce, the scatter step and the accumulation over samples.  Every arithmetic step is an existing __device__ function
+// (shade_terms, ao_sample_ray, shadow_ray, pack_rgb8, camera_ray / generate_ray).
+// Path slot i of a batch of ns samples starting at s0 = (pixel list[i / ns], sample s0 + i % ns); a path's state stays in its slot,
+// and the rays of a depth are those of the slots still listed as live (ray q belongs to slot live[q]).
+// ---------------------------------------------------------------------------------------------
+// per pixel t of rows [y0,y1): geo[t] = (I, hit?), nrm[t] = (N, 0), dir[t] = (direction of the primary ray, 0), lit[t] = (Lit of the
+// primary hit with the occlusion bit the shadow frame launch left in its record | background, 0), alb[t] = (Alb, 0); pixels with a hit
+// are appended to list[] (count in hdr[0])
+// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
+template <bool CAM>
+__global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
+  if (ctl_reset && blockIdx.x == 0)
+    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
+  bool hit_c[PREP_CHUNKS];
+  uint32_t t_c[PREP_CHUNKS];
+#pragma unroll
+  for (int c = 0; c < PREP_CHUNKS; ++c) {
+    const uint64_t t64 = ((uint64_t)blockIdx.x * PREP_CHUNKS + c) * 256u + threadIdx.x;
+    const uint32_t t = (uint32_t)t64;
+    bool hit = false;
+    if (t64 < n) {
+      const uint32_t x = t % W, y = y0 + t / W;
+      HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
+      const bool occ = (h.blasIdx & 0x80000000u) != 0u;
+      h.blasIdx &= 0x7fffffffu;
+      float ox, oy, oz, dx, dy, dz;
+      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
+      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
+      if (h.dist == RT_LARGE_FLOAT) {
+        geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        lit[t] = make_float4(p.bg[0], p.bg[1], p.bg[2], 0.f);
+      } else {
+        float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
+        shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
+        float thr = 1.0f;
+        thr *= refl;
+        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+        geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
+        nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
+        dir[t] = make_float4(dx, dy, dz, 0.f);
+        lit[t] = make_float4(r, g, b, 0.f);
+        alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
+        hit = true;
+      }
+    }
+    hit_c[c] = hit; t_c[c] = t;
+  }
+  wg_append<PREP_CHUNKS>(hit_c, t_c, list, hdr);
+}
+
+// start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
+__global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, uint32_t* __restrict__ live) {
+  const uint64_t want = (uint64_t)hdr[0] * ns;
+  const uint32_t total = want < cap ? (uint32_t)want : cap;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i == 0) hdr[1] = total;
+  if (i >= total) return;
+  const uint32_t t = list[i / ns];
+  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
+  live[i] = i;
+}
+
+// the bounce rays of one depth: ray q leaves the last vertex of slot live[q] (user seed = seed + depth); zeroes the next depth's count
+__global__ __launch_bounds__(256) void rt_path_bounce_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, unsigned long long* rays_traced) {
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q == 0) {
+    *n_next = 0u;
+    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one)
+  }
+  if (q >= total) return;
+  const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
+  const uint32_t x = t % W, y = y0 + t / W;
+  const float4 I = pI[slot], N = pN[slot], D = pD[slot];
+  float r6[6];
+  ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
+  float* o = rays + (size_t)q * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = r6[k];
+}
+
+// the occlusion rays of one depth (light sampling): one per bounce ray that hit; a miss gets a ray nothing can hit, which is not
+// counted (see rt_bounce_shadow_rays_kernel).  One atomic per workgroup on the ray counter.
+__global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams p, uint32_t cap, const uint32_t* n_live, const float* __restrict__ rays,
+    const HitRec* __restrict__ hits, float* __restrict__ srays, float* __restrict__ stmax, unsigned long long* rays_traced) {
+  __shared__ uint32_t s_real;
+  if (threadIdx.x == 0) s_real = 0u;
+  __syncthreads();
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  bool real = false;
+  if (q < total) {
+    const float* rp = rays + (size_t)q * 6;
+    float* sp = srays + (size_t)q * 6;
+    const float d = hits[q].dist;
+    if (d == RT_LARGE_FLOAT) {
+      sp[0] = 0.f; sp[1] = 0.f; sp[2] = 0.f; sp[3] = 1.f; sp[4] = 1.f; sp[5] = 1.f;
+      stmax[q] = -1.0f;
+    } else {
+      float sdist;
+      shadow_ray(p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], d, sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sdist);
+      stmax[q] = sdist;
+      real = true;
+    }
+  }
+  const unsigned long long m = __ballot(real);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
+  __syncthreads();
+  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
+}
+
+// the scatter step of one depth.  Miss: Lc = Lc + thr * background, the path ends.  Hit: Lc = Lc + thr * Lit (occluded iff shits[q]
+// hit), then thr = thr * Alb and the hit becomes the slot's last vertex; with `next` the slot is appended to the next depth's live list.
+__global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next) {
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  bool go[1] = {false};
+  uint32_t val[1] = {0u};
+  if (q < total) {
+    const uint32_t slot = live[q];
+    const float* rp = rays + (size_t)q * 6;
+    HitRec h = hits[q];
+    h.blasIdx &= 0x7fffffffu;
+    float4 L = pL[slot];
+    const float4 T = pT[slot];
+    if (h.dist == RT_LARGE_FLOAT) {
+      L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
+    } else {
+      const bool occ = shits != nullptr && shits[q].dist != RT_LARGE_FLOAT;
+      float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
+      shade_terms<false>(sc, p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
+      float thr = 1.0f;
+      thr *= refl;
+      r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+      L.x = L.x + T.x * r; L.y = L.y + T.y * g; L.z = L.z + T.z * b;
+      if (next) {
+        pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
+        pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
+        pN[slot] = make_float4(Nx, Ny, Nz, 0.f);
+        pD[slot] = make_float4(rp[3], rp[4], rp[5], 0.f);
+        go[0] = true; val[0] = slot;
+      }
+    }
+    pL[slot] = L;
+  }
+  if (next) wg_append<1>(go, val, next, n_next);   // (uniform over the launch)
+}
+
+// after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
+// starts it); one thread per listed pixel
+__global__ __launch_bounds__(256) void rt_path_accumulate_kernel(uint32_t n, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
+    uint32_t first, const float4* __restrict__ pL, float4* __restrict__ acc) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= min(hdr[0], n)) return;
+  const uint32_t t = list[j];
+  const float4* L = pL + (size_t)j * ns;
+  float4 a = first ? L[0] : acc[t];
+  for (uint32_t s = first ? 1u : 0u; s < ns; ++s) { const float4 c = L[s]; a.x = a.x + c.x; a.y = a.y + c.y; a.z = a.z + c.z; }
+  acc[t] = a;
+}
+
+// colour = acc / spp, pack, write.  flat (bounces = 0): every sample's Lc is the pixel's Lit, summed here the same way.
+__global__ __launch_bounds__(256) void rt_path_final_kernel(uint32_t n, uint32_t W, uint32_t y0, const float4* __restrict__ geo, const float4* __restrict__ lit,
+    const float4* __restrict__ acc, uint32_t spp, uint32_t flat, uint32_t* __restrict__ dst, float* __restrict__ colors_out) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t x = t % W, y = y0 + t / W;
+  const size_t e = (size_t)x + (size_t)y * W;
+  const float4 c = lit[t];
+  float r = c.x, g = c.y, b = c.z;   // (a miss: the background)
+  if (geo[t].w != 0.f) {
+    if (flat) { for (uint32_t s = 1; s < spp; ++s) { r = r + c.x; g = g + c.y; b = b + c.z; } }
+    else { const float4 a = acc[t]; r = a.x; g = a.y; b = a.z; }
+    const float f = (float)spp;
+    r = r / f; g = g / f; b = b / f;
+  }
+  dst[e] = pack_rgb8(r, g, b);
+  if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Secondary rays re-sorted before they are traced (north_star: "ray packets re-sorted ... to tame divergence").
+// The rays of a bounce / AO pass leave the compaction in pixel order with directions spread over a hemisphere: a wavefront of
+// 64 consecutive rays shares origins but not directions.  Counting sort by key = direction octant x origin cell (the 16x16-pixel
+// cell of the ray's pixel: hit points of neighbouring pixels are neighbours in space), so that 64 consecutive queue positions
+// hold rays that start in one small region AND point into the same octant.  Only the ORDER in which rays are traced changes:
+// the kernel reads ray order[q] and writes hit record order[q], so every result is bit-identical (tests compare them all).
+// ---------------------------------------------------------------------------------------------
+#define BIN_CELL_SHIFT 4u   // 16 x 16 pixels
+__global__ __launch_bounds__(256) void rt_bin_count_kernel(uint64_t cap, const uint32_t* __restrict__ hdr, const float* __restrict__ rays,
+    const uint32_t* __restrict__ list, uint32_t ns, uint32_t W, uint32_t cells_x, uint32_t n_cells, uint32_t* __restrict__ hist, uint32_t* __restrict__ keys) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= hdr[1] || i >= cap) return;
+  const uint32_t t = list[i / ns];
+  const uint32_t cell = ((t / W) >> BIN_CELL_SHIFT) * cells_x + ((t % W) >> BIN_CELL_SHIFT);
+  const float* r = rays + i * 6;
+  const uint32_t oct = (__float_as_uint(r[3]) >> 31) | ((__float_as_uint(r[4]) >> 31) << 1) | ((__float_as_uint(r[5]) >> 31) << 2);
+  const uint32_t key = oct * n_cells + cell;
+  keys[i] = key;
+  atomicAdd(&hist[key], 1u);
+}
+// exclusive scan of hist[0..n) in place, one workgroup of 1024 threads, `per` consecutive counters per thread
+__global__ __launch_bounds__(1024) void rt_bin_scan_kernel(uint32_t* __restrict__ hist, uint32_t n, uint32_t per) {
+  __shared__ uint32_t wsum[16];
+  const uint32_t lo = threadIdx.x * per, hi = min(lo + per, n);
+  uint32_t sum = 0;
+  for (uint32_t k = lo; k < hi; ++k) sum += hist[k];
+  uint32_t inc = sum;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
+  if (lane == 63u) wsum[wave] = inc;
+  __syncthreads();
+  uint32_t base = inc - sum;
+  for (uint32_t w = 0; w < wave; ++w) base += wsum[w];
+  for (uint32_t k = lo; k < hi; ++k) { const uint32_t v = hist[k]; hist[k] = base; base += v; }
+}
+__global__ __launch_bounds__(256) void rt_bin_scatter_kernel(uint64_t cap, const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ keys,
+                                                            uint32_t* __restrict__ hist, uint32_t* __restrict__ order) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= hdr[1] || i >= cap) return;
+  order[atomicAdd(&hist[keys[i]], 1u)] = (uint32_t)i;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host: the three tails render_common (rt_kernels.hip) ends such a frame with
+// ---------------------------------------------------------------------------------------------
+#include <algorithm>
+#include <cstdlib>
+
+// Paths per batch of a path frame (VXRT_PATH_BATCH).  A path costs 136 bytes of frame-context storage -- 80 of state (I, N, dir, Lc, thr:
+// five float4), 24 + 24 of bounce ray and hit record, 2 x 4 of live-list entries -- and 52 more with light sampling (occlusion ray, tmax,
+// hit record): 4 Mi paths are 0.53 / 0.73 GiB per frame context, and at 1920x1080 two samples per batch, i.e. ray-buffer launches of up to
+// 4 M rays for a machine that holds 0.4 M lanes of the traversal kernel -- launch ramps and tails stay a small part of each.
+#define PATH_BATCH_PATHS (4ull << 20)
+#define AO_BATCH_RAYS (32ull << 20)   // rays per batch of an ambient-occlusion frame
+
+// The two measurement knobs of this unit (docs/KNOBS.md), read from the environment once per process, together: on the first call that
+// asks for one.  Each keeps the parsing it always had.
+struct SecondaryKnobs {
+  uint64_t path_batch;   // paths per batch of a path frame (see render_path_tail)
+  // VXRT_SORT_SECONDARY=1: trace the secondary rays in (direction octant, origin cell) order instead of generation order.  OFF by
+  // default: measured SLOWER on both passes that use it (diffuse bounce 1.53 -> 1.95 ms, 10M-triangle hairball AO 9.2 -> 16.6 ms,
+  // profiles/r02_f_secondary_sort.txt).  The traversal is bound by per-lane VALU work, which coherence does not reduce, and the
+  // generation order already puts the 16 samples of one pixel (AO) / 64 neighbouring pixels (bounce) side by side.
+  bool sort_secondary;
+};
+static const SecondaryKnobs& secondary_knobs() {
+  static const SecondaryKnobs knobs = [] {
+    SecondaryKnobs k;
+    { const char* e = getenv("VXRT_PATH_BATCH"); const long long v = e ? atoll(e) : 0; k.path_batch = v > 0 ? (uint64_t)v : PATH_BATCH_PATHS; }
+    { const char* e = getenv("VXRT_SORT_SECONDARY"); k.sort_secondary = e && e[0] == '1'; }
+    return k;
+  }();
+  return knobs;
+}
+
+// The buffers of a bounce level for n entries: the terms; unless only_term the rays, hit records, parents and colours; with `shadow`
+// the occlusion rays, which a level gets at the first frame with the shadow extension.  Each group has its own capacity.  (No wait
+// of its own: hipFree orders itself behind the device, and the tail has waited for the level before.)
+static bool level_reserve(FrameCtx::Level& l, uint64_t n, bool shadow, bool only_term) {
+  if (!grow_device({{(void**)&l.term, 16}}, &l.cap, n, GrowSync::NONE, nullptr)) return false;
+  if (only_term) return true;
+  if (!grow_device({{(void**)&l.rays, 24}, {(void**)&l.hits, sizeof(HitRec)}, {(void**)&l.parent, 4}, {(void**)&l.col, 12}}, &l.ray_cap, n, GrowSync::NONE, nullptr)) return false;
+  return !shadow || grow_device({{(void**)&l.srays, 24}, {(void**)&l.stmax, 4}, {(void**)&l.shits, sizeof(HitRec)}}, &l.shadow_cap, n, GrowSync::NONE, nullptr);
+}
+
+// Tail of a frame with reflective instances (replaces the plain shading pass): shade level 0, then per
+// bounce level trace -> (occlusion rays ->) shade, then fold the colours back.  The level sizes come back
+// to the host between levels, so this path synchronises the stream (it is not the benchmarked one).
+// (utab / vtab: the tables the traversal used; a camera frame's utab is its camera block)
+int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  const SceneDev& sc = a->dev;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  const bool shadow = r.shadow != 0;
+  uint32_t* dst = r.dst; float* colors = r.colors;
+  unsigned long long* rays_traced = r.counters;
+  hipStream_t s = (hipStream_t)r.stream;
+  const uint64_t npix = (uint64_t)width * (y1 - y0);          // entries of level 0 (addressed by pixel index)
+  const uint64_t pix_span = (uint64_t)width * y1;              // term[] of level 0 is indexed by x + y*W
+  if (npix > 0x7fffffffull) return -1;
+  if (!c->bcount && hipMalloc((void**)&c->bcount, sizeof(uint32_t)) != hipSuccess) return -1;
+  if (c->lv.size() < 2) c->lv.resize(2);
+  if (!level_reserve(c->lv[0], pix_span, false, true)) return -1;
+  if (!level_reserve(c->lv[1], npix, shadow, false)) return -1;
+  dim3 block(256);
+  if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
+  const auto k_level0 = r.cams ? rt_shade_bounce_kernel<true, true> : rt_shade_bounce_kernel<true, false>;
+  const auto k_deeper = rt_shade_bounce_kernel<false, false>;   // (the deeper levels hold ray buffers, whatever the camera)
+  hipLaunchKernelGGL(k_level0, dim3((uint32_t)((npix + 255) / 256)), block, 0, s, sc, p, 0u, npix, width, r.height, y0, utab, vtab,
+                     (const HitRec*)c->hitbuf, (const float*)nullptr, (const HitRec*)nullptr, c->lv[0].term, (float*)nullptr, dst, (HitRec*)r.hits, colors,
+                     c->bcount, c->lv[1].rays, c->lv[1].parent, c->ctl);
+  if (hipGetLastError() != hipSuccess) return -1;
+  c->ctl_dirty = false;
+  uint32_t depth = 0;   // deepest level that holds rays
+  for (uint32_t k = 1; k < p.max_depth; ++k) {
+    uint32_t n = 0;
+    if (hipMemcpyAsync(&n, c->bcount, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (n == 0) break;
+    FrameCtx::Level& L = c->lv[k];
+    L.n = n;
+    depth = k;
+    if (rays_traced) hipLaunchKernelGGL(add_counter_kernel, dim3(1), dim3(64), 0, s, rays_traced, (unsigned long long)n);
+    if (trace_on_ctx(a, c, L.rays, n, nullptr, L.hits, VXRT_MODE_CLOSEST, s) != 0) return -1;
+    const dim3 grid((n + 255u) / 256u);
+    if (shadow) {
+      hipLaunchKernelGGL(rt_bounce_shadow_rays_kernel, grid, block, 0, s, p, n, (const float*)L.rays, (const HitRec*)L.hits, L.srays, L.stmax, rays_traced);
+      if (trace_on_ctx(a, c, L.srays, n, L.stmax, L.shits, MODE_ANY_UNORDERED, s) != 0) return -1;
+    }
+    if (c->lv.size() < (size_t)k + 2) c->lv.resize((size_t)k + 2);
+    FrameCtx::Level& Nx = c->lv[k + 1];
+    const bool more = k + 1 < p.max_depth;
+    if (more && !level_reserve(Nx, n, shadow, false)) return -1;
+    FrameCtx::Level& Lk = c->lv[k];   // (resize may have moved the vector)
+    if (hipMemsetAsync(c->bcount, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_deeper, grid, block, 0, s, sc, p, k, (uint64_t)n, width, r.height, y0, utab, vtab,
+                       (const HitRec*)Lk.hits, (const float*)Lk.rays, shadow ? (const HitRec*)Lk.shits : (const HitRec*)nullptr, Lk.term, Lk.col,
+                       (uint32_t*)nullptr, (HitRec*)nullptr, (float*)nullptr, c->bcount, more ? Nx.rays : (float*)nullptr, more ? Nx.parent : (uint32_t*)nullptr,
+                       (uint32_t*)nullptr);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (!more) break;
+  }
+  for (uint32_t k = depth; k >= 1; --k) {
+    FrameCtx::Level& L = c->lv[k];
+    const dim3 grid((L.n + 255u) / 256u);
+    if (k == 1) hipLaunchKernelGGL(rt_bounce_unwind_kernel<true>, grid, block, 0, s, L.n, (const uint32_t*)L.parent, (const float*)L.col, (const float4*)c->lv[0].term, (float*)nullptr, dst, colors);
+    else        hipLaunchKernelGGL(rt_bounce_unwind_kernel<false>, grid, block, 0, s, L.n, (const uint32_t*)L.parent, (const float*)L.col, (const float4*)c->lv[k - 1].term, c->lv[k - 1].col, (uint32_t*)nullptr, (float*)nullptr);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Tail of an ambient-occlusion frame (replaces the plain shading pass): the pixels with a hit are listed on
+// the device, their occlusion rays are generated in batches of whole samples (<= AO_BATCH_RAYS rays) and each
+// batch is one any-hit launch whose job count stays in device memory.  No host synchronisation unless a buffer grows.
+int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  const SceneDev& sc = a->dev;
+  const vxrt_ao_params_t* ao = r.ao;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  hipStream_t s = (hipStream_t)r.stream;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (ao->reserved == VXRT_AO_MODE_DIFFUSE_BOUNCE) return -1;    // (the diffuse-bounce frame is JOB_RENDER_GI: it has no tail)
+  if (n > 0x7fffffffull || ao->spp == 0) return -1;
+  uint32_t ns = (uint32_t)std::min<uint64_t>(ao->spp, std::max<uint64_t>(1, AO_BATCH_RAYS / n));   // samples per batch
+  const uint64_t ray_cap = n * ns;
+  if (ray_cap > 0x7fffffffull) return -1;
+  if (!c->ao_hdr && hipMalloc((void**)&c->ao_hdr, 8) != hipSuccess) return -1;
+  if (!grow_device({{(void**)&c->ao_geo, 16}, {(void**)&c->ao_nrm, 16}, {(void**)&c->ao_col, 16}, {(void**)&c->ao_cnt, 4}, {(void**)&c->ao_list, 4}},
+                   &c->ao_cap, n, GrowSync::STREAM, s)) return -1;
+  if (!grow_device({{(void**)&c->ao_rays, 24}, {(void**)&c->ao_tmax, 4}, {(void**)&c->ao_hits, sizeof(HitRec)}}, &c->ao_ray_cap, ray_cap, GrowSync::STREAM, s)) return -1;
+  const dim3 block(256), grid((uint32_t)((n + 255) / 256)), rgrid((uint32_t)((ray_cap + 255) / 256));
+  const bool sort_on = secondary_knobs().sort_secondary;
+  const uint32_t cells_x = (width + (1u << BIN_CELL_SHIFT) - 1) >> BIN_CELL_SHIFT, cells_y = (y1 - y0 + (1u << BIN_CELL_SHIFT) - 1) >> BIN_CELL_SHIFT;
+  const uint32_t n_cells = cells_x * cells_y, n_bins = 8u * n_cells;
+  if (sort_on && !(grow_device({{(void**)&c->bin_hist, 4}}, &c->bin_cap, n_bins, GrowSync::STREAM, s) &&
+                   grow_device({{(void**)&c->bin_keys, 4}, {(void**)&c->bin_order, 4}}, &c->bin_ray_cap, ray_cap, GrowSync::STREAM, s))) return -1;
+  auto bin_rays = [&](uint32_t ns_batch) -> const uint32_t* {   // ao_rays of the current batch -> bin_order
+    if (!sort_on) return nullptr;
+    if (hipMemsetAsync(c->bin_hist, 0, (size_t)n_bins * 4, s) != hipSuccess) return nullptr;
+    hipLaunchKernelGGL(rt_bin_count_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_hdr, (const float*)c->ao_rays, (const uint32_t*)c->ao_list, ns_batch,
+                       width, cells_x, n_cells, c->bin_hist, c->bin_keys);
+    hipLaunchKernelGGL(rt_bin_scan_kernel, dim3(1), dim3(1024), 0, s, c->bin_hist, n_bins, (n_bins + 1023u) / 1024u);
+    hipLaunchKernelGGL(rt_bin_scatter_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_hdr, (const uint32_t*)c->bin_keys, c->bin_hist, c->bin_order);
+    return c->bin_order;
+  };
+  if (hipMemsetAsync(c->ao_hdr, 0, 8, s) != hipSuccess) return -1;
+  const dim3 pgrid((uint32_t)((n + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS)));
+  // (the two passes that derive the primary ray again: the camera forms for a camera frame)
+  hipLaunchKernelGGL(r.cams ? rt_ao_prepare_kernel<true> : rt_ao_prepare_kernel<false>, pgrid, block, 0, s, sc, p, n, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
+                     c->ao_geo, c->ao_nrm, c->ao_col, c->ao_cnt, c->ao_list, c->ao_hdr, c->ctl, (float4*)nullptr);
+  if (hipGetLastError() != hipSuccess) return -1;
+  c->ctl_dirty = false;
+  for (uint32_t s0 = 0; s0 < ao->spp; s0 += ns) {
+    const uint32_t k = std::min(ns, ao->spp - s0);
+    hipLaunchKernelGGL(r.cams ? rt_ao_rays_kernel<true> : rt_ao_rays_kernel<false>, rgrid, block, 0, s, ray_cap, width, y0, utab, vtab, (const float4*)c->ao_geo,
+                       (const float4*)c->ao_nrm, (const uint32_t*)c->ao_list, c->ao_hdr, ao->spp, s0, k, ao->seed, ao->radius, c->ao_rays, c->ao_tmax);
+    if (trace_on_ctx(a, c, c->ao_rays, n * k, c->ao_tmax, c->ao_hits, MODE_ANY_UNORDERED, s, c->ao_hdr + 1, nullptr, bin_rays(k)) != 0) return -1;
+    hipLaunchKernelGGL(rt_ao_accumulate_kernel, rgrid, block, 0, s, ray_cap, (const uint32_t*)c->ao_list, (const uint32_t*)c->ao_hdr, k,
+                       (const HitRec*)c->ao_hits, c->ao_cnt);
+  }
+  hipLaunchKernelGGL(rt_ao_final_kernel, grid, block, 0, s, n, width, y0, (const float4*)c->ao_geo, (const float4*)c->ao_col, (const uint32_t*)c->ao_cnt,
+                     ao->spp, r.dst, r.colors, r.unoccluded, r.counters);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// End of a denoised path frame's tail in place of rt_path_final_kernel (the kernels and their launches are in rt_denoise.hip): demodulate
+// the pixels' accumulators into the context's first signal buffer and write the guide outputs, then one launch per a-trous iteration,
+// ping-pong between the two signal buffers, the last of which remodulates, packs and writes.  n = pixels of the window.
+static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
+  hipStream_t s = (hipStream_t)r.stream;
+  if (!grow_device({{(void**)&c->dn_sig[0], 16}, {(void**)&c->dn_sig[1], 16}}, &c->dn_cap, n, GrowSync::STREAM, s)) return -1;
+  if (dn_launch_demodulate(s, n, r.width, r.y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, r.path->spp, r.path->bounces == 0 ? 1u : 0u,
+                           c->dn_sig[0], r.aov) != 0) return -1;
+  return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);
+}
+
+// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
+// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
+// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
+// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
+// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
+// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
+int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  const SceneDev& sc = a->dev;
+  const vxrt_path_params_t& pp = *r.path;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  hipStream_t s = (hipStream_t)r.stream;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull) return -1;
+  const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
+  const uint64_t path_cap = pp.bounces ? n * ns : 0, shadow_cap = pp.shadow ? path_cap : 0;
+  if (path_cap > 0x7fffffffull) return -1;
+  // (per pixel; per path -- none without bounces; per occlusion ray -- none without light sampling)
+  if (!c->pt_hdr && hipMalloc((void**)&c->pt_hdr, 16) != hipSuccess) return -1;
+  if (!grow_device({{(void**)&c->pt_geo, 16}, {(void**)&c->pt_nrm, 16}, {(void**)&c->pt_dir, 16}, {(void**)&c->pt_lit, 16}, {(void**)&c->pt_alb, 16},
+                    {(void**)&c->pt_acc, 16}, {(void**)&c->pt_list, 4}}, &c->pt_cap, n, GrowSync::STREAM, s)) return -1;
+  if (!grow_device({{(void**)&c->pt_I, 16}, {(void**)&c->pt_N, 16}, {(void**)&c->pt_D, 16}, {(void**)&c->pt_L, 16}, {(void**)&c->pt_T, 16}, {(void**)&c->pt_live[0], 4},
+                    {(void**)&c->pt_live[1], 4}, {(void**)&c->pt_rays, 24}, {(void**)&c->pt_hits, sizeof(HitRec)}}, &c->pt_path_cap, path_cap, GrowSync::STREAM, s)) return -1;
+  if (!grow_device({{(void**)&c->pt_srays, 24}, {(void**)&c->pt_stmax, 4}, {(void**)&c->pt_shits, sizeof(HitRec)}}, &c->pt_shadow_cap, shadow_cap, GrowSync::STREAM, s)) return -1;
+  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
+  const dim3 block(256), grid((n32 + 255u) / 256u), pgrid((n32 + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS)), rgrid((cap + 255u) / 256u);
+  if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
+  hipLaunchKernelGGL(r.cams ? rt_path_prepare_kernel<true> : rt_path_prepare_kernel<false>, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
+                     c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl);
+  if (hipGetLastError() != hipSuccess) return -1;
+  c->ctl_dirty = false;
+  for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
+    const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
+    hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
+                       (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
+    for (uint32_t d = 0; d < pp.bounces; ++d) {
+      uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
+      uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
+      const uint32_t* live = c->pt_live[d & 1u];
+      const bool more = d + 1u < pp.bounces;
+      hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
+                         (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
+      if (trace_on_ctx(a, c, c->pt_rays, (uint64_t)n * k, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
+      if (pp.shadow) {
+        hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                           c->pt_srays, c->pt_stmax, r.counters);
+        if (trace_on_ctx(a, c, c->pt_srays, (uint64_t)n * k, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+      }
+      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                         pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T,
+                         more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr, n_next);
+    }
+    hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
+                       (const float4*)c->pt_L, c->pt_acc);
+  }
+  if (r.denoise && r.denoise->iterations) return render_denoise_tail(c, r, n32);
+  if (r.denoise && r.aov && dn_launch_demodulate(s, n32, width, y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, pp.spp, pp.bounces == 0 ? 1u : 0u,
+                                                 nullptr, r.aov) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
+  hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
+                     pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
