@@ -165,11 +165,12 @@ __device__ __forceinline__ float child_box(const uint32_t* pl, float px, float p
   return (tmax < tmin || tmax <= 0) ? RT_LARGE_FLOAT : tmin;
 }
 
-// Box tests of the <=4 children of an internal node.
+// Box tests of the <=4 children of an internal node, raw form: c[k].d is the slab distance whatever the test said, ok[k] says whether
+// child k is to be visited (a real slot whose box the ray enters before its hit distance).
 template <bool EXACT, bool LDEXP>
-__device__ __forceinline__ void eval_children(const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const uint32_t* __restrict__ ref_node,
-                                              float rox, float roy, float roz, float rix, float riy, float riz,
-                                              float hit_dist, Cand* c) {
+__device__ __forceinline__ void eval_children_raw(const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const uint32_t* __restrict__ ref_node,
+                                                  float rox, float roy, float roz, float rix, float riy, float riz,
+                                                  float hit_dist, Cand* c, bool* ok) {
   const float px = __uint_as_float(q0.x), py = __uint_as_float(q0.y), pz = __uint_as_float(q0.z);
   // plane scales 2^e as floats (fma decode); the ldexp decode takes the exponents from the reference node
   const float sx = __uint_as_float(q0.w), sy = __uint_as_float(q3.z), sz = __uint_as_float(q3.w);
@@ -193,10 +194,22 @@ __device__ __forceinline__ void eval_children(const uint4 q0, const uint4 q1, co
   d[3] = child_box<3, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const bool ok = (desc[k] != DESC_NONE) && (d[k] < hit_dist);     // :60, :71
-    c[k].d = ok ? d[k] : __builtin_inff();
+    ok[k] = (desc[k] != DESC_NONE) && (d[k] < hit_dist);     // :60, :71
+    c[k].d = d[k];
     c[k].desc = desc[k];
   }
+}
+
+// ... and the form every caller but the frame kernel's occlusion arm takes: a child that is not to be visited carries +inf.
+// (ok implies d < hit_dist <= RT_LARGE_FLOAT < inf, so `c[k].d < inf` IS ok[k], and a child that is visited carries its slab distance.)
+template <bool EXACT, bool LDEXP>
+__device__ __forceinline__ void eval_children(const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const uint32_t* __restrict__ ref_node,
+                                              float rox, float roy, float roz, float rix, float riy, float riz,
+                                              float hit_dist, Cand* c) {
+  bool ok[4];
+  eval_children_raw<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, rox, roy, roz, rix, riy, riz, hit_dist, c, ok);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) c[k].d = ok[k] ? c[k].d : __builtin_inff();
 }
 
 // per-lane fetch counters of the STATS build (algorithmic bytes): what the
@@ -346,6 +359,13 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 // through re-reading its first triangle -- was built on top of it and lost 3 % against this form: DESIGN.md s5, rejected.)
 #ifndef RT_LEAF_FLAT
 #define RT_LEAF_FLAT 1
+#endif
+// RT_OCC_OK_MASKS: the occlusion arm of the timed plain / shadow frame jobs' node step takes the validity of the four children from the box
+// tests themselves (eval_children_raw) instead of from `d < inf` on distances that were set to +inf for that purpose, and pushes the raw
+// distance: 4 selects and 4 compares less per occlusion-ray step, +1.3 % on the headline frame.  0 = the form before (the A/B: docs/KNOBS.md).
+// Ray buffers, the diffuse-bounce job, the EXACT launch, the alpha-tested and the counting instantiations keep eval_children whatever the value.
+#ifndef RT_OCC_OK_MASKS
+#define RT_OCC_OK_MASKS 1
 #endif
 // (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
 
@@ -928,14 +948,21 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
         if (LDEXP) ref_node = top ? sc.ref_tlas + (size_t)ni * RT_NODE_DWORDS : sc.ref_bvh + (size_t)(ni - sc.n_tlas) * RT_NODE_DWORDS;
         if (STATS) fx.node++;
         Cand c[4];
-        eval_children<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
+        // timed plain / shadow frame jobs: the occlusion arm works on the box tests' own masks (RT_OCC_OK_MASKS above)
+        constexpr bool OK_MASKS = RT_OCC_OK_MASKS && !EXACT && STATS == 0 && !ALPHA && (job_base(JOB) == JOB_RENDER || job_base(JOB) == JOB_RENDER_SHADOW);
+        bool ok[4] = {false, false, false, false};
+        if (OK_MASKS) eval_children_raw<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c, ok);
+        else eval_children<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
         RT_MARK("stack");
         if (((job_base(JOB) == JOB_RENDER_SHADOW && RT_UNORDERED_OCCLUSION) || JOB == JOB_TRACE_UNORDERED) && STATS != 1 && __all((flags & F_ANYHIT) != 0u)) {   // STATS keeps the reference's order, hence its fetch counts
           // occlusion rays of a frame only feed a boolean (is anything hit before the light?): the set
           // of triangles an any-hit traversal can reach does not depend on the visiting order, so the
           // ordering network and the path_m bookkeeping are skipped (vxrt_trace's MODE_ANY, which
           // returns the reference's FIRST accepted candidate, keeps the ordered path)
-          const bool v0 = c[0].d < __builtin_inff(), v1 = c[1].d < __builtin_inff(), v2 = c[2].d < __builtin_inff(), v3 = c[3].d < __builtin_inff();
+          // (OK_MASKS: c[k].d is the raw slab distance here -- an occlusion ray's pushed distance is only ever compared with its constant hitd,
+          // and a child that is pushed carries the same value in both forms)
+          const bool v0 = OK_MASKS ? ok[0] : c[0].d < __builtin_inff(), v1 = OK_MASKS ? ok[1] : c[1].d < __builtin_inff();
+          const bool v2 = OK_MASKS ? ok[2] : c[2].d < __builtin_inff(), v3 = OK_MASKS ? ok[3] : c[3].d < __builtin_inff();
           if (v0 || v1 || v2 || v3) {
             bool more = true;
             if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
@@ -946,6 +973,10 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
             pop_next();
           }
         } else {
+          if (OK_MASKS) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[k].d = ok[k] ? c[k].d : __builtin_inff();
+          }
           order_children(c);   // valid children first (d < inf), nearest in c[0]
           // (path_m and the candidates' distances are never NaN -- a filtered child carries +inf -- so the maxima need no
           // canonicalising v_max x, x in front of them)
