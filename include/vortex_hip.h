@@ -577,6 +577,93 @@ uint64_t vxrt_denoise_scratch_bytes(uint32_t width, uint32_t rows);
 int vxrt_denoise(uint32_t width, uint32_t rows, const float* signal, const float* position, const float* normal,
                  const vxrt_denoise_params_t* dn, float* out, void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* Temporal accumulation for denoised path frames (extension; absent from the reference): the demodulated indirect term E of a frame is
+ * blended with the accumulated term of the previous frame, fetched where the previous CAMERA saw the pixel's primary hit.  Every
+ * + - * / below is one fp32 operation in the order written, without contraction; `/` is the correctly rounded division; floorf and
+ * fabsf are exact; min(a, b) = b < a ? b : a and max(a, b) = a < b ? b : a; dot(a, b) = (ax * bx + ay * by) + az * bz as in the filter.
+ * The one exception is the reciprocal basis of the previous camera, which the host computes in double precision by the rule below.
+ * tests/temporal_ref.py restates all of it.
+ *
+ * HISTORY.  A vxrt_history_t is opaque, caller-owned and independent of any accel or frame context.  For a window of rows x width
+ * pixels it holds two sets of three float4 buffers (a frame reads its predecessor's neighbours while it writes its own): per set
+ * HE = (E_acc.rgb, len), HP = (I, hit), HN = (N, .); 96 bytes per pixel, allocated at create.  On the host it keeps the previous
+ * frame's vxrt_camera_t and geometry (W, H, y0, y1).  A history is EMPTY after create and after reset, and it counts as empty in a call
+ * whose (W, H, y0, y1) differ from the stored ones: another window is an implicit reset.
+ *
+ * RECIPROCAL BASIS of the previous camera cam'.  With R, U, F = right, up, forward of cam' as doubles:
+ *   UF = U x F, FR = F x R, RU = R x U, each component a_y * b_z - a_z * b_y (etc.) as two products and one subtraction;
+ *   det = (R_x * UF_x + R_y * UF_y) + R_z * UF_z;  Rr = UF / det, Ur = FR / det, Fr = RU / det per component,
+ * each rounded once to fp32 (a magnitude beyond the fp32 range becomes the infinity of its sign).  No special cases: a singular basis
+ * gives infinities or NaNs, and the range tests below then reject every pixel.
+ *
+ * THE STEP  out = T(E, P, N; history, cam', prm) over the window; E = 3 floats per pixel, P = (I, hit) and N as for the filter, prm =
+ * vxrt_temporal_params_t.  For pixel p = (x, y) of the window (frame row y0 + y), rows = y1 - y0:
+ *   p is not a hit (P.w != 0 is false): out = (E, 0).
+ *   else sw = +0, se = (+0, +0, +0), sl = +0, and if the history is not empty:
+ *     d = I - pos' per component;  a = dot(d, Rr), b = dot(d, Ur), c = dot(d, Fr).
+ *     if c > 0 (false for a NaN):
+ *       fx = (((a / c) / viewplane'[0]) + 0.5f) * (float)W - 0.5f
+ *       fy = ((((b / c) / viewplane'[1]) + 0.5f) * (float)H - 0.5f) - (float)y0
+ *       if fx > -1 && fx < (float)W && fy > -1 && fy < (float)rows  (only now do coordinates become integers):
+ *         x0 = floorf(fx), yy = floorf(fy), tx = fx - (float)x0, ty = fy - (float)yy.
+ *         The four taps are visited in the order (i, j) = (0,0), (1,0), (0,1), (1,1), q = (x0 + i, yy + j).  A tap is skipped if q lies
+ *         outside the window; or HP[q].w != 0 is false or HE[q].w > 0 is false; or dot(N, HN[q]) >= normal_min is false; or
+ *         fabsf(dot(N, HP[q].xyz - I)) / sigma_z <= 1 is false.  For a tap that is kept:
+ *           w = (i ? tx : 1 - tx) * (j ? ty : 1 - ty);  if w > 0: sw = sw + w, se = se + w * HE[q].rgb per channel, sl = sl + w * HE[q].w.
+ *   if sw > 0:  Eh = se / sw per channel, L = sl / sw, L1 = min(L + 1, (float)max_len), al = max(1 / L1, alpha_min),
+ *               out = (Eh + al * (E - Eh), L1)
+ *   else        out = (E, 1).
+ * The new history is HE = out, HP = P, HN = N, cam' = cam, with the call's geometry.  Guide values that are not finite and normals that
+ * are not unit vectors are legal input: the result is whatever the operations above give.
+ * Parameters: alpha_min in (0, 1]; max_len in 1..VXRT_TEMPORAL_MAX_LEN; sigma_z > 0 (+inf is legal and switches the plane test off);
+ * normal_min finite.  Anything else is refused.
+ *
+ * THE LIMIT.  Reprojection follows the CAMERA.  There are no motion vectors: for an instance that moved (vxrt_accel_set_transforms)
+ * or vertices that were refitted (vxrt_accel_refit) the previous frame is looked up as if the surface had stood still.  The plane and
+ * normal tests then reject most of the stale history; vxrt_history_reset is the sure way.
+ *
+ * THE FRAME.  vxrt_render_path_temporal is vxrt_render_path_denoised with one step more: between demodulation and the first a-trous
+ * pass out = T(E, P, N; history, cam', temporal) with the frame's own guides, the filter runs on out.rgb, remodulation and pack are
+ * unchanged.  With dn->iterations = 0 the accumulated signal is remodulated directly: colour = D + A * out.rgb, the background for a
+ * miss.  The first frame on an empty history with iterations >= 1 is therefore vxrt_render_path_denoised bit for bit.  One launch more
+ * per frame; nothing else changes, no rays are traced for it and no host synchronisation is added.
+ *
+ * Contract of the calls below.  Asynchronous on `stream`.  Calls on one history are the caller's to order (one stream, or events);
+ * histories are independent of each other and of vxrt_accel_frames_in_flight.  A call that returns -1 returns before anything is
+ * launched and leaves the history, dst and out4 as they were: null pointers, a camera field that is not finite, position / normal not
+ * 16-byte aligned, a window of 2^31 pixels or more, a window of more pixels than the history was created for (width * rows), bad
+ * parameters, W or H = 0, y0 > y1, y1 > H.  An empty window (y0 == y1) returns 0 and leaves the history as it was. */
+#define VXRT_TEMPORAL_MAX_LEN 1024
+typedef struct vxrt_temporal_params {
+  float alpha_min;     /* lower bound of the weight of the new frame, in (0, 1]; 1 = no accumulation */
+  uint32_t max_len;    /* cap of the accumulated length, 1..VXRT_TEMPORAL_MAX_LEN */
+  float sigma_z;       /* a tap is kept when its hit point lies within sigma_z of the pixel's tangent plane, > 0 */
+  float normal_min;    /* a tap is kept when dot(N, N') >= normal_min; finite */
+} vxrt_temporal_params_t;
+typedef struct vxrt_history vxrt_history_t;
+/* buffers for windows of up to width * rows pixels (96 bytes each); -1 for width or rows = 0, 2^31 pixels or more, or no memory */
+int vxrt_history_create(uint32_t width, uint32_t rows, vxrt_history_t** history);
+/* frees the buffers; work in flight that uses the history has to be finished (the call waits for the device) */
+int vxrt_history_destroy(vxrt_history_t* history);
+/* makes the history empty (host state only: nothing is launched) */
+int vxrt_history_reset(vxrt_history_t* history);
+/* HE of the last frame, (E_acc.rgb, len) per pixel of its window, into out4 (device, rows * width * 4 floats): one copy on `stream`.
+ * -1 for an empty history (there is no window to read) or a null pointer. */
+int vxrt_history_read(vxrt_history_t* history, float* out4, void* stream);
+/* The step alone on caller-owned DEVICE buffers of the window (rows [y0, y1) of a W x H frame seen from `cam`): signal 3 floats per
+ * pixel, position and normal 4 floats per pixel and 16-byte aligned, out4 = out, 4 floats per pixel.  `cam` and `prm` are host pointers
+ * read during the call. */
+int vxrt_temporal_accumulate(vxrt_history_t* history, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                             const float* signal, const float* position, const float* normal, const vxrt_temporal_params_t* prm,
+                             float* out4, void* stream);
+/* The frame.  cam must not be NULL (the fixed camera has no vxrt_camera_t); everything vxrt_render_path_denoised refuses is refused,
+ * a non-zero alpha table included. */
+int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                              const vxrt_temporal_params_t* temporal, vxrt_history_t* history,
+                              uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
+                              unsigned long long* rays_traced /* optional */, void* stream);
+
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,
  * invTransform, bvh_offset@128, tex_offset@136, tex_width@144, tex_height@148, reflectivity@152),

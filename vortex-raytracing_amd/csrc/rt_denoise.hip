@@ -1,5 +1,6 @@
 // Guided a-trous filter of denoised path frames (vxrt_render_path_denoised, vxrt_denoise; the definition is in include/vortex_hip.h,
-// tests/denoise_ref.py restates it, DESIGN.md s2 "Denoised path frames" has the launch sequence and the measurements).
+// tests/denoise_ref.py restates it, DESIGN.md s2 "Denoised path frames" has the launch sequence and the measurements), and below it the
+// temporal accumulation that may precede it (vxrt_render_path_temporal, vxrt_temporal_accumulate; DESIGN.md s2 "Temporal accumulation").
 //
 // Per iteration one launch: a 25-tap stencil with stride `step` over three float4 arrays per pixel -- the signal S = (r, g, b, lum), the
 // position guide P = (I, hit flag) and the normal guide N.  The luminance travels in the signal's fourth component: the pass that
@@ -15,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <cmath>
 #include "rt_internal.h"
 
 #define DN_TX 32u   // tile: 32 x 8 pixels, one per thread of a 256-thread workgroup (a wavefront = 2 rows of 32)
@@ -149,6 +151,101 @@ __global__ __launch_bounds__(256) void rt_dn_demodulate_kernel(uint32_t n, uint3
 }
 
 // ---------------------------------------------------------------------------------------------
+// Temporal accumulation (vxrt_temporal_accumulate, vxrt_render_path_temporal; the definition is in include/vortex_hip.h,
+// tests/temporal_ref.py restates it).  One launch per frame, one thread per pixel of a 32 x 8 tile as in the a-trous kernel: the pixel's
+// hit point goes through the previous camera's reciprocal basis (computed on the host in double, passed by value), and up to four taps of
+// three 16-byte loads each are gathered from the previous frame's set of history buffers.  Reprojection is a translation locally, so
+// the lanes of a row read neighbouring addresses and every history line is used by the four pixels around it out of L1 / L2.  The taps'
+// loads are issued before any of them is tested (a tap outside the window reads the pixel's own address and is dropped).  Almost no
+// arithmetic: the pass is bound by its 160 B per pixel of compulsory traffic (E, P, N in; the signal and the three history entries out;
+// HE, HP, HN of the previous frame once each).
+// ---------------------------------------------------------------------------------------------
+enum { TP_OUT_SIGNAL = 0, TP_OUT_LEN = 1, TP_OUT_PATH = 2 };
+
+struct TpArgs {
+  uint32_t W, rows, tiles_x, have, max_len;     // have: the history is not empty
+  float fW, fH, fy0, frows;                     // (float) of the frame's size, the window's first row and its number of rows
+  float pos[3], Rr[3], Ur[3], Fr[3], vp[2];     // previous camera: position, reciprocal basis, viewplane
+  float alpha_min, sigma_z, normal_min;
+  const float4* E4; const float* E3;            // the frame's signal (E, lum) | a stand-alone call's, 3 floats per pixel
+  const float4* P; const float4* N;
+  const float4* he; const float4* hp; const float4* hn;   // the previous frame's set
+  float4* he_o; float4* hp_o; float4* hn_o;               // this frame's
+  float4* sig;                                  // TP_OUT_SIGNAL: (out.rgb, lum) for the first a-trous pass (may be E4: a pixel reads only its own entry)
+  float* out4;                                  // TP_OUT_LEN: (out.rgb, len)
+  DnArgs path;                                  // TP_OUT_PATH: lit, alb, dst, colors, y0, W
+};
+
+__device__ __forceinline__ float tp_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+template <int OUT>
+__global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(TpArgs A) {
+  const uint32_t bx = blockIdx.x % A.tiles_x, by = blockIdx.x / A.tiles_x;
+  const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
+  if (x >= A.W || y >= A.rows) return;
+  const size_t p = (size_t)y * A.W + x;
+  float er, eg, eb;
+  if constexpr (OUT == TP_OUT_LEN) { er = A.E3[3 * p]; eg = A.E3[3 * p + 1]; eb = A.E3[3 * p + 2]; }
+  else { const float4 e = A.E4[p]; er = e.x; eg = e.y; eb = e.z; }
+  const float4 Pp = A.P[p], Np = A.N[p];
+  const bool hit = Pp.w != 0.f;
+  float orr = er, og = eg, ob = eb, olen = hit ? 1.f : 0.f;
+  if (hit && A.have) {
+    const float dx = Pp.x - A.pos[0], dy = Pp.y - A.pos[1], dz = Pp.z - A.pos[2];
+    const float a = tp_dot(dx, dy, dz, A.Rr[0], A.Rr[1], A.Rr[2]);
+    const float b = tp_dot(dx, dy, dz, A.Ur[0], A.Ur[1], A.Ur[2]);
+    const float c = tp_dot(dx, dy, dz, A.Fr[0], A.Fr[1], A.Fr[2]);
+    if (c > 0.f) {
+      const float fx = (((a / c) / A.vp[0]) + 0.5f) * A.fW - 0.5f;
+      const float fy = ((((b / c) / A.vp[1]) + 0.5f) * A.fH - 0.5f) - A.fy0;
+      if (fx > -1.f && fx < A.fW && fy > -1.f && fy < A.frows) {
+        const float flx = floorf(fx), fly = floorf(fy);
+        const float tx = fx - flx, ty = fy - fly;
+        const int64_t x0 = (int64_t)flx, yy = (int64_t)fly;   // (-1 .. W - 1, -1 .. rows - 1)
+        float4 He[4], Hp[4], Hn[4];
+        bool in[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int64_t qx = x0 + (k & 1), qy = yy + (k >> 1);
+          in[k] = qx >= 0 && qx < (int64_t)A.W && qy >= 0 && qy < (int64_t)A.rows;
+          const size_t q = in[k] ? (size_t)qy * A.W + (size_t)qx : p;
+          He[k] = A.he[q]; Hp[k] = A.hp[q]; Hn[k] = A.hn[q];
+        }
+        float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!in[k]) continue;
+          if (!(Hp[k].w != 0.f) || !(He[k].w > 0.f)) continue;
+          if (!(tp_dot(Np.x, Np.y, Np.z, Hn[k].x, Hn[k].y, Hn[k].z) >= A.normal_min)) continue;
+          const float ex = Hp[k].x - Pp.x, ey = Hp[k].y - Pp.y, ez = Hp[k].z - Pp.z;
+          if (!(fabsf(tp_dot(Np.x, Np.y, Np.z, ex, ey, ez)) / A.sigma_z <= 1.f)) continue;
+          const float w = ((k & 1) ? tx : 1.f - tx) * ((k >> 1) ? ty : 1.f - ty);
+          if (w > 0.f) {
+            sw = sw + w;
+            sr = sr + w * He[k].x; sg = sg + w * He[k].y; sb = sb + w * He[k].z;
+            sl = sl + w * He[k].w;
+          }
+        }
+        if (sw > 0.f) {
+          const float hr = sr / sw, hg = sg / sw, hb = sb / sw, L = sl / sw;
+          const float L1 = std_min(L + 1.f, (float)A.max_len);
+          const float r1 = 1.f / L1;
+          const float al = r1 < A.alpha_min ? A.alpha_min : r1;
+          orr = hr + al * (er - hr); og = hg + al * (eg - hg); ob = hb + al * (eb - hb);
+          olen = L1;
+        }
+      }
+    }
+  }
+  A.he_o[p] = make_float4(orr, og, ob, olen);
+  A.hp_o[p] = Pp;
+  A.hn_o[p] = Np;
+  if constexpr (OUT == TP_OUT_SIGNAL) A.sig[p] = make_float4(orr, og, ob, dn_lum(orr, og, ob));
+  else if constexpr (OUT == TP_OUT_LEN) { float* o = A.out4 + 4 * p; o[0] = orr; o[1] = og; o[2] = ob; o[3] = olen; }
+  else dn_write<DN_OUT_PATH>(A.path, x, y, orr, og, ob, hit);
+}
+
+// ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
 bool dn_params_ok(const vxrt_denoise_params_t* dn) {
@@ -193,7 +290,132 @@ int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0,
   return dn_filter(s, W, rows, dn, sig, geo, nrm, DN_OUT_PATH, last);
 }
 
+// ---- temporal accumulation: the history and the launch ----
+struct vxrt_history {
+  uint64_t cap = 0;                  // pixels each buffer holds
+  float4* he[2] = {nullptr, nullptr}; float4* hp[2] = {nullptr, nullptr}; float4* hn[2] = {nullptr, nullptr};
+  uint32_t cur = 0;                  // the set the last frame wrote
+  bool empty = true;
+  vxrt_camera_t cam{};               // of the last frame, with its geometry
+  uint32_t W = 0, H = 0, y0 = 0, y1 = 0;
+};
+
+static bool tp_camera_ok(const vxrt_camera_t* c) {
+  if (!c) return false;
+  const float* f = &c->pos[0];
+  for (int i = 0; i < 14; ++i) if (!std::isfinite(f[i])) return false;
+  return true;
+}
+
+static bool tp_params_ok(const vxrt_temporal_params_t* t) {
+  return t && t->alpha_min > 0.0f && t->alpha_min <= 1.0f && t->max_len >= 1u && t->max_len <= VXRT_TEMPORAL_MAX_LEN && t->sigma_z > 0.0f &&
+         std::isfinite(t->normal_min);   // (the comparisons are false for NaN)
+}
+
+bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels) {
+  return h && tp_params_ok(t) && pixels <= h->cap;
+}
+
+// the reciprocal basis of camera c (the header's rule: doubles, no contraction, one rounding to fp32 per component)
+static void tp_reciprocal_basis(const vxrt_camera_t& c, float Rr[3], float Ur[3], float Fr[3]) {
+  const double R[3] = {c.right[0], c.right[1], c.right[2]}, U[3] = {c.up[0], c.up[1], c.up[2]}, F[3] = {c.forward[0], c.forward[1], c.forward[2]};
+  auto cross = [](const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+  };
+  double UF[3], FR[3], RU[3];
+  cross(U, F, UF); cross(F, R, FR); cross(R, U, RU);
+  const double det = (R[0] * UF[0] + R[1] * UF[1]) + R[2] * UF[2];
+  for (int k = 0; k < 3; ++k) { Rr[k] = (float)(UF[k] / det); Ur[k] = (float)(FR[k] / det); Fr[k] = (float)(RU[k] / det); }
+}
+
+// One step on history h: the checks are the caller's (window of at most h->cap pixels, not empty).  Launches, then makes the written set,
+// `cam` and the geometry the history's state.
+static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
+                     const vxrt_temporal_params_t* t, int out, TpArgs A) {
+  const uint32_t rows = y1 - y0;
+  const bool have = !h->empty && h->W == W && h->H == H && h->y0 == y0 && h->y1 == y1;   // (another window: an implicit reset)
+  const uint32_t prev = h->cur, next = have ? h->cur ^ 1u : h->cur;
+  A.W = W; A.rows = rows; A.tiles_x = (W + DN_TX - 1u) / DN_TX; A.have = have ? 1u : 0u; A.max_len = t->max_len;
+  A.fW = (float)W; A.fH = (float)H; A.fy0 = (float)y0; A.frows = (float)rows;
+  if (have) {
+    for (int k = 0; k < 3; ++k) A.pos[k] = h->cam.pos[k];
+    tp_reciprocal_basis(h->cam, A.Rr, A.Ur, A.Fr);
+    A.vp[0] = h->cam.viewplane[0]; A.vp[1] = h->cam.viewplane[1];
+  }
+  A.alpha_min = t->alpha_min; A.sigma_z = t->sigma_z; A.normal_min = t->normal_min;
+  A.he = h->he[prev]; A.hp = h->hp[prev]; A.hn = h->hn[prev];
+  A.he_o = h->he[next]; A.hp_o = h->hp[next]; A.hn_o = h->hn[next];
+  const dim3 grid(A.tiles_x * ((rows + DN_TY - 1u) / DN_TY)), block(256);
+  if (out == TP_OUT_SIGNAL) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_SIGNAL>), grid, block, 0, s, A);
+  else if (out == TP_OUT_LEN) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_LEN>), grid, block, 0, s, A);
+  else hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_PATH>), grid, block, 0, s, A);
+  if (hipGetLastError() != hipSuccess) return -1;
+  h->cur = next; h->empty = false; h->cam = *cam; h->W = W; h->H = H; h->y0 = y0; h->y1 = y1;
+  return 0;
+}
+
+int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
+                   const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
+                   const float4* alb, uint32_t* dst, float* colors) {
+  TpArgs A{};
+  A.E4 = sig; A.P = geo; A.N = nrm; A.sig = sig;
+  A.path.W = W; A.path.lit = lit; A.path.alb = alb; A.path.dst = dst; A.path.colors = colors; A.path.y0 = y0;
+  return tp_launch(s, h, cam, W, H, y0, y1, t, filtered ? TP_OUT_SIGNAL : TP_OUT_PATH, A);
+}
+
 extern "C" {
+
+int vxrt_history_create(uint32_t width, uint32_t rows, vxrt_history_t** history) {
+  const uint64_t n = (uint64_t)width * rows;
+  if (!history || n == 0 || n > 0x7fffffffull) return -1;
+  vxrt_history_t* h = new vxrt_history;
+  bool ok = true;
+  for (int k = 0; k < 2 && ok; ++k)
+    ok = hipMalloc((void**)&h->he[k], n * 16u) == hipSuccess && hipMalloc((void**)&h->hp[k], n * 16u) == hipSuccess &&
+         hipMalloc((void**)&h->hn[k], n * 16u) == hipSuccess;
+  if (!ok) {
+    for (int k = 0; k < 2; ++k) { (void)hipFree(h->he[k]); (void)hipFree(h->hp[k]); (void)hipFree(h->hn[k]); }
+    delete h;
+    return -1;
+  }
+  h->cap = n;
+  *history = h;
+  return 0;
+}
+
+int vxrt_history_destroy(vxrt_history_t* h) {
+  if (!h) return -1;
+  (void)hipDeviceSynchronize();
+  for (int k = 0; k < 2; ++k) { (void)hipFree(h->he[k]); (void)hipFree(h->hp[k]); (void)hipFree(h->hn[k]); }
+  delete h;
+  return 0;
+}
+
+int vxrt_history_reset(vxrt_history_t* h) {
+  if (!h) return -1;
+  h->empty = true;
+  return 0;
+}
+
+int vxrt_history_read(vxrt_history_t* h, float* out4, void* stream) {
+  if (!h || !out4 || h->empty) return -1;
+  const uint64_t n = (uint64_t)h->W * (h->y1 - h->y0);
+  return hipMemcpyAsync(out4, h->he[h->cur], n * 16u, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? 0 : -1;
+}
+
+int vxrt_temporal_accumulate(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                             const float* signal, const float* position, const float* normal, const vxrt_temporal_params_t* prm,
+                             float* out4, void* stream) {
+  if (!h || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;
+  if ((((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
+  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
+  if (y0 == y1) return 0;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull || n > h->cap) return -1;
+  TpArgs A{};
+  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
+  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A);
+}
 
 uint64_t vxrt_denoise_scratch_bytes(uint32_t width, uint32_t rows) { return 32ull * width * rows; }
 

@@ -1,6 +1,6 @@
 // Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
 // level-2 entry points), rt_accel.hip (acceleration-layout build, refit), rt_secondary.hip (the tails of mirror-bounce,
-// ambient-occlusion and path frames) and rt_denoise.hip (the a-trous filter of denoised path frames) share: the types, and the
+// ambient-occlusion and path frames) and rt_denoise.hip (the a-trous filter and the temporal accumulation of denoised path frames) share: the types, and the
 // few host functions one unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of
 // shading, which rt_kernels.hip and rt_secondary.hip share, is in rt_shading.h.
 #pragma once
@@ -185,6 +185,15 @@ int dn_launch_demodulate(hipStream_t s, uint32_t n, uint32_t W, uint32_t y0, con
 // dst / colors (full-frame addressing, rows from y0)
 int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn, float4* const sig[2], const float4* geo,
                           const float4* nrm, const float4* lit, const float4* alb, uint32_t* dst, float* colors);
+// temporal accumulation (vxrt_render_path_temporal): what the entry point checks before anything is launched -- the parameters, and that
+// the history holds a window of `pixels` pixels
+bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels);
+// out = T(E, P, N; h, the history's camera, t) for the window, one launch: E = sig's rgb, P = geo, N = nrm.  filtered: (out.rgb, lum) goes
+// back into sig (in place: a pixel reads only its own entry) for dn_launch_path_filter; else the pass remodulates out.rgb with lit / alb,
+// packs and writes dst / colors itself.  The history then holds this frame, `cam` and the geometry.
+int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
+                   const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
+                   const float4* alb, uint32_t* dst, float* colors);
 
 // ---------------------------------------------------------------------------------------------
 // rt_kernels.hip <-> rt_secondary.hip: a frame as an entry point asks for it, the per-frame control block, growing device buffers,
@@ -220,6 +229,8 @@ struct RenderRequest {
   const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;
+  const vxrt_temporal_params_t* temporal = nullptr; // ... with temporal accumulation before the filter (vxrt_render_path_temporal), into
+  vxrt_history_t* history = nullptr;                //     this history
   void* stream = nullptr;
   Counting counting = Counting::TIMED;
   bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set

@@ -1918,6 +1918,8 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
                  r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
+  // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
+  if ((r.temporal || r.history) && (!r.denoise || !r.cams || !r.temporal || !r.history)) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
   return 1;
@@ -2470,6 +2472,21 @@ int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
   r.denoise = dn; r.aov = aov;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+// Denoised path frame with temporal accumulation (see the header): the step of rt_denoise.hip between demodulation and the filter
+int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                              const vxrt_temporal_params_t* temporal, vxrt_history_t* history, uint32_t* dst, float* colors,
+                              const vxrt_path_aov_t* aov, unsigned long long* rays_traced, void* stream) {
+  if (!path || !dn || !camera_ok(cam)) return -1;
+  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;   // (a bad window is check_request's to refuse)
+  if (!tp_request_ok(history, temporal, pixels)) return -1;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history;
   r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }

@@ -674,11 +674,19 @@ int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const S
 // End of a denoised path frame's tail in place of rt_path_final_kernel (the kernels and their launches are in rt_denoise.hip): demodulate
 // the pixels' accumulators into the context's first signal buffer and write the guide outputs, then one launch per a-trous iteration,
 // ping-pong between the two signal buffers, the last of which remodulates, packs and writes.  n = pixels of the window.
+// With temporal accumulation (vxrt_render_path_temporal) one launch between the two blends the first signal buffer with the reprojected
+// history, in place, so the ping-pong order stays; without iterations that launch is the end of the frame.
 static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
   hipStream_t s = (hipStream_t)r.stream;
   if (!grow_device({{(void**)&c->dn_sig[0], 16}, {(void**)&c->dn_sig[1], 16}}, &c->dn_cap, n, GrowSync::STREAM, s)) return -1;
   if (dn_launch_demodulate(s, n, r.width, r.y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, r.path->spp, r.path->bounces == 0 ? 1u : 0u,
                            c->dn_sig[0], r.aov) != 0) return -1;
+  if (r.temporal) {
+    const bool filtered = r.denoise->iterations != 0;
+    if (tp_launch_path(s, r.history, r.cams, r.width, r.height, r.y0, r.y1, r.temporal, c->dn_sig[0], c->pt_geo, c->pt_nrm, filtered, c->pt_lit, c->pt_alb,
+                       r.dst, r.colors) != 0) return -1;
+    if (!filtered) return 0;
+  }
   return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);
 }
 
@@ -736,7 +744,7 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
     hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
                        (const float4*)c->pt_L, c->pt_acc);
   }
-  if (r.denoise && r.denoise->iterations) return render_denoise_tail(c, r, n32);
+  if (r.denoise && (r.denoise->iterations || r.temporal)) return render_denoise_tail(c, r, n32);
   if (r.denoise && r.aov && dn_launch_demodulate(s, n32, width, y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, pp.spp, pp.bounces == 0 ? 1u : 0u,
                                                  nullptr, r.aov) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
   hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,

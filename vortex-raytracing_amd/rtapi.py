@@ -574,3 +574,80 @@ def denoise(width, rows, signal_ptr, position_ptr, normal_ptr, denoise, out_ptr,
     """vxrt_denoise: the a-trous filter alone over a window of rows x width pixels (signal / out: 3 floats per pixel; position / normal: 4)."""
     check(_denoise_lib().vxrt_denoise(width, rows, signal_ptr, position_ptr, normal_ptr, C.byref(denoise), out_ptr, scratch_ptr, scratch_bytes, stream),
           "vxrt_denoise")
+
+
+TEMPORAL_MAX_LEN = 1024   # VXRT_TEMPORAL_MAX_LEN
+
+
+class TemporalParams(C.Structure):   # vxrt_temporal_params_t
+    _fields_ = [("alpha_min", C.c_float), ("max_len", C.c_uint32), ("sigma_z", C.c_float), ("normal_min", C.c_float)]
+
+
+def _temporal_lib():
+    L = _denoise_lib()
+    L.vxrt_history_create.restype = C.c_int
+    L.vxrt_history_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    for f in (L.vxrt_history_destroy, L.vxrt_history_reset):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+    L.vxrt_history_read.restype = C.c_int
+    L.vxrt_history_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_temporal_accumulate.restype = C.c_int
+    L.vxrt_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]
+    L.vxrt_render_path_temporal.restype = C.c_int
+    L.vxrt_render_path_temporal.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
+                                            C.POINTER(PathParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(PathAov), C.c_void_p, C.c_void_p]
+    return L
+
+
+class History:
+    """vxrt_history_t: the accumulated signal of the previous frame of one window, for windows of up to width * rows pixels (96 bytes per
+    pixel of device memory).  A context manager; `handle` is what the C calls take.  Calls on one history are the caller's to order."""
+
+    def __init__(self, width, rows):
+        h = C.c_void_p()
+        check(_temporal_lib().vxrt_history_create(int(width), int(rows), C.byref(h)), "vxrt_history_create")
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            check(_temporal_lib().vxrt_history_destroy(self.handle), "vxrt_history_destroy")
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def reset(self):
+        """makes the history empty: the next frame starts the accumulation again"""
+        check(_temporal_lib().vxrt_history_reset(self.handle), "vxrt_history_reset")
+
+    def read(self, out_ptr, stream=None):
+        """vxrt_history_read: (E_acc.rgb, len) per pixel of the last frame's window into device memory; raises for an empty history"""
+        check(_temporal_lib().vxrt_history_read(self.handle, out_ptr, stream), "vxrt_history_read")
+
+
+def _history(h):
+    return h.handle if isinstance(h, History) else h
+
+
+def temporal_accumulate(history, cam, width, height, y0, y1, signal_ptr, position_ptr, normal_ptr, temporal, out_ptr, stream=None):
+    """vxrt_temporal_accumulate: the accumulation step alone over rows [y0, y1) of a width x height frame seen from `cam` (signal: 3 floats
+    per pixel; position / normal: 4; out: 4 = the blended signal and the accumulated length); `temporal`: a TemporalParams."""
+    check(_temporal_lib().vxrt_temporal_accumulate(_history(history), C.byref(_camera(cam)), width, height, y0, y1, signal_ptr, position_ptr, normal_ptr,
+                                                   C.byref(temporal), out_ptr, stream), "vxrt_temporal_accumulate")
+
+
+def render_path_temporal(accel, cam, width, height, y0, y1, params, spp, bounces, denoise, temporal, history, dst_ptr, seed=0, shadow=0, colors_ptr=None,
+                         aov=None, rays_ptr=None, stream=None):
+    """vxrt_render_path_temporal: render_path_denoised whose demodulated indirect term is first blended with `history` (a History),
+    reprojected through the camera of the history's previous frame; `temporal`: a TemporalParams.  `cam` must be a camera."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_temporal_lib().vxrt_render_path_temporal(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), C.byref(denoise),
+                                                    C.byref(temporal), _history(history), dst_ptr, colors_ptr, None if aov is None else C.byref(aov),
+                                                    rays_ptr, stream), "vxrt_render_path_temporal")
