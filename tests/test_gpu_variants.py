@@ -55,6 +55,26 @@ def test_ray_pool_trace_kernel_stays_bit_equal(vrt, gpu_device):
         assert " passed" in r.stdout
 
 
+def test_secondary_ray_sort_stays_bit_equal(vrt, gpu_device):
+    """The secondary-ray sort (rt_bin_count_kernel / rt_bin_scan_kernel / rt_bin_scatter_kernel, csrc/rt_secondary.hip, and the
+    order[] indirection of the trace kernel with a job count that stays on the device) lost its A/B (profiles/r02_f_secondary_sort.txt)
+    and is off by default; VXRT_SORT_SECONDARY=1 switches it on for the ambient-occlusion tail, its one caller.  A child process runs
+    the AO tests through it -- the sample counts, row windows and the frame without a hit of tests/test_gpu_ao_tail.py, its two
+    windows of more than 128 cells (the scan then takes 2 and 3 counters per thread), and the AO tests there were before -- and a second
+    one adds VXRT_AO_BATCH=2880, so that the sort is redone per batch, with another number of samples in the last one.  The line the
+    library prints under VXRT_DEBUG shows that the children ran with the knobs."""
+    files = [os.path.join(ROOT, "tests", f) for f in ("test_gpu_ao_tail.py", "test_gpu_parity.py", "test_gpu_camera_secondary.py")]
+    new = "(test_gpu_ao_tail and (in_process or large_windows))"
+    old = "ambient_occlusion or (test_gpu_camera_secondary and not lds_staging and not refusals and not stale_accel)"
+    for extra, select, line in (({}, new + " or " + old, "ao_batch=%d sort_secondary=1" % (32 << 20)),
+                                ({"VXRT_AO_BATCH": "2880"}, new, "ao_batch=2880 sort_secondary=1")):
+        env = dict(os.environ, VXRT_SORT_SECONDARY="1", VXRT_DEBUG="1", **extra)
+        r = subprocess.run([sys.executable, "-m", "pytest"] + files + ["-x", "-q", "-s", "-m", "gpu", "-k", select],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        assert r.returncode == 0, (extra, r.stdout[-3000:], r.stderr[-1500:])
+        assert " passed" in r.stdout and line in r.stderr, (extra, r.stdout[-1500:], r.stderr[-1500:])
+
+
 def test_gpu_builder_without_reinsertion_and_with_other_schedules(vrt, gpu_device):
     """vxrt_bvh_build optimises its binary tree by parallel reinsertion (csrc/bvh_builder.hip step 4b, four iterations by default).  The plain
     PLOC tree (VXRT_BVH_REINSERT=0: the builder of rounds 3-4) and a longer, sparser schedule (12 iterations, every third node searching per

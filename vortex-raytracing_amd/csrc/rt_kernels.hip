@@ -1647,8 +1647,8 @@ static uint32_t* status_word() {
 #endif
 
 // Measurement knobs of the render and trace path (docs/KNOBS.md), read from the environment once per process: on the first call
-// that asks for one.  Each keeps the parsing it always had (atoi, atoll, or "first character is 0").  (The two of the secondary
-// tails, VXRT_PATH_BATCH and VXRT_SORT_SECONDARY, are read the same way in rt_secondary.hip.)
+// that asks for one.  Each keeps the parsing it always had (atoi, atoll, or "first character is 0").  (The three of the secondary
+// tails, VXRT_PATH_BATCH, VXRT_AO_BATCH and VXRT_SORT_SECONDARY, are read the same way in rt_secondary.hip.)
 struct HostKnobs {
   uint32_t shard_rot, lpt_batch_max;
   bool lpt, lpt_batch;                  // on unless the value begins with '0'

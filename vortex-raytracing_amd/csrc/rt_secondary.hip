@@ -473,7 +473,11 @@ __global__ __launch_bounds__(256) void rt_path_final_kernel(uint32_t n, uint32_t
 // 64 consecutive rays shares origins but not directions.  Counting sort by key = direction octant x origin cell (the 16x16-pixel
 // cell of the ray's pixel: hit points of neighbouring pixels are neighbours in space), so that 64 consecutive queue positions
 // hold rays that start in one small region AND point into the same octant.  Only the ORDER in which rays are traced changes:
-// the kernel reads ray order[q] and writes hit record order[q], so every result is bit-identical (tests compare them all).
+// the kernel reads ray order[q] and writes hit record order[q], so every result is bit-identical.
+// Only the ambient-occlusion tail calls the sort today (render_ao_tail, per batch of samples): the one diffuse bounce it was also
+// measured on has since become a single persistent launch without a ray buffer.  It is off by default (VXRT_SORT_SECONDARY=1 turns it
+// on); tests/test_gpu_variants.py::test_secondary_ray_sort_stays_bit_equal runs the AO tests with it in child processes -- frames whose
+// scan takes one, two and three counters per thread among them, and frames whose batches are sorted one by one.
 // ---------------------------------------------------------------------------------------------
 #define BIN_CELL_SHIFT 4u   // 16 x 16 pixels
 __global__ __launch_bounds__(256) void rt_bin_count_kernel(uint64_t cap, const uint32_t* __restrict__ hdr, const float* __restrict__ rays,
@@ -514,6 +518,7 @@ __global__ __launch_bounds__(256) void rt_bin_scatter_kernel(uint64_t cap, const
 // host: the three tails render_common (rt_kernels.hip) ends such a frame with
 // ---------------------------------------------------------------------------------------------
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 // Paths per batch of a path frame (VXRT_PATH_BATCH).  A path costs 136 bytes of frame-context storage -- 80 of state (I, N, dir, Lc, thr:
@@ -523,12 +528,14 @@ __global__ __launch_bounds__(256) void rt_bin_scatter_kernel(uint64_t cap, const
 #define PATH_BATCH_PATHS (4ull << 20)
 #define AO_BATCH_RAYS (32ull << 20)   // rays per batch of an ambient-occlusion frame
 
-// The two measurement knobs of this unit (docs/KNOBS.md), read from the environment once per process, together: on the first call that
-// asks for one.  Each keeps the parsing it always had.
+// The three measurement knobs of this unit (docs/KNOBS.md), read from the environment once per process, together: on the first call that
+// asks for one.  Each keeps the parsing it always had.  With VXRT_DEBUG set, the values read go to stderr in one line, so that a test
+// that runs a child process with a knob can see that the child took it.
 struct SecondaryKnobs {
   uint64_t path_batch;   // paths per batch of a path frame (see render_path_tail)
+  uint64_t ao_batch;     // rays per batch of an ambient-occlusion frame (see render_ao_tail); VXRT_AO_BATCH, parsed as VXRT_PATH_BATCH is
   // VXRT_SORT_SECONDARY=1: trace the secondary rays in (direction octant, origin cell) order instead of generation order.  OFF by
-  // default: measured SLOWER on both passes that use it (diffuse bounce 1.53 -> 1.95 ms, 10M-triangle hairball AO 9.2 -> 16.6 ms,
+  // default: measured SLOWER on both passes that used it then (diffuse bounce 1.53 -> 1.95 ms, 10M-triangle hairball AO 9.2 -> 16.6 ms,
   // profiles/r02_f_secondary_sort.txt).  The traversal is bound by per-lane VALU work, which coherence does not reduce, and the
   // generation order already puts the 16 samples of one pixel (AO) / 64 neighbouring pixels (bounce) side by side.
   bool sort_secondary;
@@ -537,7 +544,11 @@ static const SecondaryKnobs& secondary_knobs() {
   static const SecondaryKnobs knobs = [] {
     SecondaryKnobs k;
     { const char* e = getenv("VXRT_PATH_BATCH"); const long long v = e ? atoll(e) : 0; k.path_batch = v > 0 ? (uint64_t)v : PATH_BATCH_PATHS; }
+    { const char* e = getenv("VXRT_AO_BATCH"); const long long v = e ? atoll(e) : 0; k.ao_batch = v > 0 ? (uint64_t)v : AO_BATCH_RAYS; }
     { const char* e = getenv("VXRT_SORT_SECONDARY"); k.sort_secondary = e && e[0] == '1'; }
+    if (getenv("VXRT_DEBUG"))
+      fprintf(stderr, "[vxrt] secondary knobs: path_batch=%llu ao_batch=%llu sort_secondary=%d\n", (unsigned long long)k.path_batch,
+              (unsigned long long)k.ao_batch, k.sort_secondary ? 1 : 0);
     return k;
   }();
   return knobs;
@@ -619,7 +630,7 @@ int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, con
 }
 
 // Tail of an ambient-occlusion frame (replaces the plain shading pass): the pixels with a hit are listed on
-// the device, their occlusion rays are generated in batches of whole samples (<= AO_BATCH_RAYS rays) and each
+// the device, their occlusion rays are generated in batches of whole samples (<= AO_BATCH_RAYS rays, or VXRT_AO_BATCH) and each
 // batch is one any-hit launch whose job count stays in device memory.  No host synchronisation unless a buffer grows.
 int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
   const SceneDev& sc = a->dev;
@@ -629,7 +640,7 @@ int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const S
   const uint64_t n = (uint64_t)width * (y1 - y0);
   if (ao->reserved == VXRT_AO_MODE_DIFFUSE_BOUNCE) return -1;    // (the diffuse-bounce frame is JOB_RENDER_GI: it has no tail)
   if (n > 0x7fffffffull || ao->spp == 0) return -1;
-  uint32_t ns = (uint32_t)std::min<uint64_t>(ao->spp, std::max<uint64_t>(1, AO_BATCH_RAYS / n));   // samples per batch
+  uint32_t ns = (uint32_t)std::min<uint64_t>(ao->spp, std::max<uint64_t>(1, secondary_knobs().ao_batch / n));   // samples per batch
   const uint64_t ray_cap = n * ns;
   if (ray_cap > 0x7fffffffull) return -1;
   if (!c->ao_hdr && hipMalloc((void**)&c->ao_hdr, 8) != hipSuccess) return -1;
