@@ -210,7 +210,8 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* accel);
  * to 17; 1 -> 1 if the scene is at most 16 levels deep and its timed launches keep 48-entry traversal stacks (deeper scenes: the
  * reference's 32 levels, 96 entries + the LDS part); 2 -> 1 if the TLAS root is a single identity instance; 3 -> 1 if the scene
  * takes the ldexp decode / generic slab form; 4 -> 1 while a non-zero alpha table is set (vxrt_accel_set_alpha_test); 5 -> 1 if the
- * timed plain / shadow frames take the identity-root kernels (2 holds, 1 holds, 3 and 4 do not). */
+ * timed plain / shadow frames take the identity-root kernels (2 holds, 1 holds, 3 and 4 do not); 6 -> the VXRT_REFIT_* mask of the
+ * motion snapshot the accel holds (vxrt_accel_motion_snapshot), 0 for none. */
 int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
 
 /* Refit: new boxes for a scene whose instances or vertices moved, in place, without a rebuild (extension; the reference has no refit,
@@ -618,9 +619,12 @@ int vxrt_denoise(uint32_t width, uint32_t rows, const float* signal, const float
  * Parameters: alpha_min in (0, 1]; max_len in 1..VXRT_TEMPORAL_MAX_LEN; sigma_z > 0 (+inf is legal and switches the plane test off);
  * normal_min finite.  Anything else is refused.
  *
- * THE LIMIT.  Reprojection follows the CAMERA.  There are no motion vectors: for an instance that moved (vxrt_accel_set_transforms)
- * or vertices that were refitted (vxrt_accel_refit) the previous frame is looked up as if the surface had stood still.  The plane and
- * normal tests then reject most of the stale history; vxrt_history_reset is the sure way.
+ * THE LIMIT.  The step T follows the CAMERA alone: for an instance that moved (vxrt_accel_set_transforms) or vertices that were
+ * refitted (vxrt_accel_refit) it looks the previous frame up as if the surface had stood still, and the plane and normal tests then
+ * reject most of the stale history.  The step T_m further below ("Motion") follows the surface instead: it takes the previous-frame
+ * position of every pixel's hit point from a snapshot of the scene (vxrt_accel_motion_snapshot).  What neither follows: the light
+ * (a shadow that moves over a surface is accumulated as if it had not), and anything seen through a mirror bounce.
+ * vxrt_history_reset remains the sure way after a cut.
  *
  * THE FRAME.  vxrt_render_path_temporal is vxrt_render_path_denoised with one step more: between demodulation and the first a-trous
  * pass out = T(E, P, N; history, cam', temporal) with the frame's own guides, the filter runs on out.rgb, remodulation and pack are
@@ -663,6 +667,65 @@ int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
                               const vxrt_temporal_params_t* temporal, vxrt_history_t* history,
                               uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
                               unsigned long long* rays_traced /* optional */, void* stream);
+
+/* Motion: temporal accumulation that reprojects through moved instances and refitted vertices (extension; absent from the reference).
+ * The arithmetic rules are those of the temporal section above: one fp32 operation per symbol, in the order written, no contraction.
+ *
+ * THE SNAPSHOT.  vxrt_accel_motion_snapshot(accel, what, stream) means "the scene as it is now is the previous frame".  `what` is a mask
+ * of the VXRT_REFIT_* bits: with VXRT_REFIT_INSTANCES the accel copies the scene's n_blas instance records (160 bytes each, transform
+ * and invTransform included) into storage it owns; with VXRT_REFIT_GEOMETRY it also copies the n_tris tri_t vertices (36 bytes each),
+ * which is legal only together with VXRT_REFIT_INSTANCES; what == 0 frees the snapshot.  A later snapshot replaces the earlier one;
+ * storage is reallocated only when `what` changes.  Ordered after every call already issued on this accel, on any stream, and
+ * synchronous with respect to `stream`, like vxrt_accel_refit.  The snapshot survives vxrt_accel_refit, vxrt_accel_set_transforms and
+ * vxrt_accel_set_alpha_test.  Returns -1, with nothing changed, for a null or stale accel, unknown bits in `what`,
+ * VXRT_REFIT_GEOMETRY without VXRT_REFIT_INSTANCES, or an allocation failure.  vxrt_accel_info(accel, 6) is the mask held (0: none);
+ * vxrt_accel_bytes includes the snapshot.  The intended loop: render frame k, snapshot, move (vxrt_accel_set_transforms /
+ * vxrt_accel_refit, any number of calls), render frame k + 1.
+ *
+ * THE PREVIOUS-POSITION GUIDE of a hit record h.  V0, V1, V2 = the snapshot's vertices of triangle h.triIdx if the snapshot holds
+ * geometry, else the scene's current ones (tri_t is v0, v1, v2; the barycentrics weight v1, v2, v0 as in vxrt_shade_rays).  M' and
+ * Minv' = transform and invTransform of the snapshot's record h.blasIdx & 0x7fffffff, as cell[4 * row + column].  (bx, by, bz) = h's.
+ *   o_c = (V1_c * bx + V2_c * by) + V0_c * bz                                   c = x, y, z
+ *   Q_c = ((M'[c][0] * o_x + M'[c][1] * o_y) + M'[c][2] * o_z) + M'[c][3]
+ *   n_c = (N1_c * bx + N2_c * by) + N0_c * bz                                   N0..N2 = the CURRENT tri_ex_t normals of h.triIdx
+ *   t_c = ((Minv'[0][c] * n_x + Minv'[1][c] * n_y) + Minv'[2][c] * n_z) + 0.0f * 0.0f
+ *   N'  = t * (1.0f / sqrtf((t_x * t_x + t_y * t_y) + t_z * t_z))               -- vxrt_shade_rays' shading normal with Minv' for Minv
+ * The guide is Q4 = (Q, 1) and N'4 = (N', 0).  A miss (h.dist == 1e30f) gives all zeros in both, and so does a record whose masked
+ * blasIdx >= n_blas or whose triIdx >= n_tris: nothing is read for such a record.  Barycentrics that are not finite are legal input; the
+ * result is whatever the operations give.
+ * vxrt_previous_positions computes the guide for n hit records on the device -- vxrt_trace's, the `hits` output of vxrt_render, any
+ * others -- into prev_position4 and prev_normal4 (4 floats per record, 16-byte aligned).  Asynchronous on `stream`.  Returns -1 before
+ * anything is launched for an accel without a snapshot, a null or stale accel, a scene without triEx, and null or misaligned buffers;
+ * 0 for n == 0.
+ *
+ * THE STEP WITH MOTION  out = T_m(E, P, N, Q, N'; history, cam', prm) is the step T with three substitutions and nothing else:
+ *   d = Q.xyz - pos' replaces d = I - pos';
+ *   in the normal test dot(N', HN[q]) replaces dot(N, HN[q]);
+ *   in the plane test fabsf(dot(N', HP[q].xyz - Q.xyz)) / sigma_z replaces fabsf(dot(N, HP[q].xyz - I)) / sigma_z.
+ * A pixel that is a hit (P.w != 0) but for which Q.w != 0 is false has no previous position and takes out = (E, 1).  The new history is
+ * written as by T: HE = out, HP = P, HN = N -- the CURRENT frame's position and normal.  The history's layout, vxrt_history_t and
+ * vxrt_history_read are unchanged, and the two steps may alternate on one history.  With Q = P and N' = N, T_m is T bit for bit.
+ * vxrt_temporal_accumulate_motion is vxrt_temporal_accumulate with the two guides more (4 floats per pixel of the window each, 16-byte
+ * aligned), under the same contract.
+ *
+ * THE FRAME WITH MOTION.  vxrt_render_path_temporal_motion is vxrt_render_path_temporal with T_m in place of T; Q and N' are the guide
+ * of every pixel's primary hit record, computed in the launch that prepares the frame's other guides.  It refuses what that call refuses,
+ * and an accel without a snapshot.  No launch, no traced ray and no host synchronisation more than vxrt_render_path_temporal.
+ * prev_position (optional): Q4 per pixel, 4 floats, addressed like `colors` (pixel (x, y) of the frame at x + y * width).
+ * With a snapshot taken and nothing moved the frame is NOT bit-equal to vxrt_render_path_temporal's: Q is a barycentric interpolation
+ * of the vertices, I is o + d * dist, and their bits differ. */
+int vxrt_accel_motion_snapshot(vxrt_accel_t* accel, uint32_t what, void* stream);
+int vxrt_previous_positions(vxrt_accel_t* accel, uint32_t n, const vxrt_hit_t* hits /* device */,
+                            float* prev_position4, float* prev_normal4 /* device, 16-byte aligned */, void* stream);
+int vxrt_temporal_accumulate_motion(vxrt_history_t* history, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0,
+                                    uint32_t y1, const float* signal, const float* position, const float* normal,
+                                    const float* prev_position, const float* prev_normal, const vxrt_temporal_params_t* prm,
+                                    float* out4, void* stream);
+int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0,
+                                     uint32_t y1, const vxrt_shade_params_t* params, const vxrt_path_params_t* path,
+                                     const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, vxrt_history_t* history,
+                                     uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
+                                     float* prev_position /* optional */, unsigned long long* rays_traced /* optional */, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

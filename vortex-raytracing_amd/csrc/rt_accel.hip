@@ -459,6 +459,7 @@ static void accel_free(vxrt_accel* a) {
   refit_plan_free(a->refit);
   (void)hipFree(a->uvtab); (void)hipFree(a->apriori);
   (void)hipFree(a->alpha_mat); (void)hipFree(a->alpha_tri);
+  (void)hipFree(a->motion_blas); (void)hipFree(a->motion_tri);
   for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) (void)hipFree(a->batch_order[k]);
   for (FrameCtx& c : a->ctx) {
     (void)hipFree(c.hitbuf); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
@@ -467,7 +468,7 @@ static void accel_free(vxrt_accel* a) {
     (void)hipFree(c.bin_hist); (void)hipFree(c.bin_keys); (void)hipFree(c.bin_order);
     for (void* q : {(void*)c.pt_geo, (void*)c.pt_nrm, (void*)c.pt_dir, (void*)c.pt_lit, (void*)c.pt_alb, (void*)c.pt_acc, (void*)c.pt_list, (void*)c.pt_hdr,
                     (void*)c.pt_I, (void*)c.pt_N, (void*)c.pt_D, (void*)c.pt_L, (void*)c.pt_T, (void*)c.pt_live[0], (void*)c.pt_live[1], (void*)c.pt_rays,
-                    (void*)c.pt_hits, (void*)c.pt_srays, (void*)c.pt_stmax, (void*)c.pt_shits, (void*)c.dn_sig[0], (void*)c.dn_sig[1]}) (void)hipFree(q);
+                    (void*)c.pt_hits, (void*)c.pt_srays, (void*)c.pt_stmax, (void*)c.pt_shits, (void*)c.dn_sig[0], (void*)c.dn_sig[1], (void*)c.mo_pos, (void*)c.mo_nrm}) (void)hipFree(q);
     for (FrameCtx::Level& l : c.lv) {
       (void)hipFree(l.rays); (void)hipFree(l.hits); (void)hipFree(l.parent); (void)hipFree(l.term); (void)hipFree(l.col);
       (void)hipFree(l.srays); (void)hipFree(l.stmax); (void)hipFree(l.shits);
@@ -614,7 +615,9 @@ int vxrt_accel_destroy(vxrt_accel_t* a) {
 uint64_t vxrt_accel_bytes(const vxrt_accel_t* a) {
   if (!a) return 0;
   return (uint64_t)a->ref.n_tlas_nodes * CNODE_VEC4 * 16 + (uint64_t)a->ref.n_bvh_nodes * CNODE_VEC4 * 16 +
-         (uint64_t)a->ref.n_tris * WTRI_FLOATS * 4 + (uint64_t)a->ref.n_blas * 4;
+         (uint64_t)a->ref.n_tris * WTRI_FLOATS * 4 + (uint64_t)a->ref.n_blas * 4 +
+         ((a->motion_what & VXRT_REFIT_INSTANCES) ? (uint64_t)a->ref.n_blas * RT_BLAS_STRIDE : 0) +   // (the motion snapshot)
+         ((a->motion_what & VXRT_REFIT_GEOMETRY) ? (uint64_t)a->ref.n_tris * RT_TRI_BYTES : 0);
 }
 
 int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
@@ -626,6 +629,7 @@ int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
   case 3: *value = a->dev.exact_decode; return 0;  // the scene takes the ldexp decode / generic slab form
   case 4: *value = a->alpha_on ? 1u : 0u; return 0; // a non-zero alpha table is set (vxrt_accel_set_alpha_test)
   case 5: *value = ident_root_form(a) ? 1u : 0u; return 0; // timed plain / shadow frames take the identity-root kernels (no TLAS level in the loop)
+  case 6: *value = a->motion_what; return 0;       // the VXRT_REFIT_* mask of the motion snapshot held (vxrt_accel_motion_snapshot)
   }
   return -1;
 }
@@ -675,6 +679,45 @@ int vxrt_accel_set_alpha_test(vxrt_accel_t* a, const uint8_t* thresholds, uint32
   if (hipStreamSynchronize(st) != hipSuccess) { a->alpha_on = false; return -1; }
   a->alpha_on = any;
   return 0;
+}
+
+// The motion snapshot (see the header, "Motion").  Every refusal comes before anything is changed; then, behind everything already
+// issued on the accel, the scene's instance records (and vertices) are copied to the accel's own storage.  Storage that a new mask no
+// longer asks for is freed behind a device synchronisation: motion frames in flight on any stream read it.
+int vxrt_accel_motion_snapshot(vxrt_accel_t* a, uint32_t what, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!a || a->stale || (what & ~(uint32_t)(VXRT_REFIT_INSTANCES | VXRT_REFIT_GEOMETRY)) != 0u) return -1;
+  if ((what & VXRT_REFIT_GEOMETRY) && !(what & VXRT_REFIT_INSTANCES)) return -1;
+  const vxrt_scene_t& s = a->ref;
+  const size_t blas_bytes = (size_t)s.n_blas * RT_BLAS_STRIDE, tri_bytes = (size_t)s.n_tris * RT_TRI_BYTES;
+  // ordered after every call already issued on this accel, on any stream (frames in flight read the snapshot this call rewrites)
+  for (uint32_t k = 0; k < MAX_FRAMES_IN_FLIGHT; ++k) {
+    FrameCtx& c = a->ctx[k];
+    if (!c.busy || c.last_stream == st) continue;
+    if (c.done_recorded) { if (hipStreamWaitEvent(st, c.ev_done, 0) != hipSuccess) return -1; }
+    else if (hipDeviceSynchronize() != hipSuccess) return -1;
+  }
+  if (what != a->motion_what) {
+    uint32_t* nb = nullptr; float* nt = nullptr;
+    const bool want_b = (what & VXRT_REFIT_INSTANCES) && !a->motion_blas, want_t = (what & VXRT_REFIT_GEOMETRY) && !a->motion_tri;
+    if ((want_b && hipMalloc((void**)&nb, blas_bytes) != hipSuccess) || (want_t && hipMalloc((void**)&nt, tri_bytes) != hipSuccess)) {
+      (void)hipFree(nb); (void)hipFree(nt); (void)hipGetLastError();
+      return -1;
+    }
+    const bool drop_b = !(what & VXRT_REFIT_INSTANCES) && a->motion_blas, drop_t = !(what & VXRT_REFIT_GEOMETRY) && a->motion_tri;
+    if ((drop_b || drop_t) && hipDeviceSynchronize() != hipSuccess) { (void)hipFree(nb); (void)hipFree(nt); return -1; }
+    if (drop_b) { (void)hipFree(a->motion_blas); a->motion_blas = nullptr; }
+    if (drop_t) { (void)hipFree(a->motion_tri); a->motion_tri = nullptr; }
+    if (want_b) a->motion_blas = nb;
+    if (want_t) a->motion_tri = nt;
+    a->motion_what = 0;   // (until the copies below have landed)
+  }
+  if (what == 0u) return 0;
+  bool ok = hipMemcpyAsync(a->motion_blas, s.blas, blas_bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  if (ok && (what & VXRT_REFIT_GEOMETRY)) ok = hipMemcpyAsync(a->motion_tri, s.tri, tri_bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  ok = hipStreamSynchronize(st) == hipSuccess && ok;
+  a->motion_what = ok ? what : 0u;
+  return ok ? 0 : -1;
 }
 
 int vxrt_accel_frames_in_flight(vxrt_accel_t* a, uint32_t n) {

@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <cmath>
+#include <type_traits>
 #include "rt_internal.h"
 
 #define DN_TX 32u   // tile: 32 x 8 pixels, one per thread of a 256-thread workgroup (a wavefront = 2 rows of 32)
@@ -158,7 +159,8 @@ __global__ __launch_bounds__(256) void rt_dn_demodulate_kernel(uint32_t n, uint3
 // the lanes of a row read neighbouring addresses and every history line is used by the four pixels around it out of L1 / L2.  The taps'
 // loads are issued before any of them is tested (a tap outside the window reads the pixel's own address and is dropped).  Almost no
 // arithmetic: the pass is bound by its 160 B per pixel of compulsory traffic (E, P, N in; the signal and the three history entries out;
-// HE, HP, HN of the previous frame once each).
+// HE, HP, HN of the previous frame once each).  The MOTION instantiations (vxrt_temporal_accumulate_motion, vxrt_render_path_temporal_motion;
+// tests/motion_ref.py) read 32 B more per pixel: the previous position and normal of the pixel's surface point.
 // ---------------------------------------------------------------------------------------------
 enum { TP_OUT_SIGNAL = 0, TP_OUT_LEN = 1, TP_OUT_PATH = 2 };
 
@@ -176,10 +178,15 @@ struct TpArgs {
   DnArgs path;                                  // TP_OUT_PATH: lit, alb, dst, colors, y0, W
 };
 
+// the step with motion, T_m (MOTION instantiations): the two guides more, per pixel of the window
+struct TpMotionArgs : TpArgs { const float4* Q; const float4* Nq; };
+
 __device__ __forceinline__ float tp_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
-template <int OUT>
-__global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(TpArgs A) {
+// MOTION: the pixel's previous position Q and previous normal N' (two 16-byte loads more, issued with the pixel's other loads) take the
+// place of its hit point and normal in the reprojection and in the two tap tests; the history written is the current frame's as ever.
+template <int OUT, bool MOTION = false>
+__global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_t<MOTION, TpMotionArgs, TpArgs> A) {
   const uint32_t bx = blockIdx.x % A.tiles_x, by = blockIdx.x / A.tiles_x;
   const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
   if (x >= A.W || y >= A.rows) return;
@@ -188,10 +195,12 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(TpArgs A) {
   if constexpr (OUT == TP_OUT_LEN) { er = A.E3[3 * p]; eg = A.E3[3 * p + 1]; eb = A.E3[3 * p + 2]; }
   else { const float4 e = A.E4[p]; er = e.x; eg = e.y; eb = e.z; }
   const float4 Pp = A.P[p], Np = A.N[p];
+  float4 Qp = Pp, Nq = Np;   // what the reprojection and the tap tests go by
+  if constexpr (MOTION) { Qp = A.Q[p]; Nq = A.Nq[p]; }
   const bool hit = Pp.w != 0.f;
   float orr = er, og = eg, ob = eb, olen = hit ? 1.f : 0.f;
-  if (hit && A.have) {
-    const float dx = Pp.x - A.pos[0], dy = Pp.y - A.pos[1], dz = Pp.z - A.pos[2];
+  if (hit && A.have && (!MOTION || Qp.w != 0.f)) {
+    const float dx = Qp.x - A.pos[0], dy = Qp.y - A.pos[1], dz = Qp.z - A.pos[2];
     const float a = tp_dot(dx, dy, dz, A.Rr[0], A.Rr[1], A.Rr[2]);
     const float b = tp_dot(dx, dy, dz, A.Ur[0], A.Ur[1], A.Ur[2]);
     const float c = tp_dot(dx, dy, dz, A.Fr[0], A.Fr[1], A.Fr[2]);
@@ -216,9 +225,9 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(TpArgs A) {
         for (int k = 0; k < 4; ++k) {
           if (!in[k]) continue;
           if (!(Hp[k].w != 0.f) || !(He[k].w > 0.f)) continue;
-          if (!(tp_dot(Np.x, Np.y, Np.z, Hn[k].x, Hn[k].y, Hn[k].z) >= A.normal_min)) continue;
-          const float ex = Hp[k].x - Pp.x, ey = Hp[k].y - Pp.y, ez = Hp[k].z - Pp.z;
-          if (!(fabsf(tp_dot(Np.x, Np.y, Np.z, ex, ey, ez)) / A.sigma_z <= 1.f)) continue;
+          if (!(tp_dot(Nq.x, Nq.y, Nq.z, Hn[k].x, Hn[k].y, Hn[k].z) >= A.normal_min)) continue;
+          const float ex = Hp[k].x - Qp.x, ey = Hp[k].y - Qp.y, ez = Hp[k].z - Qp.z;
+          if (!(fabsf(tp_dot(Nq.x, Nq.y, Nq.z, ex, ey, ez)) / A.sigma_z <= 1.f)) continue;
           const float w = ((k & 1) ? tx : 1.f - tx) * ((k >> 1) ? ty : 1.f - ty);
           if (w > 0.f) {
             sw = sw + w;
@@ -330,8 +339,9 @@ static void tp_reciprocal_basis(const vxrt_camera_t& c, float Rr[3], float Ur[3]
 
 // One step on history h: the checks are the caller's (window of at most h->cap pixels, not empty).  Launches, then makes the written set,
 // `cam` and the geometry the history's state.
+// Q / Nq: both null (the step T) or both set (the step with motion, T_m).
 static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
-                     const vxrt_temporal_params_t* t, int out, TpArgs A) {
+                     const vxrt_temporal_params_t* t, int out, TpArgs A, const float4* Q = nullptr, const float4* Nq = nullptr) {
   const uint32_t rows = y1 - y0;
   const bool have = !h->empty && h->W == W && h->H == H && h->y0 == y0 && h->y1 == y1;   // (another window: an implicit reset)
   const uint32_t prev = h->cur, next = have ? h->cur ^ 1u : h->cur;
@@ -346,7 +356,13 @@ static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam,
   A.he = h->he[prev]; A.hp = h->hp[prev]; A.hn = h->hn[prev];
   A.he_o = h->he[next]; A.hp_o = h->hp[next]; A.hn_o = h->hn[next];
   const dim3 grid(A.tiles_x * ((rows + DN_TY - 1u) / DN_TY)), block(256);
-  if (out == TP_OUT_SIGNAL) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_SIGNAL>), grid, block, 0, s, A);
+  if (Q) {
+    TpMotionArgs M{};
+    static_cast<TpArgs&>(M) = A; M.Q = Q; M.Nq = Nq;
+    if (out == TP_OUT_SIGNAL) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_SIGNAL, true>), grid, block, 0, s, M);
+    else if (out == TP_OUT_LEN) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_LEN, true>), grid, block, 0, s, M);
+    else hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_PATH, true>), grid, block, 0, s, M);
+  } else if (out == TP_OUT_SIGNAL) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_SIGNAL>), grid, block, 0, s, A);
   else if (out == TP_OUT_LEN) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_LEN>), grid, block, 0, s, A);
   else hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_PATH>), grid, block, 0, s, A);
   if (hipGetLastError() != hipSuccess) return -1;
@@ -356,11 +372,11 @@ static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam,
 
 int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
                    const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
-                   const float4* alb, uint32_t* dst, float* colors) {
+                   const float4* alb, uint32_t* dst, float* colors, const float4* prev_pos, const float4* prev_nrm) {
   TpArgs A{};
   A.E4 = sig; A.P = geo; A.N = nrm; A.sig = sig;
   A.path.W = W; A.path.lit = lit; A.path.alb = alb; A.path.dst = dst; A.path.colors = colors; A.path.y0 = y0;
-  return tp_launch(s, h, cam, W, H, y0, y1, t, filtered ? TP_OUT_SIGNAL : TP_OUT_PATH, A);
+  return tp_launch(s, h, cam, W, H, y0, y1, t, filtered ? TP_OUT_SIGNAL : TP_OUT_PATH, A, prev_pos, prev_nrm);
 }
 
 extern "C" {
@@ -415,6 +431,21 @@ int vxrt_temporal_accumulate(vxrt_history_t* h, const vxrt_camera_t* cam, uint32
   TpArgs A{};
   A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
   return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A);
+}
+
+// the step with motion alone (see the header, "Motion"): vxrt_temporal_accumulate's checks, and the two guides more
+int vxrt_temporal_accumulate_motion(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                    const float* signal, const float* position, const float* normal, const float* prev_position,
+                                    const float* prev_normal, const vxrt_temporal_params_t* prm, float* out4, void* stream) {
+  if (!h || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !prev_position || !prev_normal || !out4) return -1;
+  if ((((uintptr_t)position | (uintptr_t)normal | (uintptr_t)prev_position | (uintptr_t)prev_normal) & 15u) != 0) return -1;
+  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
+  if (y0 == y1) return 0;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull || n > h->cap) return -1;
+  TpArgs A{};
+  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
+  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A, (const float4*)prev_position, (const float4*)prev_normal);
 }
 
 uint64_t vxrt_denoise_scratch_bytes(uint32_t width, uint32_t rows) { return 32ull * width * rows; }

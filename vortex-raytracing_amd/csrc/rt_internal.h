@@ -110,6 +110,9 @@ struct FrameCtx {
   // denoised path frames (vxrt_render_path_denoised; allocated on first use): the two signal buffers the a-trous iterations ping-pong
   // between, one float4 (E, lum(E)) per pixel of the window; the guides are pt_geo and pt_nrm
   float4* dn_sig[2] = {nullptr, nullptr}; uint64_t dn_cap = 0;
+  // frames with motion (vxrt_render_path_temporal_motion; allocated on first use): the previous-position guide of every pixel's primary
+  // hit, Q4 and N'4, written by the prepare launch and read by the temporal step
+  float4* mo_pos = nullptr; float4* mo_nrm = nullptr; uint64_t mo_cap = 0;
   void* pool_spill = nullptr; uint64_t pool_spill_bytes = 0;  // ray-pool trace kernel: the part of the slots' stacks that does not fit LDS
   hipStream_t side = nullptr;
   hipEvent_t ev_in = nullptr, ev_side = nullptr, ev_done = nullptr;
@@ -146,7 +149,17 @@ struct vxrt_accel {
   // (alpha_tri[t] = alpha_mat[triEx[t].texId]: what the traversal reads).  alpha_on: some threshold is non-zero.
   uint8_t* alpha_mat = nullptr; uint8_t* alpha_tri = nullptr;
   bool alpha_on = false;
+  // motion snapshot (vxrt_accel_motion_snapshot): the instance records and, with VXRT_REFIT_GEOMETRY, the tri_t vertices of the previous frame
+  uint32_t* motion_blas = nullptr; float* motion_tri = nullptr;
+  uint32_t motion_what = 0;        // the VXRT_REFIT_* mask held; 0: no snapshot
 };
+
+// What the previous-position guide reads besides the SceneDev (see the header, "Motion"): the snapshot's instance records, the vertices
+// (the snapshot's, or the scene's current ones) and the two bounds a hit record is checked against
+struct MotionSrc { const uint32_t* blas; const float* tri; uint32_t n_blas, n_tris; };
+static inline MotionSrc motion_src(const vxrt_accel* a) {
+  return MotionSrc{a->motion_blas, (a->motion_what & VXRT_REFIT_GEOMETRY) ? (const float*)a->motion_tri : (const float*)a->ref.tri, a->ref.n_blas, a->ref.n_tris};
+}
 
 // RT_IDENT_ROOT_KERNEL: accels whose TLAS root is one identity instance take frame kernels that compile the TLAS level out of the
 // traversal loop (the IDENT template argument of rt_persistent_kernel).  0 = no such instantiations (the A/B: docs/KNOBS.md).
@@ -191,9 +204,10 @@ bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uin
 // out = T(E, P, N; h, the history's camera, t) for the window, one launch: E = sig's rgb, P = geo, N = nrm.  filtered: (out.rgb, lum) goes
 // back into sig (in place: a pixel reads only its own entry) for dn_launch_path_filter; else the pass remodulates out.rgb with lit / alb,
 // packs and writes dst / colors itself.  The history then holds this frame, `cam` and the geometry.
+// prev_pos / prev_nrm (both or neither): the step with motion, T_m, with Q = prev_pos and N' = prev_nrm.
 int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
                    const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
-                   const float4* alb, uint32_t* dst, float* colors);
+                   const float4* alb, uint32_t* dst, float* colors, const float4* prev_pos = nullptr, const float4* prev_nrm = nullptr);
 
 // ---------------------------------------------------------------------------------------------
 // rt_kernels.hip <-> rt_secondary.hip: a frame as an entry point asks for it, the per-frame control block, growing device buffers,
@@ -231,6 +245,8 @@ struct RenderRequest {
   const vxrt_path_aov_t* aov = nullptr;
   const vxrt_temporal_params_t* temporal = nullptr; // ... with temporal accumulation before the filter (vxrt_render_path_temporal), into
   vxrt_history_t* history = nullptr;                //     this history
+  bool motion = false;                              // ... through the accel's motion snapshot (vxrt_render_path_temporal_motion), with its
+  float* prev_position = nullptr;                   //     optional guide output
   void* stream = nullptr;
   Counting counting = Counting::TIMED;
   bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set

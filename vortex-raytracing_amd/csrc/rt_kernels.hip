@@ -1920,6 +1920,8 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
   // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
   if ((r.temporal || r.history) && (!r.denoise || !r.cams || !r.temporal || !r.history)) return -1;
+  // ... through moved instances: the accel holds a motion snapshot
+  if ((r.motion || r.prev_position) && (!r.motion || !r.temporal || a->motion_what == 0u)) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
   return 1;
@@ -2487,6 +2489,21 @@ int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+// ... whose step reprojects through the accel's motion snapshot (see the header, "Motion"): the guides ride in the prepare launch
+int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                     const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                                     const vxrt_temporal_params_t* temporal, vxrt_history_t* history, uint32_t* dst, float* colors,
+                                     const vxrt_path_aov_t* aov, float* prev_position, unsigned long long* rays_traced, void* stream) {
+  if (!path || !dn || !camera_ok(cam)) return -1;
+  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
+  if (!tp_request_ok(history, temporal, pixels)) return -1;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = true; r.prev_position = prev_position;
   r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }

@@ -1,10 +1,12 @@
 // Tails of the frames that trace secondary rays, and their kernels: what render_common (rt_kernels.hip) runs in place of the plain
 // shading pass of a frame with reflective instances (the mirror-bounce wavefront), of an ambient-occlusion frame and of a path frame
-// (whose denoised end is in rt_denoise.hip), and the binning of secondary rays.  None of it is timed by bench.py, and none of it can
+// (whose denoised end is in rt_denoise.hip; with it the previous-position guide of frames with motion, motion_guide, and
+// vxrt_previous_positions), and the binning of secondary rays.  None of it is timed by bench.py, and none of it can
 // reach the traversal kernel's unit: the seam is in rt_internal.h -- the ray buffers are traced through trace_on_ctx, buffers grow
 // through grow_device -- and the shading arithmetic is that of the frame kernels, rt_shading.h.  Same build flags (-ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rt_internal.h"
 #include "rt_shading.h"
 
@@ -286,11 +288,62 @@ __global__ __launch_bounds__(256) void rt_ao_final_kernel(uint64_t n, uint32_t W
 // primary hit with the occlusion bit the shadow frame launch left in its record | background, 0), alb[t] = (Alb, 0); pixels with a hit
 // are appended to list[] (count in hdr[0])
 // (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
-template <bool CAM>
+// The previous-position guide of hit record h (the header's "Motion", operation for operation): where the surface point under h was
+// when the accel's snapshot was taken, Q4 = (Q, 1), and the shading normal it had there, N'4 = (N', 0).  All zeros for a miss and for
+// a record that names an instance or a triangle the scene does not have (nothing is read for it).  h.blasIdx: bit 31 is masked here.
+__device__ __forceinline__ void motion_guide(const SceneDev& sc, const MotionSrc& m, const HitRec& h, float4& Q4, float4& N4) {
+  Q4 = make_float4(0.f, 0.f, 0.f, 0.f); N4 = Q4;
+  const uint32_t bi = h.blasIdx & 0x7fffffffu;
+  if (h.dist == RT_LARGE_FLOAT || bi >= m.n_blas || h.triIdx >= m.n_tris) return;
+  const float* v = m.tri + (size_t)h.triIdx * (RT_TRI_BYTES / 4);        // tri_t: v0, v1, v2
+  const uint32_t* bp = m.blas + (size_t)bi * (RT_BLAS_STRIDE / 4);       // invTransform @ word 1, transform @ word 17
+  float o[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c] = (v[3 + c] * h.bx + v[6 + c] * h.by) + v[c] * h.bz;
+  float q[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint32_t* r = bp + 17 + 4 * c;
+    q[c] = ((__uint_as_float(r[0]) * o[0] + __uint_as_float(r[1]) * o[1]) + __uint_as_float(r[2]) * o[2]) + __uint_as_float(r[3]);
+  }
+  // shade_terms' shading normal with the snapshot's invTransform
+  const rt_triex_t te = sc.triEx[h.triIdx];
+  const float Nx = te.N1[0] * h.bx + te.N2[0] * h.by + te.N0[0] * h.bz;
+  const float Ny = te.N1[1] * h.bx + te.N2[1] * h.by + te.N0[1] * h.bz;
+  const float Nz = te.N1[2] * h.bx + te.N2[2] * h.by + te.N0[2] * h.bz;
+  const float m0 = __uint_as_float(bp[1]), m1 = __uint_as_float(bp[2]), m2 = __uint_as_float(bp[3]);
+  const float m4 = __uint_as_float(bp[5]), m5 = __uint_as_float(bp[6]), m6 = __uint_as_float(bp[7]);
+  const float m8 = __uint_as_float(bp[9]), m9 = __uint_as_float(bp[10]), m10 = __uint_as_float(bp[11]);
+  const float z0 = 0.0f * 0.0f;
+  const float Tx = m0 * Nx + m4 * Ny + m8 * Nz + z0;
+  const float Ty = m1 * Nx + m5 * Ny + m9 * Nz + z0;
+  const float Tz = m2 * Nx + m6 * Ny + m10 * Nz + z0;
+  const float inv = 1.0f / sqrtf(Tx * Tx + Ty * Ty + Tz * Tz);
+  Q4 = make_float4(q[0], q[1], q[2], 1.0f);
+  N4 = make_float4(Tx * inv, Ty * inv, Tz * inv, 0.f);
+}
+
+// vxrt_previous_positions: the guide of n hit records, one per thread
+__global__ __launch_bounds__(256) void rt_previous_positions_kernel(SceneDev sc, MotionSrc m, uint32_t n, const HitRec* __restrict__ hits,
+    float4* __restrict__ pos, float4* __restrict__ nrm) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  float4 Q4, N4;
+  motion_guide(sc, m, hits[t], Q4, N4);
+  pos[t] = Q4; nrm[t] = N4;
+}
+
+// what the MOTION flavour of rt_path_prepare_kernel takes besides: the guide's sources, its two per-pixel buffers of the frame context
+// and the caller's optional prev_position (frame addressing)
+struct PrepMotion { MotionSrc src; float4* pos; float4* nrm; float* out; };
+struct PrepNoMotion {};
+
+// (MOTION: the frame with motion -- the previous-position guide of the pixel's record, computed where the record is in registers)
+template <bool CAM, bool MOTION = false>
 __global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
     const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
     float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset) {
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo) {
   if (ctl_reset && blockIdx.x == 0)
     for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
   bool hit_c[PREP_CHUNKS];
@@ -323,6 +376,12 @@ __global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, Shade
         lit[t] = make_float4(r, g, b, 0.f);
         alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
         hit = true;
+      }
+      if constexpr (MOTION) {
+        float4 Q4, N4;
+        motion_guide(sc, mo.src, h, Q4, N4);
+        mo.pos[t] = Q4; mo.nrm[t] = N4;
+        if (mo.out) { float* o = mo.out + 4 * ((size_t)x + (size_t)y * W); o[0] = Q4.x; o[1] = Q4.y; o[2] = Q4.z; o[3] = Q4.w; }
       }
     }
     hit_c[c] = hit; t_c[c] = t;
@@ -695,7 +754,7 @@ static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) 
   if (r.temporal) {
     const bool filtered = r.denoise->iterations != 0;
     if (tp_launch_path(s, r.history, r.cams, r.width, r.height, r.y0, r.y1, r.temporal, c->dn_sig[0], c->pt_geo, c->pt_nrm, filtered, c->pt_lit, c->pt_alb,
-                       r.dst, r.colors) != 0) return -1;
+                       r.dst, r.colors, r.motion ? c->mo_pos : nullptr, r.motion ? c->mo_nrm : nullptr) != 0) return -1;
     if (!filtered) return 0;
   }
   return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);
@@ -724,11 +783,17 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   if (!grow_device({{(void**)&c->pt_I, 16}, {(void**)&c->pt_N, 16}, {(void**)&c->pt_D, 16}, {(void**)&c->pt_L, 16}, {(void**)&c->pt_T, 16}, {(void**)&c->pt_live[0], 4},
                     {(void**)&c->pt_live[1], 4}, {(void**)&c->pt_rays, 24}, {(void**)&c->pt_hits, sizeof(HitRec)}}, &c->pt_path_cap, path_cap, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_srays, 24}, {(void**)&c->pt_stmax, 4}, {(void**)&c->pt_shits, sizeof(HitRec)}}, &c->pt_shadow_cap, shadow_cap, GrowSync::STREAM, s)) return -1;
+  if (r.motion && !grow_device({{(void**)&c->mo_pos, 16}, {(void**)&c->mo_nrm, 16}}, &c->mo_cap, n, GrowSync::STREAM, s)) return -1;
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
   const dim3 block(256), grid((n32 + 255u) / 256u), pgrid((n32 + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS)), rgrid((cap + 255u) / 256u);
   if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
-  hipLaunchKernelGGL(r.cams ? rt_path_prepare_kernel<true> : rt_path_prepare_kernel<false>, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
-                     c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl);
+  if (r.motion) {   // (a camera frame: check_request)
+    hipLaunchKernelGGL((rt_path_prepare_kernel<true, true>), pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
+                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position});
+  } else {
+    hipLaunchKernelGGL(r.cams ? rt_path_prepare_kernel<true> : rt_path_prepare_kernel<false>, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
+                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, PrepNoMotion{});
+  }
   if (hipGetLastError() != hipSuccess) return -1;
   c->ctl_dirty = false;
   for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
@@ -760,5 +825,15 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
                                                  nullptr, r.aov) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
   hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
                      pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The previous-position guide of caller-owned hit records (see the header, "Motion"): one launch, asynchronous on `stream`
+extern "C" int vxrt_previous_positions(vxrt_accel_t* a, uint32_t n, const vxrt_hit_t* hits, float* prev_position4, float* prev_normal4, void* stream) {
+  if (!a || a->stale || a->motion_what == 0u || !a->ref.triEx) return -1;
+  if (!hits || !prev_position4 || !prev_normal4 || (((uintptr_t)prev_position4 | (uintptr_t)prev_normal4) & 15u) != 0) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_previous_positions_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, a->dev, motion_src(a), n, (const HitRec*)hits,
+                     (float4*)prev_position4, (float4*)prev_normal4);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -651,3 +651,52 @@ def render_path_temporal(accel, cam, width, height, y0, y1, params, spp, bounces
     check(_temporal_lib().vxrt_render_path_temporal(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), C.byref(denoise),
                                                     C.byref(temporal), _history(history), dst_ptr, colors_ptr, None if aov is None else C.byref(aov),
                                                     rays_ptr, stream), "vxrt_render_path_temporal")
+
+
+# ---- motion: temporal accumulation that reprojects through moved instances (the header's "Motion") ----
+def _motion_lib():
+    L = _temporal_lib()
+    L.vxrt_accel_motion_snapshot.restype = C.c_int
+    L.vxrt_accel_motion_snapshot.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.vxrt_previous_positions.restype = C.c_int
+    L.vxrt_previous_positions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_temporal_accumulate_motion.restype = C.c_int
+    L.vxrt_temporal_accumulate_motion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]
+    L.vxrt_render_path_temporal_motion.restype = C.c_int
+    L.vxrt_render_path_temporal_motion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
+                                                   C.POINTER(PathParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.POINTER(PathAov), C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+def accel_motion_snapshot(accel, what, stream=None):
+    """vxrt_accel_motion_snapshot: "the scene as it is now is the previous frame" -- the accel copies the instance records
+    (REFIT_INSTANCES) and the vertices as well (REFIT_INSTANCES | REFIT_GEOMETRY); 0 frees the snapshot.  Raises on a refusal."""
+    check(_motion_lib().vxrt_accel_motion_snapshot(accel, int(what), stream), "vxrt_accel_motion_snapshot")
+
+
+def previous_positions(accel, n, hits_ptr, prev_position_ptr, prev_normal_ptr, stream=None):
+    """vxrt_previous_positions: where the surface point of each of n hit records was when the snapshot was taken, and its shading normal
+    there (4 floats per record each, device, 16-byte aligned)."""
+    check(_motion_lib().vxrt_previous_positions(accel, int(n), hits_ptr, prev_position_ptr, prev_normal_ptr, stream), "vxrt_previous_positions")
+
+
+def temporal_accumulate_motion(history, cam, width, height, y0, y1, signal_ptr, position_ptr, normal_ptr, prev_position_ptr, prev_normal_ptr, temporal,
+                               out_ptr, stream=None):
+    """vxrt_temporal_accumulate_motion: temporal_accumulate that reprojects every pixel's previous position (4 floats per pixel) and tests
+    the taps against it and the previous normal."""
+    check(_motion_lib().vxrt_temporal_accumulate_motion(_history(history), C.byref(_camera(cam)), width, height, y0, y1, signal_ptr, position_ptr,
+                                                        normal_ptr, prev_position_ptr, prev_normal_ptr, C.byref(temporal), out_ptr, stream),
+          "vxrt_temporal_accumulate_motion")
+
+
+def render_path_temporal_motion(accel, cam, width, height, y0, y1, params, spp, bounces, denoise, temporal, history, dst_ptr, seed=0, shadow=0,
+                                colors_ptr=None, aov=None, prev_position_ptr=None, rays_ptr=None, stream=None):
+    """vxrt_render_path_temporal_motion: render_path_temporal whose history is looked up where the accel's motion snapshot puts every
+    pixel's surface point; `prev_position_ptr` (optional) receives that position, 4 floats per pixel of the frame."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_motion_lib().vxrt_render_path_temporal_motion(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+                                                         C.byref(denoise), C.byref(temporal), _history(history), dst_ptr, colors_ptr,
+                                                         None if aov is None else C.byref(aov), prev_position_ptr, rays_ptr, stream),
+          "vxrt_render_path_temporal_motion")

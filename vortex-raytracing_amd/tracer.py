@@ -212,6 +212,15 @@ class DeviceScene:
         with torch.cuda.device(dev):
             rtapi.accel_refit(self.accel, rtapi.REFIT_GEOMETRY if geometry else rtapi.REFIT_INSTANCES, torch.cuda.current_stream().cuda_stream)
 
+    def snapshot_motion(self, what=rtapi.REFIT_INSTANCES):
+        """The scene as it is now is the previous frame (vxrt_accel_motion_snapshot): call it after a frame and before set_transforms /
+        refit move the scene for the next one.  what: rtapi.REFIT_INSTANCES (moved instances), | rtapi.REFIT_GEOMETRY (moved vertices as
+        well), 0 frees the snapshot.  rtapi.render_path_temporal_motion and rtapi.previous_positions need one."""
+        import torch
+        dev = self.t["blas"].device
+        with torch.cuda.device(dev):
+            rtapi.accel_motion_snapshot(self.accel, what, torch.cuda.current_stream().cuda_stream)
+
     def set_alpha_test(self, thresholds):
         """Cutout textures: one threshold byte per material (0 = opaque); a candidate whose texel has a top byte below its material's
         threshold is rejected inside the traversal (vxrt_accel_set_alpha_test).  None switches the test off.  Survives set_transforms
