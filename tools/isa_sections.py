@@ -17,6 +17,9 @@ usage: tools/isa_sections.py [--kernel SUBSTRING] [--list] [--label TEXT] [--src
   --list     print the mangled names of all instantiations and stop
   --src      another copy of rt_kernels.hip (a checkout of the parent commit, for the comparison)
 
+A kernel built with RT_OCC_LOOP holds the traversal loop twice; the sections of its occlusion-only form carry the prefix occ_ and are
+summed in the row "occ_loop", those of the general form in "loop" as before.
+
 The "stack" mark sits between the child tests and the pushes / pops of a node step, but the slab arithmetic has no side effect and
 the compiler moves most of it behind the mark: read "node" + "stack" together as the node step."""
 import collections
@@ -35,6 +38,7 @@ SRC = os.path.join(bld.CSRC, "rt_kernels.hip")
 FLAGS = [f for f in bld.HIP_FLAGS if f != "-fPIC"] + ["-w", "-S", "--cuda-device-only", "-DRT_ISA_MARKS"]
 # <JOB_RENDER_SHADOW, STATS 0, LDEXP false, EXACT false, PACKED true, SHALLOW true, ALPHA false [, IDENT true]>
 HEADLINE = ("ILi1ELi0ELb0ELb0ELb1ELb1ELb0ELb1EE", "ILi1ELi0ELb0ELb0ELb1ELb1ELb0EE")
+LOOP_SECTIONS = ("loop_top", "node", "stack", "inst", "leaf", "leaf_tris", "leaf_pop", "loop_exit")
 CLASSES = (("valu", "v_"), ("branch", "s_cbranch"), ("ds", "ds_"), ("global", "global_"), ("scratch", "scratch_"))
 
 
@@ -110,16 +114,19 @@ def main():
     print("# %s" % (label or "rt_kernels.hip"))
     print("# flags: %s" % " ".join(extra or ["(none)"]))
     print("# kernel: %s" % name)
-    print("%-10s" % "section" + "".join("%9s" % c for c in cols))
+    print("%-14s" % "section" + "".join("%9s" % c for c in cols))
     total = collections.Counter()
     for sec, c in counts.items():
-        print("%-10s" % sec + "".join("%9d" % c[k] for k in cols))
+        print("%-14s" % sec + "".join("%9d" % c[k] for k in cols))
         total.update(c)
-    loop = collections.Counter()
-    for sec in ("loop_top", "node", "stack", "inst", "leaf", "leaf_tris", "leaf_pop", "loop_exit"):
-        loop.update(counts.get(sec, {}))
-    print("%-10s" % "loop" + "".join("%9d" % loop[k] for k in cols))
-    print("%-10s" % "kernel" + "".join("%9d" % total[k] for k in cols))
+    # the traversal loop, and its occlusion-only form where the kernel holds one (RT_OCC_LOOP: the same marks with the prefix occ_)
+    for prefix, row in (("", "loop"), ("occ_", "occ_loop")):
+        loop = collections.Counter()
+        for sec in LOOP_SECTIONS:
+            loop.update(counts.get(prefix + sec, {}))
+        if loop:
+            print("%-14s" % row + "".join("%9d" % loop[k] for k in cols))
+    print("%-14s" % "kernel" + "".join("%9d" % total[k] for k in cols))
 
 
 if __name__ == "__main__":

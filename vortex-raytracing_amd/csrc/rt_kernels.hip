@@ -164,10 +164,36 @@ __device__ __forceinline__ float child_box(const uint32_t* pl, float px, float p
   const float tmax = fminf(fminf(tx2, ty2), tz2);
   return (tmax < tmin || tmax <= 0) ? RT_LARGE_FLOAT : tmin;
 }
+// The fast form (!EXACT && !LDEXP) of child_box without its select: the slab distance tmin whatever the test says, and the test's verdict
+// in `enters` (the ray's interval with the box is not empty and not behind the origin).  eval_children_raw's NO_SELECT form.
+template <int K>
+__device__ __forceinline__ float child_box_raw(const uint32_t* pl, float px, float py, float pz, float sx, float sy, float sz,
+                                               float rox, float roy, float roz, float rix, float riy, float riz, bool& enters) {
+  const float ax = __fmaf_rn(qbyte<K>(pl[0]), sx, px), ay = __fmaf_rn(qbyte<K>(pl[1]), sy, py), az = __fmaf_rn(qbyte<K>(pl[2]), sz, pz);
+  const float bx = __fmaf_rn(qbyte<K>(pl[3]), sx, px), by = __fmaf_rn(qbyte<K>(pl[4]), sy, py), bz = __fmaf_rn(qbyte<K>(pl[5]), sz, pz);
+  const float tx1 = (ax - rox) * rix, tx2 = (bx - rox) * rix;
+  const float ty1 = (ay - roy) * riy, ty2 = (by - roy) * riy;
+  const float tz1 = (az - roz) * riz, tz2 = (bz - roz) * riz;
+  const float tmin = fmaxf(fmaxf(tx1, ty1), tz1);
+  const float tmax = fminf(fminf(tx2, ty2), tz2);
+  enters = !(tmax < tmin || tmax <= 0);
+  return tmin;
+}
+
+// RT_BOX_NO_SELECT: the box tests feed their verdict into ok[k] as a condition instead of selecting RT_LARGE_FLOAT into the distance and
+// comparing that with the hit distance: one v_cndmask per child less.  The same ok[k]: hit_dist <= RT_LARGE_FLOAT (start_ray clamps it, and
+// it only shrinks), so `RT_LARGE_FLOAT < hit_dist` is false and a missed box was never ok; where ok[k] holds the distance is tmin in both
+// forms, and no caller reads the distance of a child that is not ok (eval_children and the ordered arm overwrite it with +inf, the occlusion
+// arm pushes only children that are ok).  0 = the select (the A/B: docs/KNOBS.md).  Taken by the identity-root shadow frame kernels only
+// (eval_children_raw's NO_SELECT): there it is worth +1.0 %; no other kernel gained with it in a measurement (the general
+// kernels' figures with and without it: DESIGN.md s5, rejected), so every other kernel keeps the select.
+#ifndef RT_BOX_NO_SELECT
+#define RT_BOX_NO_SELECT 1
+#endif
 
 // Box tests of the <=4 children of an internal node, raw form: c[k].d is the slab distance whatever the test said, ok[k] says whether
 // child k is to be visited (a real slot whose box the ray enters before its hit distance).
-template <bool EXACT, bool LDEXP>
+template <bool EXACT, bool LDEXP, bool NO_SELECT = false>
 __device__ __forceinline__ void eval_children_raw(const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const uint32_t* __restrict__ ref_node,
                                                   float rox, float roy, float roz, float rix, float riy, float riz,
                                                   float hit_dist, Cand* c, bool* ok) {
@@ -188,13 +214,23 @@ __device__ __forceinline__ void eval_children_raw(const uint4 q0, const uint4 q1
   }
   const uint32_t desc[4] = {q2.z, q2.w, q3.x, q3.y};   // complete work descriptors, DESC_NONE for an empty slot (:60)
   float d[4];
-  d[0] = child_box<0, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
-  d[1] = child_box<1, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
-  d[2] = child_box<2, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
-  d[3] = child_box<3, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
+  bool in[4] = {true, true, true, true};
+  if constexpr (NO_SELECT) {
+    static_assert(!EXACT && !LDEXP, "the select-free box test is the fast form's");
+    d[0] = child_box_raw<0>(pl, px, py, pz, sx, sy, sz, rox, roy, roz, rix, riy, riz, in[0]);
+    d[1] = child_box_raw<1>(pl, px, py, pz, sx, sy, sz, rox, roy, roz, rix, riy, riz, in[1]);
+    d[2] = child_box_raw<2>(pl, px, py, pz, sx, sy, sz, rox, roy, roz, rix, riy, riz, in[2]);
+    d[3] = child_box_raw<3>(pl, px, py, pz, sx, sy, sz, rox, roy, roz, rix, riy, riz, in[3]);
+  } else {
+    d[0] = child_box<0, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
+    d[1] = child_box<1, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
+    d[2] = child_box<2, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
+    d[3] = child_box<3, EXACT, LDEXP>(pl, px, py, pz, sx, sy, sz, ex, ey, ez, rox, roy, roz, rix, riy, riz);
+  }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    ok[k] = (desc[k] != DESC_NONE) && (d[k] < hit_dist);     // :60, :71
+    if constexpr (NO_SELECT) ok[k] = (desc[k] != DESC_NONE) && in[k] && (d[k] < hit_dist);
+    else ok[k] = (desc[k] != DESC_NONE) && (d[k] < hit_dist);     // :60, :71
     c[k].d = d[k];
     c[k].desc = desc[k];
   }
@@ -367,6 +403,19 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #ifndef RT_OCC_OK_MASKS
 #define RT_OCC_OK_MASKS 1
 #endif
+// RT_OCC_LOOP: the timed shadow frame job's identity-root kernels hold the traversal loop twice, and a wavefront in which every lane that holds work holds
+// an any-hit ray (a tile whose primary rays all hit, in its second half) takes the occlusion-only form: the node step is the occlusion arm
+// alone (no phase ballot, no ordered arm, no path_m), stack entries are the 4-byte descriptor (twice the levels in the same LDS), pop_next
+// takes the top without the re-filter, an accepted candidate ends the ray.  A mixed wavefront takes the general loop.  Same results, same
+// visiting order.  0 = one loop (the A/B: docs/KNOBS.md).  Needs RT_BATCH_PUSH, RT_OCC_OK_MASKS, RT_UNORDERED_OCCLUSION and whole-tile batches
+// (RT_DEAD_MAX 64, RT_SHADOW_FINISH_MIN off); the general (non-identity-root) kernels, ray buffers, the diffuse-bounce job, the EXACT launch,
+// the alpha-tested and the counting instantiations keep the one loop whatever the value.
+#ifndef RT_OCC_LOOP
+#define RT_OCC_LOOP 1
+#endif
+#ifndef RT_OCC_LOOP_CHECK
+#define RT_OCC_LOOP_CHECK 0
+#endif
 // (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
 
 // -DRT_ISA_MARKS: comment-only markers in the listing (hipcc -S) that delimit the regions of the traversal loop for
@@ -376,6 +425,8 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #else
 #define RT_MARK(name)
 #endif
+// marks inside the traversal loop, which a kernel may hold in two forms (RT_OCC_LOOP): those of the occlusion-only form carry the prefix occ_
+#define RT_LOOP_MARK(name) do { if constexpr (OCC) { RT_MARK("occ_" name); } else { RT_MARK(name); } } while (0)
 
 // (hit_index, rt_shading.h: hit records of a frame window are kept TILE-MAJOR between the traversal and the shading pass)
 // frame row of local row lr: the window's k-th tile row is frame rows y0 + k * row_step ... + 7 (row_step = 8 for a contiguous
@@ -509,6 +560,14 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   }
   __syncthreads();
   uint2* const lstk = &s_stk[threadIdx.x >> 6][0][lane];
+  // the same rows as 2 * LSTK rows of 64 dwords (occlusion-only loop).  Formed where it is used, from the lane number through an empty asm
+  // statement: as a value of its own it is one more register alive for the whole kernel, which the 8-wavefront kernels reload from scratch
+  // in front of every stack access.
+  auto lstk4_here = [&]() -> uint32_t* {
+    uint32_t l = lane;
+    asm volatile("" : "+v"(l));
+    return (uint32_t*)lstk - l;
+  };
   uint32_t* const ctx = &s_ctx[threadIdx.x >> 6][0][lane];
 #define CTX(i) ctx[((NCTX == 8 && (i) > 5) ? (i) - 1 : (i)) * 64]
   // top of the tree staged in LDS (north_star: "BVH nodes staged through LDS"): the first levels are what every ray of every
@@ -539,6 +598,13 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   static_assert(STACK_CAP > LSTK, "stack");
   uint32_t ovf_d[STACK_CAP - LSTK];
   float ovf_m[STACK_CAP - LSTK];
+  // (IDENT implies a timed plain / shadow frame job that is not EXACT and not ALPHA: the static_assert above)
+  constexpr bool BOX_NO_SELECT = RT_BOX_NO_SELECT && RT_OCC_OK_MASKS && IDENT && job_base(JOB) == JOB_RENDER_SHADOW;   // (RT_BOX_NO_SELECT above)
+  // timed shadow frame jobs, identity-root kernels: the occlusion-only form of the traversal loop beside the general one (RT_OCC_LOOP above)
+  // IDENT only: in the general kernels the second loop (with its own instance step) costs the register allocation 17 - 26 more spilled
+  // VGPRs, some of them reloaded inside both loops (profiles/r13_a_isa_sections.txt; DESIGN.md s5, rejected)
+  constexpr bool OCC_LOOP = RT_OCC_LOOP && IDENT && RT_BATCH_PUSH && RT_UNORDERED_OCCLUSION && RT_OCC_OK_MASKS && job_base(JOB) == JOB_RENDER_SHADOW &&
+                            DEAD_MAX >= 64u && FINISH_MIN > 64u && STACK_CAP > 2 * LSTK;
   // wave-uniform job-queue state
   bool queue_empty = false;
   // Home shard = the PHYSICAL XCD the wavefront runs on (HW_REG_XCC_ID, 0..7), so that band s of the frame is traced by the same XCD in every
@@ -712,7 +778,16 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   // set once, and a lane decides once where its slots lie: all in LDS, all in scratch, or (the step that crosses the boundary) entry by
   // entry as push() does.  The three arms are per-lane branches: the compiler keeps them apart in this listing (an arm no lane takes is
   // jumped over with EXEC empty), but nothing in the source forces that -- tools/isa_sections.py shows what a compiler made of it.
-  auto push_pending = [&](bool p0, uint32_t d0, float m0, bool p1, uint32_t d1, float m1, bool p2, uint32_t d2, float m2) {
+  //
+  // The occlusion-only form of the traversal loop (`occ`, RT_OCC_LOOP; OCC_LOOP above says which kernels hold it) keeps the descriptor alone:
+  // an occlusion ray's hitd is the constant distance to the light until the ray stops, a child is only pushed when its box is entered before
+  // hitd, so the path maximum of an entry always passes pop_next's `m < hitd` and is never needed.  Its entries are 4 bytes: the LDS rows
+  // of s_stk hold 2 * LSTK of them per lane (rows of 64 dwords, lstk4), the rest goes to ovf_d (STACK_CAP - 2 * LSTK < STACK_CAP - LSTK
+  // entries); STACK_CAP and the heights are the same in both forms.  The two layouts never meet: start_ray empties the stack, and a ray's
+  // whole traversal lies inside ONE invocation of ONE form of the loop -- with whole-tile batches (DEAD_MAX 64, FINISH_MIN off: required by
+  // OCC_LOOP) the loop is only left when no lane holds work, and lanes receive rays outside it.
+  auto push_pending = [&](auto occ, bool p0, uint32_t d0, float m0, bool p1, uint32_t d1, float m1, bool p2, uint32_t d2, float m2) {
+    constexpr bool OCC = decltype(occ)::value;
     if (!RT_BATCH_PUSH) {
       if (p0) push(d0, m0);
       if (p1) push(d1, m1);
@@ -723,6 +798,28 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     const bool w_top = tos_d != DESC_DONE;          // the old top goes to slot sp
     const bool w0 = p0 && (p1 || p2), w1 = p1 && p2;   // (d2 is never stored: if it is pushed, it is the new top)
     const int q0 = sp + (w_top ? 1 : 0), q1 = q0 + (w0 ? 1 : 0), end = q1 + (w1 ? 1 : 0);   // slots of d0, of d1; the new sp
+    if constexpr (OCC) {
+      // 4-byte entries: 2 * LSTK rows of 64 dwords in LDS, then ovf_d
+      constexpr int LROWS = 2 * LSTK;
+      uint32_t* const lstk4 = lstk4_here();
+      if (end <= LROWS) {
+        if (w_top) lstk4[sp * 64] = tos_d;
+        if (w0) lstk4[q0 * 64] = d0;
+        if (w1) lstk4[q1 * 64] = d1;
+      } else if (sp >= LROWS) {
+        if (w_top) ovf_d[sp - LROWS] = tos_d;
+        if (w0) ovf_d[q0 - LROWS] = d0;
+        if (w1) ovf_d[q1 - LROWS] = d1;
+      } else {
+        auto put = [&](int q, uint32_t d) {
+          if (q < LROWS) lstk4[q * 64] = d;
+          else ovf_d[q - LROWS] = d;
+        };
+        if (w_top) put(sp, tos_d);
+        if (w0) put(q0, d0);
+        if (w1) put(q1, d1);
+      }
+    } else
     if (end <= LSTK) {
       if (w_top) lstk[sp * 64] = make_uint2(tos_d, __float_as_uint(tos_m));
       if (w0) lstk[q0 * 64] = make_uint2(d0, __float_as_uint(m0));
@@ -742,31 +839,44 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     }
     sp = end;
     tos_d = p2 ? d2 : (p1 ? d1 : d0);
-    tos_m = p2 ? m2 : (p1 ? m1 : m0);
+    if constexpr (!OCC) tos_m = p2 ? m2 : (p1 ? m1 : m0);
   };
   // entry `i` of the stack's memory part (LDS, then scratch)
-  auto stack_load = [&](int i, uint32_t& d, float& m) {
+  auto stack_load = [&](auto occ, int i, uint32_t& d, float& m) {
     // (LDS-typed pointer: through two plain pointers the compiler merges the arms into flat loads of a selected address)
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    typedef __attribute__((address_space(3))) const u32x2_t lds_u32x2_t;
-    if (i < LSTK) { const u32x2_t e = ((lds_u32x2_t*)lstk)[i * 64]; d = e.x; m = __uint_as_float(e.y); }
-    else { d = ovf_d[i - LSTK]; m = ovf_m[i - LSTK]; }
+    if constexpr (decltype(occ)::value) {
+      typedef __attribute__((address_space(3))) const uint32_t lds_u32_t;
+      if (i < 2 * LSTK) d = ((lds_u32_t*)lstk4_here())[i * 64];
+      else d = ovf_d[i - 2 * LSTK];
+    } else {
+      typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+      typedef __attribute__((address_space(3))) const u32x2_t lds_u32x2_t;
+      if (i < LSTK) { const u32x2_t e = ((lds_u32x2_t*)lstk)[i * 64]; d = e.x; m = __uint_as_float(e.y); }
+      else { d = ovf_d[i - LSTK]; m = ovf_m[i - LSTK]; }
+    }
   };
   // next pending work item of this lane (m < hit.dist: the reference's re-filtering),
   // or DESC_DONE when its stack is exhausted.  The refill of the register top from LDS is not waited for.
-  auto pop_next = [&]() {
+  auto pop_next = [&](auto occ) {
+    if constexpr (decltype(occ)::value) {
+      // (every entry passes the re-filter, see above: the top is taken as it is)
+      cur = tos_d;
+      tos_d = DESC_DONE;
+      if (cur != DESC_DONE && sp > 0) { --sp; float m; stack_load(occ, sp, tos_d, m); }
+      return;
+    }
     if (RT_BATCH_PUSH) {
       // the candidates are the register top, then the memory part from sp - 1 down.  Entries that the shrunken hit distance filters (rare)
       // are skipped first, reading memory directly; the register top is then refilled ONCE, behind the entry that was taken.
       uint32_t d = tos_d; float m = tos_m;
       while (d != DESC_DONE && !(m < hitd)) {
-        if (sp > 0) { --sp; stack_load(sp, d, m); } else d = DESC_DONE;
+        if (sp > 0) { --sp; stack_load(occ, sp, d, m); } else d = DESC_DONE;
       }
       cur = d;
       tos_d = DESC_DONE;
       if (d != DESC_DONE) {
         path_m = m;
-        if (sp > 0) { --sp; stack_load(sp, tos_d, tos_m); }
+        if (sp > 0) { --sp; stack_load(occ, sp, tos_d, tos_m); }
       }
       return;
     }
@@ -905,196 +1015,26 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     if (STATS && A.wave_log) wl_tf += __builtin_readcyclecounter() - wl_tmark;
 
     // ================= traverse: one step of whatever each lane holds, per iteration =================
-    for (;;) {
-      RT_MARK("loop_top");
-      if (!is_trace_job(JOB) && !EXACT) ++lpt_work;   // (wave-uniform: one scalar add per iteration)
-      if (STATS && A.wave_log) {
-        const unsigned long long nm = __ballot(is_node_desc(cur));
-        ++wl_iter;
-        if (nm) {
-          ++wl_node_x; wl_node_l += (unsigned)__popcll(nm);
-          const uint32_t c0 = __shfl(cur, __ffsll((long long)nm) - 1);
-          if (__ballot(is_node_desc(cur) && cur == c0) == nm) ++wl_no3;   // every node lane of the wavefront is at the same node
-        }
-      }
-      if (STATS && A.wave_log) wl_t0 = __builtin_readcyclecounter();
-      RT_MARK("node");
-      if (is_node_desc(cur)) {
-        // ---- internal node: 4 box tests, order, push the far ones, continue with the nearest ----
-        const bool top = !IDENT && (cur >> 30) == DK_TLAS;   // (IDENT: no lane is at TLAS level inside the loop)
-        if (top && !(flags & F_WORLD)) {   // back at TLAS level after an instance (multi-instance scenes only)
-          float ox, oy, oz, dx, dy, dz, tm;
-          world_ray(ox, oy, oz, dx, dy, dz, tm);
-          arx = ox; ary = oy; arz = oz; aix = 1.0f / dx; aiy = 1.0f / dy; aiz = 1.0f / dz;
-          flags |= F_WORLD;
-        }
-        const uint32_t ni = cur & PAYLOAD_MASK;
-        uint4 q0, q1, q2, q3;
-        if (USE_TOP && (cur & DESC_TOP_FLAG)) {
-          // (volatile, LDS-typed pointer: through plain pointers the compiler merges the two arms into FLAT loads of a
-          // selected address -- thirteen flat_load instead of four ds_read_b128 / global_load_dwordx4)
-          typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-          typedef __attribute__((address_space(3))) const volatile u32x4_t lds_u32x4_t;
-          lds_u32x4_t* tp = (lds_u32x4_t*)&s_top[0][0] + (cur & DESC_TOP_SLOT);
-          const u32x4_t t0 = tp[0], t1 = tp[RT_TOP_NODES], t2 = tp[2 * RT_TOP_NODES], t3 = tp[3 * RT_TOP_NODES];
-          q0 = make_uint4(t0.x, t0.y, t0.z, t0.w); q1 = make_uint4(t1.x, t1.y, t1.z, t1.w);
-          q2 = make_uint4(t2.x, t2.y, t2.z, t2.w); q3 = make_uint4(t3.x, t3.y, t3.z, t3.w);
-          if (STATS && A.wave_log) ++wl_no23;
-        } else {
-          const uint4* np = sc.nodes_c + (size_t)ni * CNODE_VEC4;
-          q0 = np[0]; q1 = np[1]; q2 = np[2]; q3 = np[3];
-        }
-        const uint32_t* ref_node = nullptr;
-        if (LDEXP) ref_node = top ? sc.ref_tlas + (size_t)ni * RT_NODE_DWORDS : sc.ref_bvh + (size_t)(ni - sc.n_tlas) * RT_NODE_DWORDS;
-        if (STATS) fx.node++;
-        Cand c[4];
-        // timed plain / shadow frame jobs: the occlusion arm works on the box tests' own masks (RT_OCC_OK_MASKS above)
-        constexpr bool OK_MASKS = RT_OCC_OK_MASKS && !EXACT && STATS == 0 && !ALPHA && (job_base(JOB) == JOB_RENDER || job_base(JOB) == JOB_RENDER_SHADOW);
-        bool ok[4] = {false, false, false, false};
-        if (OK_MASKS) eval_children_raw<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c, ok);
-        else eval_children<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
-        RT_MARK("stack");
-        if (((job_base(JOB) == JOB_RENDER_SHADOW && RT_UNORDERED_OCCLUSION) || JOB == JOB_TRACE_UNORDERED) && STATS != 1 && __all((flags & F_ANYHIT) != 0u)) {   // STATS keeps the reference's order, hence its fetch counts
-          // occlusion rays of a frame only feed a boolean (is anything hit before the light?): the set
-          // of triangles an any-hit traversal can reach does not depend on the visiting order, so the
-          // ordering network and the path_m bookkeeping are skipped (vxrt_trace's MODE_ANY, which
-          // returns the reference's FIRST accepted candidate, keeps the ordered path)
-          // (OK_MASKS: c[k].d is the raw slab distance here -- an occlusion ray's pushed distance is only ever compared with its constant hitd,
-          // and a child that is pushed carries the same value in both forms)
-          const bool v0 = OK_MASKS ? ok[0] : c[0].d < __builtin_inff(), v1 = OK_MASKS ? ok[1] : c[1].d < __builtin_inff();
-          const bool v2 = OK_MASKS ? ok[2] : c[2].d < __builtin_inff(), v3 = OK_MASKS ? ok[3] : c[3].d < __builtin_inff();
-          if (v0 || v1 || v2 || v3) {
-            bool more = true;
-            if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-            cur = v0 ? c[0].desc : (v1 ? c[1].desc : (v2 ? c[2].desc : c[3].desc));
-            // (slot order: the first valid child is visited, the others are pushed as they come)
-            push_pending(more && v1 && v0, c[1].desc, c[1].d, more && v2 && (v0 || v1), c[2].desc, c[2].d, more && v3 && (v0 || v1 || v2), c[3].desc, c[3].d);
-          } else {
-            pop_next();
-          }
-        } else {
-          if (OK_MASKS) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c[k].d = ok[k] ? c[k].d : __builtin_inff();
-          }
-          order_children(c);   // valid children first (d < inf), nearest in c[0]
-          // (path_m and the candidates' distances are never NaN -- a filtered child carries +inf -- so the maxima need no
-          // canonicalising v_max x, x in front of them)
-          if (c[0].d < __builtin_inff()) {
-            bool more = true;
-            if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-            // far first so that the nearest pending sibling is on top (:98-103)
-            push_pending(more && c[3].d < __builtin_inff(), c[3].desc, vmax_nonan(path_m, c[3].d), more && c[2].d < __builtin_inff(), c[2].desc, vmax_nonan(path_m, c[2].d),
-                         more && c[1].d < __builtin_inff(), c[1].desc, vmax_nonan(path_m, c[1].d));
-            cur = c[0].desc;
-            path_m = vmax_nonan(path_m, c[0].d);
-          } else {
-            pop_next();
-          }
-        }
-      }
-      if (STATS && A.wave_log) { const unsigned long long t1 = __builtin_readcyclecounter(); wl_tn += t1 - wl_t0; wl_t0 = t1; }
-      RT_MARK("inst");
-      if (!IDENT && __any(is_inst_desc(cur))) {
-        if (is_inst_desc(cur)) {
-          float ox, oy, oz, dx, dy, dz, tm;
-          world_ray(ox, oy, oz, dx, dy, dz, tm);
-          enter_instance(cur & PAYLOAD_MASK, ox, oy, oz, dx, dy, dz);
-        }
-      }
-      // leaves are postponed until RT_LEAF_MIN lanes hold one (or no lane has a node left): the leaf
-      // body then runs for many lanes at once instead of once per iteration for a few
-      RT_MARK("leaf");
-      const unsigned long long leafm = __ballot(is_leaf_desc(cur));
-      if (leafm != 0ull && ((uint32_t)__popcll(leafm) >= (is_trace_job(JOB) ? RT_TRACE_LEAF_MIN : RT_LEAF_MIN) || __ballot(is_node_desc(cur) || (!IDENT && is_inst_desc(cur))) == 0ull)) {
-        // ---- BLAS leaf (:123-161): triangles in index order, strict '<' ----
-        if (STATS && A.wave_log) { ++wl_leaf_x; wl_leaf_l += (unsigned)__popcll(leafm); }
-        if (!is_trace_job(JOB) && !EXACT) lpt_work += 2u;   // (a leaf-body run costs about 2.5 node-body runs: tools/wave_balance.py)
-        {
-          // triangles through LDS (RT_TRI_LDS): the lanes of a tile reach the same leaves, and every one of them loads the leaf's
-          // triangles for itself.  The leaf of the first leaf lane is loaded ONCE, by 3 lanes per triangle, and handed to the lanes
-          // that hold it by broadcast reads; the others load theirs as before.
-          bool tri_from_lds = false;
-          if (TRI_LDS) {
-            const uint32_t L0 = __shfl(cur, __ffsll((long long)leafm) - 1);
-            const uint32_t c0 = (L0 >> LEAF_FIRST_BITS) & LEAF_MAX_INLINE;
-            const unsigned long long same = __ballot(cur == L0);
-            if (c0 != 0u && c0 <= (uint32_t)RT_TRI_LDS && (uint32_t)__popcll(same) >= (uint32_t)RT_TRI_LDS_MIN) {   // (wave-uniform)
-              if (lane < 3u * c0) s_tri[threadIdx.x >> 6][lane] = sc.tri_w[(size_t)(L0 & LEAF_FIRST_MASK) * 3 + lane];
-              tri_from_lds = cur == L0;
-              if (STATS && A.wave_log) wl_no23 += (unsigned)__popcll(same);
-            }
-          }
-          if (is_leaf_desc(cur)) {
-            if (STATS) fx.node++;
-            uint32_t leftFirst = cur & LEAF_FIRST_MASK, triCount = (cur >> LEAF_FIRST_BITS) & LEAF_MAX_INLINE;
-            if (triCount == 0u) {   // leaf with more than 15 triangles: range kept in the reference node
-              const uint32_t* rn = sc.ref_bvh + (size_t)leftFirst * RT_NODE_DWORDS;
-              leftFirst = rn[4]; triCount = rn[5];
-            }
-            const float cdx = __uint_as_float(CTX(0)), cdy = __uint_as_float(CTX(1)), cdz = __uint_as_float(CTX(2));
-            bool stop = false;
-            // ray buffers (incoherent rays, latency-bound leaves): the next triangle's 48 bytes are requested before the
-            // current one is tested, +3 %; camera tiles lose 1.5 % to the extra registers, so they load in place
-            constexpr bool PREFETCH = is_trace_job(JOB) && RT_TRI_PREFETCH;
-            float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, n2 = n0;
-            if (PREFETCH) { const float4* tp0 = sc.tri_w + (size_t)leftFirst * 3; n0 = tp0[0]; n1 = tp0[1]; n2 = tp0[2]; }
-            // the plain / shadow frame jobs (RT_LEAF_FLAT above); the others keep the two-trip triangle test
-            constexpr bool FLAT_TEST = RT_LEAF_FLAT >= 1 && !EXACT && !ALPHA && (job_base(JOB) == JOB_RENDER || job_base(JOB) == JOB_RENDER_SHADOW);
-            RT_MARK("leaf_tris");
-            for (uint32_t i = 0; i < triCount; ++i) {
-              const uint32_t triIdx = leftFirst + i;
-              float4 t0, t1, t2;
-              if (TRI_LDS && tri_from_lds) {
-                // (typed LDS pointer: through a plain pointer the compiler would merge this arm and the global one into flat loads)
-                typedef float f32x4_t __attribute__((ext_vector_type(4)));
-                typedef __attribute__((address_space(3))) const volatile f32x4_t lds_f32x4_t;
-                lds_f32x4_t* lp = (lds_f32x4_t*)&s_tri[threadIdx.x >> 6][0] + 3u * i;
-                const f32x4_t a0 = lp[0], a1 = lp[1], a2 = lp[2];
-                t0 = make_float4(a0.x, a0.y, a0.z, a0.w); t1 = make_float4(a1.x, a1.y, a1.z, a1.w); t2 = make_float4(a2.x, a2.y, a2.z, a2.w);
-              } else
-              if (PREFETCH) {
-                t0 = n0; t1 = n1; t2 = n2;
-                if (i + 1u < triCount) { const float4* tn = sc.tri_w + (size_t)(triIdx + 1u) * 3; n0 = tn[0]; n1 = tn[1]; n2 = tn[2]; }
-              } else {
-                const float4* tp = sc.tri_w + (size_t)triIdx * 3;
-                t0 = tp[0]; t1 = tp[1]; t2 = tp[2];
-              }
-              if (STATS) fx.tri++;
-              float bx, by, bz;
-              const float d = FLAT_TEST ? ray_tri_flat(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz) : ray_tri(arx, ary, arz, cdx, cdy, cdz, t0, t1, t2, bx, by, bz);
-              if (d < hitd) {
-                // a rejected candidate is a triangle the ray missed: no record, no abandon test, no stop, on to the leaf's next triangle
-                if constexpr (ALPHA) { if (alpha_rejects(sc, A.alpha_tri, triIdx, bx, by, bz)) continue; }
-                hitd = d;
-                flags |= F_FOUND;
-                // (a frame's occlusion ray only feeds a boolean; slots 3-7 keep the pixel's primary hit meanwhile)
-                if (!(job_base(JOB) == JOB_RENDER_SHADOW && (flags & F_SHADOW))) { CTX(3) = __float_as_uint(bx); CTX(4) = __float_as_uint(by); CTX(6) = CTX(8); CTX(7) = triIdx; }
-                if (flags & F_ANYHIT) { stop = true; break; }
-                // the reference re-descends from the root with the shrunken hit.dist; if any box on the
-                // current path no longer passes `d < hit.dist` it abandons this subtree
-                if (!(path_m < hitd)) break;
-              }
-            }
-            RT_MARK("leaf_pop");
-            if (stop) { sp = 0; tos_d = DESC_DONE; cur = DESC_DONE; }
-            else pop_next();
-          }
-        }
-      }
-      if (STATS && A.wave_log) { const unsigned long long t1 = __builtin_readcyclecounter(); wl_tl += t1 - wl_t0; }
-      RT_MARK("loop_exit");
-      // leave when nothing traverses any more, or when enough lanes are dead weight AND leaving can
-      // revive them (finished rays to retire, or idle lanes while jobs remain)
-      const unsigned long long work = __ballot(is_work_desc(cur));
-      if (work == 0ull) break;
-      // (every lane that holds no work is finished or idle: while those are fewer than the smaller of the two bounds, neither test below
-      // can hold, and the one ballot above has decided)
-      if (RT_BATCH_PUSH && 64u - (uint32_t)__popcll(work) < (DEAD_MAX < FINISH_MIN ? DEAD_MAX : FINISH_MIN)) continue;
-      const unsigned long long done = __ballot(cur == DESC_DONE);
-      const uint32_t n_done = (uint32_t)__popcll(done);
-      const uint32_t n_idle = queue_empty && loc_next == loc_end ? 0u : 64u - (uint32_t)__popcll(work | done);
-      if (n_done + n_idle >= DEAD_MAX || n_done >= FINISH_MIN) break;
+    // The loop's text is rt_traverse_loop.inc, written once over the compile-time flag OCC.  A kernel that holds the occlusion-only form
+    // (OCC_LOOP) compiles it twice, as the two instantiations of a generic lambda; `occ` = every lane that holds work holds an any-hit ray,
+    // for as long as the loop runs -- lanes only receive rays in the fetch and finish sections, defer() only makes a lane idle.  Every
+    // other kernel has the text in place, outside any lambda, with OCC false: those kernels' listings are the parent form's (wrapped in
+    // the lambda and with the 8-byte push restated through shared helpers they computed the same and ran 2.3 % slower: DESIGN.md s5).
+    if constexpr (OCC_LOOP) {
+      auto traverse = [&](auto occ) {
+        constexpr bool OCC = decltype(occ)::value;
+#include "rt_traverse_loop.inc"
+      };
+      // -DRT_OCC_LOOP_CHECK=1 (variant libraries only): the invariant the two stack layouts rest on -- a lane that holds work in front of
+      // the loop holds a ray fresh from start_ray, with an empty stack -- reported as STATUS_ITER_LIMIT, which every test reads as a failure
+      if (RT_OCC_LOOP_CHECK && is_work_desc(cur) && (sp != 0 || tos_d != DESC_DONE)) atomicOr(A.status, STATUS_ITER_LIMIT);
+      // (is_work_desc: a lane that is finished or idle keeps the flags of its last ray)
+      if (__all(!is_work_desc(cur) || (flags & F_ANYHIT) != 0u)) traverse(std::true_type());
+      else traverse(std::false_type());
+    } else {
+      constexpr bool OCC = false;
+      const std::false_type occ;
+#include "rt_traverse_loop.inc"
     }
 
     // ================= finish: rays whose traversal ended =================
