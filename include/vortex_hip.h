@@ -727,6 +727,89 @@ int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* c
                                      uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
                                      float* prev_position /* optional */, unsigned long long* rays_traced /* optional */, void* stream);
 
+/* Variance guidance: per-pixel luminance moments steer the a-trous filter (extension; absent from the reference).  The luminance
+ * edge-stopping term of atrous has one global scale, halved every pass; here every pixel gets its own, from the variance of its
+ * accumulated luminance (SVGF: the temporal variance where the history is long, a spatial estimate where it is short), and the variance
+ * is filtered along with the signal, so later passes narrow by themselves.  The arithmetic rules are those of the temporal section: one
+ * fp32 operation per symbol, in the order written, no contraction; `/` and sqrtf are correctly rounded; min / max / dot / lum as there;
+ * (float) of an integer is exact for the ranges allowed.  tests/variance_ref.py restates all of it.
+ *
+ * A HISTORY WITH MOMENTS (vxrt_history_create_moments) is vxrt_history_create's plus one float2 buffer per set, HM = (m1, m2): 112 bytes
+ * per pixel.  The two kinds do not mix: vxrt_temporal_accumulate[_motion] and vxrt_render_path_temporal[_motion] return -1 for a history
+ * with moments (its moments would silently go stale), the calls of this section return -1 for one without.  vxrt_history_destroy,
+ * vxrt_history_reset and vxrt_history_read work on both.  vxrt_history_read_moments copies HM of the last frame's window, 2 floats per
+ * pixel; -1 for an empty history, one without moments or a null pointer.
+ *
+ * THE STEP WITH MOMENTS  T_v is the step T (given both motion guides: T_m) with additions and nothing else changed.  lE = lum(E) of the
+ * pixel's input signal; s1 = s2 = +0.
+ *   for every tap that T keeps and whose w > 0, right after sl = sl + w * HE[q].w:  s1 = s1 + w * HM[q].x,  s2 = s2 + w * HM[q].y
+ *   if sw > 0:  M1 = s1 / sw, M2 = s2 / sw,  m1 = M1 + al * (lE - M1),  m2 = M2 + al * (lE * lE - M2)
+ *   else, a hit pixel:  m1 = lE, m2 = lE * lE   (an empty history, a pixel behind the previous camera or outside its view, no tap kept,
+ *                                                a motion pixel for which Q.w != 0 is false)
+ *   a pixel that is not a hit:  m1 = m2 = +0
+ * The new history is that of T plus HM = (m1, m2); out = (E_acc, len) is bit for bit what T / T_m give on a history without moments fed
+ * the same frames.  The temporal variance of a pixel is vt = max(m2 - m1 * m1, 0).
+ * vxrt_temporal_accumulate_moments has the contract of vxrt_temporal_accumulate_motion; prev_position and prev_normal are both NULL (T_v
+ * over T) or both set (T_v over T_m), one of the two NULL returns -1.
+ *
+ * THE INITIAL VARIANCE  V0 of the history's current set: A = HE = (E_acc, len), HM, HP, HN as the step just wrote them; dn =
+ * vxrt_denoise_params_t (normal_power and sigma_z are used), vp = vxrt_variance_params_t.  For pixel p of the window:
+ *   p is not a hit: V0 = 0.     A[p].w >= (float)min_len: V0 = vt.
+ *   else sw = s1 = s2 = +0; the taps are visited in the order dy = -radius..radius (outer), dx = -radius..radius (inner), q = p + (dx, dy).
+ *   A tap outside the window or not a hit is skipped; the centre is a tap like any other.  For a tap that is not skipped:
+ *     dn = the filter's normal weight of (Np, Nq): max(dot, +0) squared normal_power times
+ *     t = fabsf(dot(Np, Pq - Pp)) / sigma_z;  wz = 1 / (1 + t * t);  w = dn * wz
+ *     if w > 0:  l = lum(A[q].rgb),  sw = sw + w,  s1 = s1 + w * l,  s2 = s2 + w * (l * l)
+ *   if sw > 0:  a1 = s1 / sw,  vs = max(s2 / sw - a1 * a1, 0),  V0 = vs * ((float)min_len / A[p].w)
+ *   else V0 = vt.
+ * vxrt_history_variance writes V0 of the last frame's window, 1 float per pixel: one launch, no host synchronisation; -1 for an empty
+ * history, one without moments, bad parameters or a null pointer.
+ *
+ * THE VARIANCE-GUIDED FILTER  (F, VF) = atrous_v(S, V, P, N, dn, vp); S, P, N, dn as for atrous, V one float per pixel.  For iteration i,
+ * step = 1 << i, in / vin = the previous iteration's outputs (S / V for i = 0):
+ *   p is not a hit: out[p] = in[p], vout[p] = vin[p].
+ *   else the prefiltered variance: gw = gs = +0; dy = -1..1 (outer), dx = -1..1 (inner), q = p + (dx, dy) -- stride 1 whatever step is; a
+ *   tap outside the window or not a hit is skipped; c = kk[dy+1] * kk[dx+1], kk = {1/4, 1/2, 1/4}; gw = gw + c, gs = gs + c * vin[q].
+ *     g = gs / gw;  den = sigma_l * sqrtf(g) + epsilon      (sigma_l is NOT halved per pass here: the variance shrinks instead)
+ *   then the 25 taps of atrous, in its order and with its skips, with u = fabsf(lum(in[p]) - lum(in[q])) / den in place of the division
+ *   by sl; w = ((h * dn) * wz) * wc as there; if w > 0: sw = sw + w, sc = sc + w * in[q] per channel, sv = sv + (w * w) * vin[q] (sv from +0).
+ *   if sw > 0: out[p] = sc / sw, vout[p] = sv / (sw * sw); else out[p] = in[p], vout[p] = vin[p].
+ * A NaN or negative variance is legal input: the result is whatever the operations give (sqrtf of a negative is NaN, and every tap of
+ * that pixel is then dropped).  vxrt_denoise_variance has the contract of vxrt_denoise; variance: device, 1 float per pixel; out_variance
+ * (optional) receives VF and must not alias variance.  iterations = 0: out and out_variance are copies of signal and variance.
+ *
+ * THE FRAME.  vxrt_render_path_variance with motion = 0 is vxrt_render_path_temporal with T_v in place of T, with motion = 1
+ * vxrt_render_path_temporal_motion with T_v in place of T_m; after the step one launch writes V0, and atrous_v runs on (out.rgb, V0);
+ * remodulation and pack are unchanged and stay in the last pass.  With dn->iterations = 0 no variance is computed, except into `variance`
+ * if that output is asked for, and the frame is vxrt_render_path_temporal[_motion] bit for bit: pixels, colours, rays traced and HE.
+ * variance (optional): V0, 1 float per pixel, addressed like `colors`.  It refuses what that call refuses, and: bad vp, a history
+ * without moments, motion > 1, motion = 0 with a non-null prev_position -- before anything is launched, the history and dst left as
+ * they were.  One launch more than the temporal frame, no traced ray and no host synchronisation more. */
+typedef struct vxrt_variance_params {
+  float epsilon;      /* added to the luminance scale of a tap, > 0 and finite */
+  uint32_t min_len;   /* accumulated lengths below this take the spatial estimate, 1..VXRT_TEMPORAL_MAX_LEN */
+  uint32_t radius;    /* half width of the spatial estimate's window, 1..3 */
+  uint32_t reserved;  /* 0 */
+} vxrt_variance_params_t;
+int vxrt_history_create_moments(uint32_t width, uint32_t rows, vxrt_history_t** history);
+int vxrt_history_read_moments(vxrt_history_t* history, float* out2, void* stream);
+int vxrt_temporal_accumulate_moments(vxrt_history_t* history, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0,
+                                     uint32_t y1, const float* signal, const float* position, const float* normal,
+                                     const float* prev_position /* or NULL */, const float* prev_normal /* or NULL */,
+                                     const vxrt_temporal_params_t* prm, float* out4, void* stream);
+int vxrt_history_variance(vxrt_history_t* history, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp,
+                          float* variance /* device, 1 float per pixel of the window */, void* stream);
+uint64_t vxrt_denoise_variance_scratch_bytes(uint32_t width, uint32_t rows);
+int vxrt_denoise_variance(uint32_t width, uint32_t rows, const float* signal, const float* variance, const float* position,
+                          const float* normal, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out,
+                          float* out_variance /* optional */, void* scratch, uint64_t scratch_bytes, void* stream);
+int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                              const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp, vxrt_history_t* history,
+                              int motion, uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
+                              float* prev_position /* optional, motion only */, float* variance /* optional */,
+                              unsigned long long* rays_traced /* optional */, void* stream);
+
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,
  * invTransform, bvh_offset@128, tex_offset@136, tex_width@144, tex_height@148, reflectivity@152),

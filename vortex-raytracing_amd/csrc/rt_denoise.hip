@@ -1,6 +1,7 @@
 // Guided a-trous filter of denoised path frames (vxrt_render_path_denoised, vxrt_denoise; the definition is in include/vortex_hip.h,
 // tests/denoise_ref.py restates it, DESIGN.md s2 "Denoised path frames" has the launch sequence and the measurements), and below it the
-// temporal accumulation that may precede it (vxrt_render_path_temporal, vxrt_temporal_accumulate; DESIGN.md s2 "Temporal accumulation").
+// temporal accumulation that may precede it (vxrt_render_path_temporal, vxrt_temporal_accumulate; DESIGN.md s2 "Temporal accumulation"),
+// and below that the variance guidance that builds on both (vxrt_render_path_variance; DESIGN.md s2 "Variance guidance").
 //
 // Per iteration one launch: a 25-tap stencil with stride `step` over three float4 arrays per pixel -- the signal S = (r, g, b, lum), the
 // position guide P = (I, hit flag) and the normal guide N.  The luminance travels in the signal's fourth component: the pass that
@@ -180,13 +181,18 @@ struct TpArgs {
 
 // the step with motion, T_m (MOTION instantiations): the two guides more, per pixel of the window
 struct TpMotionArgs : TpArgs { const float4* Q; const float4* Nq; };
+// the step with moments, T_v (MOMENTS instantiations, over either of the two): HM = (m1, m2) of the previous frame's set and of this frame's
+template <class Base> struct TpMomentArgs : Base { const float2* hm; float2* hm_o; };
+template <bool MOTION, bool MOMENTS> struct TpKernelArgs { using base = std::conditional_t<MOTION, TpMotionArgs, TpArgs>; using type = std::conditional_t<MOMENTS, TpMomentArgs<base>, base>; };
 
 __device__ __forceinline__ float tp_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
 // MOTION: the pixel's previous position Q and previous normal N' (two 16-byte loads more, issued with the pixel's other loads) take the
 // place of its hit point and normal in the reprojection and in the two tap tests; the history written is the current frame's as ever.
-template <int OUT, bool MOTION = false>
-__global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_t<MOTION, TpMotionArgs, TpArgs> A) {
+// MOMENTS (the header's "Variance guidance"): the first and second luminance moments travel with the signal -- one 8-byte load per tap,
+// issued with the tap's other loads, two multiply-adds per kept tap, one 8-byte store; nothing of the step itself changes.
+template <int OUT, bool MOTION = false, bool MOMENTS = false>
+__global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(typename TpKernelArgs<MOTION, MOMENTS>::type A) {
   const uint32_t bx = blockIdx.x % A.tiles_x, by = blockIdx.x / A.tiles_x;
   const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
   if (x >= A.W || y >= A.rows) return;
@@ -199,6 +205,11 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_
   if constexpr (MOTION) { Qp = A.Q[p]; Nq = A.Nq[p]; }
   const bool hit = Pp.w != 0.f;
   float orr = er, og = eg, ob = eb, olen = hit ? 1.f : 0.f;
+  float lE = 0.f, m1 = 0.f, m2 = 0.f;   // (MOMENTS)
+  if constexpr (MOMENTS) {
+    lE = dn_lum(er, eg, eb);
+    if (hit) { m1 = lE; m2 = lE * lE; }
+  }
   if (hit && A.have && (!MOTION || Qp.w != 0.f)) {
     const float dx = Qp.x - A.pos[0], dy = Qp.y - A.pos[1], dz = Qp.z - A.pos[2];
     const float a = tp_dot(dx, dy, dz, A.Rr[0], A.Rr[1], A.Rr[2]);
@@ -212,6 +223,7 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_
         const float tx = fx - flx, ty = fy - fly;
         const int64_t x0 = (int64_t)flx, yy = (int64_t)fly;   // (-1 .. W - 1, -1 .. rows - 1)
         float4 He[4], Hp[4], Hn[4];
+        float2 Hm[4];
         bool in[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -219,8 +231,9 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_
           in[k] = qx >= 0 && qx < (int64_t)A.W && qy >= 0 && qy < (int64_t)A.rows;
           const size_t q = in[k] ? (size_t)qy * A.W + (size_t)qx : p;
           He[k] = A.he[q]; Hp[k] = A.hp[q]; Hn[k] = A.hn[q];
+          if constexpr (MOMENTS) Hm[k] = A.hm[q];
         }
-        float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
+        float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f, s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           if (!in[k]) continue;
@@ -233,6 +246,7 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_
             sw = sw + w;
             sr = sr + w * He[k].x; sg = sg + w * He[k].y; sb = sb + w * He[k].z;
             sl = sl + w * He[k].w;
+            if constexpr (MOMENTS) { s1 = s1 + w * Hm[k].x; s2 = s2 + w * Hm[k].y; }
           }
         }
         if (sw > 0.f) {
@@ -242,6 +256,10 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_
           const float al = r1 < A.alpha_min ? A.alpha_min : r1;
           orr = hr + al * (er - hr); og = hg + al * (eg - hg); ob = hb + al * (eb - hb);
           olen = L1;
+          if constexpr (MOMENTS) {
+            const float M1 = s1 / sw, M2 = s2 / sw;
+            m1 = M1 + al * (lE - M1); m2 = M2 + al * (lE * lE - M2);
+          }
         }
       }
     }
@@ -249,9 +267,187 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(std::conditional_
   A.he_o[p] = make_float4(orr, og, ob, olen);
   A.hp_o[p] = Pp;
   A.hn_o[p] = Np;
+  if constexpr (MOMENTS) A.hm_o[p] = make_float2(m1, m2);
   if constexpr (OUT == TP_OUT_SIGNAL) A.sig[p] = make_float4(orr, og, ob, dn_lum(orr, og, ob));
   else if constexpr (OUT == TP_OUT_LEN) { float* o = A.out4 + 4 * p; o[0] = orr; o[1] = og; o[2] = ob; o[3] = olen; }
   else dn_write<DN_OUT_PATH>(A.path, x, y, orr, og, ob, hit);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Variance guidance (vxrt_history_variance, vxrt_denoise_variance, vxrt_render_path_variance; the definition is the header's "Variance
+// guidance", tests/variance_ref.py restates it).  Two kernels on the 32 x 8 tile, one pixel per thread.
+//   rt_vr_initial_kernel    V0 of the history's current set.  A pixel with a long history takes the temporal variance of its own moments:
+//                           four loads and five operations.  Only a pixel with a short history walks the (2 radius + 1)^2 window of three
+//                           16-byte loads per tap.  The walk sits behind `if (need)`: a wavefront in which no lane needs it branches over
+//                           the loop on an empty exec mask, and after the first few frames that is nearly every wavefront; inside a
+//                           wavefront that does walk, the trip count is uniform (radius), only the lanes that walk differ.
+//   rt_vr_iteration_kernel  one pass of atrous_v.  The variance travels in the signal's fourth component, S = (r, g, b, V), in place of
+//                           the luminance the plain filter keeps there: a tap stays three 16-byte loads, lum() of a tap is recomputed
+//                           (three operations against about 100), and the nine prefilter taps are two 4-byte loads each (V and the hit
+//                           flag) from lines the 25 taps of step 1 fetch anyway.  No buffer of its own, no fourth gather per tap.
+// ---------------------------------------------------------------------------------------------
+struct VrInitArgs {
+  uint32_t W, rows, tiles_x, npow, radius, y0;
+  float sz, fmin;                               // sigma_z, (float)min_len
+  const float4* he; const float2* hm; const float4* hp; const float4* hn;   // the history's current set
+  float* out; uint32_t out_stride;              // V0 of pixel p of the window goes to out[p * out_stride] (1: a float buffer; 4: the signal's w) ...
+  float* frame_out;                             // ... and, optional, to the frame's `variance` output (full-frame addressing, rows from y0)
+};
+
+__global__ __launch_bounds__(256) void rt_vr_initial_kernel(VrInitArgs A) {
+  const uint32_t bx = blockIdx.x % A.tiles_x, by = blockIdx.x / A.tiles_x;
+  const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
+  if (x >= A.W || y >= A.rows) return;
+  const size_t p = (size_t)y * A.W + x;
+  const float4 Ap = A.he[p], Pp = A.hp[p];
+  const float2 Mp = A.hm[p];
+  const bool hit = Pp.w != 0.f;
+  const float vd = Mp.y - Mp.x * Mp.x;
+  const float vt = vd < 0.f ? 0.f : vd;         // max(vd, 0)
+  float v0 = hit ? vt : 0.f;
+  const bool need = hit && !(Ap.w >= A.fmin);
+  if (need) {
+    const float4 Np = A.hn[p];
+    const int r = (int)A.radius;
+    float sw = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int dy = -r; dy <= r; ++dy) {
+      const int64_t qy = (int64_t)y + dy;
+      if (qy < 0 || qy >= (int64_t)A.rows) continue;
+      for (int dx = -r; dx <= r; ++dx) {
+        const int64_t qx = (int64_t)x + dx;
+        if (qx < 0 || qx >= (int64_t)A.W) continue;
+        const size_t q = (size_t)qy * A.W + (size_t)qx;
+        const float4 Pq = A.hp[q], Nq = A.hn[q], Aq = A.he[q];
+        if (!(Pq.w != 0.f)) continue;
+        const float d = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;
+        float dn = d > 0.f ? d : 0.f;
+        for (uint32_t k = 0; k < A.npow; ++k) dn = dn * dn;
+        const float ex = Pq.x - Pp.x, ey = Pq.y - Pp.y, ez = Pq.z - Pp.z;
+        const float t = fabsf((Np.x * ex + Np.y * ey) + Np.z * ez) / A.sz;
+        const float wz = 1.0f / (1.0f + t * t);
+        const float w = dn * wz;
+        if (w > 0.f) {
+          const float l = dn_lum(Aq.x, Aq.y, Aq.z);
+          sw = sw + w;
+          s1 = s1 + w * l;
+          s2 = s2 + w * (l * l);
+        }
+      }
+    }
+    if (sw > 0.f) {
+      const float a1 = s1 / sw;
+      const float sd = s2 / sw - a1 * a1;
+      const float vs = sd < 0.f ? 0.f : sd;
+      v0 = vs * (A.fmin / Ap.w);
+    }
+  }
+  if (A.out) A.out[p * A.out_stride] = v0;
+  if (A.frame_out) A.frame_out[(size_t)x + (size_t)(A.y0 + y) * A.W] = v0;
+}
+
+struct VrArgs {
+  DnArgs d;          // of the plain filter; d.sl = sigma_l (not halved: the variance shrinks instead); d.S and d.out4 hold (r, g, b, V)
+  float eps;
+  float* outv;       // DN_OUT_RGB: the filtered variance, optional
+};
+
+// one tap of atrous_v that is inside the window: dn_tap with the luminance scale `den` of the centre and the variance sum
+__device__ __forceinline__ void vr_tap(const float4& Pp, const float4& Np, float lp, const float4& Sq, const float4& Pq, const float4& Nq, float h,
+                                       uint32_t npow, float sz, float den, float& sw, float& sr, float& sg, float& sb, float& sv) {
+  if (Pq.w != 0.f) {
+    const float d = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;
+    float dn = d > 0.f ? d : 0.f;
+    for (uint32_t k = 0; k < npow; ++k) dn = dn * dn;
+    const float ex = Pq.x - Pp.x, ey = Pq.y - Pp.y, ez = Pq.z - Pp.z;
+    const float t = fabsf((Np.x * ex + Np.y * ey) + Np.z * ez) / sz;
+    const float wz = 1.0f / (1.0f + t * t);
+    const float u = fabsf(lp - dn_lum(Sq.x, Sq.y, Sq.z)) / den;
+    const float wc = 1.0f / (1.0f + u * u);
+    const float w = ((h * dn) * wz) * wc;
+    if (w > 0.f) {
+      sw = sw + w;
+      sr = sr + w * Sq.x; sg = sg + w * Sq.y; sb = sb + w * Sq.z;
+      sv = sv + (w * w) * Sq.w;
+    }
+  }
+}
+
+template <int OUT>
+__device__ __forceinline__ void vr_write(const VrArgs& A, uint32_t x, uint32_t y, float r, float g, float b, float v, bool hit) {
+  const size_t p = (size_t)y * A.d.W + x;
+  if constexpr (OUT == DN_OUT_SIGNAL) {
+    A.d.out4[p] = make_float4(r, g, b, v);
+  } else {
+    dn_write<OUT>(A.d, x, y, r, g, b, hit);
+    if constexpr (OUT == DN_OUT_RGB) { if (A.outv) A.outv[p] = v; }
+  }
+}
+
+__device__ __forceinline__ float vr_kk(int i) { return i == 1 ? 0.5f : 0.25f; }
+
+template <int OUT>
+__global__ __launch_bounds__(256) void rt_vr_iteration_kernel(VrArgs A) {
+  const DnArgs& D = A.d;
+  const uint32_t bx = blockIdx.x % D.tiles_x, by = blockIdx.x / D.tiles_x;
+  const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
+  if (x >= D.W || y >= D.rows) return;
+  const size_t p = (size_t)y * D.W + x;
+  const float4 Sp = D.S[p], Pp = D.P[p];
+  if (!(Pp.w != 0.f)) { vr_write<OUT>(A, x, y, Sp.x, Sp.y, Sp.z, Sp.w, false); return; }
+  const float4 Np = D.N[p];
+  // the prefiltered variance of the centre: 3 x 3 at stride 1, hit taps of the window only (a tap outside reads the centre and is dropped)
+  float gw = 0.f, gs = 0.f;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy) {
+    const int64_t qy = (int64_t)y + dy;
+    const bool iny = qy >= 0 && qy < (int64_t)D.rows;
+    float Vq[3], Fq[3];
+    bool in[3];
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int64_t qx = (int64_t)x + dx;
+      in[dx + 1] = iny && qx >= 0 && qx < (int64_t)D.W;
+      const size_t q = in[dx + 1] ? (size_t)qy * D.W + (size_t)qx : p;
+      Vq[dx + 1] = D.S[q].w; Fq[dx + 1] = D.P[q].w;
+    }
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx)
+      if (in[dx + 1] && Fq[dx + 1] != 0.f) {
+        const float c = vr_kk(dy + 1) * vr_kk(dx + 1);
+        gw = gw + c;
+        gs = gs + c * Vq[dx + 1];
+      }
+  }
+  const float g = gs / gw;
+  const float den = D.sl * sqrtf(g) + A.eps;
+  const float lp = dn_lum(Sp.x, Sp.y, Sp.z);
+  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+  for (int dy = -2; dy <= 2; ++dy) {
+    const int64_t qy = (int64_t)y + (int64_t)dy * D.step;
+    if (qy < 0 || qy >= (int64_t)D.rows) continue;   // (uniform over a row of the tile)
+    const float ky = dn_k(dy + 2);
+    float4 Sq[5], Pq[5], Nq[5];
+    bool in[5];
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      const int64_t qx = (int64_t)x + (int64_t)dx * D.step;
+      in[dx + 2] = qx >= 0 && qx < (int64_t)D.W;
+      const size_t q = in[dx + 2] ? (size_t)qy * D.W + (size_t)qx : p;
+      Sq[dx + 2] = D.S[q]; Pq[dx + 2] = D.P[q]; Nq[dx + 2] = D.N[q];
+    }
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx)
+      if (in[dx + 2]) vr_tap(Pp, Np, lp, Sq[dx + 2], Pq[dx + 2], Nq[dx + 2], ky * dn_k(dx + 2), D.npow, D.sz, den, sw, sr, sg, sb, sv);
+  }
+  if (sw > 0.f) vr_write<OUT>(A, x, y, sr / sw, sg / sw, sb / sw, sv / (sw * sw), true);
+  else vr_write<OUT>(A, x, y, Sp.x, Sp.y, Sp.z, Sp.w, true);
+}
+
+// the signal of a stand-alone call: (r, g, b), V -> (r, g, b, V)
+__global__ __launch_bounds__(256) void rt_vr_load_kernel(uint32_t n, const float* __restrict__ sig3, const float* __restrict__ var, float4* __restrict__ out) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  out[t] = make_float4(sig3[3 * (size_t)t], sig3[3 * (size_t)t + 1], sig3[3 * (size_t)t + 2], var[t]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -303,6 +499,8 @@ int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0,
 struct vxrt_history {
   uint64_t cap = 0;                  // pixels each buffer holds
   float4* he[2] = {nullptr, nullptr}; float4* hp[2] = {nullptr, nullptr}; float4* hn[2] = {nullptr, nullptr};
+  float2* hm[2] = {nullptr, nullptr};   // HM = (m1, m2): a history with moments only (vxrt_history_create_moments)
+  bool moments = false;
   uint32_t cur = 0;                  // the set the last frame wrote
   bool empty = true;
   vxrt_camera_t cam{};               // of the last frame, with its geometry
@@ -321,8 +519,13 @@ static bool tp_params_ok(const vxrt_temporal_params_t* t) {
          std::isfinite(t->normal_min);   // (the comparisons are false for NaN)
 }
 
-bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels) {
-  return h && tp_params_ok(t) && pixels <= h->cap;
+bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels, bool moments) {
+  return h && h->moments == moments && tp_params_ok(t) && pixels <= h->cap;
+}
+
+bool vr_params_ok(const vxrt_variance_params_t* v) {
+  return v && v->epsilon > 0.0f && std::isfinite(v->epsilon) && v->min_len >= 1u && v->min_len <= VXRT_TEMPORAL_MAX_LEN && v->radius >= 1u &&
+         v->radius <= 3u && v->reserved == 0u;
 }
 
 // the reciprocal basis of camera c (the header's rule: doubles, no contraction, one rounding to fp32 per component)
@@ -339,7 +542,24 @@ static void tp_reciprocal_basis(const vxrt_camera_t& c, float Rr[3], float Ur[3]
 
 // One step on history h: the checks are the caller's (window of at most h->cap pixels, not empty).  Launches, then makes the written set,
 // `cam` and the geometry the history's state.
-// Q / Nq: both null (the step T) or both set (the step with motion, T_m).
+// Q / Nq: both null (the step T) or both set (the step with motion, T_m).  A history with moments takes the MOMENTS instantiations
+// (T_v over either): the kind of the history is the caller's to check against the call.
+template <int OUT, bool MOTION, bool MOMENTS>
+static void tp_launch_kernel(hipStream_t s, dim3 grid, const vxrt_history_t* h, uint32_t prev, uint32_t next, const TpArgs& A, const float4* Q, const float4* Nq) {
+  typename TpKernelArgs<MOTION, MOMENTS>::type K{};
+  static_cast<TpArgs&>(K) = A;
+  if constexpr (MOTION) { K.Q = Q; K.Nq = Nq; }
+  if constexpr (MOMENTS) { K.hm = h->hm[prev]; K.hm_o = h->hm[next]; }
+  hipLaunchKernelGGL((rt_tp_accumulate_kernel<OUT, MOTION, MOMENTS>), grid, dim3(256), 0, s, K);
+}
+
+template <bool MOTION, bool MOMENTS>
+static void tp_launch_out(hipStream_t s, dim3 grid, const vxrt_history_t* h, uint32_t prev, uint32_t next, int out, const TpArgs& A, const float4* Q, const float4* Nq) {
+  if (out == TP_OUT_SIGNAL) tp_launch_kernel<TP_OUT_SIGNAL, MOTION, MOMENTS>(s, grid, h, prev, next, A, Q, Nq);
+  else if (out == TP_OUT_LEN) tp_launch_kernel<TP_OUT_LEN, MOTION, MOMENTS>(s, grid, h, prev, next, A, Q, Nq);
+  else tp_launch_kernel<TP_OUT_PATH, MOTION, MOMENTS>(s, grid, h, prev, next, A, Q, Nq);
+}
+
 static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
                      const vxrt_temporal_params_t* t, int out, TpArgs A, const float4* Q = nullptr, const float4* Nq = nullptr) {
   const uint32_t rows = y1 - y0;
@@ -355,16 +575,12 @@ static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam,
   A.alpha_min = t->alpha_min; A.sigma_z = t->sigma_z; A.normal_min = t->normal_min;
   A.he = h->he[prev]; A.hp = h->hp[prev]; A.hn = h->hn[prev];
   A.he_o = h->he[next]; A.hp_o = h->hp[next]; A.hn_o = h->hn[next];
-  const dim3 grid(A.tiles_x * ((rows + DN_TY - 1u) / DN_TY)), block(256);
-  if (Q) {
-    TpMotionArgs M{};
-    static_cast<TpArgs&>(M) = A; M.Q = Q; M.Nq = Nq;
-    if (out == TP_OUT_SIGNAL) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_SIGNAL, true>), grid, block, 0, s, M);
-    else if (out == TP_OUT_LEN) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_LEN, true>), grid, block, 0, s, M);
-    else hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_PATH, true>), grid, block, 0, s, M);
-  } else if (out == TP_OUT_SIGNAL) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_SIGNAL>), grid, block, 0, s, A);
-  else if (out == TP_OUT_LEN) hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_LEN>), grid, block, 0, s, A);
-  else hipLaunchKernelGGL((rt_tp_accumulate_kernel<TP_OUT_PATH>), grid, block, 0, s, A);
+  const dim3 grid(A.tiles_x * ((rows + DN_TY - 1u) / DN_TY));
+  if (h->moments) {
+    if (Q) tp_launch_out<true, true>(s, grid, h, prev, next, out, A, Q, Nq);
+    else tp_launch_out<false, true>(s, grid, h, prev, next, out, A, Q, Nq);
+  } else if (Q) tp_launch_out<true, false>(s, grid, h, prev, next, out, A, Q, Nq);
+  else tp_launch_out<false, false>(s, grid, h, prev, next, out, A, Q, Nq);
   if (hipGetLastError() != hipSuccess) return -1;
   h->cur = next; h->empty = false; h->cam = *cam; h->W = W; h->H = H; h->y0 = y0; h->y1 = y1;
   return 0;
@@ -379,31 +595,83 @@ int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, u
   return tp_launch(s, h, cam, W, H, y0, y1, t, filtered ? TP_OUT_SIGNAL : TP_OUT_PATH, A, prev_pos, prev_nrm);
 }
 
-extern "C" {
+static void tp_history_free(vxrt_history_t* h) {
+  for (int k = 0; k < 2; ++k) { (void)hipFree(h->he[k]); (void)hipFree(h->hp[k]); (void)hipFree(h->hn[k]); (void)hipFree(h->hm[k]); }
+  delete h;
+}
 
-int vxrt_history_create(uint32_t width, uint32_t rows, vxrt_history_t** history) {
+static int tp_history_create(uint32_t width, uint32_t rows, bool moments, vxrt_history_t** history) {
   const uint64_t n = (uint64_t)width * rows;
   if (!history || n == 0 || n > 0x7fffffffull) return -1;
   vxrt_history_t* h = new vxrt_history;
   bool ok = true;
   for (int k = 0; k < 2 && ok; ++k)
     ok = hipMalloc((void**)&h->he[k], n * 16u) == hipSuccess && hipMalloc((void**)&h->hp[k], n * 16u) == hipSuccess &&
-         hipMalloc((void**)&h->hn[k], n * 16u) == hipSuccess;
+         hipMalloc((void**)&h->hn[k], n * 16u) == hipSuccess && (!moments || hipMalloc((void**)&h->hm[k], n * 8u) == hipSuccess);
   if (!ok) {
-    for (int k = 0; k < 2; ++k) { (void)hipFree(h->he[k]); (void)hipFree(h->hp[k]); (void)hipFree(h->hn[k]); }
-    delete h;
+    tp_history_free(h);
     return -1;
   }
   h->cap = n;
+  h->moments = moments;
   *history = h;
   return 0;
 }
 
+// V0 of the history's current set (the checks are the caller's): to out[p * out_stride] and / or to frame_out, full-frame addressing
+static int vr_launch_initial(hipStream_t s, const vxrt_history_t* h, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out,
+                             uint32_t out_stride, float* frame_out) {
+  VrInitArgs A{};
+  A.W = h->W; A.rows = h->y1 - h->y0; A.tiles_x = (A.W + DN_TX - 1u) / DN_TX; A.npow = dn->normal_power; A.radius = vp->radius; A.y0 = h->y0;
+  A.sz = dn->sigma_z; A.fmin = (float)vp->min_len;
+  A.he = h->he[h->cur]; A.hm = h->hm[h->cur]; A.hp = h->hp[h->cur]; A.hn = h->hn[h->cur];
+  A.out = out; A.out_stride = out_stride; A.frame_out = frame_out;
+  hipLaunchKernelGGL(rt_vr_initial_kernel, dim3(A.tiles_x * ((A.rows + DN_TY - 1u) / DN_TY)), dim3(256), 0, s, A);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int OUT>
+static void vr_launch_iteration(hipStream_t s, const VrArgs& A) {
+  const dim3 grid(A.d.tiles_x * ((A.d.rows + DN_TY - 1u) / DN_TY)), block(256);
+  hipLaunchKernelGGL((rt_vr_iteration_kernel<OUT>), grid, block, 0, s, A);
+}
+
+// atrous_v: iterations >= 1 passes from sig[0] = (r, g, b, V); `last` holds the outputs of the final pass (DN_OUT_RGB or DN_OUT_PATH)
+static int vr_filter(hipStream_t s, uint32_t W, uint32_t rows, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float4* const sig[2],
+                     const float4* P, const float4* N, int last_out, VrArgs last) {
+  const uint32_t tiles_x = (W + DN_TX - 1u) / DN_TX;
+  for (uint32_t i = 0; i < dn->iterations; ++i) {
+    VrArgs A = last;
+    A.d.W = W; A.d.rows = rows; A.d.tiles_x = tiles_x; A.d.step = 1u << i; A.d.npow = dn->normal_power;
+    A.d.sz = dn->sigma_z; A.d.sl = dn->sigma_l; A.eps = vp->epsilon;
+    A.d.S = sig[i & 1u]; A.d.P = P; A.d.N = N; A.d.out4 = sig[(i + 1u) & 1u];
+    if (i + 1u < dn->iterations) vr_launch_iteration<DN_OUT_SIGNAL>(s, A);
+    else if (last_out == DN_OUT_RGB) vr_launch_iteration<DN_OUT_RGB>(s, A);
+    else vr_launch_iteration<DN_OUT_PATH>(s, A);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int vr_launch_path(hipStream_t s, const vxrt_history_t* h, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn,
+                   const vxrt_variance_params_t* vp, float4* const sig[2], const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
+                   uint32_t* dst, float* colors, float* variance) {
+  if (dn->iterations == 0) return variance ? vr_launch_initial(s, h, dn, vp, nullptr, 0, variance) : 0;
+  if (vr_launch_initial(s, h, dn, vp, &sig[0]->w, 4, variance) != 0) return -1;
+  VrArgs last{};
+  last.d.lit = lit; last.d.alb = alb; last.d.dst = dst; last.d.colors = colors; last.d.y0 = y0;
+  return vr_filter(s, W, rows, dn, vp, sig, geo, nrm, DN_OUT_PATH, last);
+}
+
+extern "C" {
+
+int vxrt_history_create(uint32_t width, uint32_t rows, vxrt_history_t** history) { return tp_history_create(width, rows, false, history); }
+
+int vxrt_history_create_moments(uint32_t width, uint32_t rows, vxrt_history_t** history) { return tp_history_create(width, rows, true, history); }
+
 int vxrt_history_destroy(vxrt_history_t* h) {
   if (!h) return -1;
   (void)hipDeviceSynchronize();
-  for (int k = 0; k < 2; ++k) { (void)hipFree(h->he[k]); (void)hipFree(h->hp[k]); (void)hipFree(h->hn[k]); }
-  delete h;
+  tp_history_free(h);
   return 0;
 }
 
@@ -419,10 +687,16 @@ int vxrt_history_read(vxrt_history_t* h, float* out4, void* stream) {
   return hipMemcpyAsync(out4, h->he[h->cur], n * 16u, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? 0 : -1;
 }
 
+int vxrt_history_read_moments(vxrt_history_t* h, float* out2, void* stream) {
+  if (!h || !out2 || h->empty || !h->moments) return -1;
+  const uint64_t n = (uint64_t)h->W * (h->y1 - h->y0);
+  return hipMemcpyAsync(out2, h->hm[h->cur], n * 8u, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? 0 : -1;
+}
+
 int vxrt_temporal_accumulate(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                              const float* signal, const float* position, const float* normal, const vxrt_temporal_params_t* prm,
                              float* out4, void* stream) {
-  if (!h || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;
+  if (!h || h->moments || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;   // (moments would go stale)
   if ((((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
   if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
   if (y0 == y1) return 0;
@@ -437,7 +711,7 @@ int vxrt_temporal_accumulate(vxrt_history_t* h, const vxrt_camera_t* cam, uint32
 int vxrt_temporal_accumulate_motion(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                                     const float* signal, const float* position, const float* normal, const float* prev_position,
                                     const float* prev_normal, const vxrt_temporal_params_t* prm, float* out4, void* stream) {
-  if (!h || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !prev_position || !prev_normal || !out4) return -1;
+  if (!h || h->moments || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !prev_position || !prev_normal || !out4) return -1;
   if ((((uintptr_t)position | (uintptr_t)normal | (uintptr_t)prev_position | (uintptr_t)prev_normal) & 15u) != 0) return -1;
   if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
   if (y0 == y1) return 0;
@@ -448,7 +722,53 @@ int vxrt_temporal_accumulate_motion(vxrt_history_t* h, const vxrt_camera_t* cam,
   return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A, (const float4*)prev_position, (const float4*)prev_normal);
 }
 
+// the step with moments alone (see the header, "Variance guidance"): T_v over T (both motion guides null) or over T_m (both set)
+int vxrt_temporal_accumulate_moments(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                     const float* signal, const float* position, const float* normal, const float* prev_position,
+                                     const float* prev_normal, const vxrt_temporal_params_t* prm, float* out4, void* stream) {
+  if (!h || !h->moments || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;
+  if ((prev_position == nullptr) != (prev_normal == nullptr)) return -1;
+  if ((((uintptr_t)position | (uintptr_t)normal | (uintptr_t)prev_position | (uintptr_t)prev_normal) & 15u) != 0) return -1;
+  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
+  if (y0 == y1) return 0;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull || n > h->cap) return -1;
+  TpArgs A{};
+  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
+  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A, (const float4*)prev_position, (const float4*)prev_normal);
+}
+
+// V0 of the last frame's window (see the header, "Variance guidance"): one launch
+int vxrt_history_variance(vxrt_history_t* h, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* variance, void* stream) {
+  if (!h || h->empty || !h->moments || !dn_params_ok(dn) || !vr_params_ok(vp) || !variance) return -1;
+  return vr_launch_initial((hipStream_t)stream, h, dn, vp, variance, 1, nullptr);
+}
+
 uint64_t vxrt_denoise_scratch_bytes(uint32_t width, uint32_t rows) { return 32ull * width * rows; }
+
+uint64_t vxrt_denoise_variance_scratch_bytes(uint32_t width, uint32_t rows) { return 32ull * width * rows; }
+
+// atrous_v alone: vxrt_denoise's checks, the variance in and (optional) out
+int vxrt_denoise_variance(uint32_t width, uint32_t rows, const float* signal, const float* variance, const float* position, const float* normal,
+                          const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out, float* out_variance, void* scratch,
+                          uint64_t scratch_bytes, void* stream) {
+  const uint64_t n = (uint64_t)width * rows;
+  if (!dn_params_ok(dn) || !vr_params_ok(vp) || n > 0x7fffffffull) return -1;
+  if (n == 0) return 0;
+  if (!signal || !variance || !position || !normal || !out || out == signal || out_variance == variance ||
+      (((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
+  if (dn->iterations && (!scratch || ((uintptr_t)scratch & 15u) != 0 || scratch_bytes < vxrt_denoise_variance_scratch_bytes(width, rows))) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  if (dn->iterations == 0) {
+    if (hipMemcpyAsync(out, signal, n * 12u, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
+    return !out_variance || hipMemcpyAsync(out_variance, variance, n * 4u, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -1;
+  }
+  float4* const sig[2] = {(float4*)scratch, (float4*)scratch + n};
+  hipLaunchKernelGGL(rt_vr_load_kernel, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, s, (uint32_t)n, signal, variance, sig[0]);
+  VrArgs last{};
+  last.d.out3 = out; last.outv = out_variance;
+  return vr_filter(s, width, rows, dn, vp, sig, (const float4*)position, (const float4*)normal, DN_OUT_RGB, last);
+}
 
 int vxrt_denoise(uint32_t width, uint32_t rows, const float* signal, const float* position, const float* normal, const vxrt_denoise_params_t* dn,
                  float* out, void* scratch, uint64_t scratch_bytes, void* stream) {

@@ -200,7 +200,8 @@ int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0,
                           const float4* nrm, const float4* lit, const float4* alb, uint32_t* dst, float* colors);
 // temporal accumulation (vxrt_render_path_temporal): what the entry point checks before anything is launched -- the parameters, and that
 // the history holds a window of `pixels` pixels
-bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels);
+// moments: the kind of history the entry point takes (vxrt_render_path_variance: one with moments; the others: one without)
+bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels, bool moments = false);
 // out = T(E, P, N; h, the history's camera, t) for the window, one launch: E = sig's rgb, P = geo, N = nrm.  filtered: (out.rgb, lum) goes
 // back into sig (in place: a pixel reads only its own entry) for dn_launch_path_filter; else the pass remodulates out.rgb with lit / alb,
 // packs and writes dst / colors itself.  The history then holds this frame, `cam` and the geometry.
@@ -208,6 +209,14 @@ bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uin
 int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
                    const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
                    const float4* alb, uint32_t* dst, float* colors, const float4* prev_pos = nullptr, const float4* prev_nrm = nullptr);
+// variance guidance (vxrt_render_path_variance): the checks of vxrt_variance_params_t, and what follows tp_launch_path on a history with
+// moments (the step is then T_v) -- one launch that writes V0 of the history's current set into the w of sig[0] and, if asked for, into
+// `variance` (full-frame addressing), then dn->iterations passes of atrous_v in place of dn_launch_path_filter.  dn->iterations == 0:
+// only the `variance` output, if asked for.
+bool vr_params_ok(const vxrt_variance_params_t* v);
+int vr_launch_path(hipStream_t s, const vxrt_history_t* h, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn,
+                   const vxrt_variance_params_t* vp, float4* const sig[2], const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
+                   uint32_t* dst, float* colors, float* variance);
 
 // ---------------------------------------------------------------------------------------------
 // rt_kernels.hip <-> rt_secondary.hip: a frame as an entry point asks for it, the per-frame control block, growing device buffers,
@@ -247,6 +256,8 @@ struct RenderRequest {
   vxrt_history_t* history = nullptr;                //     this history
   bool motion = false;                              // ... through the accel's motion snapshot (vxrt_render_path_temporal_motion), with its
   float* prev_position = nullptr;                   //     optional guide output
+  const vxrt_variance_params_t* variance = nullptr; // ... with moments in the history and the variance-guided filter (vxrt_render_path_variance),
+  float* variance_out = nullptr;                    //     with its optional output V0
   void* stream = nullptr;
   Counting counting = Counting::TIMED;
   bool honours_alpha = false;                       // the entry point traces every ray of its frame through the accel's alpha table, if one is set

@@ -1862,6 +1862,8 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if ((r.temporal || r.history) && (!r.denoise || !r.cams || !r.temporal || !r.history)) return -1;
   // ... through moved instances: the accel holds a motion snapshot
   if ((r.motion || r.prev_position) && (!r.motion || !r.temporal || a->motion_what == 0u)) return -1;
+  // ... with variance guidance: a temporal frame (the entry point has checked that the history holds moments)
+  if ((r.variance || r.variance_out) && (!r.temporal || !vr_params_ok(r.variance))) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
   return 1;
@@ -2444,6 +2446,23 @@ int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* c
   RenderRequest r;
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = true; r.prev_position = prev_position;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return render_common(accel, r);
+}
+
+// ... on a history with moments, filtered by atrous_v (see the header, "Variance guidance"): T_v in place of T (motion = 0) or T_m (1)
+int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                              const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp, vxrt_history_t* history, int motion,
+                              uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, float* prev_position, float* variance,
+                              unsigned long long* rays_traced, void* stream) {
+  if (!path || !dn || !vp || !camera_ok(cam) || motion < 0 || motion > 1) return -1;
+  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
+  if (!tp_request_ok(history, temporal, pixels, true)) return -1;
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
+  r.variance = vp; r.variance_out = variance;
   r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }

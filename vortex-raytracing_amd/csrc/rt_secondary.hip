@@ -746,6 +746,8 @@ int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const S
 // ping-pong between the two signal buffers, the last of which remodulates, packs and writes.  n = pixels of the window.
 // With temporal accumulation (vxrt_render_path_temporal) one launch between the two blends the first signal buffer with the reprojected
 // history, in place, so the ping-pong order stays; without iterations that launch is the end of the frame.
+// With variance guidance (vxrt_render_path_variance) the history holds moments, the same launch is the step T_v, and what follows it is
+// the launch of the initial variance and the passes of atrous_v (vr_launch_path) in place of the plain filter.
 static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
   hipStream_t s = (hipStream_t)r.stream;
   if (!grow_device({{(void**)&c->dn_sig[0], 16}, {(void**)&c->dn_sig[1], 16}}, &c->dn_cap, n, GrowSync::STREAM, s)) return -1;
@@ -755,6 +757,9 @@ static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) 
     const bool filtered = r.denoise->iterations != 0;
     if (tp_launch_path(s, r.history, r.cams, r.width, r.height, r.y0, r.y1, r.temporal, c->dn_sig[0], c->pt_geo, c->pt_nrm, filtered, c->pt_lit, c->pt_alb,
                        r.dst, r.colors, r.motion ? c->mo_pos : nullptr, r.motion ? c->mo_nrm : nullptr) != 0) return -1;
+    if (r.variance)   // (the history holds moments: the step was T_v)
+      return vr_launch_path(s, r.history, r.width, r.y1 - r.y0, r.y0, r.denoise, r.variance, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst,
+                            r.colors, r.variance_out);
     if (!filtered) return 0;
   }
   return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);

@@ -604,12 +604,18 @@ def _temporal_lib():
 
 class History:
     """vxrt_history_t: the accumulated signal of the previous frame of one window, for windows of up to width * rows pixels (96 bytes per
-    pixel of device memory).  A context manager; `handle` is what the C calls take.  Calls on one history are the caller's to order."""
+    pixel of device memory).  A context manager; `handle` is what the C calls take.  Calls on one history are the caller's to order.
+    moments=True: the history also holds the luminance moments of every pixel (112 bytes per pixel) and is the kind the variance-guided
+    calls take -- and the only kind: the two do not mix."""
 
-    def __init__(self, width, rows):
+    def __init__(self, width, rows, moments=False):
         h = C.c_void_p()
-        check(_temporal_lib().vxrt_history_create(int(width), int(rows), C.byref(h)), "vxrt_history_create")
+        if moments:
+            check(_variance_lib().vxrt_history_create_moments(int(width), int(rows), C.byref(h)), "vxrt_history_create_moments")
+        else:
+            check(_temporal_lib().vxrt_history_create(int(width), int(rows), C.byref(h)), "vxrt_history_create")
         self.handle = h
+        self.moments = bool(moments)
 
     def close(self):
         if self.handle:
@@ -630,6 +636,10 @@ class History:
     def read(self, out_ptr, stream=None):
         """vxrt_history_read: (E_acc.rgb, len) per pixel of the last frame's window into device memory; raises for an empty history"""
         check(_temporal_lib().vxrt_history_read(self.handle, out_ptr, stream), "vxrt_history_read")
+
+    def read_moments(self, out_ptr, stream=None):
+        """vxrt_history_read_moments: (m1, m2) per pixel of the last frame's window; raises for an empty history or one without moments"""
+        check(_variance_lib().vxrt_history_read_moments(self.handle, out_ptr, stream), "vxrt_history_read_moments")
 
 
 def _history(h):
@@ -700,3 +710,70 @@ def render_path_temporal_motion(accel, cam, width, height, y0, y1, params, spp, 
                                                          C.byref(denoise), C.byref(temporal), _history(history), dst_ptr, colors_ptr,
                                                          None if aov is None else C.byref(aov), prev_position_ptr, rays_ptr, stream),
           "vxrt_render_path_temporal_motion")
+
+
+# ---- variance guidance: luminance moments in the history steer the a-trous filter (the header's "Variance guidance") ----
+class VarianceParams(C.Structure):   # vxrt_variance_params_t
+    _fields_ = [("epsilon", C.c_float), ("min_len", C.c_uint32), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _variance_lib():
+    L = _motion_lib()
+    L.vxrt_history_create_moments.restype = C.c_int
+    L.vxrt_history_create_moments.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.vxrt_history_read_moments.restype = C.c_int
+    L.vxrt_history_read_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_temporal_accumulate_moments.restype = C.c_int
+    L.vxrt_temporal_accumulate_moments.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]
+    L.vxrt_history_variance.restype = C.c_int
+    L.vxrt_history_variance.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), C.c_void_p, C.c_void_p]
+    L.vxrt_denoise_variance_scratch_bytes.restype = C.c_uint64
+    L.vxrt_denoise_variance_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    L.vxrt_denoise_variance.restype = C.c_int
+    L.vxrt_denoise_variance.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams),
+                                        C.POINTER(VarianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.vxrt_render_path_variance.restype = C.c_int
+    L.vxrt_render_path_variance.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
+                                            C.POINTER(PathParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams),
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PathAov), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+def temporal_accumulate_moments(history, cam, width, height, y0, y1, signal_ptr, position_ptr, normal_ptr, temporal, out_ptr, prev_position_ptr=None,
+                                prev_normal_ptr=None, stream=None):
+    """vxrt_temporal_accumulate_moments: temporal_accumulate (or, with both previous-frame guides, temporal_accumulate_motion) on a
+    History(moments=True), which then also carries the first and second luminance moments of every pixel."""
+    check(_variance_lib().vxrt_temporal_accumulate_moments(_history(history), C.byref(_camera(cam)), width, height, y0, y1, signal_ptr, position_ptr,
+                                                           normal_ptr, prev_position_ptr, prev_normal_ptr, C.byref(temporal), out_ptr, stream),
+          "vxrt_temporal_accumulate_moments")
+
+
+def history_variance(history, denoise, variance, variance_ptr, stream=None):
+    """vxrt_history_variance: the initial variance V0 of the last frame of a History(moments=True), 1 float per pixel of its window --
+    the temporal variance of a pixel with at least variance.min_len frames, a spatial estimate below that."""
+    check(_variance_lib().vxrt_history_variance(_history(history), C.byref(denoise), C.byref(variance), variance_ptr, stream), "vxrt_history_variance")
+
+
+def denoise_variance_scratch_bytes(width, rows):
+    return int(_variance_lib().vxrt_denoise_variance_scratch_bytes(width, rows))
+
+
+def denoise_variance(width, rows, signal_ptr, variance_ptr, position_ptr, normal_ptr, denoise, variance, out_ptr, out_variance_ptr, scratch_ptr,
+                     scratch_bytes, stream=None):
+    """vxrt_denoise_variance: the variance-guided a-trous filter alone (signal / out: 3 floats per pixel; variance / out_variance: 1;
+    position / normal: 4); `variance`: a VarianceParams; out_variance_ptr may be None."""
+    check(_variance_lib().vxrt_denoise_variance(width, rows, signal_ptr, variance_ptr, position_ptr, normal_ptr, C.byref(denoise), C.byref(variance),
+                                                out_ptr, out_variance_ptr, scratch_ptr, scratch_bytes, stream), "vxrt_denoise_variance")
+
+
+def render_path_variance(accel, cam, width, height, y0, y1, params, spp, bounces, denoise, temporal, variance, history, dst_ptr, motion=0, seed=0,
+                         shadow=0, colors_ptr=None, aov=None, prev_position_ptr=None, variance_ptr=None, rays_ptr=None, stream=None):
+    """vxrt_render_path_variance: render_path_temporal (motion=0) or render_path_temporal_motion (motion=1) on a History(moments=True),
+    filtered with a per-pixel luminance scale from the variance of the accumulated luminance; `variance`: a VarianceParams;
+    `variance_ptr` (optional) receives the initial variance, 1 float per pixel of the frame."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_variance_lib().vxrt_render_path_variance(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), C.byref(denoise),
+                                                    C.byref(temporal), C.byref(variance), _history(history), int(motion), dst_ptr, colors_ptr,
+                                                    None if aov is None else C.byref(aov), prev_position_ptr, variance_ptr, rays_ptr, stream),
+          "vxrt_render_path_variance")
