@@ -3,6 +3,10 @@
 // temporal accumulation that may precede it (vxrt_render_path_temporal, vxrt_temporal_accumulate; DESIGN.md s2 "Temporal accumulation"),
 // and below that the variance guidance that builds on both (vxrt_render_path_variance; DESIGN.md s2 "Variance guidance").
 //
+// One of each: one guided pass (rt_dn_iteration_kernel<OUT, VAR>, VAR = the variance-guided form, with one tap and one write function),
+// one host loop that runs it in ping-pong (dn_filter), one accumulation kernel (rt_tp_accumulate_kernel<OUT, MOTION, MOMENTS>), and one
+// door for a path frame (render_denoise_tail, which alone knows what follows what); a new form is an argument of these, not a copy.
+//
 // Per iteration one launch: a 25-tap stencil with stride `step` over three float4 arrays per pixel -- the signal S = (r, g, b, lum), the
 // position guide P = (I, hit flag) and the normal guide N.  The luminance travels in the signal's fourth component: the pass that
 // writes a signal computes lum() of what it writes, the same three operations the definition applies to a tap, so a tap costs three
@@ -35,36 +39,57 @@ struct DnArgs {
   const float4* lit; const float4* alb; uint32_t* dst; float* colors; uint32_t y0;   // DN_OUT_PATH: full-frame addressing, window from row y0
 };
 
+// atrous_v (VAR): sl = sigma_l (not halved: the variance shrinks instead); S and out4 hold (r, g, b, V)
+struct VrArgs : DnArgs {
+  float eps;
+  float* outv;                        // DN_OUT_RGB: the filtered variance, optional
+};
+template <bool VAR> using DnKernelArgs = std::conditional_t<VAR, VrArgs, DnArgs>;   // (the plain form does not carry eps / outv)
+
 __device__ __forceinline__ float dn_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
-// one tap that is inside the window: q's signal, position and normal against the centre's (Pp, Np, lum lp); h = k[dy+2] * k[dx+2]
+// the two guide factors of neighbour q against the centre (Pp, Np): dn = max(Np . Nq, 0) after npow squarings, wz = 1 / (1 + t * t) with
+// t = |Np . (Pq - Pp)| / sz.  Returned apart: how they are multiplied (with what, in which order) is each caller's part of the definition.
+struct DnGuide { float dn, wz; };
+__device__ __forceinline__ DnGuide dn_guide_weights(const float4& Pp, const float4& Np, const float4& Pq, const float4& Nq, uint32_t npow, float sz) {
+  const float d = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;
+  float dn = d > 0.f ? d : 0.f;
+  for (uint32_t k = 0; k < npow; ++k) dn = dn * dn;
+  const float ex = Pq.x - Pp.x, ey = Pq.y - Pp.y, ez = Pq.z - Pp.z;
+  const float t = fabsf((Np.x * ex + Np.y * ey) + Np.z * ez) / sz;
+  const float wz = 1.0f / (1.0f + t * t);
+  return DnGuide{dn, wz};
+}
+
+// one tap that is inside the window: q's signal, position and normal against the centre's (Pp, Np, lum lp); h = k[dy+2] * k[dx+2].
+// VAR: Sq.w is q's variance, so lum() of the tap is recomputed, sl is the centre's luminance scale, and sv sums the variance.
+// (sv is a pack of one float with VAR and of none without: a plain tap with a fifth sum it never touches compiles to other code.)
+template <bool VAR, class... SV>
 __device__ __forceinline__ void dn_tap(const float4& Pp, const float4& Np, float lp, const float4& Sq, const float4& Pq, const float4& Nq, float h,
-                                       uint32_t npow, float sz, float sl, float& sw, float& sr, float& sg, float& sb) {
+                                       uint32_t npow, float sz, float sl, float& sw, float& sr, float& sg, float& sb, SV&... sv) {
   if (Pq.w != 0.f) {
-    const float d = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;
-    float dn = d > 0.f ? d : 0.f;
-    for (uint32_t k = 0; k < npow; ++k) dn = dn * dn;
-    const float ex = Pq.x - Pp.x, ey = Pq.y - Pp.y, ez = Pq.z - Pp.z;
-    const float t = fabsf((Np.x * ex + Np.y * ey) + Np.z * ez) / sz;
-    const float wz = 1.0f / (1.0f + t * t);
-    const float u = fabsf(lp - Sq.w) / sl;
+    const DnGuide G = dn_guide_weights(Pp, Np, Pq, Nq, npow, sz);
+    const float lq = VAR ? dn_lum(Sq.x, Sq.y, Sq.z) : Sq.w;
+    const float u = fabsf(lp - lq) / sl;
     const float wc = 1.0f / (1.0f + u * u);
-    const float w = ((h * dn) * wz) * wc;
+    const float w = ((h * G.dn) * G.wz) * wc;
     if (w > 0.f) {
       sw = sw + w;
       sr = sr + w * Sq.x; sg = sg + w * Sq.y; sb = sb + w * Sq.z;
+      if constexpr (VAR) ((sv = sv + (w * w) * Sq.w), ...);
     }
   }
 }
 
-// what pixel (x, y) of the window becomes: (r, g, b) = the filtered signal (or the input, see the definition)
-template <int OUT>
-__device__ __forceinline__ void dn_write(const DnArgs& A, uint32_t x, uint32_t y, float r, float g, float b, bool hit) {
+// what pixel (x, y) of the window becomes: (r, g, b) = the filtered signal (or the input, see the definition); VAR: v = its variance
+template <int OUT, bool VAR = false>
+__device__ __forceinline__ void dn_write(const DnKernelArgs<VAR>& A, uint32_t x, uint32_t y, float r, float g, float b, bool hit, float v = 0.f) {
   const size_t p = (size_t)y * A.W + x;
   if constexpr (OUT == DN_OUT_SIGNAL) {
-    A.out4[p] = make_float4(r, g, b, dn_lum(r, g, b));
+    A.out4[p] = make_float4(r, g, b, VAR ? v : dn_lum(r, g, b));
   } else if constexpr (OUT == DN_OUT_RGB) {
     A.out3[3 * p] = r; A.out3[3 * p + 1] = g; A.out3[3 * p + 2] = b;
+    if constexpr (VAR) { if (A.outv) A.outv[p] = v; }
   } else {
     const float4 D = A.lit[p];
     float cr = D.x, cg = D.y, cb = D.z;   // (a miss: the background)
@@ -80,17 +105,49 @@ __device__ __forceinline__ void dn_write(const DnArgs& A, uint32_t x, uint32_t y
 
 __device__ __forceinline__ float dn_k(int i) { return i == 2 ? 0.375f : ((i == 1 || i == 3) ? 0.25f : 0.0625f); }
 
+__device__ __forceinline__ float vr_kk(int i) { return i == 1 ? 0.5f : 0.25f; }
+
 // one iteration: every tap from global memory.  A tap outside the window reads the centre's address instead and is dropped.
-template <int OUT>
-__global__ __launch_bounds__(256) void rt_dn_iteration_kernel(DnArgs A) {
+// VAR: one pass of atrous_v (see "Variance guidance" below) -- the 3 x 3 prefilter of the centre's variance in front, the other tap.
+template <int OUT, bool VAR>
+__global__ __launch_bounds__(256) void rt_dn_iteration_kernel(DnKernelArgs<VAR> A) {
   const uint32_t bx = blockIdx.x % A.tiles_x, by = blockIdx.x / A.tiles_x;
   const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
   if (x >= A.W || y >= A.rows) return;
   const size_t p = (size_t)y * A.W + x;
   const float4 Sp = A.S[p], Pp = A.P[p];
-  if (!(Pp.w != 0.f)) { dn_write<OUT>(A, x, y, Sp.x, Sp.y, Sp.z, false); return; }
+  if (!(Pp.w != 0.f)) { dn_write<OUT, VAR>(A, x, y, Sp.x, Sp.y, Sp.z, false, Sp.w); return; }
   const float4 Np = A.N[p];
-  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+  float lp = Sp.w, sl = A.sl;   // the centre's luminance and the luminance scale of its taps
+  if constexpr (VAR) {
+    // the prefiltered variance of the centre: 3 x 3 at stride 1, hit taps of the window only (a tap outside reads the centre and is dropped)
+    float gw = 0.f, gs = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+      const int64_t qy = (int64_t)y + dy;
+      const bool iny = qy >= 0 && qy < (int64_t)A.rows;
+      float Vq[3], Fq[3];
+      bool in[3];
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int64_t qx = (int64_t)x + dx;
+        in[dx + 1] = iny && qx >= 0 && qx < (int64_t)A.W;
+        const size_t q = in[dx + 1] ? (size_t)qy * A.W + (size_t)qx : p;
+        Vq[dx + 1] = A.S[q].w; Fq[dx + 1] = A.P[q].w;
+      }
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx)
+        if (in[dx + 1] && Fq[dx + 1] != 0.f) {
+          const float c = vr_kk(dy + 1) * vr_kk(dx + 1);
+          gw = gw + c;
+          gs = gs + c * Vq[dx + 1];
+        }
+    }
+    const float g = gs / gw;
+    sl = A.sl * sqrtf(g) + A.eps;
+    lp = dn_lum(Sp.x, Sp.y, Sp.z);
+  }
+  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
   for (int dy = -2; dy <= 2; ++dy) {
     const int64_t qy = (int64_t)y + (int64_t)dy * A.step;
     if (qy < 0 || qy >= (int64_t)A.rows) continue;   // (uniform over a row of the tile)
@@ -106,10 +163,13 @@ __global__ __launch_bounds__(256) void rt_dn_iteration_kernel(DnArgs A) {
     }
 #pragma unroll
     for (int dx = -2; dx <= 2; ++dx)
-      if (in[dx + 2]) dn_tap(Pp, Np, Sp.w, Sq[dx + 2], Pq[dx + 2], Nq[dx + 2], ky * dn_k(dx + 2), A.npow, A.sz, A.sl, sw, sr, sg, sb);
+      if (in[dx + 2]) {
+        if constexpr (VAR) dn_tap<VAR>(Pp, Np, lp, Sq[dx + 2], Pq[dx + 2], Nq[dx + 2], ky * dn_k(dx + 2), A.npow, A.sz, sl, sw, sr, sg, sb, sv);
+        else dn_tap<VAR>(Pp, Np, lp, Sq[dx + 2], Pq[dx + 2], Nq[dx + 2], ky * dn_k(dx + 2), A.npow, A.sz, sl, sw, sr, sg, sb);
+      }
   }
-  if (sw > 0.f) dn_write<OUT>(A, x, y, sr / sw, sg / sw, sb / sw, true);
-  else dn_write<OUT>(A, x, y, Sp.x, Sp.y, Sp.z, true);
+  if (sw > 0.f) dn_write<OUT, VAR>(A, x, y, sr / sw, sg / sw, sb / sw, true, VAR ? sv / (sw * sw) : 0.f);
+  else dn_write<OUT, VAR>(A, x, y, Sp.x, Sp.y, Sp.z, true, Sp.w);
 }
 
 // the signal of a stand-alone call: (r, g, b) -> (r, g, b, lum)
@@ -276,15 +336,16 @@ __global__ __launch_bounds__(256) void rt_tp_accumulate_kernel(typename TpKernel
 // ---------------------------------------------------------------------------------------------
 // Variance guidance (vxrt_history_variance, vxrt_denoise_variance, vxrt_render_path_variance; the definition is the header's "Variance
 // guidance", tests/variance_ref.py restates it).  Two kernels on the 32 x 8 tile, one pixel per thread.
+//   rt_dn_iteration_kernel<OUT, true> (above)
+//                           one pass of atrous_v.  The variance travels in the signal's fourth component, S = (r, g, b, V), in place of
+//                           the luminance the plain filter keeps there: a tap stays three 16-byte loads, lum() of a tap is recomputed
+//                           (three operations against about 100), and the nine prefilter taps are two 4-byte loads each (V and the hit
+//                           flag) from lines the 25 taps of step 1 fetch anyway.  No buffer of its own, no fourth gather per tap.
 //   rt_vr_initial_kernel    V0 of the history's current set.  A pixel with a long history takes the temporal variance of its own moments:
 //                           four loads and five operations.  Only a pixel with a short history walks the (2 radius + 1)^2 window of three
 //                           16-byte loads per tap.  The walk sits behind `if (need)`: a wavefront in which no lane needs it branches over
 //                           the loop on an empty exec mask, and after the first few frames that is nearly every wavefront; inside a
 //                           wavefront that does walk, the trip count is uniform (radius), only the lanes that walk differ.
-//   rt_vr_iteration_kernel  one pass of atrous_v.  The variance travels in the signal's fourth component, S = (r, g, b, V), in place of
-//                           the luminance the plain filter keeps there: a tap stays three 16-byte loads, lum() of a tap is recomputed
-//                           (three operations against about 100), and the nine prefilter taps are two 4-byte loads each (V and the hit
-//                           flag) from lines the 25 taps of step 1 fetch anyway.  No buffer of its own, no fourth gather per tap.
 // ---------------------------------------------------------------------------------------------
 struct VrInitArgs {
   uint32_t W, rows, tiles_x, npow, radius, y0;
@@ -319,13 +380,8 @@ __global__ __launch_bounds__(256) void rt_vr_initial_kernel(VrInitArgs A) {
         const size_t q = (size_t)qy * A.W + (size_t)qx;
         const float4 Pq = A.hp[q], Nq = A.hn[q], Aq = A.he[q];
         if (!(Pq.w != 0.f)) continue;
-        const float d = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;
-        float dn = d > 0.f ? d : 0.f;
-        for (uint32_t k = 0; k < A.npow; ++k) dn = dn * dn;
-        const float ex = Pq.x - Pp.x, ey = Pq.y - Pp.y, ez = Pq.z - Pp.z;
-        const float t = fabsf((Np.x * ex + Np.y * ey) + Np.z * ez) / A.sz;
-        const float wz = 1.0f / (1.0f + t * t);
-        const float w = dn * wz;
+        const DnGuide G = dn_guide_weights(Pp, Np, Pq, Nq, A.npow, A.sz);
+        const float w = G.dn * G.wz;
         if (w > 0.f) {
           const float l = dn_lum(Aq.x, Aq.y, Aq.z);
           sw = sw + w;
@@ -345,104 +401,6 @@ __global__ __launch_bounds__(256) void rt_vr_initial_kernel(VrInitArgs A) {
   if (A.frame_out) A.frame_out[(size_t)x + (size_t)(A.y0 + y) * A.W] = v0;
 }
 
-struct VrArgs {
-  DnArgs d;          // of the plain filter; d.sl = sigma_l (not halved: the variance shrinks instead); d.S and d.out4 hold (r, g, b, V)
-  float eps;
-  float* outv;       // DN_OUT_RGB: the filtered variance, optional
-};
-
-// one tap of atrous_v that is inside the window: dn_tap with the luminance scale `den` of the centre and the variance sum
-__device__ __forceinline__ void vr_tap(const float4& Pp, const float4& Np, float lp, const float4& Sq, const float4& Pq, const float4& Nq, float h,
-                                       uint32_t npow, float sz, float den, float& sw, float& sr, float& sg, float& sb, float& sv) {
-  if (Pq.w != 0.f) {
-    const float d = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;
-    float dn = d > 0.f ? d : 0.f;
-    for (uint32_t k = 0; k < npow; ++k) dn = dn * dn;
-    const float ex = Pq.x - Pp.x, ey = Pq.y - Pp.y, ez = Pq.z - Pp.z;
-    const float t = fabsf((Np.x * ex + Np.y * ey) + Np.z * ez) / sz;
-    const float wz = 1.0f / (1.0f + t * t);
-    const float u = fabsf(lp - dn_lum(Sq.x, Sq.y, Sq.z)) / den;
-    const float wc = 1.0f / (1.0f + u * u);
-    const float w = ((h * dn) * wz) * wc;
-    if (w > 0.f) {
-      sw = sw + w;
-      sr = sr + w * Sq.x; sg = sg + w * Sq.y; sb = sb + w * Sq.z;
-      sv = sv + (w * w) * Sq.w;
-    }
-  }
-}
-
-template <int OUT>
-__device__ __forceinline__ void vr_write(const VrArgs& A, uint32_t x, uint32_t y, float r, float g, float b, float v, bool hit) {
-  const size_t p = (size_t)y * A.d.W + x;
-  if constexpr (OUT == DN_OUT_SIGNAL) {
-    A.d.out4[p] = make_float4(r, g, b, v);
-  } else {
-    dn_write<OUT>(A.d, x, y, r, g, b, hit);
-    if constexpr (OUT == DN_OUT_RGB) { if (A.outv) A.outv[p] = v; }
-  }
-}
-
-__device__ __forceinline__ float vr_kk(int i) { return i == 1 ? 0.5f : 0.25f; }
-
-template <int OUT>
-__global__ __launch_bounds__(256) void rt_vr_iteration_kernel(VrArgs A) {
-  const DnArgs& D = A.d;
-  const uint32_t bx = blockIdx.x % D.tiles_x, by = blockIdx.x / D.tiles_x;
-  const uint32_t x = bx * DN_TX + (threadIdx.x & (DN_TX - 1u)), y = by * DN_TY + threadIdx.x / DN_TX;
-  if (x >= D.W || y >= D.rows) return;
-  const size_t p = (size_t)y * D.W + x;
-  const float4 Sp = D.S[p], Pp = D.P[p];
-  if (!(Pp.w != 0.f)) { vr_write<OUT>(A, x, y, Sp.x, Sp.y, Sp.z, Sp.w, false); return; }
-  const float4 Np = D.N[p];
-  // the prefiltered variance of the centre: 3 x 3 at stride 1, hit taps of the window only (a tap outside reads the centre and is dropped)
-  float gw = 0.f, gs = 0.f;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy) {
-    const int64_t qy = (int64_t)y + dy;
-    const bool iny = qy >= 0 && qy < (int64_t)D.rows;
-    float Vq[3], Fq[3];
-    bool in[3];
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int64_t qx = (int64_t)x + dx;
-      in[dx + 1] = iny && qx >= 0 && qx < (int64_t)D.W;
-      const size_t q = in[dx + 1] ? (size_t)qy * D.W + (size_t)qx : p;
-      Vq[dx + 1] = D.S[q].w; Fq[dx + 1] = D.P[q].w;
-    }
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx)
-      if (in[dx + 1] && Fq[dx + 1] != 0.f) {
-        const float c = vr_kk(dy + 1) * vr_kk(dx + 1);
-        gw = gw + c;
-        gs = gs + c * Vq[dx + 1];
-      }
-  }
-  const float g = gs / gw;
-  const float den = D.sl * sqrtf(g) + A.eps;
-  const float lp = dn_lum(Sp.x, Sp.y, Sp.z);
-  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
-  for (int dy = -2; dy <= 2; ++dy) {
-    const int64_t qy = (int64_t)y + (int64_t)dy * D.step;
-    if (qy < 0 || qy >= (int64_t)D.rows) continue;   // (uniform over a row of the tile)
-    const float ky = dn_k(dy + 2);
-    float4 Sq[5], Pq[5], Nq[5];
-    bool in[5];
-#pragma unroll
-    for (int dx = -2; dx <= 2; ++dx) {
-      const int64_t qx = (int64_t)x + (int64_t)dx * D.step;
-      in[dx + 2] = qx >= 0 && qx < (int64_t)D.W;
-      const size_t q = in[dx + 2] ? (size_t)qy * D.W + (size_t)qx : p;
-      Sq[dx + 2] = D.S[q]; Pq[dx + 2] = D.P[q]; Nq[dx + 2] = D.N[q];
-    }
-#pragma unroll
-    for (int dx = -2; dx <= 2; ++dx)
-      if (in[dx + 2]) vr_tap(Pp, Np, lp, Sq[dx + 2], Pq[dx + 2], Nq[dx + 2], ky * dn_k(dx + 2), D.npow, D.sz, den, sw, sr, sg, sb, sv);
-  }
-  if (sw > 0.f) vr_write<OUT>(A, x, y, sr / sw, sg / sw, sb / sw, sv / (sw * sw), true);
-  else vr_write<OUT>(A, x, y, Sp.x, Sp.y, Sp.z, Sp.w, true);
-}
-
 // the signal of a stand-alone call: (r, g, b), V -> (r, g, b, V)
 __global__ __launch_bounds__(256) void rt_vr_load_kernel(uint32_t n, const float* __restrict__ sig3, const float* __restrict__ var, float4* __restrict__ out) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -457,42 +415,34 @@ bool dn_params_ok(const vxrt_denoise_params_t* dn) {
   return dn && dn->iterations <= VXRT_DENOISE_MAX_ITERATIONS && dn->normal_power <= 7u && dn->sigma_z > 0.0f && dn->sigma_l > 0.0f;   // (false for NaN)
 }
 
-template <int OUT>
-static void dn_launch_iteration(hipStream_t s, const DnArgs& A) {
-  const dim3 grid(A.tiles_x * ((A.rows + DN_TY - 1u) / DN_TY)), block(256);
-  hipLaunchKernelGGL((rt_dn_iteration_kernel<OUT>), grid, block, 0, s, A);
+// the one-dimensional grid of 32 x 8 tiles over a window of W x rows pixels (W * rows < 2^31: at most 2^28 + 2^26 tiles)
+static uint32_t dn_tiles_x(uint32_t W) { return (W + DN_TX - 1u) / DN_TX; }
+static dim3 dn_grid(uint32_t W, uint32_t rows) { return dim3(dn_tiles_x(W) * ((rows + DN_TY - 1u) / DN_TY)); }
+
+template <bool VAR>
+static void dn_launch_iteration(hipStream_t s, int out, const VrArgs& A) {
+  const DnKernelArgs<VAR> K = A;   // (the plain form: the DnArgs part)
+  const dim3 grid = dn_grid(A.W, A.rows), block(256);
+  if (out == DN_OUT_SIGNAL) hipLaunchKernelGGL((rt_dn_iteration_kernel<DN_OUT_SIGNAL, VAR>), grid, block, 0, s, K);
+  else if (out == DN_OUT_RGB) hipLaunchKernelGGL((rt_dn_iteration_kernel<DN_OUT_RGB, VAR>), grid, block, 0, s, K);
+  else hipLaunchKernelGGL((rt_dn_iteration_kernel<DN_OUT_PATH, VAR>), grid, block, 0, s, K);
 }
 
-// iterations >= 1 passes from sig[0]; `last` holds the outputs of the final pass (DN_OUT_RGB or DN_OUT_PATH)
-static int dn_filter(hipStream_t s, uint32_t W, uint32_t rows, const vxrt_denoise_params_t* dn, float4* const sig[2], const float4* P, const float4* N,
-                     int last_out, DnArgs last) {
-  const uint32_t tiles_x = (W + DN_TX - 1u) / DN_TX;   // (W * rows < 2^31: at most 2^28 + 2^26 tiles)
+// iterations >= 1 passes from sig[0]; `A` holds the outputs of the final pass (last_out: DN_OUT_RGB or DN_OUT_PATH).
+// vp null: the plain filter, sig = (r, g, b, lum).  vp set: atrous_v, sig = (r, g, b, V).
+static int dn_filter(hipStream_t s, uint32_t W, uint32_t rows, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float4* const sig[2],
+                     const float4* P, const float4* N, int last_out, VrArgs A) {
+  A.W = W; A.rows = rows; A.tiles_x = dn_tiles_x(W); A.npow = dn->normal_power; A.sz = dn->sigma_z; A.P = P; A.N = N;
   for (uint32_t i = 0; i < dn->iterations; ++i) {
-    DnArgs A = last;
-    A.W = W; A.rows = rows; A.tiles_x = tiles_x; A.step = 1u << i; A.npow = dn->normal_power;
-    A.sz = dn->sigma_z; A.sl = dn->sigma_l * (1.0f / (float)(1u << i));
-    A.S = sig[i & 1u]; A.P = P; A.N = N; A.out4 = sig[(i + 1u) & 1u];
-    if (i + 1u < dn->iterations) dn_launch_iteration<DN_OUT_SIGNAL>(s, A);
-    else if (last_out == DN_OUT_RGB) dn_launch_iteration<DN_OUT_RGB>(s, A);
-    else dn_launch_iteration<DN_OUT_PATH>(s, A);
+    A.step = 1u << i;
+    A.sl = vp ? dn->sigma_l : dn->sigma_l * (1.0f / (float)(1u << i));   // (atrous_v: the variance shrinks instead)
+    A.eps = vp ? vp->epsilon : 0.0f;
+    A.S = sig[i & 1u]; A.out4 = sig[(i + 1u) & 1u];
+    const int out = i + 1u < dn->iterations ? DN_OUT_SIGNAL : last_out;
+    if (vp) dn_launch_iteration<true>(s, out, A);
+    else dn_launch_iteration<false>(s, out, A);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int dn_launch_demodulate(hipStream_t s, uint32_t n, uint32_t W, uint32_t y0, const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
-                         const float4* acc, uint32_t spp, uint32_t flat, float4* sig, const vxrt_path_aov_t* aov) {
-  vxrt_path_aov_t o;
-  memset(&o, 0, sizeof(o));
-  if (aov) o = *aov;
-  hipLaunchKernelGGL(rt_dn_demodulate_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, W, y0, geo, nrm, lit, alb, acc, spp, flat, sig, o);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn, float4* const sig[2], const float4* geo,
-                          const float4* nrm, const float4* lit, const float4* alb, uint32_t* dst, float* colors) {
-  DnArgs last{};
-  last.lit = lit; last.alb = alb; last.dst = dst; last.colors = colors; last.y0 = y0;
-  return dn_filter(s, W, rows, dn, sig, geo, nrm, DN_OUT_PATH, last);
 }
 
 // ---- temporal accumulation: the history and the launch ----
@@ -506,13 +456,6 @@ struct vxrt_history {
   vxrt_camera_t cam{};               // of the last frame, with its geometry
   uint32_t W = 0, H = 0, y0 = 0, y1 = 0;
 };
-
-static bool tp_camera_ok(const vxrt_camera_t* c) {
-  if (!c) return false;
-  const float* f = &c->pos[0];
-  for (int i = 0; i < 14; ++i) if (!std::isfinite(f[i])) return false;
-  return true;
-}
 
 static bool tp_params_ok(const vxrt_temporal_params_t* t) {
   return t && t->alpha_min > 0.0f && t->alpha_min <= 1.0f && t->max_len >= 1u && t->max_len <= VXRT_TEMPORAL_MAX_LEN && t->sigma_z > 0.0f &&
@@ -565,7 +508,7 @@ static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam,
   const uint32_t rows = y1 - y0;
   const bool have = !h->empty && h->W == W && h->H == H && h->y0 == y0 && h->y1 == y1;   // (another window: an implicit reset)
   const uint32_t prev = h->cur, next = have ? h->cur ^ 1u : h->cur;
-  A.W = W; A.rows = rows; A.tiles_x = (W + DN_TX - 1u) / DN_TX; A.have = have ? 1u : 0u; A.max_len = t->max_len;
+  A.W = W; A.rows = rows; A.tiles_x = dn_tiles_x(W); A.have = have ? 1u : 0u; A.max_len = t->max_len;
   A.fW = (float)W; A.fH = (float)H; A.fy0 = (float)y0; A.frows = (float)rows;
   if (have) {
     for (int k = 0; k < 3; ++k) A.pos[k] = h->cam.pos[k];
@@ -575,7 +518,7 @@ static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam,
   A.alpha_min = t->alpha_min; A.sigma_z = t->sigma_z; A.normal_min = t->normal_min;
   A.he = h->he[prev]; A.hp = h->hp[prev]; A.hn = h->hn[prev];
   A.he_o = h->he[next]; A.hp_o = h->hp[next]; A.hn_o = h->hn[next];
-  const dim3 grid(A.tiles_x * ((rows + DN_TY - 1u) / DN_TY));
+  const dim3 grid = dn_grid(W, rows);
   if (h->moments) {
     if (Q) tp_launch_out<true, true>(s, grid, h, prev, next, out, A, Q, Nq);
     else tp_launch_out<false, true>(s, grid, h, prev, next, out, A, Q, Nq);
@@ -584,15 +527,6 @@ static int tp_launch(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam,
   if (hipGetLastError() != hipSuccess) return -1;
   h->cur = next; h->empty = false; h->cam = *cam; h->W = W; h->H = H; h->y0 = y0; h->y1 = y1;
   return 0;
-}
-
-int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
-                   const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
-                   const float4* alb, uint32_t* dst, float* colors, const float4* prev_pos, const float4* prev_nrm) {
-  TpArgs A{};
-  A.E4 = sig; A.P = geo; A.N = nrm; A.sig = sig;
-  A.path.W = W; A.path.lit = lit; A.path.alb = alb; A.path.dst = dst; A.path.colors = colors; A.path.y0 = y0;
-  return tp_launch(s, h, cam, W, H, y0, y1, t, filtered ? TP_OUT_SIGNAL : TP_OUT_PATH, A, prev_pos, prev_nrm);
 }
 
 static void tp_history_free(vxrt_history_t* h) {
@@ -622,44 +556,122 @@ static int tp_history_create(uint32_t width, uint32_t rows, bool moments, vxrt_h
 static int vr_launch_initial(hipStream_t s, const vxrt_history_t* h, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out,
                              uint32_t out_stride, float* frame_out) {
   VrInitArgs A{};
-  A.W = h->W; A.rows = h->y1 - h->y0; A.tiles_x = (A.W + DN_TX - 1u) / DN_TX; A.npow = dn->normal_power; A.radius = vp->radius; A.y0 = h->y0;
+  A.W = h->W; A.rows = h->y1 - h->y0; A.tiles_x = dn_tiles_x(A.W); A.npow = dn->normal_power; A.radius = vp->radius; A.y0 = h->y0;
   A.sz = dn->sigma_z; A.fmin = (float)vp->min_len;
   A.he = h->he[h->cur]; A.hm = h->hm[h->cur]; A.hp = h->hp[h->cur]; A.hn = h->hn[h->cur];
   A.out = out; A.out_stride = out_stride; A.frame_out = frame_out;
-  hipLaunchKernelGGL(rt_vr_initial_kernel, dim3(A.tiles_x * ((A.rows + DN_TY - 1u) / DN_TY)), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(rt_vr_initial_kernel, dn_grid(A.W, A.rows), dim3(256), 0, s, A);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <int OUT>
-static void vr_launch_iteration(hipStream_t s, const VrArgs& A) {
-  const dim3 grid(A.d.tiles_x * ((A.d.rows + DN_TY - 1u) / DN_TY)), block(256);
-  hipLaunchKernelGGL((rt_vr_iteration_kernel<OUT>), grid, block, 0, s, A);
+// ---- the tail of a denoised path frame (render_path_tail in rt_secondary.hip ends in one of the two functions below) ----
+// The window and the buffers every launch of the tail shares, read from the context and the request in this one place.  Per pixel of the
+// window: geo = P (w = hit?), nrm = N, lit / alb of the primary hit, acc = the accumulator over samples, sig = the two signal buffers.
+struct DnFrame {
+  hipStream_t s;
+  uint32_t W, H, y0, y1, n;           // rows [y0, y1) of a W x H frame, n = W * (y1 - y0)
+  const float4* geo; const float4* nrm; const float4* lit; const float4* alb; const float4* acc;
+  uint32_t spp, flat;                 // flat: no bounces, the colour is the flat sum of Lit_0
+  float4* sig[2];
+  uint32_t* dst; float* colors;       // full-frame addressing
+};
+
+static DnFrame dn_frame(const FrameCtx* c, const RenderRequest& r, uint32_t n) {
+  return DnFrame{(hipStream_t)r.stream, r.width, r.height, r.y0, r.y1, n, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc,
+                 r.path->spp, r.path->bounces == 0 ? 1u : 0u, {c->dn_sig[0], c->dn_sig[1]}, r.dst, r.colors};
 }
 
-// atrous_v: iterations >= 1 passes from sig[0] = (r, g, b, V); `last` holds the outputs of the final pass (DN_OUT_RGB or DN_OUT_PATH)
-static int vr_filter(hipStream_t s, uint32_t W, uint32_t rows, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float4* const sig[2],
-                     const float4* P, const float4* N, int last_out, VrArgs last) {
-  const uint32_t tiles_x = (W + DN_TX - 1u) / DN_TX;
-  for (uint32_t i = 0; i < dn->iterations; ++i) {
-    VrArgs A = last;
-    A.d.W = W; A.d.rows = rows; A.d.tiles_x = tiles_x; A.d.step = 1u << i; A.d.npow = dn->normal_power;
-    A.d.sz = dn->sigma_z; A.d.sl = dn->sigma_l; A.eps = vp->epsilon;
-    A.d.S = sig[i & 1u]; A.d.P = P; A.d.N = N; A.d.out4 = sig[(i + 1u) & 1u];
-    if (i + 1u < dn->iterations) vr_launch_iteration<DN_OUT_SIGNAL>(s, A);
-    else if (last_out == DN_OUT_RGB) vr_launch_iteration<DN_OUT_RGB>(s, A);
-    else vr_launch_iteration<DN_OUT_PATH>(s, A);
+// per pixel t of the window: c = the path frame's colour (acc / spp | the flat sum of Lit_0 | the background), the optional guide
+// outputs, and with `sig` the demodulated signal (E, lum(E)) the filter starts from
+static int dn_launch_demodulate(const DnFrame& f, float4* sig, const vxrt_path_aov_t* aov) {
+  vxrt_path_aov_t o;
+  memset(&o, 0, sizeof(o));
+  if (aov) o = *aov;
+  hipLaunchKernelGGL(rt_dn_demodulate_kernel, dim3((f.n + 255u) / 256u), dim3(256), 0, f.s, f.n, f.W, f.y0, f.geo, f.nrm, f.lit, f.alb, f.acc, f.spp, f.flat,
+                     sig, o);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// what the pass that ends the frame needs (DN_OUT_PATH, TP_OUT_PATH): it remodulates with lit / alb, packs and writes dst / colors
+static VrArgs dn_path_out(const DnFrame& f) {
+  VrArgs A{};
+  A.W = f.W; A.lit = f.lit; A.alb = f.alb; A.dst = f.dst; A.colors = f.colors; A.y0 = f.y0;
+  return A;
+}
+
+// out = T(E, P, N; h, the history's camera, t) for the window, one launch: E = sig[0]'s rgb.  filtered: (out.rgb, lum) goes back into sig[0]
+// (in place: a pixel reads only its own entry) for the passes; else this launch ends the frame.  The history then holds this frame, its
+// camera and the geometry.  Q / Nq (both or neither): the step with motion, T_m.  A history with moments: the step is T_v.
+static int tp_launch_path(const DnFrame& f, const RenderRequest& r, bool filtered, const float4* Q, const float4* Nq) {
+  TpArgs A{};
+  A.E4 = f.sig[0]; A.P = f.geo; A.N = f.nrm; A.sig = f.sig[0];
+  A.path = dn_path_out(f);
+  return tp_launch(f.s, r.history, r.cams, f.W, f.H, f.y0, f.y1, r.temporal, filtered ? TP_OUT_SIGNAL : TP_OUT_PATH, A, Q, Nq);
+}
+
+int render_denoise_aov(FrameCtx* c, const RenderRequest& r, uint32_t n) { return dn_launch_demodulate(dn_frame(c, r, n), nullptr, r.aov); }
+
+// The one place that knows the order: demodulate -> temporal step -> initial variance -> passes.
+//   demodulate   the pixels' accumulators into sig[0], and the guide outputs.
+//   temporal     (r.temporal) one launch blends sig[0] with the reprojected history, in place, so the ping-pong order stays; without
+//                iterations that launch remodulates, packs and writes, and is the end of the frame.
+//   variance     (r.variance, which check_request admits with r.temporal only: the history holds moments, the step was T_v) one launch
+//                writes V0 of the history's current set into the w of sig[0], if passes follow, and into r.variance_out, if asked for.
+//   passes       dn->iterations launches, ping-pong between sig[0] and sig[1] (atrous_v after a variance launch), the last of which
+//                remodulates, packs and writes.
+int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
+  if (!grow_device({{(void**)&c->dn_sig[0], 16}, {(void**)&c->dn_sig[1], 16}}, &c->dn_cap, n, GrowSync::STREAM, (hipStream_t)r.stream)) return -1;
+  const DnFrame f = dn_frame(c, r, n);
+  const bool filtered = r.denoise->iterations != 0;
+  if (dn_launch_demodulate(f, f.sig[0], r.aov) != 0) return -1;
+  if (r.temporal) {
+    if (tp_launch_path(f, r, filtered, r.motion ? c->mo_pos : nullptr, r.motion ? c->mo_nrm : nullptr) != 0) return -1;
+    if (r.variance && (filtered || r.variance_out) &&
+        vr_launch_initial(f.s, r.history, r.denoise, r.variance, filtered ? &f.sig[0]->w : nullptr, 4, r.variance_out) != 0) return -1;
+    if (!filtered) return 0;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return dn_filter(f.s, f.W, f.y1 - f.y0, r.denoise, r.variance, f.sig, f.geo, f.nrm, DN_OUT_PATH, dn_path_out(f));
 }
 
-int vr_launch_path(hipStream_t s, const vxrt_history_t* h, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn,
-                   const vxrt_variance_params_t* vp, float4* const sig[2], const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
-                   uint32_t* dst, float* colors, float* variance) {
-  if (dn->iterations == 0) return variance ? vr_launch_initial(s, h, dn, vp, nullptr, 0, variance) : 0;
-  if (vr_launch_initial(s, h, dn, vp, &sig[0]->w, 4, variance) != 0) return -1;
+// ---- the stand-alone calls: what the entry points of a family share behind each one's own refusals ----
+// The step alone.  The caller has checked the kind of history and which of the motion guides Q / Nq are null; a null guide passes the
+// alignment test, so the test is over exactly the pointers the entry point has.
+static int tp_accumulate(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const float* signal,
+                         const float* position, const float* normal, const float* Q, const float* Nq, const vxrt_temporal_params_t* prm, float* out4,
+                         void* stream) {
+  if (!camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;
+  if ((((uintptr_t)position | (uintptr_t)normal | (uintptr_t)Q | (uintptr_t)Nq) & 15u) != 0) return -1;
+  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
+  if (y0 == y1) return 0;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull || n > h->cap) return -1;
+  TpArgs A{};
+  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
+  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A, (const float4*)Q, (const float4*)Nq);
+}
+
+// The filter alone.  vp null: vxrt_denoise (variance and out_variance are null).  vp set and checked: atrous_v, the variance in and (optional) out.
+static int dn_denoise(uint32_t width, uint32_t rows, const float* signal, const float* variance, const float* position, const float* normal,
+                      const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out, float* out_variance, void* scratch,
+                      uint64_t scratch_bytes, void* stream) {
+  const uint64_t n = (uint64_t)width * rows;
+  if (!dn_params_ok(dn) || n > 0x7fffffffull) return -1;
+  if (n == 0) return 0;
+  if (!signal || !position || !normal || !out || out == signal || (((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
+  if (vp && (!variance || out_variance == variance)) return -1;
+  if (dn->iterations && (!scratch || ((uintptr_t)scratch & 15u) != 0 || scratch_bytes < vxrt_denoise_scratch_bytes(width, rows))) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  if (dn->iterations == 0) {
+    if (hipMemcpyAsync(out, signal, n * 12u, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
+    return !out_variance || hipMemcpyAsync(out_variance, variance, n * 4u, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -1;
+  }
+  float4* const sig[2] = {(float4*)scratch, (float4*)scratch + n};
+  const dim3 grid(((uint32_t)n + 255u) / 256u), block(256);
+  if (vp) hipLaunchKernelGGL(rt_vr_load_kernel, grid, block, 0, s, (uint32_t)n, signal, variance, sig[0]);
+  else hipLaunchKernelGGL(rt_dn_load_kernel, grid, block, 0, s, (uint32_t)n, signal, sig[0]);
   VrArgs last{};
-  last.d.lit = lit; last.d.alb = alb; last.d.dst = dst; last.d.colors = colors; last.d.y0 = y0;
-  return vr_filter(s, W, rows, dn, vp, sig, geo, nrm, DN_OUT_PATH, last);
+  last.out3 = out; last.outv = out_variance;
+  return dn_filter(s, width, rows, dn, vp, sig, (const float4*)position, (const float4*)normal, DN_OUT_RGB, last);
 }
 
 extern "C" {
@@ -696,46 +708,24 @@ int vxrt_history_read_moments(vxrt_history_t* h, float* out2, void* stream) {
 int vxrt_temporal_accumulate(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                              const float* signal, const float* position, const float* normal, const vxrt_temporal_params_t* prm,
                              float* out4, void* stream) {
-  if (!h || h->moments || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;   // (moments would go stale)
-  if ((((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
-  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
-  if (y0 == y1) return 0;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull || n > h->cap) return -1;
-  TpArgs A{};
-  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
-  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A);
+  if (!h || h->moments) return -1;   // (moments would go stale)
+  return tp_accumulate(h, cam, width, height, y0, y1, signal, position, normal, nullptr, nullptr, prm, out4, stream);
 }
 
 // the step with motion alone (see the header, "Motion"): vxrt_temporal_accumulate's checks, and the two guides more
 int vxrt_temporal_accumulate_motion(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                                     const float* signal, const float* position, const float* normal, const float* prev_position,
                                     const float* prev_normal, const vxrt_temporal_params_t* prm, float* out4, void* stream) {
-  if (!h || h->moments || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !prev_position || !prev_normal || !out4) return -1;
-  if ((((uintptr_t)position | (uintptr_t)normal | (uintptr_t)prev_position | (uintptr_t)prev_normal) & 15u) != 0) return -1;
-  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
-  if (y0 == y1) return 0;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull || n > h->cap) return -1;
-  TpArgs A{};
-  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
-  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A, (const float4*)prev_position, (const float4*)prev_normal);
+  if (!h || h->moments || !prev_position || !prev_normal) return -1;
+  return tp_accumulate(h, cam, width, height, y0, y1, signal, position, normal, prev_position, prev_normal, prm, out4, stream);
 }
 
 // the step with moments alone (see the header, "Variance guidance"): T_v over T (both motion guides null) or over T_m (both set)
 int vxrt_temporal_accumulate_moments(vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                                      const float* signal, const float* position, const float* normal, const float* prev_position,
                                      const float* prev_normal, const vxrt_temporal_params_t* prm, float* out4, void* stream) {
-  if (!h || !h->moments || !tp_camera_ok(cam) || !tp_params_ok(prm) || !signal || !position || !normal || !out4) return -1;
-  if ((prev_position == nullptr) != (prev_normal == nullptr)) return -1;
-  if ((((uintptr_t)position | (uintptr_t)normal | (uintptr_t)prev_position | (uintptr_t)prev_normal) & 15u) != 0) return -1;
-  if (width == 0 || height == 0 || y0 > y1 || y1 > height) return -1;
-  if (y0 == y1) return 0;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull || n > h->cap) return -1;
-  TpArgs A{};
-  A.E3 = signal; A.P = (const float4*)position; A.N = (const float4*)normal; A.out4 = out4;
-  return tp_launch((hipStream_t)stream, h, cam, width, height, y0, y1, prm, TP_OUT_LEN, A, (const float4*)prev_position, (const float4*)prev_normal);
+  if (!h || !h->moments || (prev_position == nullptr) != (prev_normal == nullptr)) return -1;
+  return tp_accumulate(h, cam, width, height, y0, y1, signal, position, normal, prev_position, prev_normal, prm, out4, stream);
 }
 
 // V0 of the last frame's window (see the header, "Variance guidance"): one launch
@@ -752,38 +742,13 @@ uint64_t vxrt_denoise_variance_scratch_bytes(uint32_t width, uint32_t rows) { re
 int vxrt_denoise_variance(uint32_t width, uint32_t rows, const float* signal, const float* variance, const float* position, const float* normal,
                           const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out, float* out_variance, void* scratch,
                           uint64_t scratch_bytes, void* stream) {
-  const uint64_t n = (uint64_t)width * rows;
-  if (!dn_params_ok(dn) || !vr_params_ok(vp) || n > 0x7fffffffull) return -1;
-  if (n == 0) return 0;
-  if (!signal || !variance || !position || !normal || !out || out == signal || out_variance == variance ||
-      (((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
-  if (dn->iterations && (!scratch || ((uintptr_t)scratch & 15u) != 0 || scratch_bytes < vxrt_denoise_variance_scratch_bytes(width, rows))) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  if (dn->iterations == 0) {
-    if (hipMemcpyAsync(out, signal, n * 12u, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
-    return !out_variance || hipMemcpyAsync(out_variance, variance, n * 4u, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -1;
-  }
-  float4* const sig[2] = {(float4*)scratch, (float4*)scratch + n};
-  hipLaunchKernelGGL(rt_vr_load_kernel, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, s, (uint32_t)n, signal, variance, sig[0]);
-  VrArgs last{};
-  last.d.out3 = out; last.outv = out_variance;
-  return vr_filter(s, width, rows, dn, vp, sig, (const float4*)position, (const float4*)normal, DN_OUT_RGB, last);
+  if (!vr_params_ok(vp)) return -1;
+  return dn_denoise(width, rows, signal, variance, position, normal, dn, vp, out, out_variance, scratch, scratch_bytes, stream);
 }
 
 int vxrt_denoise(uint32_t width, uint32_t rows, const float* signal, const float* position, const float* normal, const vxrt_denoise_params_t* dn,
                  float* out, void* scratch, uint64_t scratch_bytes, void* stream) {
-  const uint64_t n = (uint64_t)width * rows;
-  if (!dn_params_ok(dn) || n > 0x7fffffffull) return -1;
-  if (n == 0) return 0;
-  if (!signal || !position || !normal || !out || out == signal || (((uintptr_t)position | (uintptr_t)normal) & 15u) != 0) return -1;
-  if (dn->iterations && (!scratch || ((uintptr_t)scratch & 15u) != 0 || scratch_bytes < vxrt_denoise_scratch_bytes(width, rows))) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  if (dn->iterations == 0) return hipMemcpyAsync(out, signal, n * 12u, hipMemcpyDeviceToDevice, s) == hipSuccess ? 0 : -1;
-  float4* const sig[2] = {(float4*)scratch, (float4*)scratch + n};
-  hipLaunchKernelGGL(rt_dn_load_kernel, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, s, (uint32_t)n, signal, sig[0]);
-  DnArgs last{};
-  last.out3 = out;
-  return dn_filter(s, width, rows, dn, sig, (const float4*)position, (const float4*)normal, DN_OUT_RGB, last);
+  return dn_denoise(width, rows, signal, nullptr, position, normal, dn, nullptr, out, nullptr, scratch, scratch_bytes, stream);
 }
 
 }

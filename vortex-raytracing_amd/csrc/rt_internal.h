@@ -1,7 +1,7 @@
 // Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
 // level-2 entry points), rt_accel.hip (acceleration-layout build, refit), rt_secondary.hip (the tails of mirror-bounce,
-// ambient-occlusion and path frames) and rt_denoise.hip (the a-trous filter and the temporal accumulation of denoised path frames) share: the types, and the
-// few host functions one unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of
+// ambient-occlusion and path frames) and rt_denoise.hip (the end of a denoised path frame's tail: a-trous filter, temporal accumulation,
+// variance guidance) share: the types, and the few host functions one unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of
 // shading, which rt_kernels.hip and rt_secondary.hip share, is in rt_shading.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,37 +186,25 @@ __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // c
 }
 
 // ---------------------------------------------------------------------------------------------
-// rt_denoise.hip: the launches of a denoised path frame's tail (render_path_tail in rt_secondary.hip calls them; all asynchronous on `s`)
+// rt_denoise.hip: what an entry point of rt_kernels.hip checks before a denoised path frame is launched, and the two ends that
+// render_path_tail (rt_secondary.hip) hands such a frame to.  The launches behind them, and their order, are that unit's own.
 // ---------------------------------------------------------------------------------------------
-// the checks of vxrt_denoise_params_t both entry points share
+struct RenderRequest;
+// the checks of vxrt_denoise_params_t / vxrt_variance_params_t every entry point that takes one shares
 bool dn_params_ok(const vxrt_denoise_params_t* dn);
-// per pixel t of the window: c = the path frame's colour (acc / spp | the flat sum of Lit_0 | the background), the optional guide
-// outputs, and with `sig` the demodulated signal (E, lum(E)) the filter starts from
-int dn_launch_demodulate(hipStream_t s, uint32_t n, uint32_t W, uint32_t y0, const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
-                         const float4* acc, uint32_t spp, uint32_t flat, float4* sig, const vxrt_path_aov_t* aov);
-// dn->iterations (>= 1) a-trous passes over sig[0] (ping-pong with sig[1]); the last one remodulates with lit / alb, packs and writes
-// dst / colors (full-frame addressing, rows from y0)
-int dn_launch_path_filter(hipStream_t s, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn, float4* const sig[2], const float4* geo,
-                          const float4* nrm, const float4* lit, const float4* alb, uint32_t* dst, float* colors);
-// temporal accumulation (vxrt_render_path_temporal): what the entry point checks before anything is launched -- the parameters, and that
-// the history holds a window of `pixels` pixels
-// moments: the kind of history the entry point takes (vxrt_render_path_variance: one with moments; the others: one without)
-bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels, bool moments = false);
-// out = T(E, P, N; h, the history's camera, t) for the window, one launch: E = sig's rgb, P = geo, N = nrm.  filtered: (out.rgb, lum) goes
-// back into sig (in place: a pixel reads only its own entry) for dn_launch_path_filter; else the pass remodulates out.rgb with lit / alb,
-// packs and writes dst / colors itself.  The history then holds this frame, `cam` and the geometry.
-// prev_pos / prev_nrm (both or neither): the step with motion, T_m, with Q = prev_pos and N' = prev_nrm.
-int tp_launch_path(hipStream_t s, vxrt_history_t* h, const vxrt_camera_t* cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,
-                   const vxrt_temporal_params_t* t, float4* sig, const float4* geo, const float4* nrm, bool filtered, const float4* lit,
-                   const float4* alb, uint32_t* dst, float* colors, const float4* prev_pos = nullptr, const float4* prev_nrm = nullptr);
-// variance guidance (vxrt_render_path_variance): the checks of vxrt_variance_params_t, and what follows tp_launch_path on a history with
-// moments (the step is then T_v) -- one launch that writes V0 of the history's current set into the w of sig[0] and, if asked for, into
-// `variance` (full-frame addressing), then dn->iterations passes of atrous_v in place of dn_launch_path_filter.  dn->iterations == 0:
-// only the `variance` output, if asked for.
 bool vr_params_ok(const vxrt_variance_params_t* v);
-int vr_launch_path(hipStream_t s, const vxrt_history_t* h, uint32_t W, uint32_t rows, uint32_t y0, const vxrt_denoise_params_t* dn,
-                   const vxrt_variance_params_t* vp, float4* const sig[2], const float4* geo, const float4* nrm, const float4* lit, const float4* alb,
-                   uint32_t* dst, float* colors, float* variance);
+// temporal accumulation: the parameters, and that the history is of the kind the entry point takes (moments: vxrt_render_path_variance
+// takes one with moments, the others one without) and holds a window of `pixels` pixels
+bool tp_request_ok(const vxrt_history_t* h, const vxrt_temporal_params_t* t, uint64_t pixels, bool moments = false);
+// a camera whose every field is finite: what the entry points of both units that take a camera accept (rt_kernels.hip)
+bool camera_ok(const vxrt_camera_t* c);
+// End of a denoised path frame's tail in place of rt_path_final_kernel, for a frame with iterations or a history.  n = pixels of the window;
+// the context holds the primary hits' P, N, Lit, Alb and the accumulators.  Demodulates into the context's signal buffers (grown here) and
+// writes the guide outputs; then the temporal step, the initial variance and the a-trous passes as the request asks for them, the last
+// launch of which remodulates, packs and writes dst / colors.  All asynchronous on the request's stream; 0, or -1 when a HIP call failed.
+int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n);
+// The guide outputs only (r.aov), one launch: the frame without iterations and without a history, which rt_path_final_kernel then ends.
+int render_denoise_aov(FrameCtx* c, const RenderRequest& r, uint32_t n);
 
 // ---------------------------------------------------------------------------------------------
 // rt_kernels.hip <-> rt_secondary.hip: a frame as an entry point asks for it, the per-frame control block, growing device buffers,

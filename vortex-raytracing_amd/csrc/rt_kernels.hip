@@ -2203,6 +2203,23 @@ static int render_common(vxrt_accel_t* a, const RenderRequest& r) {
   return release_ctx(a, c, s);
 }
 
+// A camera whose every field is finite (what the camera entry points accept, those of rt_denoise.hip too: rt_internal.h)
+bool camera_ok(const vxrt_camera_t* c) {
+  if (!c) return false;
+  const float* f = &c->pos[0];
+  for (int i = 0; i < 14; ++i) if (!std::isfinite(f[i])) return false;
+  return true;
+}
+
+// What the vxrt_render_path* entry points ask for alike (path is not null: theirs to check, as the camera is); each adds its own fields
+static RenderRequest path_request(const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                                  const vxrt_path_params_t* path, uint32_t* dst, float* colors, unsigned long long* rays_traced, void* stream) {
+  RenderRequest r;
+  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
+  return r;
+}
+
 extern "C" {
 
 const char* vxrt_version(void) { return "vortex-rt-mi355x 0.3 (gfx950, compact 64-byte nodes, persistent wavefronts)"; }
@@ -2278,14 +2295,6 @@ int vxrt_render_interleaved_batch_wave_log(vxrt_accel_t* accel, uint32_t width, 
 int vxrt_render_batch(vxrt_accel_t* accel, uint32_t width, uint32_t height, uint32_t n_frames, const vxrt_shade_params_t* params, int shadow,
                       uint32_t* dst, uint64_t dst_frame_stride, unsigned long long* rays_traced, void* stream) {
   return vxrt_render_interleaved_batch(accel, width, height, 0, 1, n_frames, params, shadow, dst, dst_frame_stride, rays_traced, stream);
-}
-
-// A camera whose every field is finite (what the camera entry points accept)
-static bool camera_ok(const vxrt_camera_t* c) {
-  if (!c) return false;
-  const float* f = &c->pos[0];
-  for (int i = 0; i < 14; ++i) if (!std::isfinite(f[i])) return false;
-  return true;
 }
 
 // vxrt_render from a caller-supplied pinhole camera (see the header)
@@ -2401,10 +2410,7 @@ int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t wid
                      unsigned long long* rays_traced, void* stream) {
   if (!path) return -1;
   if (cam && !camera_ok(cam)) return -1;
-  RenderRequest r;
-  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
-  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
-  return render_common(accel, r);
+  return render_common(accel, path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream));
 }
 
 // Denoised path frame (see the header): vxrt_render_path whose tail ends in the a-trous filter of rt_denoise.hip
@@ -2413,10 +2419,8 @@ int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
                               const vxrt_path_aov_t* aov, unsigned long long* rays_traced, void* stream) {
   if (!path || !dn) return -1;
   if (cam && !camera_ok(cam)) return -1;
-  RenderRequest r;
-  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
   r.denoise = dn; r.aov = aov;
-  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }
 
@@ -2428,10 +2432,8 @@ int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
   if (!path || !dn || !camera_ok(cam)) return -1;
   const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;   // (a bad window is check_request's to refuse)
   if (!tp_request_ok(history, temporal, pixels)) return -1;
-  RenderRequest r;
-  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history;
-  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }
 
@@ -2443,10 +2445,8 @@ int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* c
   if (!path || !dn || !camera_ok(cam)) return -1;
   const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
   if (!tp_request_ok(history, temporal, pixels)) return -1;
-  RenderRequest r;
-  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = true; r.prev_position = prev_position;
-  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }
 
@@ -2459,11 +2459,9 @@ int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
   if (!path || !dn || !vp || !camera_ok(cam) || motion < 0 || motion > 1) return -1;
   const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
   if (!tp_request_ok(history, temporal, pixels, true)) return -1;
-  RenderRequest r;
-  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
   r.variance = vp; r.variance_out = variance;
-  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
 }
 

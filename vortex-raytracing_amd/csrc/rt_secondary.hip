@@ -741,36 +741,14 @@ int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const S
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// End of a denoised path frame's tail in place of rt_path_final_kernel (the kernels and their launches are in rt_denoise.hip): demodulate
-// the pixels' accumulators into the context's first signal buffer and write the guide outputs, then one launch per a-trous iteration,
-// ping-pong between the two signal buffers, the last of which remodulates, packs and writes.  n = pixels of the window.
-// With temporal accumulation (vxrt_render_path_temporal) one launch between the two blends the first signal buffer with the reprojected
-// history, in place, so the ping-pong order stays; without iterations that launch is the end of the frame.
-// With variance guidance (vxrt_render_path_variance) the history holds moments, the same launch is the step T_v, and what follows it is
-// the launch of the initial variance and the passes of atrous_v (vr_launch_path) in place of the plain filter.
-static int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n) {
-  hipStream_t s = (hipStream_t)r.stream;
-  if (!grow_device({{(void**)&c->dn_sig[0], 16}, {(void**)&c->dn_sig[1], 16}}, &c->dn_cap, n, GrowSync::STREAM, s)) return -1;
-  if (dn_launch_demodulate(s, n, r.width, r.y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, r.path->spp, r.path->bounces == 0 ? 1u : 0u,
-                           c->dn_sig[0], r.aov) != 0) return -1;
-  if (r.temporal) {
-    const bool filtered = r.denoise->iterations != 0;
-    if (tp_launch_path(s, r.history, r.cams, r.width, r.height, r.y0, r.y1, r.temporal, c->dn_sig[0], c->pt_geo, c->pt_nrm, filtered, c->pt_lit, c->pt_alb,
-                       r.dst, r.colors, r.motion ? c->mo_pos : nullptr, r.motion ? c->mo_nrm : nullptr) != 0) return -1;
-    if (r.variance)   // (the history holds moments: the step was T_v)
-      return vr_launch_path(s, r.history, r.width, r.y1 - r.y0, r.y0, r.denoise, r.variance, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst,
-                            r.colors, r.variance_out);
-    if (!filtered) return 0;
-  }
-  return dn_launch_path_filter(s, r.width, r.y1 - r.y0, r.y0, r.denoise, c->dn_sig, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, r.dst, r.colors);
-}
-
 // Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
 // occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
 // pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
 // occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
 // batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
 // device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
+// A denoised frame with iterations or a history ends in rt_denoise.hip instead (render_denoise_tail: demodulate, temporal step, initial
+// variance, a-trous passes -- that unit owns the order); one without either gets its guide outputs there and ends here as every path frame.
 int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
   const SceneDev& sc = a->dev;
   const vxrt_path_params_t& pp = *r.path;
@@ -826,8 +804,7 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
                        (const float4*)c->pt_L, c->pt_acc);
   }
   if (r.denoise && (r.denoise->iterations || r.temporal)) return render_denoise_tail(c, r, n32);
-  if (r.denoise && r.aov && dn_launch_demodulate(s, n32, width, y0, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc, pp.spp, pp.bounces == 0 ? 1u : 0u,
-                                                 nullptr, r.aov) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
+  if (r.denoise && r.aov && render_denoise_aov(c, r, n32) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
   hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
                      pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
   return hipGetLastError() == hipSuccess ? 0 : -1;

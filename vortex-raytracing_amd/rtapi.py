@@ -60,8 +60,13 @@ def _lib():
         L.vxrt_status.restype = C.c_int
         L.vxrt_status.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.vxrt_version.restype = C.c_char_p
+        _declare_path_family(L)
         _proto = True
     return L
+
+
+# (the families below once declared their own prototypes; theirs are _lib()'s now, the names stay for callers of the raw library)
+_denoise_lib = _temporal_lib = _motion_lib = _variance_lib = _lib
 
 
 def accel_build(scene, stream=None):
@@ -522,9 +527,6 @@ def render_path(accel, cam, width, height, y0, y1, params, spp, bounces, dst_ptr
     """vxrt_render_path: `spp` paths per pixel of `bounces` diffuse bounces each, the light sampled at every vertex with shadow=1, seen
     from pinhole camera `cam` (a Camera or 14 floats; None = the fixed camera of vxrt_render)."""
     L = _lib()
-    L.vxrt_render_path.restype = C.c_int
-    L.vxrt_render_path.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
-                                   C.POINTER(PathParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
     check(L.vxrt_render_path(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), dst_ptr,
                              colors_ptr, rays_ptr, stream), "vxrt_render_path")
@@ -539,20 +541,6 @@ class DenoiseParams(C.Structure):   # vxrt_denoise_params_t
 
 class PathAov(C.Structure):   # vxrt_path_aov_t: device pointers, any of them None
     _fields_ = [("noisy", C.c_void_p), ("direct", C.c_void_p), ("albedo", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p)]
-
-
-def _denoise_lib():
-    L = _lib()
-    L.vxrt_render_path_denoised.restype = C.c_int
-    L.vxrt_render_path_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
-                                            C.POINTER(PathParams), C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(PathAov), C.c_void_p,
-                                            C.c_void_p]
-    L.vxrt_denoise_scratch_bytes.restype = C.c_uint64
-    L.vxrt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
-    L.vxrt_denoise.restype = C.c_int
-    L.vxrt_denoise.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_uint64,
-                               C.c_void_p]
-    return L
 
 
 def render_path_denoised(accel, cam, width, height, y0, y1, params, spp, bounces, denoise, dst_ptr, seed=0, shadow=0, colors_ptr=None, aov=None,
@@ -581,25 +569,6 @@ TEMPORAL_MAX_LEN = 1024   # VXRT_TEMPORAL_MAX_LEN
 
 class TemporalParams(C.Structure):   # vxrt_temporal_params_t
     _fields_ = [("alpha_min", C.c_float), ("max_len", C.c_uint32), ("sigma_z", C.c_float), ("normal_min", C.c_float)]
-
-
-def _temporal_lib():
-    L = _denoise_lib()
-    L.vxrt_history_create.restype = C.c_int
-    L.vxrt_history_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-    for f in (L.vxrt_history_destroy, L.vxrt_history_reset):
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p]
-    L.vxrt_history_read.restype = C.c_int
-    L.vxrt_history_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vxrt_temporal_accumulate.restype = C.c_int
-    L.vxrt_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]
-    L.vxrt_render_path_temporal.restype = C.c_int
-    L.vxrt_render_path_temporal.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
-                                            C.POINTER(PathParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.POINTER(PathAov), C.c_void_p, C.c_void_p]
-    return L
 
 
 class History:
@@ -664,22 +633,6 @@ def render_path_temporal(accel, cam, width, height, y0, y1, params, spp, bounces
 
 
 # ---- motion: temporal accumulation that reprojects through moved instances (the header's "Motion") ----
-def _motion_lib():
-    L = _temporal_lib()
-    L.vxrt_accel_motion_snapshot.restype = C.c_int
-    L.vxrt_accel_motion_snapshot.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-    L.vxrt_previous_positions.restype = C.c_int
-    L.vxrt_previous_positions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vxrt_temporal_accumulate_motion.restype = C.c_int
-    L.vxrt_temporal_accumulate_motion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]
-    L.vxrt_render_path_temporal_motion.restype = C.c_int
-    L.vxrt_render_path_temporal_motion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
-                                                   C.POINTER(PathParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.POINTER(PathAov), C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
 def accel_motion_snapshot(accel, what, stream=None):
     """vxrt_accel_motion_snapshot: "the scene as it is now is the previous frame" -- the accel copies the instance records
     (REFIT_INSTANCES) and the vertices as well (REFIT_INSTANCES | REFIT_GEOMETRY); 0 frees the snapshot.  Raises on a refusal."""
@@ -717,27 +670,38 @@ class VarianceParams(C.Structure):   # vxrt_variance_params_t
     _fields_ = [("epsilon", C.c_float), ("min_len", C.c_uint32), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-def _variance_lib():
-    L = _motion_lib()
-    L.vxrt_history_create_moments.restype = C.c_int
-    L.vxrt_history_create_moments.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-    L.vxrt_history_read_moments.restype = C.c_int
-    L.vxrt_history_read_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vxrt_temporal_accumulate_moments.restype = C.c_int
-    L.vxrt_temporal_accumulate_moments.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]
-    L.vxrt_history_variance.restype = C.c_int
-    L.vxrt_history_variance.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), C.c_void_p, C.c_void_p]
-    L.vxrt_denoise_variance_scratch_bytes.restype = C.c_uint64
-    L.vxrt_denoise_variance_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
-    L.vxrt_denoise_variance.restype = C.c_int
-    L.vxrt_denoise_variance.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams),
-                                        C.POINTER(VarianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    L.vxrt_render_path_variance.restype = C.c_int
-    L.vxrt_render_path_variance.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShadeParams),
-                                            C.POINTER(PathParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams),
-                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PathAov), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
+def _declare_path_family(L):
+    """The prototypes of the path, denoise, temporal, motion and variance families; _lib() calls this once with its own."""
+    u32, vp, i32 = C.c_uint32, C.c_void_p, C.c_int
+    frame = [vp, C.POINTER(Camera), u32, u32, u32, u32, C.POINTER(ShadeParams), C.POINTER(PathParams)]   # accel, cam, the window, params, path
+    dn, tp, vr = C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams)
+    step = [vp, C.POINTER(Camera), u32, u32, u32, u32, vp, vp, vp]   # history, cam, the window, signal, position, normal
+    protos = {
+        "vxrt_render_path": (i32, frame + [vp, vp, vp, vp]),
+        "vxrt_render_path_denoised": (i32, frame + [dn, vp, vp, C.POINTER(PathAov), vp, vp]),
+        "vxrt_denoise_scratch_bytes": (C.c_uint64, [u32, u32]),
+        "vxrt_denoise": (i32, [u32, u32, vp, vp, vp, dn, vp, vp, C.c_uint64, vp]),
+        "vxrt_history_create": (i32, [u32, u32, C.POINTER(vp)]),
+        "vxrt_history_destroy": (i32, [vp]),
+        "vxrt_history_reset": (i32, [vp]),
+        "vxrt_history_read": (i32, [vp, vp, vp]),
+        "vxrt_temporal_accumulate": (i32, step + [tp, vp, vp]),
+        "vxrt_render_path_temporal": (i32, frame + [dn, tp, vp, vp, vp, C.POINTER(PathAov), vp, vp]),
+        "vxrt_accel_motion_snapshot": (i32, [vp, u32, vp]),
+        "vxrt_previous_positions": (i32, [vp, u32, vp, vp, vp, vp]),
+        "vxrt_temporal_accumulate_motion": (i32, step + [vp, vp, tp, vp, vp]),
+        "vxrt_render_path_temporal_motion": (i32, frame + [dn, tp, vp, vp, vp, C.POINTER(PathAov), vp, vp, vp]),
+        "vxrt_history_create_moments": (i32, [u32, u32, C.POINTER(vp)]),
+        "vxrt_history_read_moments": (i32, [vp, vp, vp]),
+        "vxrt_temporal_accumulate_moments": (i32, step + [vp, vp, tp, vp, vp]),
+        "vxrt_history_variance": (i32, [vp, dn, vr, vp, vp]),
+        "vxrt_denoise_variance_scratch_bytes": (C.c_uint64, [u32, u32]),
+        "vxrt_denoise_variance": (i32, [u32, u32, vp, vp, vp, vp, dn, vr, vp, vp, vp, C.c_uint64, vp]),
+        "vxrt_render_path_variance": (i32, frame + [dn, tp, vr, vp, i32, vp, vp, C.POINTER(PathAov), vp, vp, vp, vp]),
+    }
+    for name, (restype, argtypes) in protos.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
 
 
 def temporal_accumulate_moments(history, cam, width, height, y0, y1, signal_ptr, position_ptr, normal_ptr, temporal, out_ptr, prev_position_ptr=None,
