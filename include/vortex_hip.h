@@ -810,6 +810,66 @@ int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
                               float* prev_position /* optional, motion only */, float* variance /* optional */,
                               unsigned long long* rays_traced /* optional */, void* stream);
 
+/* Adaptive sampling: path frames that take a sample count per pixel from a device buffer, and the kernel that derives such counts from a
+ * variance buffer (extension; absent from the reference).  With both, the loop "render, take V0, derive the next frame's counts,
+ * render" runs on one stream without a host synchronisation.  tests/adaptive_ref.py restates all of it.
+ *
+ * THE FRAME WITH COUNTS.  counts: device, one uint32_t per pixel of the full frame, addressed like dst (counts[x + y * W]); only rows
+ * [y0, y1) are read, and the host never reads the buffer.  For a pixel p with a primary hit n_p = min(max(counts[p], 1), path->spp): path->spp
+ * (1..4096) is the cap, and a value out of range is clamped on the device, not refused.  A pixel whose primary ray misses ignores its
+ * count and is the background.  The pixel is then exactly what vxrt_render_path defines for it with spp := n_p, everywhere that
+ * definition uses spp:
+ *   the bounce ray is the vxrt_render_ao ray of (x, y, W, n_p, s) -- the hash seed is (x + y * W) * n_p + s + 1 + ... in uint32 arithmetic;
+ *   the samples s = 0 .. n_p - 1 are summed in ascending s, starting from the first;
+ *   colour = acc / (float)n_p;   with bounces = 0: the flat sum of Lit_0, n_p times, divided by n_p.
+ * rays_traced follows vxrt_render_path's rule: the primary rays + one per occlusion ray of a real hit + one per bounce ray of a live path.
+ * Two identities follow (both are tests):
+ *   UNIFORM  counts[p] == path->spp everywhere is vxrt_render_path bit for bit: pixels, colours, rays traced.
+ *   MOSAIC   a pixel's value depends on its own n_p only: the frame is, pixel by pixel, the vxrt_render_path frame with spp = n_p of that pixel.
+ * vxrt_render_path_variance_adaptive is vxrt_render_path_variance with c, the path frame's colour that demodulation starts from, taken
+ * from the frame with counts; nothing else of its definition changes (with counts[p] == path->spp everywhere it is that call bit for
+ * bit, HE and HM of the history included; dn->iterations = 0 follows that call's own rule).
+ * Both return -1 before anything is launched, dst and the history left as they were, for a null `counts` and for everything the call
+ * without counts refuses (a non-zero alpha table included); 0 for an empty window.  Asynchronous on `stream`.  The samples are traced in
+ * batches of VXRT_PATH_BATCH consecutive paths of the frame (docs/KNOBS.md), pixels in window order, whatever the counts: per-path
+ * storage is bounded by the batch, 8 bytes per path more than vxrt_render_path's, and 12 bytes per pixel of the window for the counts
+ * and their 64-bit offsets.  The number of paths stays on the device.
+ *
+ * COUNTS FROM A VARIANCE.  vxrt_sample_counts is elementwise over n entries; the caller owns the addressing (vxrt_history_variance writes
+ * window-addressed, the frame's `variance` output is frame-addressed; with y0 = 0, y1 = H they coincide).  Every symbol is one fp32
+ * operation in the order written, ceilf is exact.  For entry i:
+ *   m = prev_counts ? (float)min(max(prev_counts[i], 1), 4096) : 1.0f
+ *   x = (variance[i] * m) * gain;   c = ceilf(x)
+ *   counts[i] = c > (float)min_spp ? (c < (float)max_spp ? (uint32_t)c : max_spp) : min_spp
+ * so a NaN gives min_spp (both comparisons are false), +inf gives max_spp, negatives and -0 give min_spp.  The factor m is a HEURISTIC:
+ * the variance of the mean of m samples, times m, is about the variance of one sample -- V0 of a frame rendered with prev_counts is
+ * roughly that of a mean, blended over the history's frames; nothing here claims more than "about".
+ * *total (optional, device) increases by the sum of the counts written (64-bit integer adds, exact in any order), which a caller can
+ * read back now and then to set gain against a budget.  One launch, asynchronous on `stream`, no host synchronisation.  Returns -1
+ * before the launch for a null variance / counts / prm, gain not > 0 or not finite, min_spp = 0 or > max_spp, max_spp > 4096,
+ * reserved != 0, n >= 2^31; 0 for n = 0. */
+typedef struct vxrt_sample_count_params {
+  float gain;        /* samples per unit of per-sample variance, > 0 and finite */
+  uint32_t min_spp;  /* 1 .. max_spp */
+  uint32_t max_spp;  /* min_spp .. 4096 */
+  uint32_t reserved; /* 0 */
+} vxrt_sample_count_params_t;
+int vxrt_render_path_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
+                              uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path /* spp: the cap */,
+                              const uint32_t* counts /* device, 1 per pixel of the frame */, uint32_t* dst, float* colors /* optional */,
+                              unsigned long long* rays_traced /* optional */, void* stream);
+int vxrt_render_path_variance_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                       const vxrt_shade_params_t* params, const vxrt_path_params_t* path /* spp: the cap */,
+                                       const uint32_t* counts /* device, 1 per pixel of the frame */, const vxrt_denoise_params_t* dn,
+                                       const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp, vxrt_history_t* history,
+                                       int motion, uint32_t* dst, float* colors /* optional */, const vxrt_path_aov_t* aov /* optional */,
+                                       float* prev_position /* optional, motion only */, float* variance /* optional */,
+                                       unsigned long long* rays_traced /* optional */, void* stream);
+int vxrt_sample_counts(uint64_t n, const float* variance /* device */, const uint32_t* prev_counts /* device, optional */,
+                       const vxrt_sample_count_params_t* prm, uint32_t* counts /* device */,
+                       unsigned long long* total /* device, optional: incremented */, void* stream);
+
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,
  * invTransform, bvh_offset@128, tex_offset@136, tex_width@144, tex_height@148, reflectivity@152),

@@ -577,8 +577,9 @@ struct DnFrame {
 };
 
 static DnFrame dn_frame(const FrameCtx* c, const RenderRequest& r, uint32_t n) {
+  // (a frame with per-pixel sample counts has divided its accumulators by each pixel's own count: spp = 1, not flat)
   return DnFrame{(hipStream_t)r.stream, r.width, r.height, r.y0, r.y1, n, c->pt_geo, c->pt_nrm, c->pt_lit, c->pt_alb, c->pt_acc,
-                 r.path->spp, r.path->bounces == 0 ? 1u : 0u, {c->dn_sig[0], c->dn_sig[1]}, r.dst, r.colors};
+                 r.sample_counts ? 1u : r.path->spp, r.sample_counts ? 0u : (r.path->bounces == 0 ? 1u : 0u), {c->dn_sig[0], c->dn_sig[1]}, r.dst, r.colors};
 }
 
 // per pixel t of the window: c = the path frame's colour (acc / spp | the flat sum of Lit_0 | the background), the optional guide

@@ -107,6 +107,14 @@ struct FrameCtx {
   float4* pt_I = nullptr; float4* pt_N = nullptr; float4* pt_D = nullptr; float4* pt_L = nullptr; float4* pt_T = nullptr;
   uint32_t* pt_live[2] = {nullptr, nullptr}; float* pt_rays = nullptr; HitRec* pt_hits = nullptr; uint64_t pt_path_cap = 0;
   float* pt_srays = nullptr; float* pt_stmax = nullptr; HitRec* pt_shits = nullptr; uint64_t pt_shadow_cap = 0;
+  // path frames with per-pixel sample counts (vxrt_render_path_adaptive; allocated on first use).  Per pixel of the window: the clamped
+  // count (0 for a miss) and the 64-bit exclusive offset of its first path among the frame's paths in window order; per scan block of
+  // PT_SCAN_BLOCK pixels: the block's sum and its 64-bit offset; [0] of pt_ctot the frame's paths.  Per path of a batch: its pixel and
+  // its sample index.
+  uint32_t* pt_cnt = nullptr; unsigned long long* pt_off = nullptr; uint64_t pt_cnt_cap = 0;
+  uint32_t* pt_bsum = nullptr; unsigned long long* pt_boff = nullptr; uint64_t pt_blk_cap = 0;
+  unsigned long long* pt_ctot = nullptr;
+  uint32_t* pt_spix = nullptr; uint32_t* pt_ssmp = nullptr; uint64_t pt_slot_cap = 0;
   // denoised path frames (vxrt_render_path_denoised; allocated on first use): the two signal buffers the a-trous iterations ping-pong
   // between, one float4 (E, lum(E)) per pixel of the window; the guides are pt_geo and pt_nrm
   float4* dn_sig[2] = {nullptr, nullptr}; uint64_t dn_cap = 0;
@@ -238,6 +246,7 @@ struct RenderRequest {
   const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
   const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
   const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
+  const uint32_t* sample_counts = nullptr;          // ... with a sample count per pixel (vxrt_render_path_adaptive): device, addressed like dst; path->spp is the cap
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;
   const vxrt_temporal_params_t* temporal = nullptr; // ... with temporal accumulation before the filter (vxrt_render_path_temporal), into
@@ -283,3 +292,6 @@ int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, co
 int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
+// rt_secondary.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
+int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
+                         unsigned long long* total, hipStream_t s);

@@ -1856,6 +1856,8 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   // path frames: whole rows of single frames, the timed build only, colours the one optional output besides the ray count
   if (r.path && (r.path->spp == 0 || r.path->spp > 4096 || r.path->bounces > VXRT_PATH_MAX_BOUNCES || r.path->shadow > 1 || stats || r.wave_log || r.ao ||
                  r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
+  // ... with a sample count per pixel: a path frame (a null buffer is the entry point's to refuse: here it means "no counts")
+  if (r.sample_counts && !r.path) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
   // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
@@ -2463,6 +2465,43 @@ int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
   r.variance = vp; r.variance_out = variance;
   return render_common(accel, r);
+}
+
+// Path frame with a sample count per pixel (see the header, "Adaptive sampling"): vxrt_render_path whose tail packs the pixels' samples
+// into batches (render_path_counts_tail in rt_secondary.hip); path->spp is the cap
+int vxrt_render_path_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const uint32_t* counts, uint32_t* dst, float* colors,
+                              unsigned long long* rays_traced, void* stream) {
+  if (!path || !counts) return -1;
+  if (cam && !camera_ok(cam)) return -1;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
+  r.sample_counts = counts;
+  return render_common(accel, r);
+}
+
+// ... as the path frame of vxrt_render_path_variance
+int vxrt_render_path_variance_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                       const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const uint32_t* counts,
+                                       const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp,
+                                       vxrt_history_t* history, int motion, uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, float* prev_position,
+                                       float* variance, unsigned long long* rays_traced, void* stream) {
+  if (!path || !counts || !dn || !vp || !camera_ok(cam) || motion < 0 || motion > 1) return -1;
+  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
+  if (!tp_request_ok(history, temporal, pixels, true)) return -1;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
+  r.sample_counts = counts;
+  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
+  r.variance = vp; r.variance_out = variance;
+  return render_common(accel, r);
+}
+
+// Sample counts from a variance buffer (see the header, "Adaptive sampling"): elementwise, one launch, no host synchronisation
+int vxrt_sample_counts(uint64_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
+                       unsigned long long* total, void* stream) {
+  if (!prm || !variance || !counts || n >= 0x80000000ull || prm->reserved != 0u) return -1;
+  if (!(prm->gain > 0.0f) || !std::isfinite(prm->gain) || prm->min_spp == 0u || prm->min_spp > prm->max_spp || prm->max_spp > 4096u) return -1;
+  if (n == 0) return 0;
+  return sample_counts_launch((uint32_t)n, variance, prev_counts, prm, counts, total, (hipStream_t)stream);
 }
 
 // vxrt_trace with the fetch counters compiled in (slower; never the timed path): counters = device u64[8],

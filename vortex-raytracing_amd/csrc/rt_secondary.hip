@@ -527,6 +527,200 @@ __global__ __launch_bounds__(256) void rt_path_final_kernel(uint32_t n, uint32_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// Path frames with a sample count per pixel (vxrt_render_path_adaptive; the definition is the header's "Adaptive sampling", the launch
+// sequence is in render_path_counts_tail and DESIGN.md s2 "Adaptive sampling").  The paths of the frame are numbered in window order:
+// pixel t owns the cnt[t] paths g = off[t] .. off[t] + cnt[t] - 1, sample g - off[t]; batch b owns g in [b * cap, (b + 1) * cap), slot
+// g - b * cap.  The numbering comes from a scan in window order, so it is the same from run to run (the atomic-ordered list of hit
+// pixels is not).  The scan is three launches and no workgroup waits for another: per-block sums, one workgroup that scans the block
+// sums in passes with a running carry, per-pixel offsets.  rt_path_prepare_kernel, rt_path_occlusion_rays_kernel and
+// rt_path_scatter_kernel are the uniform frame's: they work on slots and live lists only.
+// ---------------------------------------------------------------------------------------------
+#define PT_SCAN_BLOCK 1024u   // pixels per scan block: 256 threads x 4 consecutive pixels
+#define PT_SCAN_PASS 1024u    // block sums per pass of rt_path_scan_kernel: its threads (one pass covers PT_SCAN_PASS * PT_SCAN_BLOCK pixels)
+
+// cnt[t] = clamp(counts[pixel of t], 1, spp_cap) for a pixel with a hit, 0 for a miss (its count is not read); bsum[block] = the sum of
+// the block's cnt (at most 1,024 x 4,096)
+__global__ __launch_bounds__(256) void rt_path_counts_kernel(uint32_t n, uint32_t W, uint32_t y0, uint32_t spp_cap, const float4* __restrict__ geo,
+    const uint32_t* __restrict__ counts, uint32_t* __restrict__ cnt, uint32_t* __restrict__ bsum) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t t0 = blockIdx.x * PT_SCAN_BLOCK + threadIdx.x * 4u;
+  uint32_t sum = 0u;
+#pragma unroll
+  for (uint32_t c = 0; c < 4u; ++c) {
+    const uint32_t t = t0 + c;
+    if (t < n) {
+      uint32_t v = 0u;
+      if (geo[t].w != 0.f) {
+        const uint32_t x = t % W, y = y0 + t / W;
+        v = min(max(counts[(size_t)x + (size_t)y * W], 1u), spp_cap);
+      }
+      cnt[t] = v;
+      sum += v;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+  if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) bsum[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// boff[i] = the sum of bsum[0 .. i), 64 bit; *total = the sum of all nb.  ONE workgroup: pass k scans block sums [k * PT_SCAN_PASS,
+// (k + 1) * PT_SCAN_PASS) and every thread carries the running total into the next pass; the number of passes is known at entry.
+__global__ __launch_bounds__(1024) void rt_path_scan_kernel(uint32_t nb, const uint32_t* __restrict__ bsum, unsigned long long* __restrict__ boff,
+    unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long s_w[PT_SCAN_PASS / 64u];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t passes = (nb + PT_SCAN_PASS - 1u) / PT_SCAN_PASS;
+  unsigned long long carry = 0ull;
+  for (uint32_t k = 0; k < passes; ++k) {
+    const uint32_t i = k * PT_SCAN_PASS + threadIdx.x;
+    const unsigned long long v = i < nb ? (unsigned long long)bsum[i] : 0ull;
+    unsigned long long inc = v;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
+    if (lane == 63u) s_w[wave] = inc;
+    __syncthreads();
+    unsigned long long base = carry, pass_sum = 0ull;
+    for (uint32_t w = 0; w < PT_SCAN_PASS / 64u; ++w) { const unsigned long long x = s_w[w]; if (w < wave) base += x; pass_sum += x; }
+    if (i < nb) boff[i] = base + (inc - v);
+    carry += pass_sum;
+    __syncthreads();   // (s_w is written again by the next pass)
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+// off[t] = boff[block of t] + the sum of cnt over the block's pixels before t
+__global__ __launch_bounds__(256) void rt_path_offsets_kernel(uint32_t n, const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ boff,
+    unsigned long long* __restrict__ off) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t t0 = blockIdx.x * PT_SCAN_BLOCK + threadIdx.x * 4u;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t v[4], sum = 0u;
+#pragma unroll
+  for (uint32_t c = 0; c < 4u; ++c) { v[c] = t0 + c < n ? cnt[t0 + c] : 0u; sum += v[c]; }
+  uint32_t inc = sum;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
+  if (lane == 63u) s_w[wave] = inc;
+  __syncthreads();
+  unsigned long long base = boff[blockIdx.x] + (unsigned long long)(inc - sum);
+  for (uint32_t w = 0; w < wave; ++w) base += s_w[w];
+#pragma unroll
+  for (uint32_t c = 0; c < 4u; ++c) {
+    if (t0 + c < n) off[t0 + c] = base;
+    base += v[c];
+  }
+}
+
+// start of the batch that owns paths [g0, g0 + cap): slot i is path g = g0 + i, live while g < *total.  Its pixel is the last t with
+// off[t] <= g -- a pixel without samples shares its offset with its successor, so that t has samples -- found by a binary search of at
+// most 32 steps (n < 2^31); the slot keeps (pixel, sample) and takes the pixel's primary vertex as rt_path_start_kernel does.
+// hdr[1] = the batch's live paths (0 for a batch past the end of the frame's paths).
+__global__ __launch_bounds__(256) void rt_path_start_counts_kernel(uint32_t cap, unsigned long long g0, uint32_t n, const unsigned long long* __restrict__ total,
+    const unsigned long long* __restrict__ off, uint32_t* hdr,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, uint32_t* __restrict__ live,
+    uint32_t* __restrict__ spix, uint32_t* __restrict__ ssmp) {
+  const unsigned long long tot = *total;
+  const unsigned long long left = tot > g0 ? tot - g0 : 0ull;
+  const uint32_t n_live = left < (unsigned long long)cap ? (uint32_t)left : cap;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i == 0) hdr[1] = n_live;
+  if (i >= n_live) return;
+  const unsigned long long g = g0 + i;
+  uint32_t lo = 0u, hi = n;   // off[lo] <= g < off[hi] (off[n] = *total)
+  for (int k = 0; k < 32; ++k) {
+    if (hi - lo <= 1u) break;
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= g) lo = mid; else hi = mid;
+  }
+  const uint32_t t = lo;
+  spix[i] = t; ssmp[i] = (uint32_t)(g - off[t]);
+  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
+  live[i] = i;
+}
+
+// rt_path_bounce_rays_kernel with the slot's pixel, sample and the pixel's own sample count in place of slot / ns, s0 + slot % ns and spp
+__global__ __launch_bounds__(256) void rt_path_bounce_rays_counts_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
+    const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, unsigned long long* rays_traced) {
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q == 0) {
+    *n_next = 0u;
+    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one)
+  }
+  if (q >= total) return;
+  const uint32_t slot = live[q], t = spix[slot], smp = ssmp[slot];
+  const uint32_t x = t % W, y = y0 + t / W;
+  const float4 I = pI[slot], N = pN[slot], D = pD[slot];
+  float r6[6];
+  ao_sample_ray(x, y, W, cnt[t], smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
+  float* o = rays + (size_t)q * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = r6[k];
+}
+
+// after a batch's last depth, one thread per pixel of the window: the Lc of the pixel's samples that are in the batch [g0, g0 + cap)
+// are added to its accumulator in ascending sample order; the pixel's first sample starts it.  A pixel's samples are contiguous in g
+// and may straddle batches; the trip count is at most the pixel's count.
+__global__ __launch_bounds__(256) void rt_path_accumulate_counts_kernel(uint32_t n, uint32_t cap, unsigned long long g0, const uint32_t* __restrict__ cnt,
+    const unsigned long long* __restrict__ off, const float4* __restrict__ pL, float4* __restrict__ acc) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t c = cnt[t];
+  if (c == 0u) return;
+  const unsigned long long o = off[t], g1 = g0 + cap;
+  const unsigned long long lo = o > g0 ? o : g0, hi = o + c < g1 ? o + c : g1;
+  if (lo >= hi) return;
+  const float4* L = pL + (size_t)(lo - g0);
+  const uint32_t k = (uint32_t)(hi - lo);
+  const bool first = lo == o;
+  float4 a = first ? L[0] : acc[t];
+  for (uint32_t s = first ? 1u : 0u; s < k; ++s) { const float4 v = L[s]; a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z; }
+  acc[t] = a;
+}
+
+// after the last batch: acc[t] = acc[t] / (float)cnt[t] per channel (flat, bounces = 0: of the flat sum of Lit_0, formed here as
+// rt_path_final_kernel forms it).  What ends the frame then divides by 1.0f, which changes no bit.
+__global__ __launch_bounds__(256) void rt_path_divide_counts_kernel(uint32_t n, const uint32_t* __restrict__ cnt, const float4* __restrict__ lit, uint32_t flat,
+    float4* __restrict__ acc) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t c = cnt[t];
+  if (c == 0u) return;
+  float r, g, b;
+  if (flat) { const float4 l = lit[t]; r = l.x; g = l.y; b = l.z; for (uint32_t s = 1; s < c; ++s) { r = r + l.x; g = g + l.y; b = b + l.z; } }
+  else { const float4 a = acc[t]; r = a.x; g = a.y; b = a.z; }
+  const float f = (float)c;
+  acc[t] = make_float4(r / f, g / f, b / f, 0.f);
+}
+
+// vxrt_sample_counts (the header's "Adaptive sampling"): one entry per thread, every symbol one fp32 operation; the counts written are
+// summed per workgroup (at most 256 x 4,096) and added to *total with one 64-bit atomic
+__global__ __launch_bounds__(256) void rt_sample_counts_kernel(uint32_t n, const float* __restrict__ variance, const uint32_t* __restrict__ prev, float gain,
+    uint32_t min_spp, uint32_t max_spp, uint32_t* __restrict__ counts, unsigned long long* total) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  uint32_t v = 0u;
+  if (i < n) {
+    const float m = prev ? (float)min(max(prev[i], 1u), 4096u) : 1.0f;
+    const float x = (variance[i] * m) * gain;
+    const float c = ceilf(x);
+    v = c > (float)min_spp ? (c < (float)max_spp ? (uint32_t)c : max_spp) : min_spp;
+    counts[i] = v;
+  }
+  if (total) {   // (uniform over the launch)
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t sum = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+      if (sum) atomicAdd(total, (unsigned long long)sum);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Secondary rays re-sorted before they are traced (north_star: "ray packets re-sorted ... to tame divergence").
 // The rays of a bounce / AO pass leave the compaction in pixel order with directions spread over a hemisphere: a wavefront of
 // 64 consecutive rays shares origins but not directions.  Counting sort by key = direction octant x origin cell (the 16x16-pixel
@@ -741,25 +935,13 @@ int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const S
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
-// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
-// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
-// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
-// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
-// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
-// A denoised frame with iterations or a history ends in rt_denoise.hip instead (render_denoise_tail: demodulate, temporal step, initial
-// variance, a-trous passes -- that unit owns the order); one without either gets its guide outputs there and ends here as every path frame.
-int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+// What both tails of a path frame begin with: the context's buffers for n pixels and batches of path_cap paths (per pixel; per path --
+// none without bounces; per occlusion ray -- none without light sampling; grown behind the stream), the zeroed header, and the prepare launch
+static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab, uint64_t n, uint64_t path_cap) {
   const SceneDev& sc = a->dev;
-  const vxrt_path_params_t& pp = *r.path;
-  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  const uint32_t width = r.width, y0 = r.y0;
   hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull) return -1;
-  const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
-  const uint64_t path_cap = pp.bounces ? n * ns : 0, shadow_cap = pp.shadow ? path_cap : 0;
-  if (path_cap > 0x7fffffffull) return -1;
-  // (per pixel; per path -- none without bounces; per occlusion ray -- none without light sampling)
+  const uint64_t shadow_cap = r.path->shadow ? path_cap : 0;
   if (!c->pt_hdr && hipMalloc((void**)&c->pt_hdr, 16) != hipSuccess) return -1;
   if (!grow_device({{(void**)&c->pt_geo, 16}, {(void**)&c->pt_nrm, 16}, {(void**)&c->pt_dir, 16}, {(void**)&c->pt_lit, 16}, {(void**)&c->pt_alb, 16},
                     {(void**)&c->pt_acc, 16}, {(void**)&c->pt_list, 4}}, &c->pt_cap, n, GrowSync::STREAM, s)) return -1;
@@ -767,8 +949,8 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
                     {(void**)&c->pt_live[1], 4}, {(void**)&c->pt_rays, 24}, {(void**)&c->pt_hits, sizeof(HitRec)}}, &c->pt_path_cap, path_cap, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_srays, 24}, {(void**)&c->pt_stmax, 4}, {(void**)&c->pt_shits, sizeof(HitRec)}}, &c->pt_shadow_cap, shadow_cap, GrowSync::STREAM, s)) return -1;
   if (r.motion && !grow_device({{(void**)&c->mo_pos, 16}, {(void**)&c->mo_nrm, 16}}, &c->mo_cap, n, GrowSync::STREAM, s)) return -1;
-  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
-  const dim3 block(256), grid((n32 + 255u) / 256u), pgrid((n32 + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS)), rgrid((cap + 255u) / 256u);
+  const uint32_t n32 = (uint32_t)n;
+  const dim3 block(256), pgrid((n32 + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS));
   if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
   if (r.motion) {   // (a camera frame: check_request)
     hipLaunchKernelGGL((rt_path_prepare_kernel<true, true>), pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
@@ -779,6 +961,33 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   }
   if (hipGetLastError() != hipSuccess) return -1;
   c->ctl_dirty = false;
+  return 0;
+}
+
+static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
+
+// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
+// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
+// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
+// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
+// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
+// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
+// A denoised frame with iterations or a history ends in rt_denoise.hip instead (render_denoise_tail: demodulate, temporal step, initial
+// variance, a-trous passes -- that unit owns the order); one without either gets its guide outputs there and ends here as every path frame.
+int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  if (r.sample_counts) return render_path_counts_tail(a, c, r, p, utab, vtab);   // (a count per pixel: the tail below this one)
+  const SceneDev& sc = a->dev;
+  const vxrt_path_params_t& pp = *r.path;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  hipStream_t s = (hipStream_t)r.stream;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull) return -1;
+  const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
+  const uint64_t path_cap = pp.bounces ? n * ns : 0;
+  if (path_cap > 0x7fffffffull) return -1;
+  if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
+  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
+  const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u);
   for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
     const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
     hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
@@ -807,6 +1016,80 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   if (r.denoise && r.aov && render_denoise_aov(c, r, n32) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
   hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
                      pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Tail of a path frame with a sample count per pixel (r.sample_counts; path->spp is the cap).  The prepare launch of every path frame;
+// then the clamped counts and their scan in window order (three launches: block sums, one workgroup over the block sums, per-pixel
+// offsets); then batches of cap = clamp(VXRT_PATH_BATCH, 1, pixels * spp) consecutive paths, each the depth loop of render_path_tail
+// with the two kernels that read a slot's pixel and sample from the slot; after the last batch the accumulators are divided by their
+// pixel's count and the frame ends as every path frame, with spp = 1.  The number of paths stays on the device, so the host issues
+// ceil(pixels * spp / cap) batches whatever the counts: a batch past the end starts with zero live paths and its launches fall through.
+// Storage per path is bounded by cap.  No host synchronisation unless a buffer grows.
+static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  const SceneDev& sc = a->dev;
+  const vxrt_path_params_t& pp = *r.path;
+  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
+  hipStream_t s = (hipStream_t)r.stream;
+  const uint64_t n = (uint64_t)width * (y1 - y0);
+  if (n > 0x7fffffffull) return -1;
+  const uint64_t all = n * pp.spp;   // (the most paths the counts can ask for)
+  const uint64_t batch = std::min<uint64_t>(std::max<uint64_t>(1, secondary_knobs().path_batch), all);
+  if (batch > 0x7fffffffull) return -1;
+  const uint64_t path_cap = pp.bounces ? batch : 0;
+  const uint64_t n_blocks = (n + PT_SCAN_BLOCK - 1u) / PT_SCAN_BLOCK;
+  if (!c->pt_ctot && hipMalloc((void**)&c->pt_ctot, 8) != hipSuccess) return -1;
+  if (!grow_device({{(void**)&c->pt_cnt, 4}, {(void**)&c->pt_off, 8}}, &c->pt_cnt_cap, n, GrowSync::STREAM, s)) return -1;
+  if (!grow_device({{(void**)&c->pt_bsum, 4}, {(void**)&c->pt_boff, 8}}, &c->pt_blk_cap, n_blocks, GrowSync::STREAM, s)) return -1;
+  if (!grow_device({{(void**)&c->pt_spix, 4}, {(void**)&c->pt_ssmp, 4}}, &c->pt_slot_cap, path_cap, GrowSync::STREAM, s)) return -1;
+  if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
+  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
+  const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u), sgrid((uint32_t)n_blocks);
+  hipLaunchKernelGGL(rt_path_counts_kernel, sgrid, block, 0, s, n32, width, y0, pp.spp, (const float4*)c->pt_geo, r.sample_counts, c->pt_cnt, c->pt_bsum);
+  hipLaunchKernelGGL(rt_path_scan_kernel, dim3(1), dim3(PT_SCAN_PASS), 0, s, (uint32_t)n_blocks, (const uint32_t*)c->pt_bsum, c->pt_boff, c->pt_ctot);
+  hipLaunchKernelGGL(rt_path_offsets_kernel, sgrid, block, 0, s, n32, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_boff, c->pt_off);
+  if (hipGetLastError() != hipSuccess) return -1;
+  const uint64_t n_batches = pp.bounces ? (all + batch - 1) / batch : 0;
+  for (uint64_t b = 0; b < n_batches; ++b) {
+    const unsigned long long g0 = b * batch;   // the batch's first path
+    hipLaunchKernelGGL(rt_path_start_counts_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
+                       (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
+                       c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0], c->pt_spix, c->pt_ssmp);
+    for (uint32_t d = 0; d < pp.bounces; ++d) {
+      uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
+      uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
+      const uint32_t* live = c->pt_live[d & 1u];
+      const bool more = d + 1u < pp.bounces;
+      hipLaunchKernelGGL(rt_path_bounce_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp,
+                         (const uint32_t*)c->pt_cnt, live, (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
+                         c->pt_rays, r.counters);
+      if (trace_on_ctx(a, c, c->pt_rays, cap, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
+      if (pp.shadow) {
+        hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                           c->pt_srays, c->pt_stmax, r.counters);
+        if (trace_on_ctx(a, c, c->pt_srays, cap, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+      }
+      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                         pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T,
+                         more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr, n_next);
+    }
+    hipLaunchKernelGGL(rt_path_accumulate_counts_kernel, grid, block, 0, s, n32, cap, g0, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_off,
+                       (const float4*)c->pt_L, c->pt_acc);
+  }
+  hipLaunchKernelGGL(rt_path_divide_counts_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_cnt, (const float4*)c->pt_lit, pp.bounces == 0 ? 1u : 0u, c->pt_acc);
+  if (hipGetLastError() != hipSuccess) return -1;
+  // (the accumulators hold the colours: what ends the frame divides by spp = 1 and takes no flat sum; dn_frame passes the same)
+  if (r.denoise && (r.denoise->iterations || r.temporal)) return render_denoise_tail(c, r, n32);
+  if (r.denoise && r.aov && render_denoise_aov(c, r, n32) != 0) return -1;
+  hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
+                     1u, 0u, r.dst, r.colors);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// vxrt_sample_counts behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
+int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
+                         unsigned long long* total, hipStream_t s) {
+  hipLaunchKernelGGL(rt_sample_counts_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, variance, prev_counts, prm->gain, prm->min_spp, prm->max_spp, counts, total);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

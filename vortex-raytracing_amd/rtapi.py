@@ -670,8 +670,16 @@ class VarianceParams(C.Structure):   # vxrt_variance_params_t
     _fields_ = [("epsilon", C.c_float), ("min_len", C.c_uint32), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+ADAPTIVE_SCAN_BLOCK = 1024                        # PT_SCAN_BLOCK (rt_secondary.hip): pixels per block of the counts' scan
+ADAPTIVE_SCAN_PASS = 1024 * ADAPTIVE_SCAN_BLOCK   # PT_SCAN_PASS blocks: pixels one pass of the single-workgroup scan covers
+
+
+class SampleCountParams(C.Structure):   # vxrt_sample_count_params_t
+    _fields_ = [("gain", C.c_float), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _declare_path_family(L):
-    """The prototypes of the path, denoise, temporal, motion and variance families; _lib() calls this once with its own."""
+    """The prototypes of the path, denoise, temporal, motion, variance and adaptive families; _lib() calls this once with its own."""
     u32, vp, i32 = C.c_uint32, C.c_void_p, C.c_int
     frame = [vp, C.POINTER(Camera), u32, u32, u32, u32, C.POINTER(ShadeParams), C.POINTER(PathParams)]   # accel, cam, the window, params, path
     dn, tp, vr = C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams)
@@ -698,6 +706,9 @@ def _declare_path_family(L):
         "vxrt_denoise_variance_scratch_bytes": (C.c_uint64, [u32, u32]),
         "vxrt_denoise_variance": (i32, [u32, u32, vp, vp, vp, vp, dn, vr, vp, vp, vp, C.c_uint64, vp]),
         "vxrt_render_path_variance": (i32, frame + [dn, tp, vr, vp, i32, vp, vp, C.POINTER(PathAov), vp, vp, vp, vp]),
+        "vxrt_render_path_adaptive": (i32, frame + [vp, vp, vp, vp, vp]),
+        "vxrt_render_path_variance_adaptive": (i32, frame + [vp, dn, tp, vr, vp, i32, vp, vp, C.POINTER(PathAov), vp, vp, vp, vp]),
+        "vxrt_sample_counts": (i32, [C.c_uint64, vp, vp, C.POINTER(SampleCountParams), vp, vp, vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
@@ -741,3 +752,29 @@ def render_path_variance(accel, cam, width, height, y0, y1, params, spp, bounces
                                                     C.byref(temporal), C.byref(variance), _history(history), int(motion), dst_ptr, colors_ptr,
                                                     None if aov is None else C.byref(aov), prev_position_ptr, variance_ptr, rays_ptr, stream),
           "vxrt_render_path_variance")
+
+
+# ---- adaptive sampling: path frames with a sample count per pixel, counts from a variance (the header's "Adaptive sampling") ----
+def render_path_adaptive(accel, cam, width, height, y0, y1, params, spp, bounces, counts_ptr, dst_ptr, seed=0, shadow=0, colors_ptr=None, rays_ptr=None,
+                         stream=None):
+    """vxrt_render_path_adaptive: render_path whose pixel p takes min(max(counts[p], 1), spp) samples; `counts_ptr`: device, one uint32 per
+    pixel of the frame, addressed like dst.  `spp` is the cap."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_lib().vxrt_render_path_adaptive(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+                                                    counts_ptr, dst_ptr, colors_ptr, rays_ptr, stream), "vxrt_render_path_adaptive")
+
+
+def render_path_variance_adaptive(accel, cam, width, height, y0, y1, params, spp, bounces, counts_ptr, denoise, temporal, variance, history, dst_ptr, motion=0,
+                                  seed=0, shadow=0, colors_ptr=None, aov=None, prev_position_ptr=None, variance_ptr=None, rays_ptr=None, stream=None):
+    """vxrt_render_path_variance_adaptive: render_path_variance whose path frame is render_path_adaptive's (`counts_ptr`, `spp` the cap)."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_lib().vxrt_render_path_variance_adaptive(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), counts_ptr,
+                                                             C.byref(denoise), C.byref(temporal), C.byref(variance), _history(history), int(motion), dst_ptr,
+                                                             colors_ptr, None if aov is None else C.byref(aov), prev_position_ptr, variance_ptr, rays_ptr,
+                                                             stream), "vxrt_render_path_variance_adaptive")
+
+
+def sample_counts(n, variance_ptr, prm, counts_ptr, prev_counts_ptr=None, total_ptr=None, stream=None):
+    """vxrt_sample_counts: counts[i] = clamp(ceil(variance[i] * m * gain), min_spp, max_spp) for n entries, m = the clamped prev_counts[i]
+    (or 1); `prm`: a SampleCountParams; `total_ptr` (optional, device uint64) is incremented by the sum of the counts written."""
+    check(_lib().vxrt_sample_counts(int(n), variance_ptr, prev_counts_ptr, C.byref(prm), counts_ptr, total_ptr, stream), "vxrt_sample_counts")
