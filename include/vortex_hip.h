@@ -211,7 +211,8 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* accel);
  * reference's 32 levels, 96 entries + the LDS part); 2 -> 1 if the TLAS root is a single identity instance; 3 -> 1 if the scene
  * takes the ldexp decode / generic slab form; 4 -> 1 while a non-zero alpha table is set (vxrt_accel_set_alpha_test); 5 -> 1 if the
  * timed plain / shadow frames take the identity-root kernels (2 holds, 1 holds, 3 and 4 do not); 6 -> the VXRT_REFIT_* mask of the
- * motion snapshot the accel holds (vxrt_accel_motion_snapshot), 0 for none. */
+ * motion snapshot the accel holds (vxrt_accel_motion_snapshot), 0 for none; 7 -> the number of emitters of a valid emitter table
+ * (vxrt_accel_set_emitters), 0 for none or a stale one. */
 int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
 
 /* Refit: new boxes for a scene whose instances or vertices moved, in place, without a rebuild (extension; the reference has no refit,
@@ -869,6 +870,80 @@ int vxrt_render_path_variance_adaptive(vxrt_accel_t* accel, const vxrt_camera_t*
 int vxrt_sample_counts(uint64_t n, const float* variance /* device */, const uint32_t* prev_counts /* device, optional */,
                        const vxrt_sample_count_params_t* prm, uint32_t* counts /* device */,
                        unsigned long long* total /* device, optional: incremented */, void* stream);
+
+/* Emissive geometry: area lights in path frames (extension; absent from the reference, whose material_info_t::emissive nothing reads).
+ * Two forms of one estimator: emission found by the bounce rays (nee = 0, brute force) and emitter sampling from a device-side table
+ * (nee = 1, next-event estimation).  Every entry point that existed before ignores `emissive`, as it always has.  tests/emissive_ref.py
+ * restates all of it.  Every symbol below is one fp32 operation in the order written, without contraction: IEEE add / mul / div / sqrt
+ * only, pi = 3.14159265f.
+ *
+ * THE EMITTER TABLE.  An emitter is a pair (blasIdx, triIdx): triangle triIdx of the scene's tri buffer as instance record blasIdx
+ * places it, of a material with a positive emissive component (r > 0 || g > 0 || b > 0).  The CALLER lists the pairs: the reference
+ * formats store an instance's triangle range nowhere, so the accel cannot derive them, and that the list is complete -- every emissive
+ * triangle of every instance, each once -- is the caller's contract: a triangle that is left out still emits for nee = 0 and is dark
+ * for nee = 1.  pairs: HOST, n entries.  For entry e, on the device:
+ *   V_k = ((m[0] * x + m[1] * y) + m[2] * z) + m[3] per row m of the record's `transform`, for the triangle's vertices k = 0, 1, 2 (the
+ *         refit's TransformPosition);   V0 = V_0, E1 = V_1 - V_0, E2 = V_2 - V_0;   Le = the material's emissive
+ *   c = cross(E1, E2) = (E1.y * E2.z - E1.z * E2.y, E1.z * E2.x - E1.x * E2.z, E1.x * E2.y - E1.y * E2.x)
+ *   area = 0.5f * sqrtf((c.x * c.x + c.y * c.y) + c.z * c.z);   w_e = area * max(max(Le.r, Le.g), Le.b)
+ *   wmax = the maximum of w over the table (exact in any order);   q_e = max(1, (uint32_t)((w_e / wmax) * 65535.0f))
+ *   cum_e = q_0 + .. + q_e in uint32 (at most 65536 * 65535: no wrap), Q = cum_{n-1}
+ * so the table is the same bits whatever order the scan takes: integers are what the quantisation is for.  Emitter e is chosen with
+ * probability q_e / Q.  Ordered after every call already issued on the accel, on any stream, and synchronous with respect to `stream`,
+ * like vxrt_accel_set_alpha_test.  pairs == NULL or n == 0 drops the table.  Returns -1 with the previous table kept for a null or
+ * stale accel, a scene without triEx / mat, n > VXRT_MAX_EMITTERS, blasIdx >= n_blas or triIdx >= n_tris, a pair whose material is not
+ * emissive, a vertex or transform that is not finite, and an area or weight that is zero or not finite.
+ * The table holds WORLD-SPACE data: a vxrt_accel_refit (what != 0) or vxrt_accel_set_transforms that succeeds makes it STALE, and it
+ * stays stale until it is set again.  vxrt_accel_info(accel, 7) is the number of emitters of a valid table, 0 for none or a stale one;
+ * vxrt_accel_bytes counts the 56 bytes per entry the accel holds.  vxrt_accel_read_emitters (test / diagnostic; synchronous) copies a
+ * valid table to HOST memory: tri12[12 e ..] = V0, E1, E2, Le; q[e]; cum[e] (any of the three may be NULL); -1 without a valid table. */
+typedef struct { uint32_t blasIdx, triIdx; } vxrt_emitter_t;
+#define VXRT_MAX_EMITTERS 65536u
+int vxrt_accel_set_emitters(vxrt_accel_t* accel, const vxrt_emitter_t* pairs /* HOST, or NULL */, uint32_t n, void* stream);
+int vxrt_accel_read_emitters(vxrt_accel_t* accel, float* tri12 /* HOST, n x 12 */, uint32_t* q /* HOST */, uint32_t* cum /* HOST */, void* stream);
+
+/* THE EMITTER RAY of a surface point I with the shading normal N' that faces the viewer, from hash output `seed` (0 becomes 1) and the
+ * table (n entries, Q), xorshift = the three shifts of common.h:137-147, random_float = xorshift then (float)state * 2.3283064365387e-10f:
+ *   r0 = xorshift(state) as uint32;  a = random_float;  b = random_float
+ *   t = ((uint64_t)r0 * Q) >> 32;  e = the smallest index with cum_e > t (a binary search over [0, n-1] of at most 17 steps)
+ *   if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }      P = (V0 + a * E1) + b * E2
+ *   o = I + N' * 0.001f (the bounce ray's origin);  v = P - o;  d2 = (v.x * v.x + v.y * v.y) + v.z * v.z;  d = sqrtf(d2);  w = v / d
+ *   tmax = d - 0.001f, any-hit
+ *   cosx = max(0, (N'.x * w.x + N'.y * w.y) + N'.z * w.z)      (std::max: a NaN gives 0)
+ *   an = 0.5f * |(c.x * w.x + c.y * w.y) + c.z * w.z| with c = cross(E1, E2) as above: the emitter's projected area, both sides emit
+ *   G = (((Le * scale) * cosx) * an) / ((3.14159265f * d2) * ((float)q_e / (float)Q)) per channel
+ * SKIPPED, i.e. not traced, not counted and without a contribution, if cosx == 0, d2 == 0 or a channel of G is not finite.
+ * vxrt_emitter_rays runs this step alone on caller-owned DEVICE buffers: points = n x 6 floats (I, N'), seeds = n hash outputs;
+ * rays (n x 6: o, w), tmax (n), weight3 (n x 3: G), emitter (n: e) -- a skipped entry gets the ray (0,0,0; 1,1,1), tmax = -1 and
+ * G = 0, its e is still the one chosen.  One launch, asynchronous on `stream`.  Returns -1 before the launch for a null or stale accel,
+ * no valid table, a null buffer, scale negative or not finite, n >= 2^31; 0 for n = 0.
+ *
+ * THE FRAME.  vxrt_render_path_emissive is vxrt_render_path -- the point light, `shadow`, the batches of VXRT_PATH_BATCH, every count on
+ * the device, no host synchronisation unless a buffer grows -- with, for Emi(h) = emissive(material of h) * scale where that material
+ * has a positive emissive component (elsewhere NOTHING is added, not a zero: -0 + 0 would change a sign bit):
+ *   both modes:  Lc starts as Lit(r_0, h_0) + Emi(h_0), formed once per pixel in the prepare launch (bounces = 0: the flat sum of that).
+ *   nee = 0, at bounce k:  hit h': Lc = Lc + thr * Lit(r', h'), then Lc = Lc + thr * Emi(h'), then thr = thr * Alb(h').
+ *   nee = 1, at bounce k, before the miss / hit arm of vxrt_render_path (no emission is added at bounce hits):  the emitter ray of
+ *     (I(r, h), N'(r, h)) with seed = WangHash((x + y * W) * spp + s + 1 + u * 0x9E3779B9), u = ((seed + k) mod 2^32) ^ 0x80000000 -- the
+ *     bounce ray's hash input with a user seed no bounce of the frame takes -- is traced unless skipped; unblocked: Lc = Lc + thr * G,
+ *     thr as the vertex has it (Alb(h) included).  So every vertex a bounce ray leaves sends one emitter ray, the last vertex none, and
+ *     E[nee = 1] = E[nee = 0] for the same `bounces`.
+ *   rays_traced also counts the emitter rays that were traced.
+ * Returns -1 before anything is launched (dst untouched) for whatever vxrt_render_path refuses (a non-zero alpha table included), a
+ * null `em`, nee > 1, a non-zero reserved word, scale negative or not finite, and nee = 1 without a valid table (none set, or stale).
+ * There is no denoised, temporal, variance or adaptive form, and no multiple importance sampling. */
+typedef struct vxrt_emissive_params {
+  uint32_t nee;          /* 0: emission at bounce hits; 1: emitter sampling from the accel's table */
+  float scale;           /* multiplies every material's emissive; >= 0 and finite */
+  uint32_t reserved[2];  /* 0 */
+} vxrt_emissive_params_t;
+int vxrt_render_path_emissive(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
+                              uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_params_t* em,
+                              uint32_t* dst, float* colors /* optional */, unsigned long long* rays_traced /* optional */, void* stream);
+int vxrt_emitter_rays(vxrt_accel_t* accel, uint64_t n, const float* points /* device, n x 6: I, N' */, const uint32_t* seeds /* device */,
+                      float scale, float* rays /* device, n x 6 */, float* tmax /* device */, float* weight3 /* device, n x 3 */,
+                      uint32_t* emitter /* device */, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

@@ -1,5 +1,6 @@
 // Acceleration layout of a scene: its build from the reference-format buffers (vxrt_accel_build) and its refit in place
-// (vxrt_accel_refit / vxrt_accel_set_transforms).  No ray is traced here: the kernels that read the layout are in rt_kernels.hip.
+// (vxrt_accel_refit / vxrt_accel_set_transforms), and the tables an accel derives from the scene on request (alpha test, motion snapshot,
+// emitters).  No ray is traced here: the kernels that read the layout are in rt_kernels.hip.
 // Build: as rt_kernels.hip (one hipcc call for the whole library, no relocatable device code).
 #include <algorithm>
 #include <cmath>
@@ -460,6 +461,7 @@ static void accel_free(vxrt_accel* a) {
   (void)hipFree(a->uvtab); (void)hipFree(a->apriori);
   (void)hipFree(a->alpha_mat); (void)hipFree(a->alpha_tri);
   (void)hipFree(a->motion_blas); (void)hipFree(a->motion_tri);
+  (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum);
   for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) (void)hipFree(a->batch_order[k]);
   for (FrameCtx& c : a->ctx) {
     (void)hipFree(c.hitbuf); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
@@ -469,7 +471,8 @@ static void accel_free(vxrt_accel* a) {
     for (void* q : {(void*)c.pt_geo, (void*)c.pt_nrm, (void*)c.pt_dir, (void*)c.pt_lit, (void*)c.pt_alb, (void*)c.pt_acc, (void*)c.pt_list, (void*)c.pt_hdr,
                     (void*)c.pt_I, (void*)c.pt_N, (void*)c.pt_D, (void*)c.pt_L, (void*)c.pt_T, (void*)c.pt_live[0], (void*)c.pt_live[1], (void*)c.pt_rays,
                     (void*)c.pt_hits, (void*)c.pt_srays, (void*)c.pt_stmax, (void*)c.pt_shits, (void*)c.dn_sig[0], (void*)c.dn_sig[1], (void*)c.mo_pos, (void*)c.mo_nrm,
-                    (void*)c.pt_cnt, (void*)c.pt_off, (void*)c.pt_bsum, (void*)c.pt_boff, (void*)c.pt_ctot, (void*)c.pt_spix, (void*)c.pt_ssmp}) (void)hipFree(q);
+                    (void*)c.pt_cnt, (void*)c.pt_off, (void*)c.pt_bsum, (void*)c.pt_boff, (void*)c.pt_ctot, (void*)c.pt_spix, (void*)c.pt_ssmp,
+                    (void*)c.pt_erays, (void*)c.pt_etmax, (void*)c.pt_ehits, (void*)c.pt_eG}) (void)hipFree(q);
     for (FrameCtx::Level& l : c.lv) {
       (void)hipFree(l.rays); (void)hipFree(l.hits); (void)hipFree(l.parent); (void)hipFree(l.term); (void)hipFree(l.col);
       (void)hipFree(l.srays); (void)hipFree(l.stmax); (void)hipFree(l.shits);
@@ -481,6 +484,116 @@ static void accel_free(vxrt_accel* a) {
     if (c.ev_done) (void)hipEventDestroy(c.ev_done);
   }
   delete a;
+}
+
+// ---------------------------------------------------------------------------------------------
+// emitter table (vxrt_accel_set_emitters; the definition is the header's "Emissive geometry").  Four launches, one wavefront per
+// workgroup, no LDS and no workgroup that waits for another: per entry the world-space triangle, its weight and the table's maximum;
+// then the quantised weights and their sums per block of EM_BLOCK entries; one wavefront that scans the block sums in passes of EM_PASS
+// with a running carry (rt_path_scan_kernel's pattern); the inclusive sums.  Integer sums: the same bits in any order.
+// ---------------------------------------------------------------------------------------------
+#define EM_BLOCK 64u   // entries per block of the scan: one wavefront
+#define EM_PASS 64u    // block sums per pass of accel_emitter_scan_kernel: its one wavefront
+#define EM_ERR_INDEX 1u      // blasIdx >= n_blas, triIdx >= n_tris
+#define EM_ERR_DARK 2u       // the pair's material has no positive emissive component
+#define EM_ERR_NONFINITE 4u  // a vertex or a transform is not finite
+#define EM_ERR_AREA 8u       // the area or the weight is zero or not finite
+// res: [0] EM_ERR_*, [1] the bits of wmax (weights are positive floats: their bits order as they do)
+
+// tri[12 e ..] = V0, E1, E2, Le; w[e] = area * max(Le); an entry that is refused writes zeros (nothing of the table is used then)
+__global__ __launch_bounds__(64) void accel_emitter_tris_kernel(const vxrt_emitter_t* __restrict__ pairs, uint32_t n, const uint32_t* __restrict__ blas,
+    uint32_t n_blas, const float* __restrict__ tri, uint32_t n_tris, const rt_triex_t* __restrict__ triEx, const rt_material_t* __restrict__ mat, uint32_t n_mats,
+    float* __restrict__ out, float* __restrict__ w, uint32_t* __restrict__ res) {
+  const uint32_t e = blockIdx.x * EM_BLOCK + threadIdx.x;
+  uint32_t err = 0u;
+  float we = 0.0f;
+  if (e < n) {
+    const vxrt_emitter_t p = pairs[e];
+    float o12[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o12[k] = 0.0f;
+    if (p.blasIdx >= n_blas || p.triIdx >= n_tris || triEx[p.triIdx].texId >= n_mats) err = EM_ERR_INDEX;
+    else {
+      const rt_material_t* mt = mat + triEx[p.triIdx].texId;
+      const float lr = mt->emissive[0], lg = mt->emissive[1], lb = mt->emissive[2];
+      if (!(lr > 0.0f || lg > 0.0f || lb > 0.0f)) err = EM_ERR_DARK;
+      else {
+        const float* m = (const float*)(blas + (size_t)p.blasIdx * (RT_BLAS_STRIDE / 4) + 17);   // blas_node_t::transform @68
+        const float* v = tri + (size_t)p.triIdx * 9;
+        bool fin = true;
+        for (int k = 0; k < 12; ++k) fin = fin && isfinite(m[k]);
+        float V[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+          for (int a = 0; a < 3; ++a) { V[k][a] = refit_row(m + 4 * a, v[3 * k], v[3 * k + 1], v[3 * k + 2]); fin = fin && isfinite(V[k][a]); }
+        if (!fin) err = EM_ERR_NONFINITE;
+        else {
+          const float e1x = __fsub_rn(V[1][0], V[0][0]), e1y = __fsub_rn(V[1][1], V[0][1]), e1z = __fsub_rn(V[1][2], V[0][2]);
+          const float e2x = __fsub_rn(V[2][0], V[0][0]), e2y = __fsub_rn(V[2][1], V[0][1]), e2z = __fsub_rn(V[2][2], V[0][2]);
+          const float cx = __fsub_rn(__fmul_rn(e1y, e2z), __fmul_rn(e1z, e2y));
+          const float cy = __fsub_rn(__fmul_rn(e1z, e2x), __fmul_rn(e1x, e2z));
+          const float cz = __fsub_rn(__fmul_rn(e1x, e2y), __fmul_rn(e1y, e2x));
+          const float area = __fmul_rn(0.5f, __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(cx, cx), __fmul_rn(cy, cy)), __fmul_rn(cz, cz))));
+          const float lmax = fmaxf(fmaxf(lr, lg), lb);
+          we = __fmul_rn(area, lmax);
+          if (!(area > 0.0f) || !isfinite(area) || !(we > 0.0f) || !isfinite(we)) { err = EM_ERR_AREA; we = 0.0f; }
+          else {
+            o12[0] = V[0][0]; o12[1] = V[0][1]; o12[2] = V[0][2]; o12[3] = e1x; o12[4] = e1y; o12[5] = e1z;
+            o12[6] = e2x; o12[7] = e2y; o12[8] = e2z; o12[9] = lr; o12[10] = lg; o12[11] = lb;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) out[(size_t)e * 12 + k] = o12[k];
+    w[e] = we;
+  }
+  uint32_t wb = __float_as_uint(we);   // (we >= 0)
+  for (int o = 32; o > 0; o >>= 1) { wb = max(wb, (uint32_t)__shfl_down(wb, o)); err |= (uint32_t)__shfl_down(err, o); }
+  if (threadIdx.x == 0) {
+    if (err) atomicOr(res, err);
+    if (wb) atomicMax(res + 1, wb);
+  }
+}
+
+// q[e] = max(1, (uint32_t)((w[e] / wmax) * 65535.0f)); bsum[block] = the sum of the block's q
+__global__ __launch_bounds__(64) void accel_emitter_q_kernel(uint32_t n, const float* __restrict__ w, const uint32_t* __restrict__ res, uint32_t* __restrict__ q,
+                                                             uint32_t* __restrict__ bsum) {
+  const uint32_t e = blockIdx.x * EM_BLOCK + threadIdx.x;
+  const float wmax = __uint_as_float(res[1]);
+  uint32_t v = 0u;
+  if (e < n) {
+    const float x = __fmul_rn(__fdiv_rn(w[e], wmax), 65535.0f);   // (in [0, 65535] for a table without errors; anything else is discarded by the host)
+    v = x >= 1.0f && x <= 65535.0f ? (uint32_t)x : 1u;
+    q[e] = v;
+  }
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = v;
+}
+
+// boff[i] = the sum of bsum[0 .. i).  ONE wavefront: pass k scans block sums [k * EM_PASS, (k + 1) * EM_PASS) and every lane carries the
+// running total into the next pass; the number of passes is known at entry.
+__global__ __launch_bounds__(64) void accel_emitter_scan_kernel(uint32_t nb, const uint32_t* __restrict__ bsum, uint32_t* __restrict__ boff) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t passes = (nb + EM_PASS - 1u) / EM_PASS;
+  uint32_t carry = 0u;
+  for (uint32_t k = 0; k < passes; ++k) {
+    const uint32_t i = k * EM_PASS + lane;
+    const uint32_t v = i < nb ? bsum[i] : 0u;
+    uint32_t inc = v;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
+    if (i < nb) boff[i] = carry + (inc - v);
+    carry += (uint32_t)__shfl(inc, 63);
+  }
+}
+
+// cum[e] = boff[block of e] + the sum of q over the block's entries up to and including e
+__global__ __launch_bounds__(64) void accel_emitter_cum_kernel(uint32_t n, const uint32_t* __restrict__ q, const uint32_t* __restrict__ boff, uint32_t* __restrict__ cum) {
+  const uint32_t lane = threadIdx.x, e = blockIdx.x * EM_BLOCK + lane;
+  uint32_t inc = e < n ? q[e] : 0u;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
+  if (e < n) cum[e] = boff[blockIdx.x] + inc;
 }
 
 extern "C" {
@@ -618,7 +731,8 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* a) {
   return (uint64_t)a->ref.n_tlas_nodes * CNODE_VEC4 * 16 + (uint64_t)a->ref.n_bvh_nodes * CNODE_VEC4 * 16 +
          (uint64_t)a->ref.n_tris * WTRI_FLOATS * 4 + (uint64_t)a->ref.n_blas * 4 +
          ((a->motion_what & VXRT_REFIT_INSTANCES) ? (uint64_t)a->ref.n_blas * RT_BLAS_STRIDE : 0) +   // (the motion snapshot)
-         ((a->motion_what & VXRT_REFIT_GEOMETRY) ? (uint64_t)a->ref.n_tris * RT_TRI_BYTES : 0);
+         ((a->motion_what & VXRT_REFIT_GEOMETRY) ? (uint64_t)a->ref.n_tris * RT_TRI_BYTES : 0) +
+         (uint64_t)a->em_n * 56u;   // (the emitter table: 12 floats, q and cum per entry)
 }
 
 int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
@@ -631,6 +745,7 @@ int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
   case 4: *value = a->alpha_on ? 1u : 0u; return 0; // a non-zero alpha table is set (vxrt_accel_set_alpha_test)
   case 5: *value = ident_root_form(a) ? 1u : 0u; return 0; // timed plain / shadow frames take the identity-root kernels (no TLAS level in the loop)
   case 6: *value = a->motion_what; return 0;       // the VXRT_REFIT_* mask of the motion snapshot held (vxrt_accel_motion_snapshot)
+  case 7: *value = emitters_valid(a) ? a->em_n : 0u; return 0; // emitters of a valid emitter table (vxrt_accel_set_emitters)
   }
   return -1;
 }
@@ -719,6 +834,70 @@ int vxrt_accel_motion_snapshot(vxrt_accel_t* a, uint32_t what, void* stream) {
   ok = hipStreamSynchronize(st) == hipSuccess && ok;
   a->motion_what = ok ? what : 0u;
   return ok ? 0 : -1;
+}
+
+// The emitter table (see the header, "Emissive geometry").  The refusals that need no device work come first; then, behind everything
+// already issued on the accel, a NEW table is built next to the one held -- what the device refuses is only known at the end -- and takes
+// its place when every entry passed: the previous table is kept by every failure, and freed behind the synchronisation that ends the call.
+int vxrt_accel_set_emitters(vxrt_accel_t* a, const vxrt_emitter_t* pairs, uint32_t n, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!a || a->stale || n > VXRT_MAX_EMITTERS) return -1;
+  const vxrt_scene_t& s = a->ref;
+  const bool drop = !pairs || n == 0u;
+  if (!drop && (!s.triEx || !s.mat || s.n_mats == 0u)) return -1;
+  // ordered after every call already issued on this accel, on any stream (frames in flight read the table this call replaces)
+  for (uint32_t k = 0; k < MAX_FRAMES_IN_FLIGHT; ++k) {
+    FrameCtx& c = a->ctx[k];
+    if (!c.busy || c.last_stream == st) continue;
+    if (c.done_recorded) { if (hipStreamWaitEvent(st, c.ev_done, 0) != hipSuccess) return -1; }
+    else if (hipDeviceSynchronize() != hipSuccess) return -1;
+  }
+  if (drop) {
+    if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum);
+    a->em_tri = nullptr; a->em_q = nullptr; a->em_cum = nullptr; a->em_n = 0u; a->em_Q = 0u; a->em_valid = false;
+    return 0;
+  }
+  const uint32_t nb = (n + EM_BLOCK - 1u) / EM_BLOCK;
+  float* tri = nullptr; uint32_t* q = nullptr; uint32_t* cum = nullptr;
+  vxrt_emitter_t* d_pairs = nullptr; float* w = nullptr; uint32_t* blk = nullptr; uint32_t* res = nullptr;   // scratch: blk = bsum[nb], boff[nb]
+  uint32_t hres[2] = {0u, 0u}, Q = 0u;
+  bool ok = hipMalloc((void**)&tri, (size_t)n * 48) == hipSuccess && hipMalloc((void**)&q, (size_t)n * 4) == hipSuccess &&
+            hipMalloc((void**)&cum, (size_t)n * 4) == hipSuccess && hipMalloc((void**)&d_pairs, (size_t)n * sizeof(vxrt_emitter_t)) == hipSuccess &&
+            hipMalloc((void**)&w, (size_t)n * 4) == hipSuccess && hipMalloc((void**)&blk, (size_t)nb * 8) == hipSuccess &&
+            hipMalloc((void**)&res, 8) == hipSuccess;
+  ok = ok && hipMemcpyAsync(d_pairs, pairs, (size_t)n * sizeof(vxrt_emitter_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+       hipMemsetAsync(res, 0, 8, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(accel_emitter_tris_kernel, dim3(nb), dim3(EM_BLOCK), 0, st, (const vxrt_emitter_t*)d_pairs, n, (const uint32_t*)s.blas, s.n_blas,
+                       (const float*)s.tri, s.n_tris, (const rt_triex_t*)s.triEx, (const rt_material_t*)s.mat, s.n_mats, tri, w, res);
+    hipLaunchKernelGGL(accel_emitter_q_kernel, dim3(nb), dim3(EM_BLOCK), 0, st, n, (const float*)w, (const uint32_t*)res, q, blk);
+    hipLaunchKernelGGL(accel_emitter_scan_kernel, dim3(1), dim3(EM_PASS), 0, st, nb, (const uint32_t*)blk, blk + nb);
+    hipLaunchKernelGGL(accel_emitter_cum_kernel, dim3(nb), dim3(EM_BLOCK), 0, st, n, (const uint32_t*)q, (const uint32_t*)(blk + nb), cum);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(hres, res, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(&Q, cum + (n - 1u), 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  }
+  ok = hipStreamSynchronize(st) == hipSuccess && ok;   // (the pairs are the caller's again; frames in flight have finished with the table held)
+  (void)hipFree(d_pairs); (void)hipFree(w); (void)hipFree(blk); (void)hipFree(res);
+  if (!ok || hres[0] != 0u || Q == 0u) {
+    (void)hipFree(tri); (void)hipFree(q); (void)hipFree(cum); (void)hipGetLastError();
+    if (getenv("VXRT_DEBUG")) fprintf(stderr, "[vxrt] set_emitters refused: ok %d, errors %u\n", (int)ok, hres[0]);
+    return -1;
+  }
+  (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum);
+  a->em_tri = tri; a->em_q = q; a->em_cum = cum; a->em_n = n; a->em_Q = Q; a->em_valid = true;
+  return 0;
+}
+
+int vxrt_accel_read_emitters(vxrt_accel_t* a, float* tri12, uint32_t* q, uint32_t* cum, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!a || !emitters_valid(a)) return -1;
+  if (hipStreamSynchronize(st) != hipSuccess) return -1;
+  const size_t n = a->em_n;
+  if (tri12 && hipMemcpy(tri12, a->em_tri, n * 48, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (q && hipMemcpy(q, a->em_q, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (cum && hipMemcpy(cum, a->em_cum, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return 0;
 }
 
 int vxrt_accel_frames_in_flight(vxrt_accel_t* a, uint32_t n) {
@@ -884,6 +1063,7 @@ static int refit_run(vxrt_accel* a, uint32_t what, hipStream_t st, const float* 
     a->dev.n_top = 0; a->dev.tlas_root_top = a->dev.tlas_root; a->dev.blas_root_top = (const uint32_t*)a->blas_root;
   }
   a->stale = false;
+  if (res[6] == 0u) a->em_valid = false;   // (the emitter table holds world-space data: what moved makes it stale until it is set again)
   return res[6] != 0u ? -1 : 0;   // set_transforms: a matrix was refused, the records are unchanged (and the refit of them holds)
 }
 

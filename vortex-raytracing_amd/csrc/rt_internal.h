@@ -115,6 +115,9 @@ struct FrameCtx {
   uint32_t* pt_bsum = nullptr; unsigned long long* pt_boff = nullptr; uint64_t pt_blk_cap = 0;
   unsigned long long* pt_ctot = nullptr;
   uint32_t* pt_spix = nullptr; uint32_t* pt_ssmp = nullptr; uint64_t pt_slot_cap = 0;
+  // path frames with emitter sampling (vxrt_render_path_emissive, nee = 1; allocated on first use).  Per live path of a depth: the emitter
+  // ray, its tmax and hit record, and G (w = 1: the ray is real, 0: skipped)
+  float* pt_erays = nullptr; float* pt_etmax = nullptr; HitRec* pt_ehits = nullptr; float4* pt_eG = nullptr; uint64_t pt_em_cap = 0;
   // denoised path frames (vxrt_render_path_denoised; allocated on first use): the two signal buffers the a-trous iterations ping-pong
   // between, one float4 (E, lum(E)) per pixel of the window; the guides are pt_geo and pt_nrm
   float4* dn_sig[2] = {nullptr, nullptr}; uint64_t dn_cap = 0;
@@ -160,7 +163,17 @@ struct vxrt_accel {
   // motion snapshot (vxrt_accel_motion_snapshot): the instance records and, with VXRT_REFIT_GEOMETRY, the tri_t vertices of the previous frame
   uint32_t* motion_blas = nullptr; float* motion_tri = nullptr;
   uint32_t motion_what = 0;        // the VXRT_REFIT_* mask held; 0: no snapshot
+  // emitter table (vxrt_accel_set_emitters; the definition is in the header, "Emissive geometry"): per entry V0, E1, E2, Le in world space
+  // (12 floats), the quantised weight q and its inclusive prefix sum cum; em_Q = cum[em_n - 1].  em_valid: set, and nothing has moved since
+  float* em_tri = nullptr; uint32_t* em_q = nullptr; uint32_t* em_cum = nullptr;
+  uint32_t em_n = 0, em_Q = 0;
+  bool em_valid = false;
 };
+
+// What the emitter-sampling kernels read of the table (rt_secondary.hip)
+struct EmitterTab { const float* tri; const uint32_t* q; const uint32_t* cum; uint32_t n, Q; };
+static inline EmitterTab emitter_tab(const vxrt_accel* a) { return EmitterTab{a->em_tri, a->em_q, a->em_cum, a->em_n, a->em_Q}; }
+static inline bool emitters_valid(const vxrt_accel* a) { return a->em_valid && a->em_n != 0u && !a->stale; }
 
 // What the previous-position guide reads besides the SceneDev (see the header, "Motion"): the snapshot's instance records, the vertices
 // (the snapshot's, or the scene's current ones) and the two bounds a hit record is checked against
@@ -246,6 +259,7 @@ struct RenderRequest {
   const vxrt_ao_params_t* ao = nullptr;             // ambient-occlusion or diffuse-bounce frame
   const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
   const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
+  const vxrt_emissive_params_t* emissive = nullptr; // ... with emissive geometry (vxrt_render_path_emissive): a plain path frame otherwise
   const uint32_t* sample_counts = nullptr;          // ... with a sample count per pixel (vxrt_render_path_adaptive): device, addressed like dst; path->spp is the cap
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;
@@ -292,6 +306,9 @@ int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, co
 int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
+// rt_secondary.hip: the launch of vxrt_emitter_rays (n >= 1, a valid table; the checks are the entry point's)
+int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                        uint32_t* emitter, hipStream_t s);
 // rt_secondary.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
 int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
                          unsigned long long* total, hipStream_t s);

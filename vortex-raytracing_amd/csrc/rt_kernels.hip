@@ -1858,6 +1858,10 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
                  r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
   // ... with a sample count per pixel: a path frame (a null buffer is the entry point's to refuse: here it means "no counts")
   if (r.sample_counts && !r.path) return -1;
+  // ... with emissive geometry: a plain path frame (no counts, no filter); the parameters, and for emitter sampling a valid table
+  if (r.emissive && (!r.path || r.sample_counts || r.denoise || r.aov || r.temporal || r.history || r.motion || r.variance || r.emissive->nee > 1u ||
+                     r.emissive->reserved[0] != 0u || r.emissive->reserved[1] != 0u || !(r.emissive->scale >= 0.0f) || !std::isfinite(r.emissive->scale) ||
+                     (r.emissive->nee == 1u && !emitters_valid(a)))) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
   // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
@@ -2493,6 +2497,27 @@ int vxrt_render_path_variance_adaptive(vxrt_accel_t* accel, const vxrt_camera_t*
   r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
   r.variance = vp; r.variance_out = variance;
   return render_common(accel, r);
+}
+
+// Path frame with emissive geometry (see the header, "Emissive geometry"): vxrt_render_path whose tail adds emission at bounce hits
+// (nee = 0) or samples the accel's emitter table (nee = 1); the parameters are check_request's to refuse
+int vxrt_render_path_emissive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_params_t* em, uint32_t* dst, float* colors,
+                              unsigned long long* rays_traced, void* stream) {
+  if (!path || !em) return -1;
+  if (cam && !camera_ok(cam)) return -1;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
+  r.emissive = em;
+  return render_common(accel, r);
+}
+
+// The emitter ray alone (see the header, "Emissive geometry"): one launch on caller-owned buffers, no host synchronisation
+int vxrt_emitter_rays(vxrt_accel_t* a, uint64_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                      uint32_t* emitter, void* stream) {
+  if (!a || !emitters_valid(a) || !points || !seeds || !rays || !tmax || !weight3 || !emitter) return -1;
+  if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  return emitter_rays_launch(a, (uint32_t)n, points, seeds, scale, rays, tmax, weight3, emitter, (hipStream_t)stream);
 }
 
 // Sample counts from a variance buffer (see the header, "Adaptive sampling"): elementwise, one launch, no host synchronisation

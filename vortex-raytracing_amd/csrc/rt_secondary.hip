@@ -1,7 +1,7 @@
 // Tails of the frames that trace secondary rays, and their kernels: what render_common (rt_kernels.hip) runs in place of the plain
 // shading pass of a frame with reflective instances (the mirror-bounce wavefront), of an ambient-occlusion frame and of a path frame
-// (whose denoised end is in rt_denoise.hip; with it the previous-position guide of frames with motion, motion_guide, and
-// vxrt_previous_positions), and the binning of secondary rays.  None of it is timed by bench.py, and none of it can
+// (with emissive geometry: the emitter ray and the emissive flavours of its prepare, ray and scatter kernels; its denoised end is in
+// rt_denoise.hip; with it the previous-position guide of frames with motion, motion_guide, and vxrt_previous_positions), and the binning of secondary rays.  None of it is timed by bench.py, and none of it can
 // reach the traversal kernel's unit: the seam is in rt_internal.h -- the ray buffers are traced through trace_on_ctx, buffers grow
 // through grow_device -- and the shading arithmetic is that of the frame kernels, rt_shading.h.  Same build flags (-ffp-contract=off).
 #include <hip/hip_runtime.h>
@@ -338,12 +338,28 @@ __global__ __launch_bounds__(256) void rt_previous_positions_kernel(SceneDev sc,
 struct PrepMotion { MotionSrc src; float4* pos; float4* nrm; float* out; };
 struct PrepNoMotion {};
 
+// Emi(h) of the header's "Emissive geometry": emissive * scale of the material of triangle triIdx, if it has a positive component
+// (false: the material does not emit, and nothing is to be added)
+__device__ __forceinline__ bool emission(const SceneDev& sc, uint32_t triIdx, float scale, float (&e3)[3]) {
+  const rt_material_t* mat = sc.mat + sc.triEx[triIdx].texId;
+  const float r = mat->emissive[0], g = mat->emissive[1], b = mat->emissive[2];
+  if (!(r > 0.0f || g > 0.0f || b > 0.0f)) return false;
+  e3[0] = r * scale; e3[1] = g * scale; e3[2] = b * scale;
+  return true;
+}
+
+// what the emissive flavour of the prepare launch takes besides (EMI: lit[t] = Lit_0 + Emi(h_0))
+struct PrepEmi { float scale; };
+struct PrepNoEmi {};
+
+// The prepare launch of every path frame; its kernels are below.
 // (MOTION: the frame with motion -- the previous-position guide of the pixel's record, computed where the record is in registers)
-template <bool CAM, bool MOTION = false>
-__global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+template <bool CAM, bool MOTION, bool EMI>
+__device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadeParams& p, uint32_t n, uint32_t W, uint32_t y0,
     const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
     float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo) {
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo,
+    std::conditional_t<EMI, PrepEmi, PrepNoEmi> em) {
   if (ctl_reset && blockIdx.x == 0)
     for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
   bool hit_c[PREP_CHUNKS];
@@ -370,6 +386,10 @@ __global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, Shade
         float thr = 1.0f;
         thr *= refl;
         r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+        if constexpr (EMI) {
+          float e3[3];
+          if (emission(sc, h.triIdx, em.scale, e3)) { r = r + e3[0]; g = g + e3[1]; b = b + e3[2]; }
+        }
         geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
         nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
         dir[t] = make_float4(dx, dy, dz, 0.f);
@@ -387,6 +407,23 @@ __global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, Shade
     hit_c[c] = hit; t_c[c] = t;
   }
   wg_append<PREP_CHUNKS>(hit_c, t_c, list, hdr);
+}
+
+template <bool CAM, bool MOTION = false>
+__global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo) {
+  path_prepare<CAM, MOTION, false>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, mo, PrepNoEmi{});
+}
+
+// (the frame with emissive geometry, vxrt_render_path_emissive: Lit_0 + Emi(h_0) per pixel)
+template <bool CAM>
+__global__ __launch_bounds__(256) void rt_path_prepare_emissive_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float scale) {
+  path_prepare<CAM, false, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepEmi{scale});
 }
 
 // start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
@@ -424,6 +461,113 @@ __global__ __launch_bounds__(256) void rt_path_bounce_rays_kernel(uint32_t cap, 
   for (int k = 0; k < 6; ++k) o[k] = r6[k];
 }
 
+// The emitter ray of the header's "Emissive geometry", operation for operation: from hash output `seed`, the surface point I and the
+// facing normal N' (nx, ny, nz).  ray6 = (o, w), tmax, G[3], e = the emitter chosen; false = skipped: the ray nothing can hit, tmax = -1,
+// G = 0.  The cumulative table is read from global memory (a binary search of at most 17 steps; n <= 65,536).
+__device__ __forceinline__ bool emitter_sample(const EmitterTab& tab, float scale, uint32_t seed, float Ix, float Iy, float Iz, float nx, float ny, float nz,
+                                               float (&ray6)[6], float& tmax, float (&G)[3], uint32_t& e_out) {
+  if (seed == 0u) seed = 1u;
+  seed ^= seed << 13; seed ^= seed >> 17; seed ^= seed << 5;
+  const uint32_t r0 = seed;
+  float a = random_float(seed);
+  float b = random_float(seed);
+  const uint32_t t = (uint32_t)(((uint64_t)r0 * tab.Q) >> 32);
+  uint32_t lo = 0u, hi = tab.n - 1u;   // the smallest e with cum[e] > t is in [lo, hi] (cum[n - 1] = Q > t)
+  for (int k = 0; k < 17; ++k) {
+    if (lo >= hi) break;
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (tab.cum[mid] > t) hi = mid; else lo = mid + 1u;
+  }
+  const uint32_t e = lo;
+  e_out = e;
+  const float* T = tab.tri + (size_t)e * 12;
+  const float v0x = T[0], v0y = T[1], v0z = T[2], e1x = T[3], e1y = T[4], e1z = T[5], e2x = T[6], e2y = T[7], e2z = T[8];
+  if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
+  const float Px = (v0x + a * e1x) + b * e2x, Py = (v0y + a * e1y) + b * e2y, Pz = (v0z + a * e1z) + b * e2z;
+  const float ox = Ix + nx * 0.001f, oy = Iy + ny * 0.001f, oz = Iz + nz * 0.001f;
+  const float vx = Px - ox, vy = Py - oy, vz = Pz - oz;
+  const float d2 = (vx * vx + vy * vy) + vz * vz;
+  const float d = sqrtf(d2);
+  const float wx = vx / d, wy = vy / d, wz = vz / d;
+  const float cosx = std_max(0.0f, (nx * wx + ny * wy) + nz * wz);
+  const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+  const float an = 0.5f * fabsf((cx * wx + cy * wy) + cz * wz);
+  const float den = (3.14159265f * d2) * ((float)tab.q[e] / (float)tab.Q);
+  G[0] = (((T[9] * scale) * cosx) * an) / den;
+  G[1] = (((T[10] * scale) * cosx) * an) / den;
+  G[2] = (((T[11] * scale) * cosx) * an) / den;
+  if (cosx == 0.0f || d2 == 0.0f || !isfinite(G[0]) || !isfinite(G[1]) || !isfinite(G[2])) {
+    ray6[0] = 0.f; ray6[1] = 0.f; ray6[2] = 0.f; ray6[3] = 1.f; ray6[4] = 1.f; ray6[5] = 1.f;
+    tmax = -1.0f;
+    G[0] = 0.f; G[1] = 0.f; G[2] = 0.f;
+    return false;
+  }
+  ray6[0] = ox; ray6[1] = oy; ray6[2] = oz; ray6[3] = wx; ray6[4] = wy; ray6[5] = wz;
+  tmax = d - 0.001f;
+  return true;
+}
+
+// rt_path_bounce_rays_kernel of a frame with emitter sampling (nee = 1): besides the bounce ray of slot live[q], the emitter ray of the
+// same vertex -- user seed (seed + depth) ^ 0x80000000 in the bounce ray's hash input -- with its tmax and G (w = 1: real; a skipped
+// one is not counted).  One atomic per workgroup on the ray counter for the emitter rays, thread 0's for the bounce rays.
+__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  __shared__ uint32_t s_real;
+  if (threadIdx.x == 0) s_real = 0u;
+  __syncthreads();
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q == 0) {
+    *n_next = 0u;
+    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one bounce ray)
+  }
+  bool real = false;
+  if (q < total) {
+    const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
+    const uint32_t x = t % W, y = y0 + t / W;
+    const float4 I = pI[slot], N = pN[slot], D = pD[slot];
+    float r6[6];
+    ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
+    float* o = rays + (size_t)q * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = r6[k];
+    float nx = N.x, ny = N.y, nz = N.z;
+    if (nx * D.x + ny * D.y + nz * D.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // (N' as ao_sample_ray turns it)
+    const uint32_t seed = wang_hash((x + y * W) * spp + smp + 1u + (user_seed ^ 0x80000000u) * 0x9E3779B9u);
+    float e6[6], tm, G[3];
+    uint32_t e;
+    real = emitter_sample(tab, scale, seed, I.x, I.y, I.z, nx, ny, nz, e6, tm, G, e);
+    float* eo = erays + (size_t)q * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) eo[k] = e6[k];
+    etmax[q] = tm;
+    eG[q] = make_float4(G[0], G[1], G[2], real ? 1.0f : 0.0f);
+  }
+  const unsigned long long m = __ballot(real);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
+  __syncthreads();
+  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
+}
+
+// vxrt_emitter_rays: the emitter ray of n caller-supplied (I, N') and hash outputs, one per thread
+__global__ __launch_bounds__(256) void rt_emitter_rays_kernel(EmitterTab tab, uint32_t n, const float* __restrict__ points, const uint32_t* __restrict__ seeds, float scale,
+    float* __restrict__ rays, float* __restrict__ tmax, float* __restrict__ weight3, uint32_t* __restrict__ emitter) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const float* pt = points + (size_t)i * 6;
+  float e6[6], tm, G[3];
+  uint32_t e;
+  emitter_sample(tab, scale, seeds[i], pt[0], pt[1], pt[2], pt[3], pt[4], pt[5], e6, tm, G, e);
+  float* o = rays + (size_t)i * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = e6[k];
+  tmax[i] = tm;
+  weight3[3 * (size_t)i] = G[0]; weight3[3 * (size_t)i + 1] = G[1]; weight3[3 * (size_t)i + 2] = G[2];
+  emitter[i] = e;
+}
+
 // the occlusion rays of one depth (light sampling): one per bounce ray that hit; a miss gets a ray nothing can hit, which is not
 // counted (see rt_bounce_shadow_rays_kernel).  One atomic per workgroup on the ray counter.
 __global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams p, uint32_t cap, const uint32_t* n_live, const float* __restrict__ rays,
@@ -456,10 +600,15 @@ __global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams
 
 // the scatter step of one depth.  Miss: Lc = Lc + thr * background, the path ends.  Hit: Lc = Lc + thr * Lit (occluded iff shits[q]
 // hit), then thr = thr * Alb and the hit becomes the slot's last vertex; with `next` the slot is appended to the next depth's live list.
-__global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+// (EMI: the frame with emissive geometry, the header's "Emissive geometry".  1, nee = 0: a hit adds thr * Emi(h') after thr * Lit.
+//  2, nee = 1: before the miss / hit arm Lc = Lc + thr * G for an emitter ray that is real -- eG[q].w -- and was not blocked -- ehits[q].)
+struct ScatterEmi { float scale; const HitRec* ehits; const float4* eG; };
+struct ScatterNoEmi {};
+template <int EMI>
+__device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadeParams& p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
     const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next) {
+    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>& em) {
   const uint32_t total = min(*n_live, cap);
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   bool go[1] = {false};
@@ -471,6 +620,10 @@ __global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, Shade
     h.blasIdx &= 0x7fffffffu;
     float4 L = pL[slot];
     const float4 T = pT[slot];
+    if constexpr (EMI == 2) {
+      const float4 G = em.eG[q];
+      if (G.w != 0.f && em.ehits[q].dist == RT_LARGE_FLOAT) { L.x = L.x + T.x * G.x; L.y = L.y + T.y * G.y; L.z = L.z + T.z * G.z; }
+    }
     if (h.dist == RT_LARGE_FLOAT) {
       L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
     } else {
@@ -481,6 +634,10 @@ __global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, Shade
       thr *= refl;
       r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
       L.x = L.x + T.x * r; L.y = L.y + T.y * g; L.z = L.z + T.z * b;
+      if constexpr (EMI == 1) {
+        float e3[3];
+        if (emission(sc, h.triIdx, em.scale, e3)) { L.x = L.x + T.x * e3[0]; L.y = L.y + T.y * e3[1]; L.z = L.z + T.z * e3[2]; }
+      }
       if (next) {
         pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
         pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
@@ -492,6 +649,22 @@ __global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, Shade
     pL[slot] = L;
   }
   if (next) wg_append<1>(go, val, next, n_next);   // (uniform over the launch)
+}
+
+__global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next) {
+  path_scatter<0>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, ScatterNoEmi{});
+}
+
+// (the frame with emissive geometry: EMI = 1 for nee = 0, 2 for nee = 1)
+template <int EMI>
+__global__ __launch_bounds__(256) void rt_path_scatter_emissive_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next, ScatterEmi em) {
+  path_scatter<EMI>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em);
 }
 
 // after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
@@ -952,7 +1125,10 @@ static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r,
   const uint32_t n32 = (uint32_t)n;
   const dim3 block(256), pgrid((n32 + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS));
   if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
-  if (r.motion) {   // (a camera frame: check_request)
+  if (r.emissive) {   // (never with motion: check_request)
+    hipLaunchKernelGGL(r.cams ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab,
+                       (const HitRec*)c->hitbuf, c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, r.emissive->scale);
+  } else if (r.motion) {   // (a camera frame: check_request)
     hipLaunchKernelGGL((rt_path_prepare_kernel<true, true>), pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
                        c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position});
   } else {
@@ -985,6 +1161,11 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
   const uint64_t path_cap = pp.bounces ? n * ns : 0;
   if (path_cap > 0x7fffffffull) return -1;
+  // emissive geometry (the header's "Emissive geometry"): 0 none, 1 emission at bounce hits, 2 emitter sampling -- one emitter ray per
+  // live path and depth, generated with the bounce ray and traced by a second any-hit launch
+  const int emi = r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
+  if (emi == 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
+                               path_cap, GrowSync::STREAM, s)) return -1;
   if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
   const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u);
@@ -997,17 +1178,29 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
       uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
       const uint32_t* live = c->pt_live[d & 1u];
       const bool more = d + 1u < pp.bounces;
-      hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
-                         (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
+      if (emi == 2)
+        hipLaunchKernelGGL(rt_path_bounce_emitter_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
+                           (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, emitter_tab(a),
+                           r.emissive->scale, c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
+      else
+        hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
+                           (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
       if (trace_on_ctx(a, c, c->pt_rays, (uint64_t)n * k, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
       if (pp.shadow) {
         hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
                            c->pt_srays, c->pt_stmax, r.counters);
         if (trace_on_ctx(a, c, c->pt_srays, (uint64_t)n * k, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
       }
-      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                         pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T,
-                         more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr, n_next);
+      if (emi == 2 && trace_on_ctx(a, c, c->pt_erays, (uint64_t)n * k, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+      const HitRec* shits = pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr;
+      uint32_t* next = more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr;
+      if (emi)
+        hipLaunchKernelGGL(emi == 2 ? rt_path_scatter_emissive_kernel<2> : rt_path_scatter_emissive_kernel<1>, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
+                           (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
+                           ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
+      else
+        hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
+                           shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next);
     }
     hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
                        (const float4*)c->pt_L, c->pt_acc);
@@ -1090,6 +1283,13 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
 int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
                          unsigned long long* total, hipStream_t s) {
   hipLaunchKernelGGL(rt_sample_counts_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, variance, prev_counts, prm->gain, prm->min_spp, prm->max_spp, counts, total);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// vxrt_emitter_rays behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
+int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                        uint32_t* emitter, hipStream_t s) {
+  hipLaunchKernelGGL(rt_emitter_rays_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), n, points, seeds, scale, rays, tmax, weight3, emitter);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

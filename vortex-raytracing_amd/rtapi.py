@@ -276,7 +276,8 @@ def wire_unpack(wire_all_ptr, wire_stride_bytes, width, tile_rows_per_rank, worl
 
 def accel_info(accel, which):
     """vxrt_accel_info: 0 -> internal levels of the deepest path (counted up to 17), 1 -> 48-entry stacks (depth class <= 16),
-    2 -> single identity instance under the TLAS root, 3 -> ldexp decode, 4 -> a non-zero alpha table is set."""
+    2 -> single identity instance under the TLAS root, 3 -> ldexp decode, 4 -> a non-zero alpha table is set, 7 -> emitters of a
+    valid emitter table (0: none, or stale)."""
     L = _lib()
     L.vxrt_accel_info.restype = C.c_int
     L.vxrt_accel_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -678,6 +679,13 @@ class SampleCountParams(C.Structure):   # vxrt_sample_count_params_t
     _fields_ = [("gain", C.c_float), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+MAX_EMITTERS = 65536   # VXRT_MAX_EMITTERS
+
+
+class EmissiveParams(C.Structure):   # vxrt_emissive_params_t
+    _fields_ = [("nee", C.c_uint32), ("scale", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 def _declare_path_family(L):
     """The prototypes of the path, denoise, temporal, motion, variance and adaptive families; _lib() calls this once with its own."""
     u32, vp, i32 = C.c_uint32, C.c_void_p, C.c_int
@@ -709,6 +717,10 @@ def _declare_path_family(L):
         "vxrt_render_path_adaptive": (i32, frame + [vp, vp, vp, vp, vp]),
         "vxrt_render_path_variance_adaptive": (i32, frame + [vp, dn, tp, vr, vp, i32, vp, vp, C.POINTER(PathAov), vp, vp, vp, vp]),
         "vxrt_sample_counts": (i32, [C.c_uint64, vp, vp, C.POINTER(SampleCountParams), vp, vp, vp]),
+        "vxrt_accel_set_emitters": (i32, [vp, vp, u32, vp]),
+        "vxrt_accel_read_emitters": (i32, [vp, vp, vp, vp, vp]),
+        "vxrt_render_path_emissive": (i32, frame + [C.POINTER(EmissiveParams), vp, vp, vp, vp]),
+        "vxrt_emitter_rays": (i32, [vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
@@ -778,3 +790,56 @@ def sample_counts(n, variance_ptr, prm, counts_ptr, prev_counts_ptr=None, total_
     """vxrt_sample_counts: counts[i] = clamp(ceil(variance[i] * m * gain), min_spp, max_spp) for n entries, m = the clamped prev_counts[i]
     (or 1); `prm`: a SampleCountParams; `total_ptr` (optional, device uint64) is incremented by the sum of the counts written."""
     check(_lib().vxrt_sample_counts(int(n), variance_ptr, prev_counts_ptr, C.byref(prm), counts_ptr, total_ptr, stream), "vxrt_sample_counts")
+
+
+# ---- emissive geometry: the emitter table of an accel, path frames with area lights (the header's "Emissive geometry") ----
+def emitter_pairs(buffers, ranges):
+    """Host helper: the (blasIdx, triIdx) pairs of a scene's emissive triangles, as vxrt_accel_set_emitters takes them.  `buffers`: the
+    scene buffers (triEx, mat as uint8 arrays); `ranges`: per instance record (first triangle, triangle count) -- the reference formats
+    do not store them, the caller knows them from the meshes it built the scene from.  Returns an (n, 2) uint32 array, instances in
+    order, triangles ascending, of the triangles whose material has a positive emissive component."""
+    import numpy as np
+    tex_id = np.frombuffer(np.ascontiguousarray(buffers["triEx"], np.uint8).tobytes(), np.uint32).reshape(-1, 16)[:, 15]
+    emi = np.frombuffer(np.ascontiguousarray(buffers["mat"], np.uint8).tobytes(), np.float32).reshape(-1, 22)[:, 9:12]
+    lit = (emi > 0).any(1)
+    out = []
+    for inst, (first, count) in enumerate(ranges):
+        tris = np.arange(int(first), int(first) + int(count), dtype=np.uint32)
+        tris = tris[lit[tex_id[tris]]]
+        out.append(np.stack([np.full(len(tris), inst, np.uint32), tris], 1))
+    return np.concatenate(out).astype(np.uint32) if out else np.zeros((0, 2), np.uint32)
+
+
+def accel_set_emitters(accel, pairs, stream=None):
+    """vxrt_accel_set_emitters: `pairs` = (n, 2) uint32 (blasIdx, triIdx) of every emissive triangle (see emitter_pairs); None or an
+    empty list drops the table.  Raises on a refusal (the previous table is kept then)."""
+    import numpy as np
+    if pairs is None or len(pairs) == 0:
+        check(_lib().vxrt_accel_set_emitters(accel, None, 0, stream), "vxrt_accel_set_emitters")
+        return
+    p = np.ascontiguousarray(np.asarray(pairs, np.uint32).reshape(-1, 2))
+    check(_lib().vxrt_accel_set_emitters(accel, p.ctypes.data, len(p), stream), "vxrt_accel_set_emitters")
+
+
+def accel_read_emitters(accel, stream=None):
+    """vxrt_accel_read_emitters: the valid emitter table as numpy arrays -- tri12 (n, 12) float32 (V0, E1, E2, Le), q (n,), cum (n,) uint32."""
+    import numpy as np
+    n = accel_info(accel, 7)
+    tri, q, cum = np.zeros((n, 12), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    check(_lib().vxrt_accel_read_emitters(accel, tri.ctypes.data, q.ctypes.data, cum.ctypes.data, stream), "vxrt_accel_read_emitters")
+    return tri, q, cum
+
+
+def render_path_emissive(accel, cam, width, height, y0, y1, params, spp, bounces, emissive, dst_ptr, seed=0, shadow=0, colors_ptr=None, rays_ptr=None,
+                         stream=None):
+    """vxrt_render_path_emissive: render_path with emissive triangles as area lights; `emissive`: an EmissiveParams (nee = 0: emission found
+    by the bounce rays, nee = 1: emitter sampling from the accel's table; scale multiplies every material's emissive)."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_lib().vxrt_render_path_emissive(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+                                           C.byref(emissive), dst_ptr, colors_ptr, rays_ptr, stream), "vxrt_render_path_emissive")
+
+
+def emitter_rays(accel, n, points_ptr, seeds_ptr, scale, rays_ptr, tmax_ptr, weight_ptr, emitter_ptr, stream=None):
+    """vxrt_emitter_rays: the emitter-sampling step alone on device buffers -- points (n x 6: I, N'), seeds (n hash outputs) -> rays (n x 6),
+    tmax (n), weight (n x 3: G), emitter (n: the index chosen)."""
+    check(_lib().vxrt_emitter_rays(accel, int(n), points_ptr, seeds_ptr, float(scale), rays_ptr, tmax_ptr, weight_ptr, emitter_ptr, stream), "vxrt_emitter_rays")

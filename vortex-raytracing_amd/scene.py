@@ -122,15 +122,27 @@ def procedural(name, a=0, b=0, seed=1):
     return sc
 
 
-def from_triangles(meshes, transforms=None):
-    """meshes: list of float32 arrays [n_i, 9] (v0,v1,v2).  transforms: optional list of 4x4."""
+def from_triangles(meshes, transforms=None, tri_ex=None, materials=None):
+    """meshes: list of float32 arrays [n_i, 9] (v0,v1,v2).  transforms: optional list of 4x4.  tri_ex: optional list, one uint8 array of
+    n_i tri_ex_t records (64 B) per mesh, texId local to the mesh's materials (default: flat normals, texId 0).  materials: optional
+    list, one uint8 array of material_info_t records (88 B) per mesh (default: one grey material per mesh; textures are dropped)."""
     ntris = np.array([len(m) for m in meshes], np.uint32)
     tris = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1, 9) for m in meshes]), np.float32)
-    tr = None
+    tr = ex = nmats = mats = None
     if transforms is not None:
         tr = np.ascontiguousarray(np.stack([np.asarray(t, np.float32).reshape(16) for t in transforms]), np.float32)
-    h = _load().vxs_scene_create_from_tris(len(meshes), ntris.ctypes.data, tris.ctypes.data, None,
-                                           tr.ctypes.data if tr is not None else None, None, None)
+    if tri_ex is not None:
+        ex = np.ascontiguousarray(np.concatenate([np.asarray(e, np.uint8).reshape(-1) for e in tri_ex]), np.uint8)
+        if ex.size != TRIEX_BYTES * int(ntris.sum()):
+            raise ValueError("tri_ex: one 64-byte record per triangle")
+    if materials is not None:
+        if len(materials) != len(meshes) or any(np.asarray(m).size % MAT_BYTES or np.asarray(m).size == 0 for m in materials):
+            raise ValueError("materials: one non-empty array of 88-byte records per mesh")
+        nmats = np.array([np.asarray(m).size // MAT_BYTES for m in materials], np.uint32)
+        mats = np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8).reshape(-1) for m in materials]), np.uint8)
+    h = _load().vxs_scene_create_from_tris(len(meshes), ntris.ctypes.data, tris.ctypes.data, ex.ctypes.data if ex is not None else None,
+                                           tr.ctypes.data if tr is not None else None, nmats.ctypes.data if nmats is not None else None,
+                                           mats.ctypes.data if mats is not None else None)
     return _from_handle(h, "triangles")
 
 

@@ -230,6 +230,15 @@ class DeviceScene:
         with torch.cuda.device(dev):
             rtapi.accel_set_alpha_test(self.accel, thresholds, torch.cuda.current_stream().cuda_stream)
 
+    def set_emitters(self, pairs):
+        """Area lights: the (blasIdx, triIdx) pairs of every emissive triangle (rtapi.emitter_pairs lists them from per-instance triangle
+        ranges), from which the accel builds the table rtapi.render_path_emissive samples with nee = 1 (vxrt_accel_set_emitters).  None
+        drops the table.  The table holds world-space data: set it again after set_transforms or refit."""
+        import torch
+        dev = self.t["blas"].device
+        with torch.cuda.device(dev):
+            rtapi.accel_set_emitters(self.accel, pairs, torch.cuda.current_stream().cuda_stream)
+
     def to_host(self):
         """The scene buffers as a scene.Scene (numpy), e.g. to hand a GPU-built tree to the oracle."""
         from .scene import Scene
