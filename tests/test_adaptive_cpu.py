@@ -82,7 +82,7 @@ def test_samples_straddle_the_child_batches(vrt, hall, case):
 
 
 def test_scan_constants_are_the_kernels(vrt):
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vortex-raytracing_amd", "csrc", "rt_secondary.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vortex-raytracing_amd", "csrc", "rt_path.hip")).read()
     block = int(re.search(r"#define PT_SCAN_BLOCK (\d+)u", src).group(1))
     per_pass = int(re.search(r"#define PT_SCAN_PASS (\d+)u", src).group(1))
     assert vrt.rtapi.ADAPTIVE_SCAN_BLOCK == block and vrt.rtapi.ADAPTIVE_SCAN_PASS == block * per_pass

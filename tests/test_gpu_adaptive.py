@@ -201,6 +201,13 @@ def test_path_frame_restated_odd_size_and_row_window(vrt, po, hall):
     assert (px[:13] == MARK).all() and (px[43:] == MARK).all() and (px[13:43] != MARK).any()
 
 
+def test_one_bounce_against_the_restatement(vrt, po, hall):
+    """bounces = 1: the batch's first depth is its last; with and without light sampling (ac.SCAN has one bounce, against the GPU only)"""
+    b, ds = hall
+    for shadow in (1, 0):
+        _against_ref(vrt, po, b, ds, csr.hall_cameras(vrt)["orbit_1"], "one bounce, shadow %d" % shadow, case=dict(ac.SCAN, shadow=shadow))
+
+
 # ---- 5: small batches ----
 def test_small_batches(vrt):
     """VXRT_PATH_BATCH is read once per process: a fresh child runs the mosaic and restatement tests above with CHILD_BATCH paths per batch

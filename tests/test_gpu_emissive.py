@@ -109,6 +109,13 @@ def test_sixteen_bounces(vrt, po, hall):
     _against_ref(vrt, po, hall, csr.hall_cameras(vrt)["inside_blob"], "16 bounces", configs=((1, 16, 1, 0, 1), (1, 16, 0, 0, 0)))
 
 
+def test_one_bounce_and_emission_under_light_sampling(vrt, po, hall):
+    """bounces = 1 (the batch's first depth is its last) for nee = 1 and nee = 0, each with and without light sampling; and nee = 0 with
+    light sampling over two depths, which ec.CONFIGS leaves out"""
+    _against_ref(vrt, po, hall, csr.hall_cameras(vrt)["orbit_1"], "one bounce",
+                 configs=((2, 1, 1, 3, 1), (2, 1, 0, 0, 1), (2, 1, 1, 1, 0), (2, 1, 0, 5, 0), (2, 2, 1, 1, 0)))
+
+
 def test_no_bounce_is_the_flat_sum_with_emission(vrt, po, hall):
     _against_ref(vrt, po, hall, csr.hall_cameras(vrt)["framing"], "bounces 0", configs=((3, 0, 1, 0, 1), (2, 0, 0, 0, 0)))
 

@@ -166,6 +166,12 @@ def test_sixteen_bounces(vrt, po, hall):
     _against_ref(vrt, po, b, ds, csr.hall_cameras(vrt)["inside_blob"], "16 bounces", configs=((1, 16, 1, 0),))
 
 
+def test_one_bounce_against_the_restatement(vrt, po, hall):
+    """bounces = 1: the batch's first depth is its last, so the only scatter launch compacts nothing; with and without light sampling"""
+    b, ds = hall
+    _against_ref(vrt, po, b, ds, csr.hall_cameras(vrt)["orbit_1"], "one bounce", configs=((2, 1, 1, 3), (2, 1, 0, 0)))
+
+
 def test_batches_of_two_two_and_one_samples(vrt, po, hall, gpu_device):
     """VXRT_PATH_BATCH is read once per process: a fresh child runs this test's body with 2 * W * H paths per batch, so that spp = 5
     takes batches of 2, 2 and 1 samples"""

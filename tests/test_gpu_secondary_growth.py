@@ -1,4 +1,4 @@
-"""GPU: the buffers of the secondary tails (csrc/rt_secondary.hip) as they grow.  A frame context allocates the buffers of path, denoised
+"""GPU: the buffers of the secondary tails (csrc/rt_path.hip, csrc/rt_secondary.hip) as they grow.  A frame context allocates the buffers of path, denoised
 path and ambient-occlusion frames on first use and grows them, one capacity at a time, when a frame needs more: per pixel, per path,
 per occlusion ray; per pixel and per ray of an ambient-occlusion batch; the denoiser's two signal buffers.  Each case below walks ONE
 context -- a freshly built DeviceScene, one stream -- through a sequence of frames that allocates the capacities one after the other,

@@ -564,7 +564,7 @@ static int vr_launch_initial(hipStream_t s, const vxrt_history_t* h, const vxrt_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// ---- the tail of a denoised path frame (render_path_tail in rt_secondary.hip ends in one of the two functions below) ----
+// ---- the tail of a denoised path frame (path_frame_end in rt_path.hip ends in one of the two functions below) ----
 // The window and the buffers every launch of the tail shares, read from the context and the request in this one place.  Per pixel of the
 // window: geo = P (w = hit?), nrm = N, lit / alb of the primary hit, acc = the accumulator over samples, sig = the two signal buffers.
 struct DnFrame {

@@ -1,8 +1,9 @@
 // Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
-// level-2 entry points), rt_accel.hip (acceleration-layout build, refit), rt_secondary.hip (the tails of mirror-bounce,
-// ambient-occlusion and path frames) and rt_denoise.hip (the end of a denoised path frame's tail: a-trous filter, temporal accumulation,
-// variance guidance) share: the types, and the few host functions one unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of
-// shading, which rt_kernels.hip and rt_secondary.hip share, is in rt_shading.h.
+// level-2 entry points), rt_accel.hip (acceleration-layout build, refit), rt_secondary.hip (the tails of mirror-bounce and
+// ambient-occlusion frames, the binning of secondary rays), rt_path.hip (the tail of a path frame) and rt_denoise.hip (the end of a
+// denoised path frame's tail: a-trous filter, temporal accumulation, variance guidance) share: the types, and the few host functions one
+// unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of shading, which rt_kernels.hip,
+// rt_secondary.hip and rt_path.hip share, is in rt_shading.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -98,6 +99,7 @@ struct FrameCtx {
   uint32_t* ao_list = nullptr; uint32_t* ao_hdr = nullptr;   // pixels with a hit; [0] their number, [1] rays of the current batch
   float* ao_rays = nullptr; float* ao_tmax = nullptr; HitRec* ao_hits = nullptr; uint64_t ao_cap = 0, ao_ray_cap = 0;
   uint32_t* bin_hist = nullptr; uint32_t* bin_keys = nullptr; uint32_t* bin_order = nullptr; uint64_t bin_cap = 0, bin_ray_cap = 0;   // secondary-ray binning
+  // (every pt_* and mo_* field below is grown and written by rt_path.hip; rt_denoise.hip reads the per-pixel ones)
   // path frames (vxrt_render_path; allocated on first use).  Per pixel of the window: hit point (w = hit?), shading normal, primary
   // direction, Lit, Alb of the primary hit and the accumulator over samples; the pixels with a hit ([0] of pt_hdr their number, [1] / [2]
   // the live paths of even / odd depths).  Per path of a batch: I, N, dir of its last vertex, Lc, thr; the two lists of live paths;
@@ -170,7 +172,7 @@ struct vxrt_accel {
   bool em_valid = false;
 };
 
-// What the emitter-sampling kernels read of the table (rt_secondary.hip)
+// What the emitter-sampling kernels read of the table (rt_path.hip)
 struct EmitterTab { const float* tri; const uint32_t* q; const uint32_t* cum; uint32_t n, Q; };
 static inline EmitterTab emitter_tab(const vxrt_accel* a) { return EmitterTab{a->em_tri, a->em_q, a->em_cum, a->em_n, a->em_Q}; }
 static inline bool emitters_valid(const vxrt_accel* a) { return a->em_valid && a->em_n != 0u && !a->stale; }
@@ -193,7 +195,7 @@ static inline bool ident_root_form(const vxrt_accel* a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// shared device arithmetic: the RGB8 pack of every frame (rt_kernels.hip, rt_secondary.hip, rt_denoise.hip)
+// shared device arithmetic: the RGB8 pack of every frame (rt_kernels.hip, rt_secondary.hip, rt_path.hip, rt_denoise.hip)
 // ---------------------------------------------------------------------------------------------
 // libstdc++ std::min (NaN behaviour is part of parity; std_max is in rt_shading.h)
 __device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
@@ -208,7 +210,7 @@ __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // c
 
 // ---------------------------------------------------------------------------------------------
 // rt_denoise.hip: what an entry point of rt_kernels.hip checks before a denoised path frame is launched, and the two ends that
-// render_path_tail (rt_secondary.hip) hands such a frame to.  The launches behind them, and their order, are that unit's own.
+// render_path_tail (rt_path.hip) hands such a frame to.  The launches behind them, and their order, are that unit's own.
 // ---------------------------------------------------------------------------------------------
 struct RenderRequest;
 // the checks of vxrt_denoise_params_t / vxrt_variance_params_t every entry point that takes one shares
@@ -228,8 +230,8 @@ int render_denoise_tail(FrameCtx* c, const RenderRequest& r, uint32_t n);
 int render_denoise_aov(FrameCtx* c, const RenderRequest& r, uint32_t n);
 
 // ---------------------------------------------------------------------------------------------
-// rt_kernels.hip <-> rt_secondary.hip: a frame as an entry point asks for it, the per-frame control block, growing device buffers,
-// the ray-buffer launch the secondary tails trace with and the three tails render_common ends such a frame with
+// rt_kernels.hip <-> rt_secondary.hip, rt_path.hip: a frame as an entry point asks for it, the per-frame control block, growing device
+// buffers, the ray-buffer launch the secondary tails trace with, the three tails render_common ends such a frame with and their knobs
 // ---------------------------------------------------------------------------------------------
 #ifndef QUEUE_SHARDS
 #define QUEUE_SHARDS 8u     // one device-scope counter saturates near 90 dequeues/us
@@ -300,15 +302,29 @@ constexpr int MODE_ANY_UNORDERED = 0x100;
 int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, const float* tmax, HitRec* hits, int mode, hipStream_t s,
                  const uint32_t* n_dev = nullptr, unsigned long long* stats_counters = nullptr, const uint32_t* order = nullptr);
 
-// rt_secondary.hip: what replaces the plain shading pass of a frame with reflective instances / an ambient-occlusion frame / a path
-// frame (denoised or not).  utab / vtab: the tables the traversal used (a camera frame's: the head and the tables of its camera block).
+// rt_secondary.hip: what replaces the plain shading pass of a frame with reflective instances / an ambient-occlusion frame.
+// utab / vtab: the tables the traversal used (a camera frame's: the head and the tables of its camera block).
 // Each zeroes the context's control block in its first launch.  0, or -1 when a HIP call failed.
 int render_bounce_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
+// rt_secondary.hip: the three measurement knobs of the secondary tails (docs/KNOBS.md), read from the environment once per process, together
+struct SecondaryKnobs {
+  uint64_t path_batch;   // paths per batch of a path frame (see render_path_tail); VXRT_PATH_BATCH, default PATH_BATCH_PATHS
+  uint64_t ao_batch;     // rays per batch of an ambient-occlusion frame (see render_ao_tail); VXRT_AO_BATCH, parsed as VXRT_PATH_BATCH is
+  // VXRT_SORT_SECONDARY=1: trace the secondary rays in (direction octant, origin cell) order instead of generation order.  OFF by
+  // default: measured SLOWER on both passes that used it then (diffuse bounce 1.53 -> 1.95 ms, 10M-triangle hairball AO 9.2 -> 16.6 ms,
+  // profiles/r02_f_secondary_sort.txt).  The traversal is bound by per-lane VALU work, which coherence does not reduce, and the
+  // generation order already puts the 16 samples of one pixel (AO) / 64 neighbouring pixels (bounce) side by side.
+  bool sort_secondary;
+};
+const SecondaryKnobs& secondary_knobs();
+
+// rt_path.hip: what replaces the plain shading pass of a path frame (denoised or not); as the two tails above
 int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
-// rt_secondary.hip: the launch of vxrt_emitter_rays (n >= 1, a valid table; the checks are the entry point's)
+extern const uint64_t PATH_BATCH_PATHS;   // paths per batch of a path frame unless VXRT_PATH_BATCH says otherwise
+// rt_path.hip: the launch of vxrt_emitter_rays (n >= 1, a valid table; the checks are the entry point's)
 int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
                         uint32_t* emitter, hipStream_t s);
-// rt_secondary.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
+// rt_path.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
 int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
                          unsigned long long* total, hipStream_t s);

@@ -16,8 +16,8 @@
 // per-lane stack whose entries carry m = max(entry distance along the path); DESIGN.md s3 proves
 // this returns the same hit (index included) as the reference's accept-and-re-descend loop.
 // What is not timed lives elsewhere: the acceleration-layout build and the refit in rt_accel.hip; the tails of the frames that trace
-// secondary rays (mirror bounce, ambient occlusion, path frames) and their kernels in rt_secondary.hip, the a-trous filter in
-// rt_denoise.hip; the two ray-compaction experiments (VXRT_POOL) in rt_trace_experiments.inc.  The shading arithmetic the frame
+// secondary rays and their kernels in rt_secondary.hip (mirror bounce, ambient occlusion) and rt_path.hip (path frames), the a-trous
+// filter in rt_denoise.hip; the two ray-compaction experiments (VXRT_POOL) in rt_trace_experiments.inc.  The shading arithmetic the frame
 // kernels share with those tails (shade_terms, the camera rays, the sample rays) is in rt_shading.h; SceneDev, HitRec, ShadeParams,
 // FrameCtx, vxrt_accel, RenderRequest and the seam to the other units in rt_internal.h; the constants of the compact layout in
 // rt_types.h.
@@ -1588,7 +1588,7 @@ static uint32_t* status_word() {
 
 // Measurement knobs of the render and trace path (docs/KNOBS.md), read from the environment once per process: on the first call
 // that asks for one.  Each keeps the parsing it always had (atoi, atoll, or "first character is 0").  (The three of the secondary
-// tails, VXRT_PATH_BATCH, VXRT_AO_BATCH and VXRT_SORT_SECONDARY, are read the same way in rt_secondary.hip.)
+// tails, VXRT_PATH_BATCH, VXRT_AO_BATCH and VXRT_SORT_SECONDARY, are read the same way in rt_secondary.hip, for rt_path.hip as well.)
 struct HostKnobs {
   uint32_t shard_rot, lpt_batch_max;
   bool lpt, lpt_batch;                  // on unless the value begins with '0'
@@ -2472,7 +2472,7 @@ int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uin
 }
 
 // Path frame with a sample count per pixel (see the header, "Adaptive sampling"): vxrt_render_path whose tail packs the pixels' samples
-// into batches (render_path_counts_tail in rt_secondary.hip); path->spp is the cap
+// into batches (render_path_counts_tail in rt_path.hip); path->spp is the cap
 int vxrt_render_path_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                               const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const uint32_t* counts, uint32_t* dst, float* colors,
                               unsigned long long* rays_traced, void* stream) {

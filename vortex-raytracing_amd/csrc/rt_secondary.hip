@@ -1,46 +1,15 @@
-// Tails of the frames that trace secondary rays, and their kernels: what render_common (rt_kernels.hip) runs in place of the plain
-// shading pass of a frame with reflective instances (the mirror-bounce wavefront), of an ambient-occlusion frame and of a path frame
-// (with emissive geometry: the emitter ray and the emissive flavours of its prepare, ray and scatter kernels; its denoised end is in
-// rt_denoise.hip; with it the previous-position guide of frames with motion, motion_guide, and vxrt_previous_positions), and the binning of secondary rays.  None of it is timed by bench.py, and none of it can
+// Tails of two of the frames that trace secondary rays, and their kernels: what render_common (rt_kernels.hip) runs in place of the
+// plain shading pass of a frame with reflective instances (the mirror-bounce wavefront) and of an ambient-occlusion frame, and the
+// binning of secondary rays.  The third tail, that of a path frame, is rt_path.hip; the knob reader of all three is here.
+// None of it is timed by bench.py, and none of it can
 // reach the traversal kernel's unit: the seam is in rt_internal.h -- the ray buffers are traced through trace_on_ctx, buffers grow
 // through grow_device -- and the shading arithmetic is that of the frame kernels, rt_shading.h.  Same build flags (-ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <type_traits>
 #include "rt_internal.h"
 #include "rt_shading.h"
 
 __global__ void add_counter_kernel(unsigned long long* c, unsigned long long v) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(c, v); }
-
-// The hit pixels of a frame are appended to one list.  One atomic per wavefront on the list's counter (32,400 for a 1080p frame, all on
-// one address, ~10 ns apart) was 0.3 of the AO prepare kernel's 0.37 ms: a workgroup now counts the hits of 1,024 pixels in LDS and
-// appends once.
-#define PREP_CHUNKS 4   // pixels per thread of the two prepare kernels: one list-append atomic per 1,024 pixels
-// Append value[c] of every thread with flag[c] to list[] (its length in *counter; the order is arbitrary): the workgroup counts in LDS
-// and does one atomic.  Every thread of the workgroup calls it.
-template <int C>
-__device__ __forceinline__ void wg_append(const bool (&flag)[C], const uint32_t (&value)[C], uint32_t* __restrict__ list, uint32_t* counter) {
-  __shared__ uint32_t s_cnt[C][4];
-  __shared__ uint32_t s_base;
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  uint32_t off[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const unsigned long long m = __ballot(flag[c]);
-    off[c] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[c][wv] = (uint32_t)__popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-    for (int c = 0; c < C; ++c) for (int w = 0; w < 4; ++w) { const uint32_t v = s_cnt[c][w]; s_cnt[c][w] = tot; tot += v; }
-    s_base = tot ? atomicAdd(counter, tot) : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-    if (flag[c]) list[s_base + s_cnt[c][wv] + off[c]] = value[c];
-}
 
 // ---------------------------------------------------------------------------------------------
 // Mirror bounce (closest.cpp:95-121) as a wavefront over depth levels.  The reference recurses inside
@@ -277,623 +246,6 @@ __global__ __launch_bounds__(256) void rt_ao_final_kernel(uint64_t n, uint32_t W
 }
 
 // ---------------------------------------------------------------------------------------------
-// Path frames (vxrt_render_path; the definition is in include/vortex_hip.h, the launch sequence in render_path_tail and DESIGN.md s2,
-// "Path frames").  The kernels around the ray-buffer launches: per-pixel state of the primary hit, per-path state that survives from
-// bounce to bounce, the scatter step and the accumulation over samples.  Every arithmetic step is an existing __device__ function
-// (shade_terms, ao_sample_ray, shadow_ray, pack_rgb8, camera_ray / generate_ray).
-// Path slot i of a batch of ns samples starting at s0 = (pixel list[i / ns], sample s0 + i % ns); a path's state stays in its slot,
-// and the rays of a depth are those of the slots still listed as live (ray q belongs to slot live[q]).
-// ---------------------------------------------------------------------------------------------
-// per pixel t of rows [y0,y1): geo[t] = (I, hit?), nrm[t] = (N, 0), dir[t] = (direction of the primary ray, 0), lit[t] = (Lit of the
-// primary hit with the occlusion bit the shadow frame launch left in its record | background, 0), alb[t] = (Alb, 0); pixels with a hit
-// are appended to list[] (count in hdr[0])
-// (CAM: camera frames -- utab / vtab are the camera block's head and tables, see CAM_HDR)
-// The previous-position guide of hit record h (the header's "Motion", operation for operation): where the surface point under h was
-// when the accel's snapshot was taken, Q4 = (Q, 1), and the shading normal it had there, N'4 = (N', 0).  All zeros for a miss and for
-// a record that names an instance or a triangle the scene does not have (nothing is read for it).  h.blasIdx: bit 31 is masked here.
-__device__ __forceinline__ void motion_guide(const SceneDev& sc, const MotionSrc& m, const HitRec& h, float4& Q4, float4& N4) {
-  Q4 = make_float4(0.f, 0.f, 0.f, 0.f); N4 = Q4;
-  const uint32_t bi = h.blasIdx & 0x7fffffffu;
-  if (h.dist == RT_LARGE_FLOAT || bi >= m.n_blas || h.triIdx >= m.n_tris) return;
-  const float* v = m.tri + (size_t)h.triIdx * (RT_TRI_BYTES / 4);        // tri_t: v0, v1, v2
-  const uint32_t* bp = m.blas + (size_t)bi * (RT_BLAS_STRIDE / 4);       // invTransform @ word 1, transform @ word 17
-  float o[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) o[c] = (v[3 + c] * h.bx + v[6 + c] * h.by) + v[c] * h.bz;
-  float q[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const uint32_t* r = bp + 17 + 4 * c;
-    q[c] = ((__uint_as_float(r[0]) * o[0] + __uint_as_float(r[1]) * o[1]) + __uint_as_float(r[2]) * o[2]) + __uint_as_float(r[3]);
-  }
-  // shade_terms' shading normal with the snapshot's invTransform
-  const rt_triex_t te = sc.triEx[h.triIdx];
-  const float Nx = te.N1[0] * h.bx + te.N2[0] * h.by + te.N0[0] * h.bz;
-  const float Ny = te.N1[1] * h.bx + te.N2[1] * h.by + te.N0[1] * h.bz;
-  const float Nz = te.N1[2] * h.bx + te.N2[2] * h.by + te.N0[2] * h.bz;
-  const float m0 = __uint_as_float(bp[1]), m1 = __uint_as_float(bp[2]), m2 = __uint_as_float(bp[3]);
-  const float m4 = __uint_as_float(bp[5]), m5 = __uint_as_float(bp[6]), m6 = __uint_as_float(bp[7]);
-  const float m8 = __uint_as_float(bp[9]), m9 = __uint_as_float(bp[10]), m10 = __uint_as_float(bp[11]);
-  const float z0 = 0.0f * 0.0f;
-  const float Tx = m0 * Nx + m4 * Ny + m8 * Nz + z0;
-  const float Ty = m1 * Nx + m5 * Ny + m9 * Nz + z0;
-  const float Tz = m2 * Nx + m6 * Ny + m10 * Nz + z0;
-  const float inv = 1.0f / sqrtf(Tx * Tx + Ty * Ty + Tz * Tz);
-  Q4 = make_float4(q[0], q[1], q[2], 1.0f);
-  N4 = make_float4(Tx * inv, Ty * inv, Tz * inv, 0.f);
-}
-
-// vxrt_previous_positions: the guide of n hit records, one per thread
-__global__ __launch_bounds__(256) void rt_previous_positions_kernel(SceneDev sc, MotionSrc m, uint32_t n, const HitRec* __restrict__ hits,
-    float4* __restrict__ pos, float4* __restrict__ nrm) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= n) return;
-  float4 Q4, N4;
-  motion_guide(sc, m, hits[t], Q4, N4);
-  pos[t] = Q4; nrm[t] = N4;
-}
-
-// what the MOTION flavour of rt_path_prepare_kernel takes besides: the guide's sources, its two per-pixel buffers of the frame context
-// and the caller's optional prev_position (frame addressing)
-struct PrepMotion { MotionSrc src; float4* pos; float4* nrm; float* out; };
-struct PrepNoMotion {};
-
-// Emi(h) of the header's "Emissive geometry": emissive * scale of the material of triangle triIdx, if it has a positive component
-// (false: the material does not emit, and nothing is to be added)
-__device__ __forceinline__ bool emission(const SceneDev& sc, uint32_t triIdx, float scale, float (&e3)[3]) {
-  const rt_material_t* mat = sc.mat + sc.triEx[triIdx].texId;
-  const float r = mat->emissive[0], g = mat->emissive[1], b = mat->emissive[2];
-  if (!(r > 0.0f || g > 0.0f || b > 0.0f)) return false;
-  e3[0] = r * scale; e3[1] = g * scale; e3[2] = b * scale;
-  return true;
-}
-
-// what the emissive flavour of the prepare launch takes besides (EMI: lit[t] = Lit_0 + Emi(h_0))
-struct PrepEmi { float scale; };
-struct PrepNoEmi {};
-
-// The prepare launch of every path frame; its kernels are below.
-// (MOTION: the frame with motion -- the previous-position guide of the pixel's record, computed where the record is in registers)
-template <bool CAM, bool MOTION, bool EMI>
-__device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadeParams& p, uint32_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo,
-    std::conditional_t<EMI, PrepEmi, PrepNoEmi> em) {
-  if (ctl_reset && blockIdx.x == 0)
-    for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
-  bool hit_c[PREP_CHUNKS];
-  uint32_t t_c[PREP_CHUNKS];
-#pragma unroll
-  for (int c = 0; c < PREP_CHUNKS; ++c) {
-    const uint64_t t64 = ((uint64_t)blockIdx.x * PREP_CHUNKS + c) * 256u + threadIdx.x;
-    const uint32_t t = (uint32_t)t64;
-    bool hit = false;
-    if (t64 < n) {
-      const uint32_t x = t % W, y = y0 + t / W;
-      HitRec h = hb[hit_index(x, y - y0, (W + 7u) >> 3)];
-      const bool occ = (h.blasIdx & 0x80000000u) != 0u;
-      h.blasIdx &= 0x7fffffffu;
-      float ox, oy, oz, dx, dy, dz;
-      if constexpr (CAM) camera_ray(utab, vtab, W, x, y, ox, oy, oz, dx, dy, dz);
-      else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
-      if (h.dist == RT_LARGE_FLOAT) {
-        geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        lit[t] = make_float4(p.bg[0], p.bg[1], p.bg[2], 0.f);
-      } else {
-        float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
-        shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-        float thr = 1.0f;
-        thr *= refl;
-        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
-        if constexpr (EMI) {
-          float e3[3];
-          if (emission(sc, h.triIdx, em.scale, e3)) { r = r + e3[0]; g = g + e3[1]; b = b + e3[2]; }
-        }
-        geo[t] = make_float4(Ix, Iy, Iz, 1.0f);
-        nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
-        dir[t] = make_float4(dx, dy, dz, 0.f);
-        lit[t] = make_float4(r, g, b, 0.f);
-        alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
-        hit = true;
-      }
-      if constexpr (MOTION) {
-        float4 Q4, N4;
-        motion_guide(sc, mo.src, h, Q4, N4);
-        mo.pos[t] = Q4; mo.nrm[t] = N4;
-        if (mo.out) { float* o = mo.out + 4 * ((size_t)x + (size_t)y * W); o[0] = Q4.x; o[1] = Q4.y; o[2] = Q4.z; o[3] = Q4.w; }
-      }
-    }
-    hit_c[c] = hit; t_c[c] = t;
-  }
-  wg_append<PREP_CHUNKS>(hit_c, t_c, list, hdr);
-}
-
-template <bool CAM, bool MOTION = false>
-__global__ __launch_bounds__(256) void rt_path_prepare_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo) {
-  path_prepare<CAM, MOTION, false>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, mo, PrepNoEmi{});
-}
-
-// (the frame with emissive geometry, vxrt_render_path_emissive: Lit_0 + Emi(h_0) per pixel)
-template <bool CAM>
-__global__ __launch_bounds__(256) void rt_path_prepare_emissive_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
-    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
-    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
-    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float scale) {
-  path_prepare<CAM, false, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepEmi{scale});
-}
-
-// start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
-__global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
-    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, uint32_t* __restrict__ live) {
-  const uint64_t want = (uint64_t)hdr[0] * ns;
-  const uint32_t total = want < cap ? (uint32_t)want : cap;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i == 0) hdr[1] = total;
-  if (i >= total) return;
-  const uint32_t t = list[i / ns];
-  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
-  live[i] = i;
-}
-
-// the bounce rays of one depth: ray q leaves the last vertex of slot live[q] (user seed = seed + depth); zeroes the next depth's count
-__global__ __launch_bounds__(256) void rt_path_bounce_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
-    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
-    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, unsigned long long* rays_traced) {
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  if (q == 0) {
-    *n_next = 0u;
-    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one)
-  }
-  if (q >= total) return;
-  const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
-  const uint32_t x = t % W, y = y0 + t / W;
-  const float4 I = pI[slot], N = pN[slot], D = pD[slot];
-  float r6[6];
-  ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
-  float* o = rays + (size_t)q * 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[k] = r6[k];
-}
-
-// The emitter ray of the header's "Emissive geometry", operation for operation: from hash output `seed`, the surface point I and the
-// facing normal N' (nx, ny, nz).  ray6 = (o, w), tmax, G[3], e = the emitter chosen; false = skipped: the ray nothing can hit, tmax = -1,
-// G = 0.  The cumulative table is read from global memory (a binary search of at most 17 steps; n <= 65,536).
-__device__ __forceinline__ bool emitter_sample(const EmitterTab& tab, float scale, uint32_t seed, float Ix, float Iy, float Iz, float nx, float ny, float nz,
-                                               float (&ray6)[6], float& tmax, float (&G)[3], uint32_t& e_out) {
-  if (seed == 0u) seed = 1u;
-  seed ^= seed << 13; seed ^= seed >> 17; seed ^= seed << 5;
-  const uint32_t r0 = seed;
-  float a = random_float(seed);
-  float b = random_float(seed);
-  const uint32_t t = (uint32_t)(((uint64_t)r0 * tab.Q) >> 32);
-  uint32_t lo = 0u, hi = tab.n - 1u;   // the smallest e with cum[e] > t is in [lo, hi] (cum[n - 1] = Q > t)
-  for (int k = 0; k < 17; ++k) {
-    if (lo >= hi) break;
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (tab.cum[mid] > t) hi = mid; else lo = mid + 1u;
-  }
-  const uint32_t e = lo;
-  e_out = e;
-  const float* T = tab.tri + (size_t)e * 12;
-  const float v0x = T[0], v0y = T[1], v0z = T[2], e1x = T[3], e1y = T[4], e1z = T[5], e2x = T[6], e2y = T[7], e2z = T[8];
-  if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
-  const float Px = (v0x + a * e1x) + b * e2x, Py = (v0y + a * e1y) + b * e2y, Pz = (v0z + a * e1z) + b * e2z;
-  const float ox = Ix + nx * 0.001f, oy = Iy + ny * 0.001f, oz = Iz + nz * 0.001f;
-  const float vx = Px - ox, vy = Py - oy, vz = Pz - oz;
-  const float d2 = (vx * vx + vy * vy) + vz * vz;
-  const float d = sqrtf(d2);
-  const float wx = vx / d, wy = vy / d, wz = vz / d;
-  const float cosx = std_max(0.0f, (nx * wx + ny * wy) + nz * wz);
-  const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
-  const float an = 0.5f * fabsf((cx * wx + cy * wy) + cz * wz);
-  const float den = (3.14159265f * d2) * ((float)tab.q[e] / (float)tab.Q);
-  G[0] = (((T[9] * scale) * cosx) * an) / den;
-  G[1] = (((T[10] * scale) * cosx) * an) / den;
-  G[2] = (((T[11] * scale) * cosx) * an) / den;
-  if (cosx == 0.0f || d2 == 0.0f || !isfinite(G[0]) || !isfinite(G[1]) || !isfinite(G[2])) {
-    ray6[0] = 0.f; ray6[1] = 0.f; ray6[2] = 0.f; ray6[3] = 1.f; ray6[4] = 1.f; ray6[5] = 1.f;
-    tmax = -1.0f;
-    G[0] = 0.f; G[1] = 0.f; G[2] = 0.f;
-    return false;
-  }
-  ray6[0] = ox; ray6[1] = oy; ray6[2] = oz; ray6[3] = wx; ray6[4] = wy; ray6[5] = wz;
-  tmax = d - 0.001f;
-  return true;
-}
-
-// rt_path_bounce_rays_kernel of a frame with emitter sampling (nee = 1): besides the bounce ray of slot live[q], the emitter ray of the
-// same vertex -- user seed (seed + depth) ^ 0x80000000 in the bounce ray's hash input -- with its tmax and G (w = 1: real; a skipped
-// one is not counted).  One atomic per workgroup on the ray counter for the emitter rays, thread 0's for the bounce rays.
-__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
-    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
-    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
-    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
-  __shared__ uint32_t s_real;
-  if (threadIdx.x == 0) s_real = 0u;
-  __syncthreads();
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  if (q == 0) {
-    *n_next = 0u;
-    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one bounce ray)
-  }
-  bool real = false;
-  if (q < total) {
-    const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
-    const uint32_t x = t % W, y = y0 + t / W;
-    const float4 I = pI[slot], N = pN[slot], D = pD[slot];
-    float r6[6];
-    ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
-    float* o = rays + (size_t)q * 6;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) o[k] = r6[k];
-    float nx = N.x, ny = N.y, nz = N.z;
-    if (nx * D.x + ny * D.y + nz * D.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // (N' as ao_sample_ray turns it)
-    const uint32_t seed = wang_hash((x + y * W) * spp + smp + 1u + (user_seed ^ 0x80000000u) * 0x9E3779B9u);
-    float e6[6], tm, G[3];
-    uint32_t e;
-    real = emitter_sample(tab, scale, seed, I.x, I.y, I.z, nx, ny, nz, e6, tm, G, e);
-    float* eo = erays + (size_t)q * 6;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) eo[k] = e6[k];
-    etmax[q] = tm;
-    eG[q] = make_float4(G[0], G[1], G[2], real ? 1.0f : 0.0f);
-  }
-  const unsigned long long m = __ballot(real);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
-  __syncthreads();
-  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
-}
-
-// vxrt_emitter_rays: the emitter ray of n caller-supplied (I, N') and hash outputs, one per thread
-__global__ __launch_bounds__(256) void rt_emitter_rays_kernel(EmitterTab tab, uint32_t n, const float* __restrict__ points, const uint32_t* __restrict__ seeds, float scale,
-    float* __restrict__ rays, float* __restrict__ tmax, float* __restrict__ weight3, uint32_t* __restrict__ emitter) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const float* pt = points + (size_t)i * 6;
-  float e6[6], tm, G[3];
-  uint32_t e;
-  emitter_sample(tab, scale, seeds[i], pt[0], pt[1], pt[2], pt[3], pt[4], pt[5], e6, tm, G, e);
-  float* o = rays + (size_t)i * 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[k] = e6[k];
-  tmax[i] = tm;
-  weight3[3 * (size_t)i] = G[0]; weight3[3 * (size_t)i + 1] = G[1]; weight3[3 * (size_t)i + 2] = G[2];
-  emitter[i] = e;
-}
-
-// the occlusion rays of one depth (light sampling): one per bounce ray that hit; a miss gets a ray nothing can hit, which is not
-// counted (see rt_bounce_shadow_rays_kernel).  One atomic per workgroup on the ray counter.
-__global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams p, uint32_t cap, const uint32_t* n_live, const float* __restrict__ rays,
-    const HitRec* __restrict__ hits, float* __restrict__ srays, float* __restrict__ stmax, unsigned long long* rays_traced) {
-  __shared__ uint32_t s_real;
-  if (threadIdx.x == 0) s_real = 0u;
-  __syncthreads();
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  bool real = false;
-  if (q < total) {
-    const float* rp = rays + (size_t)q * 6;
-    float* sp = srays + (size_t)q * 6;
-    const float d = hits[q].dist;
-    if (d == RT_LARGE_FLOAT) {
-      sp[0] = 0.f; sp[1] = 0.f; sp[2] = 0.f; sp[3] = 1.f; sp[4] = 1.f; sp[5] = 1.f;
-      stmax[q] = -1.0f;
-    } else {
-      float sdist;
-      shadow_ray(p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], d, sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sdist);
-      stmax[q] = sdist;
-      real = true;
-    }
-  }
-  const unsigned long long m = __ballot(real);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
-  __syncthreads();
-  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
-}
-
-// the scatter step of one depth.  Miss: Lc = Lc + thr * background, the path ends.  Hit: Lc = Lc + thr * Lit (occluded iff shits[q]
-// hit), then thr = thr * Alb and the hit becomes the slot's last vertex; with `next` the slot is appended to the next depth's live list.
-// (EMI: the frame with emissive geometry, the header's "Emissive geometry".  1, nee = 0: a hit adds thr * Emi(h') after thr * Lit.
-//  2, nee = 1: before the miss / hit arm Lc = Lc + thr * G for an emitter ray that is real -- eG[q].w -- and was not blocked -- ehits[q].)
-struct ScatterEmi { float scale; const HitRec* ehits; const float4* eG; };
-struct ScatterNoEmi {};
-template <int EMI>
-__device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadeParams& p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
-    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>& em) {
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  bool go[1] = {false};
-  uint32_t val[1] = {0u};
-  if (q < total) {
-    const uint32_t slot = live[q];
-    const float* rp = rays + (size_t)q * 6;
-    HitRec h = hits[q];
-    h.blasIdx &= 0x7fffffffu;
-    float4 L = pL[slot];
-    const float4 T = pT[slot];
-    if constexpr (EMI == 2) {
-      const float4 G = em.eG[q];
-      if (G.w != 0.f && em.ehits[q].dist == RT_LARGE_FLOAT) { L.x = L.x + T.x * G.x; L.y = L.y + T.y * G.y; L.z = L.z + T.z * G.z; }
-    }
-    if (h.dist == RT_LARGE_FLOAT) {
-      L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
-    } else {
-      const bool occ = shits != nullptr && shits[q].dist != RT_LARGE_FLOAT;
-      float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
-      shade_terms<false>(sc, p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-      float thr = 1.0f;
-      thr *= refl;
-      r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
-      L.x = L.x + T.x * r; L.y = L.y + T.y * g; L.z = L.z + T.z * b;
-      if constexpr (EMI == 1) {
-        float e3[3];
-        if (emission(sc, h.triIdx, em.scale, e3)) { L.x = L.x + T.x * e3[0]; L.y = L.y + T.y * e3[1]; L.z = L.z + T.z * e3[2]; }
-      }
-      if (next) {
-        pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
-        pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
-        pN[slot] = make_float4(Nx, Ny, Nz, 0.f);
-        pD[slot] = make_float4(rp[3], rp[4], rp[5], 0.f);
-        go[0] = true; val[0] = slot;
-      }
-    }
-    pL[slot] = L;
-  }
-  if (next) wg_append<1>(go, val, next, n_next);   // (uniform over the launch)
-}
-
-__global__ __launch_bounds__(256) void rt_path_scatter_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
-    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next) {
-  path_scatter<0>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, ScatterNoEmi{});
-}
-
-// (the frame with emissive geometry: EMI = 1 for nee = 0, 2 for nee = 1)
-template <int EMI>
-__global__ __launch_bounds__(256) void rt_path_scatter_emissive_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
-    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next, ScatterEmi em) {
-  path_scatter<EMI>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em);
-}
-
-// after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
-// starts it); one thread per listed pixel
-__global__ __launch_bounds__(256) void rt_path_accumulate_kernel(uint32_t n, const uint32_t* __restrict__ list, const uint32_t* __restrict__ hdr, uint32_t ns,
-    uint32_t first, const float4* __restrict__ pL, float4* __restrict__ acc) {
-  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= min(hdr[0], n)) return;
-  const uint32_t t = list[j];
-  const float4* L = pL + (size_t)j * ns;
-  float4 a = first ? L[0] : acc[t];
-  for (uint32_t s = first ? 1u : 0u; s < ns; ++s) { const float4 c = L[s]; a.x = a.x + c.x; a.y = a.y + c.y; a.z = a.z + c.z; }
-  acc[t] = a;
-}
-
-// colour = acc / spp, pack, write.  flat (bounces = 0): every sample's Lc is the pixel's Lit, summed here the same way.
-__global__ __launch_bounds__(256) void rt_path_final_kernel(uint32_t n, uint32_t W, uint32_t y0, const float4* __restrict__ geo, const float4* __restrict__ lit,
-    const float4* __restrict__ acc, uint32_t spp, uint32_t flat, uint32_t* __restrict__ dst, float* __restrict__ colors_out) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= n) return;
-  const uint32_t x = t % W, y = y0 + t / W;
-  const size_t e = (size_t)x + (size_t)y * W;
-  const float4 c = lit[t];
-  float r = c.x, g = c.y, b = c.z;   // (a miss: the background)
-  if (geo[t].w != 0.f) {
-    if (flat) { for (uint32_t s = 1; s < spp; ++s) { r = r + c.x; g = g + c.y; b = b + c.z; } }
-    else { const float4 a = acc[t]; r = a.x; g = a.y; b = a.z; }
-    const float f = (float)spp;
-    r = r / f; g = g / f; b = b / f;
-  }
-  dst[e] = pack_rgb8(r, g, b);
-  if (colors_out) { colors_out[3 * e] = r; colors_out[3 * e + 1] = g; colors_out[3 * e + 2] = b; }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Path frames with a sample count per pixel (vxrt_render_path_adaptive; the definition is the header's "Adaptive sampling", the launch
-// sequence is in render_path_counts_tail and DESIGN.md s2 "Adaptive sampling").  The paths of the frame are numbered in window order:
-// pixel t owns the cnt[t] paths g = off[t] .. off[t] + cnt[t] - 1, sample g - off[t]; batch b owns g in [b * cap, (b + 1) * cap), slot
-// g - b * cap.  The numbering comes from a scan in window order, so it is the same from run to run (the atomic-ordered list of hit
-// pixels is not).  The scan is three launches and no workgroup waits for another: per-block sums, one workgroup that scans the block
-// sums in passes with a running carry, per-pixel offsets.  rt_path_prepare_kernel, rt_path_occlusion_rays_kernel and
-// rt_path_scatter_kernel are the uniform frame's: they work on slots and live lists only.
-// ---------------------------------------------------------------------------------------------
-#define PT_SCAN_BLOCK 1024u   // pixels per scan block: 256 threads x 4 consecutive pixels
-#define PT_SCAN_PASS 1024u    // block sums per pass of rt_path_scan_kernel: its threads (one pass covers PT_SCAN_PASS * PT_SCAN_BLOCK pixels)
-
-// cnt[t] = clamp(counts[pixel of t], 1, spp_cap) for a pixel with a hit, 0 for a miss (its count is not read); bsum[block] = the sum of
-// the block's cnt (at most 1,024 x 4,096)
-__global__ __launch_bounds__(256) void rt_path_counts_kernel(uint32_t n, uint32_t W, uint32_t y0, uint32_t spp_cap, const float4* __restrict__ geo,
-    const uint32_t* __restrict__ counts, uint32_t* __restrict__ cnt, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t s_w[4];
-  const uint32_t t0 = blockIdx.x * PT_SCAN_BLOCK + threadIdx.x * 4u;
-  uint32_t sum = 0u;
-#pragma unroll
-  for (uint32_t c = 0; c < 4u; ++c) {
-    const uint32_t t = t0 + c;
-    if (t < n) {
-      uint32_t v = 0u;
-      if (geo[t].w != 0.f) {
-        const uint32_t x = t % W, y = y0 + t / W;
-        v = min(max(counts[(size_t)x + (size_t)y * W], 1u), spp_cap);
-      }
-      cnt[t] = v;
-      sum += v;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-  if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) bsum[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-
-// boff[i] = the sum of bsum[0 .. i), 64 bit; *total = the sum of all nb.  ONE workgroup: pass k scans block sums [k * PT_SCAN_PASS,
-// (k + 1) * PT_SCAN_PASS) and every thread carries the running total into the next pass; the number of passes is known at entry.
-__global__ __launch_bounds__(1024) void rt_path_scan_kernel(uint32_t nb, const uint32_t* __restrict__ bsum, unsigned long long* __restrict__ boff,
-    unsigned long long* __restrict__ total) {
-  __shared__ unsigned long long s_w[PT_SCAN_PASS / 64u];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t passes = (nb + PT_SCAN_PASS - 1u) / PT_SCAN_PASS;
-  unsigned long long carry = 0ull;
-  for (uint32_t k = 0; k < passes; ++k) {
-    const uint32_t i = k * PT_SCAN_PASS + threadIdx.x;
-    const unsigned long long v = i < nb ? (unsigned long long)bsum[i] : 0ull;
-    unsigned long long inc = v;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    unsigned long long base = carry, pass_sum = 0ull;
-    for (uint32_t w = 0; w < PT_SCAN_PASS / 64u; ++w) { const unsigned long long x = s_w[w]; if (w < wave) base += x; pass_sum += x; }
-    if (i < nb) boff[i] = base + (inc - v);
-    carry += pass_sum;
-    __syncthreads();   // (s_w is written again by the next pass)
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
-// off[t] = boff[block of t] + the sum of cnt over the block's pixels before t
-__global__ __launch_bounds__(256) void rt_path_offsets_kernel(uint32_t n, const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ boff,
-    unsigned long long* __restrict__ off) {
-  __shared__ uint32_t s_w[4];
-  const uint32_t t0 = blockIdx.x * PT_SCAN_BLOCK + threadIdx.x * 4u;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t v[4], sum = 0u;
-#pragma unroll
-  for (uint32_t c = 0; c < 4u; ++c) { v[c] = t0 + c < n ? cnt[t0 + c] : 0u; sum += v[c]; }
-  uint32_t inc = sum;
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
-  if (lane == 63u) s_w[wave] = inc;
-  __syncthreads();
-  unsigned long long base = boff[blockIdx.x] + (unsigned long long)(inc - sum);
-  for (uint32_t w = 0; w < wave; ++w) base += s_w[w];
-#pragma unroll
-  for (uint32_t c = 0; c < 4u; ++c) {
-    if (t0 + c < n) off[t0 + c] = base;
-    base += v[c];
-  }
-}
-
-// start of the batch that owns paths [g0, g0 + cap): slot i is path g = g0 + i, live while g < *total.  Its pixel is the last t with
-// off[t] <= g -- a pixel without samples shares its offset with its successor, so that t has samples -- found by a binary search of at
-// most 32 steps (n < 2^31); the slot keeps (pixel, sample) and takes the pixel's primary vertex as rt_path_start_kernel does.
-// hdr[1] = the batch's live paths (0 for a batch past the end of the frame's paths).
-__global__ __launch_bounds__(256) void rt_path_start_counts_kernel(uint32_t cap, unsigned long long g0, uint32_t n, const unsigned long long* __restrict__ total,
-    const unsigned long long* __restrict__ off, uint32_t* hdr,
-    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
-    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, uint32_t* __restrict__ live,
-    uint32_t* __restrict__ spix, uint32_t* __restrict__ ssmp) {
-  const unsigned long long tot = *total;
-  const unsigned long long left = tot > g0 ? tot - g0 : 0ull;
-  const uint32_t n_live = left < (unsigned long long)cap ? (uint32_t)left : cap;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i == 0) hdr[1] = n_live;
-  if (i >= n_live) return;
-  const unsigned long long g = g0 + i;
-  uint32_t lo = 0u, hi = n;   // off[lo] <= g < off[hi] (off[n] = *total)
-  for (int k = 0; k < 32; ++k) {
-    if (hi - lo <= 1u) break;
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= g) lo = mid; else hi = mid;
-  }
-  const uint32_t t = lo;
-  spix[i] = t; ssmp[i] = (uint32_t)(g - off[t]);
-  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
-  live[i] = i;
-}
-
-// rt_path_bounce_rays_kernel with the slot's pixel, sample and the pixel's own sample count in place of slot / ns, s0 + slot % ns and spp
-__global__ __launch_bounds__(256) void rt_path_bounce_rays_counts_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
-    const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
-    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
-    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, unsigned long long* rays_traced) {
-  const uint32_t total = min(*n_live, cap);
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  if (q == 0) {
-    *n_next = 0u;
-    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one)
-  }
-  if (q >= total) return;
-  const uint32_t slot = live[q], t = spix[slot], smp = ssmp[slot];
-  const uint32_t x = t % W, y = y0 + t / W;
-  const float4 I = pI[slot], N = pN[slot], D = pD[slot];
-  float r6[6];
-  ao_sample_ray(x, y, W, cnt[t], smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
-  float* o = rays + (size_t)q * 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[k] = r6[k];
-}
-
-// after a batch's last depth, one thread per pixel of the window: the Lc of the pixel's samples that are in the batch [g0, g0 + cap)
-// are added to its accumulator in ascending sample order; the pixel's first sample starts it.  A pixel's samples are contiguous in g
-// and may straddle batches; the trip count is at most the pixel's count.
-__global__ __launch_bounds__(256) void rt_path_accumulate_counts_kernel(uint32_t n, uint32_t cap, unsigned long long g0, const uint32_t* __restrict__ cnt,
-    const unsigned long long* __restrict__ off, const float4* __restrict__ pL, float4* __restrict__ acc) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= n) return;
-  const uint32_t c = cnt[t];
-  if (c == 0u) return;
-  const unsigned long long o = off[t], g1 = g0 + cap;
-  const unsigned long long lo = o > g0 ? o : g0, hi = o + c < g1 ? o + c : g1;
-  if (lo >= hi) return;
-  const float4* L = pL + (size_t)(lo - g0);
-  const uint32_t k = (uint32_t)(hi - lo);
-  const bool first = lo == o;
-  float4 a = first ? L[0] : acc[t];
-  for (uint32_t s = first ? 1u : 0u; s < k; ++s) { const float4 v = L[s]; a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z; }
-  acc[t] = a;
-}
-
-// after the last batch: acc[t] = acc[t] / (float)cnt[t] per channel (flat, bounces = 0: of the flat sum of Lit_0, formed here as
-// rt_path_final_kernel forms it).  What ends the frame then divides by 1.0f, which changes no bit.
-__global__ __launch_bounds__(256) void rt_path_divide_counts_kernel(uint32_t n, const uint32_t* __restrict__ cnt, const float4* __restrict__ lit, uint32_t flat,
-    float4* __restrict__ acc) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= n) return;
-  const uint32_t c = cnt[t];
-  if (c == 0u) return;
-  float r, g, b;
-  if (flat) { const float4 l = lit[t]; r = l.x; g = l.y; b = l.z; for (uint32_t s = 1; s < c; ++s) { r = r + l.x; g = g + l.y; b = b + l.z; } }
-  else { const float4 a = acc[t]; r = a.x; g = a.y; b = a.z; }
-  const float f = (float)c;
-  acc[t] = make_float4(r / f, g / f, b / f, 0.f);
-}
-
-// vxrt_sample_counts (the header's "Adaptive sampling"): one entry per thread, every symbol one fp32 operation; the counts written are
-// summed per workgroup (at most 256 x 4,096) and added to *total with one 64-bit atomic
-__global__ __launch_bounds__(256) void rt_sample_counts_kernel(uint32_t n, const float* __restrict__ variance, const uint32_t* __restrict__ prev, float gain,
-    uint32_t min_spp, uint32_t max_spp, uint32_t* __restrict__ counts, unsigned long long* total) {
-  __shared__ uint32_t s_w[4];
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  uint32_t v = 0u;
-  if (i < n) {
-    const float m = prev ? (float)min(max(prev[i], 1u), 4096u) : 1.0f;
-    const float x = (variance[i] * m) * gain;
-    const float c = ceilf(x);
-    v = c > (float)min_spp ? (c < (float)max_spp ? (uint32_t)c : max_spp) : min_spp;
-    counts[i] = v;
-  }
-  if (total) {   // (uniform over the launch)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const uint32_t sum = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-      if (sum) atomicAdd(total, (unsigned long long)sum);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // Secondary rays re-sorted before they are traced (north_star: "ray packets re-sorted ... to tame divergence").
 // The rays of a bounce / AO pass leave the compaction in pixel order with directions spread over a hemisphere: a wavefront of
 // 64 consecutive rays shares origins but not directions.  Counting sort by key = direction octant x origin cell (the 16x16-pixel
@@ -941,32 +293,19 @@ __global__ __launch_bounds__(256) void rt_bin_scatter_kernel(uint64_t cap, const
 }
 
 // ---------------------------------------------------------------------------------------------
-// host: the three tails render_common (rt_kernels.hip) ends such a frame with
+// host: the two tails render_common (rt_kernels.hip) ends such a frame with
 // ---------------------------------------------------------------------------------------------
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
-// Paths per batch of a path frame (VXRT_PATH_BATCH).  A path costs 136 bytes of frame-context storage -- 80 of state (I, N, dir, Lc, thr:
-// five float4), 24 + 24 of bounce ray and hit record, 2 x 4 of live-list entries -- and 52 more with light sampling (occlusion ray, tmax,
-// hit record): 4 Mi paths are 0.53 / 0.73 GiB per frame context, and at 1920x1080 two samples per batch, i.e. ray-buffer launches of up to
-// 4 M rays for a machine that holds 0.4 M lanes of the traversal kernel -- launch ramps and tails stay a small part of each.
-#define PATH_BATCH_PATHS (4ull << 20)
 #define AO_BATCH_RAYS (32ull << 20)   // rays per batch of an ambient-occlusion frame
 
-// The three measurement knobs of this unit (docs/KNOBS.md), read from the environment once per process, together: on the first call that
-// asks for one.  Each keeps the parsing it always had.  With VXRT_DEBUG set, the values read go to stderr in one line, so that a test
-// that runs a child process with a knob can see that the child took it.
-struct SecondaryKnobs {
-  uint64_t path_batch;   // paths per batch of a path frame (see render_path_tail)
-  uint64_t ao_batch;     // rays per batch of an ambient-occlusion frame (see render_ao_tail); VXRT_AO_BATCH, parsed as VXRT_PATH_BATCH is
-  // VXRT_SORT_SECONDARY=1: trace the secondary rays in (direction octant, origin cell) order instead of generation order.  OFF by
-  // default: measured SLOWER on both passes that used it then (diffuse bounce 1.53 -> 1.95 ms, 10M-triangle hairball AO 9.2 -> 16.6 ms,
-  // profiles/r02_f_secondary_sort.txt).  The traversal is bound by per-lane VALU work, which coherence does not reduce, and the
-  // generation order already puts the 16 samples of one pixel (AO) / 64 neighbouring pixels (bounce) side by side.
-  bool sort_secondary;
-};
-static const SecondaryKnobs& secondary_knobs() {
+// The three measurement knobs of the secondary tails (SecondaryKnobs, rt_internal.h; docs/KNOBS.md), read from the environment once per
+// process, together: on the first call, from this unit or from rt_path.hip, that asks for one.  Each keeps the parsing it always had.
+// With VXRT_DEBUG set, the values read go to stderr in one line, so that a test that runs a child process with a knob can see that the
+// child took it.
+const SecondaryKnobs& secondary_knobs() {
   static const SecondaryKnobs knobs = [] {
     SecondaryKnobs k;
     { const char* e = getenv("VXRT_PATH_BATCH"); const long long v = e ? atoll(e) : 0; k.path_batch = v > 0 ? (uint64_t)v : PATH_BATCH_PATHS; }
@@ -1105,200 +444,5 @@ int render_ao_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const S
   }
   hipLaunchKernelGGL(rt_ao_final_kernel, grid, block, 0, s, n, width, y0, (const float4*)c->ao_geo, (const float4*)c->ao_col, (const uint32_t*)c->ao_cnt,
                      ao->spp, r.dst, r.colors, r.unoccluded, r.counters);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// What both tails of a path frame begin with: the context's buffers for n pixels and batches of path_cap paths (per pixel; per path --
-// none without bounces; per occlusion ray -- none without light sampling; grown behind the stream), the zeroed header, and the prepare launch
-static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab, uint64_t n, uint64_t path_cap) {
-  const SceneDev& sc = a->dev;
-  const uint32_t width = r.width, y0 = r.y0;
-  hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t shadow_cap = r.path->shadow ? path_cap : 0;
-  if (!c->pt_hdr && hipMalloc((void**)&c->pt_hdr, 16) != hipSuccess) return -1;
-  if (!grow_device({{(void**)&c->pt_geo, 16}, {(void**)&c->pt_nrm, 16}, {(void**)&c->pt_dir, 16}, {(void**)&c->pt_lit, 16}, {(void**)&c->pt_alb, 16},
-                    {(void**)&c->pt_acc, 16}, {(void**)&c->pt_list, 4}}, &c->pt_cap, n, GrowSync::STREAM, s)) return -1;
-  if (!grow_device({{(void**)&c->pt_I, 16}, {(void**)&c->pt_N, 16}, {(void**)&c->pt_D, 16}, {(void**)&c->pt_L, 16}, {(void**)&c->pt_T, 16}, {(void**)&c->pt_live[0], 4},
-                    {(void**)&c->pt_live[1], 4}, {(void**)&c->pt_rays, 24}, {(void**)&c->pt_hits, sizeof(HitRec)}}, &c->pt_path_cap, path_cap, GrowSync::STREAM, s)) return -1;
-  if (!grow_device({{(void**)&c->pt_srays, 24}, {(void**)&c->pt_stmax, 4}, {(void**)&c->pt_shits, sizeof(HitRec)}}, &c->pt_shadow_cap, shadow_cap, GrowSync::STREAM, s)) return -1;
-  if (r.motion && !grow_device({{(void**)&c->mo_pos, 16}, {(void**)&c->mo_nrm, 16}}, &c->mo_cap, n, GrowSync::STREAM, s)) return -1;
-  const uint32_t n32 = (uint32_t)n;
-  const dim3 block(256), pgrid((n32 + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS));
-  if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
-  if (r.emissive) {   // (never with motion: check_request)
-    hipLaunchKernelGGL(r.cams ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab,
-                       (const HitRec*)c->hitbuf, c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, r.emissive->scale);
-  } else if (r.motion) {   // (a camera frame: check_request)
-    hipLaunchKernelGGL((rt_path_prepare_kernel<true, true>), pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
-                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position});
-  } else {
-    hipLaunchKernelGGL(r.cams ? rt_path_prepare_kernel<true> : rt_path_prepare_kernel<false>, pgrid, block, 0, s, sc, p, n32, width, y0, utab, vtab, (const HitRec*)c->hitbuf,
-                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, PrepNoMotion{});
-  }
-  if (hipGetLastError() != hipSuccess) return -1;
-  c->ctl_dirty = false;
-  return 0;
-}
-
-static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
-
-// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
-// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
-// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
-// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
-// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
-// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
-// A denoised frame with iterations or a history ends in rt_denoise.hip instead (render_denoise_tail: demodulate, temporal step, initial
-// variance, a-trous passes -- that unit owns the order); one without either gets its guide outputs there and ends here as every path frame.
-int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
-  if (r.sample_counts) return render_path_counts_tail(a, c, r, p, utab, vtab);   // (a count per pixel: the tail below this one)
-  const SceneDev& sc = a->dev;
-  const vxrt_path_params_t& pp = *r.path;
-  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
-  hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull) return -1;
-  const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
-  const uint64_t path_cap = pp.bounces ? n * ns : 0;
-  if (path_cap > 0x7fffffffull) return -1;
-  // emissive geometry (the header's "Emissive geometry"): 0 none, 1 emission at bounce hits, 2 emitter sampling -- one emitter ray per
-  // live path and depth, generated with the bounce ray and traced by a second any-hit launch
-  const int emi = r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
-  if (emi == 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
-                               path_cap, GrowSync::STREAM, s)) return -1;
-  if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
-  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
-  const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u);
-  for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
-    const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
-    hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
-                       (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
-    for (uint32_t d = 0; d < pp.bounces; ++d) {
-      uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
-      uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
-      const uint32_t* live = c->pt_live[d & 1u];
-      const bool more = d + 1u < pp.bounces;
-      if (emi == 2)
-        hipLaunchKernelGGL(rt_path_bounce_emitter_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
-                           (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, emitter_tab(a),
-                           r.emissive->scale, c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
-      else
-        hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
-                           (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
-      if (trace_on_ctx(a, c, c->pt_rays, (uint64_t)n * k, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
-      if (pp.shadow) {
-        hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                           c->pt_srays, c->pt_stmax, r.counters);
-        if (trace_on_ctx(a, c, c->pt_srays, (uint64_t)n * k, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-      }
-      if (emi == 2 && trace_on_ctx(a, c, c->pt_erays, (uint64_t)n * k, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-      const HitRec* shits = pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr;
-      uint32_t* next = more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr;
-      if (emi)
-        hipLaunchKernelGGL(emi == 2 ? rt_path_scatter_emissive_kernel<2> : rt_path_scatter_emissive_kernel<1>, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
-                           (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
-                           ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
-      else
-        hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                           shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next);
-    }
-    hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
-                       (const float4*)c->pt_L, c->pt_acc);
-  }
-  if (r.denoise && (r.denoise->iterations || r.temporal)) return render_denoise_tail(c, r, n32);
-  if (r.denoise && r.aov && render_denoise_aov(c, r, n32) != 0) return -1;   // (no iterations: the guide outputs, then the path frame's own end)
-  hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
-                     pp.spp, pp.bounces == 0 ? 1u : 0u, r.dst, r.colors);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// Tail of a path frame with a sample count per pixel (r.sample_counts; path->spp is the cap).  The prepare launch of every path frame;
-// then the clamped counts and their scan in window order (three launches: block sums, one workgroup over the block sums, per-pixel
-// offsets); then batches of cap = clamp(VXRT_PATH_BATCH, 1, pixels * spp) consecutive paths, each the depth loop of render_path_tail
-// with the two kernels that read a slot's pixel and sample from the slot; after the last batch the accumulators are divided by their
-// pixel's count and the frame ends as every path frame, with spp = 1.  The number of paths stays on the device, so the host issues
-// ceil(pixels * spp / cap) batches whatever the counts: a batch past the end starts with zero live paths and its launches fall through.
-// Storage per path is bounded by cap.  No host synchronisation unless a buffer grows.
-static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
-  const SceneDev& sc = a->dev;
-  const vxrt_path_params_t& pp = *r.path;
-  const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
-  hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t n = (uint64_t)width * (y1 - y0);
-  if (n > 0x7fffffffull) return -1;
-  const uint64_t all = n * pp.spp;   // (the most paths the counts can ask for)
-  const uint64_t batch = std::min<uint64_t>(std::max<uint64_t>(1, secondary_knobs().path_batch), all);
-  if (batch > 0x7fffffffull) return -1;
-  const uint64_t path_cap = pp.bounces ? batch : 0;
-  const uint64_t n_blocks = (n + PT_SCAN_BLOCK - 1u) / PT_SCAN_BLOCK;
-  if (!c->pt_ctot && hipMalloc((void**)&c->pt_ctot, 8) != hipSuccess) return -1;
-  if (!grow_device({{(void**)&c->pt_cnt, 4}, {(void**)&c->pt_off, 8}}, &c->pt_cnt_cap, n, GrowSync::STREAM, s)) return -1;
-  if (!grow_device({{(void**)&c->pt_bsum, 4}, {(void**)&c->pt_boff, 8}}, &c->pt_blk_cap, n_blocks, GrowSync::STREAM, s)) return -1;
-  if (!grow_device({{(void**)&c->pt_spix, 4}, {(void**)&c->pt_ssmp, 4}}, &c->pt_slot_cap, path_cap, GrowSync::STREAM, s)) return -1;
-  if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
-  const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
-  const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u), sgrid((uint32_t)n_blocks);
-  hipLaunchKernelGGL(rt_path_counts_kernel, sgrid, block, 0, s, n32, width, y0, pp.spp, (const float4*)c->pt_geo, r.sample_counts, c->pt_cnt, c->pt_bsum);
-  hipLaunchKernelGGL(rt_path_scan_kernel, dim3(1), dim3(PT_SCAN_PASS), 0, s, (uint32_t)n_blocks, (const uint32_t*)c->pt_bsum, c->pt_boff, c->pt_ctot);
-  hipLaunchKernelGGL(rt_path_offsets_kernel, sgrid, block, 0, s, n32, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_boff, c->pt_off);
-  if (hipGetLastError() != hipSuccess) return -1;
-  const uint64_t n_batches = pp.bounces ? (all + batch - 1) / batch : 0;
-  for (uint64_t b = 0; b < n_batches; ++b) {
-    const unsigned long long g0 = b * batch;   // the batch's first path
-    hipLaunchKernelGGL(rt_path_start_counts_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
-                       (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
-                       c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0], c->pt_spix, c->pt_ssmp);
-    for (uint32_t d = 0; d < pp.bounces; ++d) {
-      uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
-      uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
-      const uint32_t* live = c->pt_live[d & 1u];
-      const bool more = d + 1u < pp.bounces;
-      hipLaunchKernelGGL(rt_path_bounce_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp,
-                         (const uint32_t*)c->pt_cnt, live, (const uint32_t*)n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
-                         c->pt_rays, r.counters);
-      if (trace_on_ctx(a, c, c->pt_rays, cap, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
-      if (pp.shadow) {
-        hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                           c->pt_srays, c->pt_stmax, r.counters);
-        if (trace_on_ctx(a, c, c->pt_srays, cap, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-      }
-      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                         pp.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T,
-                         more ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr, n_next);
-    }
-    hipLaunchKernelGGL(rt_path_accumulate_counts_kernel, grid, block, 0, s, n32, cap, g0, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_off,
-                       (const float4*)c->pt_L, c->pt_acc);
-  }
-  hipLaunchKernelGGL(rt_path_divide_counts_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_cnt, (const float4*)c->pt_lit, pp.bounces == 0 ? 1u : 0u, c->pt_acc);
-  if (hipGetLastError() != hipSuccess) return -1;
-  // (the accumulators hold the colours: what ends the frame divides by spp = 1 and takes no flat sum; dn_frame passes the same)
-  if (r.denoise && (r.denoise->iterations || r.temporal)) return render_denoise_tail(c, r, n32);
-  if (r.denoise && r.aov && render_denoise_aov(c, r, n32) != 0) return -1;
-  hipLaunchKernelGGL(rt_path_final_kernel, grid, block, 0, s, n32, width, y0, (const float4*)c->pt_geo, (const float4*)c->pt_lit, (const float4*)c->pt_acc,
-                     1u, 0u, r.dst, r.colors);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// vxrt_sample_counts behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
-int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
-                         unsigned long long* total, hipStream_t s) {
-  hipLaunchKernelGGL(rt_sample_counts_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, variance, prev_counts, prm->gain, prm->min_spp, prm->max_spp, counts, total);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// vxrt_emitter_rays behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
-int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                        uint32_t* emitter, hipStream_t s) {
-  hipLaunchKernelGGL(rt_emitter_rays_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), n, points, seeds, scale, rays, tmax, weight3, emitter);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// The previous-position guide of caller-owned hit records (see the header, "Motion"): one launch, asynchronous on `stream`
-extern "C" int vxrt_previous_positions(vxrt_accel_t* a, uint32_t n, const vxrt_hit_t* hits, float* prev_position4, float* prev_normal4, void* stream) {
-  if (!a || a->stale || a->motion_what == 0u || !a->ref.triEx) return -1;
-  if (!hits || !prev_position4 || !prev_normal4 || (((uintptr_t)prev_position4 | (uintptr_t)prev_normal4) & 15u) != 0) return -1;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(rt_previous_positions_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, a->dev, motion_src(a), n, (const HitRec*)hits,
-                     (float4*)prev_position4, (float4*)prev_normal4);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

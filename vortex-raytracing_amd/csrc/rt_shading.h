@@ -1,6 +1,7 @@
-// Device arithmetic of shading that the frame kernels (rt_kernels.hip) and the passes of the secondary tails (rt_secondary.hip)
-// share: the closest-hit / miss shader's terms, the shadow, mirror, camera and sample rays, the tile-major index of a hit record.
-// Each unit compiles its own copy; every function is written once, here, so that both restate the reference in the same operations.
+// Device arithmetic of shading that the frame kernels (rt_kernels.hip) and the passes of the secondary tails (rt_secondary.hip,
+// rt_path.hip) share: the closest-hit / miss shader's terms, the shadow, mirror, camera and sample rays, the tile-major index of a hit
+// record, and the workgroup's list append of the two tails' prepare kernels (wg_append, PREP_CHUNKS).
+// Each unit compiles its own copy; every function is written once, here, so that all restate the reference in the same operations.
 // (shade_terms and shade_eval are plain templates, the rest is __forceinline__: the inliner's decisions inside the frame kernels
 // depend on it.)  pack_rgb8, f2i_x86 and std_min, which rt_denoise.hip takes as well, are in rt_internal.h.
 #pragma once
@@ -238,4 +239,34 @@ __device__ __forceinline__ bool alpha_rejects(const SceneDev& sc, const uint8_t*
 // `lr` = local row of the window: rows are counted through the window's tile rows (8 each) in order.
 __device__ __forceinline__ size_t hit_index(uint32_t x, uint32_t lr, uint32_t tiles_x) {
   return ((size_t)(lr >> 3) * tiles_x + (x >> 3)) * 64u + ((lr & 7u) << 3) + (x & 7u);
+}
+
+// The hit pixels of a frame are appended to one list.  One atomic per wavefront on the list's counter (32,400 for a 1080p frame, all on
+// one address, ~10 ns apart) was 0.3 of the AO prepare kernel's 0.37 ms: a workgroup now counts the hits of 1,024 pixels in LDS and
+// appends once.
+#define PREP_CHUNKS 4   // pixels per thread of the two prepare kernels: one list-append atomic per 1,024 pixels
+// Append value[c] of every thread with flag[c] to list[] (its length in *counter; the order is arbitrary): the workgroup counts in LDS
+// and does one atomic.  Every thread of the workgroup calls it.
+template <int C>
+__device__ __forceinline__ void wg_append(const bool (&flag)[C], const uint32_t (&value)[C], uint32_t* __restrict__ list, uint32_t* counter) {
+  __shared__ uint32_t s_cnt[C][4];
+  __shared__ uint32_t s_base;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t off[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const unsigned long long m = __ballot(flag[c]);
+    off[c] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[c][wv] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int c = 0; c < C; ++c) for (int w = 0; w < 4; ++w) { const uint32_t v = s_cnt[c][w]; s_cnt[c][w] = tot; tot += v; }
+    s_base = tot ? atomicAdd(counter, tot) : 0u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+    if (flag[c]) list[s_base + s_cnt[c][wv] + off[c]] = value[c];
 }

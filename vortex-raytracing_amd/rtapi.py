@@ -671,7 +671,7 @@ class VarianceParams(C.Structure):   # vxrt_variance_params_t
     _fields_ = [("epsilon", C.c_float), ("min_len", C.c_uint32), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-ADAPTIVE_SCAN_BLOCK = 1024                        # PT_SCAN_BLOCK (rt_secondary.hip): pixels per block of the counts' scan
+ADAPTIVE_SCAN_BLOCK = 1024                        # PT_SCAN_BLOCK (rt_path.hip): pixels per block of the counts' scan
 ADAPTIVE_SCAN_PASS = 1024 * ADAPTIVE_SCAN_BLOCK   # PT_SCAN_PASS blocks: pixels one pass of the single-workgroup scan covers
 
 
