@@ -1060,6 +1060,14 @@ int vxrt_debug_end_log(vxrt_accel_t* accel, unsigned long long* log);
 /* Diagnostic (tools/trace_phases.py): vxrt_trace_stats launches keep vxrt_render_wave_log's 16 u64 per wavefront in `log` (device
  * memory, 16 x 8,192 u64) from now on; NULL switches it off. */
 int vxrt_debug_trace_wave_log(vxrt_accel_t* accel, unsigned long long* log);
+/* Diagnostic (tools/child_counts.py): the wave-log launches (vxrt_render_wave_log, vxrt_render_interleaved_batch_wave_log) count their
+ * node-body runs by the largest number of valid children any node lane of the run holds.  out (host memory, 8 u64): [0..3] runs that took
+ * the ordered arm with at most 0, 1, 2 and with 3 or 4 valid children, [4..7] the same for the occlusion arm; sums over every wavefront
+ * of every such launch on the current device since the last reset.  Synchronises `stream`; reset != 0 zeroes the counts after reading.
+ * Frame launches only (the counting build of the timed traversal); the ray-buffer log of vxrt_debug_trace_wave_log is not classed.  The
+ * shader clocks the classing takes lie outside the wave log's node-body and leaf-body windows ([10], [11]), which stay comparable with
+ * logs taken before the classing existed; they are part of the wavefront's whole time ([12]). */
+int vxrt_debug_child_counts(unsigned long long* out, int reset, void* stream);
 /* diagnostic (tools/tile_tail.py): what frame context `ctx` learned for sets of `batch` frames -- per-tile cost (loop iterations of the
  * wavefront that traced it in the last launch; start clocks, durations and steal distances behind them after a wave-log launch) and the
  * tile order derived from it.  Returns the capacity in tiles. */

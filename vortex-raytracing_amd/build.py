@@ -75,7 +75,9 @@ def write_selectors():
 # The two LDS-staging variants north_star prescribes (top of the tree, triangles of shared leaves) lost their A/Bs and are compiled out of the
 # shipped library; tests/test_gpu_variants.py runs the parity tests on a library with BOTH switched on so that the code cannot rot.  Built
 # here (hipcc cross-compiles without a GPU) so that the GPU box loads it instead of compiling it.
-TEST_VARIANT_FLAGS = ["-DRT_TOP_NODES=84", "-DRT_LDS_STACK_RENDER=5", "-DRT_LDS_STACK_RENDER_PACKED=4", "-DRT_TRI_LDS=4", "-DRT_TRI_LDS_MIN=2"]
+# -DRT_ORDER_CHECK=1: the node step's paths without the sorting network (RT_ORDER_PATHS) evaluate the network as well and report a
+# difference in the status word (tests/test_gpu_order_paths.py runs its cases on this library too).
+TEST_VARIANT_FLAGS = ["-DRT_TOP_NODES=84", "-DRT_LDS_STACK_RENDER=5", "-DRT_LDS_STACK_RENDER_PACKED=4", "-DRT_TRI_LDS=4", "-DRT_TRI_LDS_MIN=2", "-DRT_ORDER_CHECK=1"]
 
 
 def build_test_variant(force=False):

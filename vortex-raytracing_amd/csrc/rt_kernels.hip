@@ -29,6 +29,7 @@
 #include "rt_internal.h"
 #include "pinhole.h"
 #include "rt_shading.h"   // (up here for std_max, which the slab test below takes)
+#include "rt_order.h"
 
 // rt_traversal.cpp:318-339 with idir hoisted (1.0f/rd is recomputed per child there; same value).
 // EXACT selects the libstdc++ min/max forms; the fast form uses v_min/v_max, which differs only
@@ -115,22 +116,7 @@ __device__ __forceinline__ float ray_tri_flat(float ox, float oy, float oz, floa
   return rejected ? RT_LARGE_FLOAT : tf;
 }
 
-struct Cand { float d; uint32_t desc; };
-// visit order: nearer first; equal distance -> higher child index first (stable far->near sort of
-// rt_traversal.cpp:76-78 read from the back).  Filtered children carry d = +inf.
-// Adjacent compare-exchange with a strict '<' never reorders equal keys, so a 6-comparator bubble
-// network over the children laid out [3, 2, 1, 0] gives exactly that order without carrying the index.
-__device__ __forceinline__ void cmpx(Cand& x, Cand& y) {
-  const bool sw = y.d < x.d;
-  const Cand tx = x, ty = y;
-  x.d = sw ? ty.d : tx.d; x.desc = sw ? ty.desc : tx.desc;
-  y.d = sw ? tx.d : ty.d; y.desc = sw ? tx.desc : ty.desc;
-}
-__device__ __forceinline__ void order_children(Cand* c) {   // in: c[k] = child k; out: c[0] nearest ... c[3] farthest
-  Cand s0 = c[3], s1 = c[2], s2 = c[1], s3 = c[0];
-  cmpx(s0, s1); cmpx(s1, s2); cmpx(s2, s3); cmpx(s0, s1); cmpx(s1, s2); cmpx(s0, s1);
-  c[0] = s0; c[1] = s1; c[2] = s2; c[3] = s3;
-}
+// (Cand, cmpx, order_children -- the visiting order of a node's children -- and the selections of RT_ORDER_PATHS: rt_order.h)
 
 template <int K>
 __device__ __forceinline__ float qbyte(uint32_t w) { return (float)((w >> (8 * K)) & 0xffu); }   // v_cvt_f32_ubyteK
@@ -416,6 +402,20 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #ifndef RT_OCC_LOOP_CHECK
 #define RT_OCC_LOOP_CHECK 0
 #endif
+// RT_ORDER_PATHS: the ordered arm of the node step asks, once per run and for the whole wavefront (a scalar test on the box tests' masks),
+// whether any of its lanes holds more than one valid child.  Where none does -- half of the ordered runs of the headline frame
+// (profiles/r19_a_child_counts.txt) -- the run skips the +inf selects, the sorting network and the push: a lane with a valid child goes on
+// with it (cur, path_m), a lane with none pops; the overflow test stays in front of every step that holds a valid child.  Same results
+// (rt_order.h; tests/test_order_paths_cpu.py; RT_ORDER_CHECK in the variant library).  0 = the network always (docs/KNOBS.md).
+// Taken by the identity-root shadow frame kernels (fixed and caller camera, 7 and 8 wavefronts), where it is measured and the loops'
+// listings stay free of spills and lane moves; every other kernel keeps the network whatever the value (DESIGN.md s5 says why).
+#ifndef RT_ORDER_PATHS
+#define RT_ORDER_PATHS 1
+#endif
+// -DRT_ORDER_CHECK=1 (variant libraries only): a run that skips the network evaluates it as well; a difference sets STATUS_ITER_LIMIT
+#ifndef RT_ORDER_CHECK
+#define RT_ORDER_CHECK 0
+#endif
 // (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
 
 // -DRT_ISA_MARKS: comment-only markers in the listing (hipcc -S) that delimit the regions of the traversal loop for
@@ -493,9 +493,7 @@ __device__ __forceinline__ bool ray_in_fast_domain(float ox, float oy, float oz,
          fabsf(ox) <= RT_FAST_POS_MAX && fabsf(oy) <= RT_FAST_POS_MAX && fabsf(oz) <= RT_FAST_POS_MAX;
 }
 
-// max of two values neither of which is a NaN: one v_max_f32 (fmaxf adds a canonicalising v_max_f32 x, x for a signalling NaN the
-// compiler cannot rule out)
-__device__ __forceinline__ float vmax_nonan(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// (vmax_nonan, the one-instruction max of two values neither of which is a NaN: rt_order.h)
 
 // per-lane flag bits
 #define F_FOUND 1u
@@ -527,6 +525,10 @@ __device__ __forceinline__ float vmax_nonan(float a, float b) { float r; asm("v_
 // through enter_instance -- and nothing ever brings a lane back: no lane holds a TLAS node or an instance descriptor inside the loop, whose
 // instance step, "back at TLAS level" test and the ballots that go with them are not compiled.  Timed plain / shadow frame jobs of shallow
 // scenes with the fma decode only (launch_traversal); every other scene keeps the general kernels.
+// diagnostic (vxrt_debug_child_counts): node-body runs of the wave-log launches on this device by the largest number of valid children any
+// node lane of the run holds -- [0..3] ordered arm with 0, 1, 2, >= 3, [4..7] occlusion arm -- summed over their wavefronts
+__device__ unsigned long long g_child_counts[8];
+
 template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false, bool ALPHA = false, bool IDENT = false>
 __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
   static_assert(!ALPHA || (STATS == 0 && !PACKED && !SHALLOW && job_base(JOB) != JOB_RENDER_GI), "alpha instantiations: see ALPHA above");
@@ -627,6 +629,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   unsigned long long t_first = 0;
   unsigned long long wl_tn = 0, wl_tl = 0, wl_t0 = 0;   // wave_log: shader clocks inside the node body / the leaf body
   unsigned wl_no23 = 0, wl_no3 = 0, wl_iter = 0, wl_node_x = 0, wl_node_l = 0, wl_leaf_x = 0, wl_leaf_l = 0;   // wave_log: lane occupancy of the two bodies
+  unsigned wl_cc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // wave_log: node-body runs by the largest valid-children count of their lanes (0, 1, 2, >= 3): ordered arm, occlusion arm
   unsigned long long wl_tstart = 0, wl_tf = 0, wl_tfin = 0, wl_tmark = 0;   // wave_log: shader clocks in the fetch / finish sections
   unsigned long long wl_tq = 0;   // wave_log: 100 MHz clock at which this wavefront found every queue shard empty
   if (STATS && A.wave_log) { t_first = wall_clock64(); wl_tstart = __builtin_readcyclecounter(); }
@@ -1145,6 +1148,9 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       w[9] = (unsigned long long)wl_no3 | ((unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) << 56);   // [63:56] physical XCD
       w[10] = wl_tn; w[11] = wl_tl; w[12] = __builtin_readcyclecounter() - wl_tstart;
       w[3] = wl_iter; w[4] = wl_node_x; w[5] = wl_node_l; w[6] = wl_leaf_x; w[7] = wl_leaf_l;
+      // (the 16 words are taken and their layout is read by tools: the child-count classes are summed over the wavefronts, vxrt_debug_child_counts)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) if (wl_cc[k]) atomicAdd(&g_child_counts[k], (unsigned long long)wl_cc[k]);
     }
   }
   if (!EXACT && A.end_log) {
@@ -2643,6 +2649,16 @@ int vxrt_wire_unpack(const uint8_t* wire_all, uint64_t wire_stride_bytes, uint32
 int vxrt_debug_trace_wave_log(vxrt_accel_t* a, unsigned long long* log) {
   if (!a) return -1;
   a->trace_wave_log = log;
+  return 0;
+}
+
+int vxrt_debug_child_counts(unsigned long long* out, int reset, void* stream) {
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_child_counts), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_child_counts), zero, sizeof(zero)) != hipSuccess) return -1;
+  }
   return 0;
 }
 

@@ -14,6 +14,7 @@
         }
       }
       if (STATS && A.wave_log) wl_t0 = __builtin_readcyclecounter();
+      unsigned wl_tag = 0;   // wave log: 1 + class + 4 * arm of this iteration's node-body run, in the lanes that took it
       RT_LOOP_MARK("node");
       if (is_node_desc(cur)) {
         // ---- internal node: 4 box tests, order, push the far ones, continue with the nearest ----
@@ -49,6 +50,15 @@
         bool ok[4] = {false, false, false, false};
         if (OK_MASKS) eval_children_raw<EXACT, LDEXP, BOX_NO_SELECT>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c, ok);
         else eval_children<EXACT, LDEXP>(q0, q1, q2, q3, ref_node, arx, ary, arz, aix, aiy, aiz, hitd, c);
+        // wave log of the timed traversal's counting build (STATS == 2 only): this run's class = the largest number of valid children any of
+        // its node lanes holds (0, 1, 2, >= 3); the arm adds 4 for the occlusion arm, and the run is counted behind the node body, where every
+        // lane of the wavefront is active again.  The clocks the classing takes are taken out of the node body's window (wl_t0 moves on).
+        if (STATS == 2 && A.wave_log) {
+          const unsigned long long ta = __builtin_readcyclecounter();
+          const bool v[4] = {c[0].d < __builtin_inff(), c[1].d < __builtin_inff(), c[2].d < __builtin_inff(), c[3].d < __builtin_inff()};
+          wl_tag = 1u + (__any(order_three_valid(v)) ? 3u : (__any(order_two_valid(v)) ? 2u : (__any(order_any_valid(v)) ? 1u : 0u)));
+          wl_t0 += __builtin_readcyclecounter() - ta;
+        }
         RT_LOOP_MARK("stack");
         // (the occlusion-only loop has the answer from its entry: no ballot per step, no ordered arm)
         if (OCC || (((job_base(JOB) == JOB_RENDER_SHADOW && RT_UNORDERED_OCCLUSION) || JOB == JOB_TRACE_UNORDERED) && STATS != 1 && __all((flags & F_ANYHIT) != 0u))) {   // STATS keeps the reference's order, hence its fetch counts
@@ -60,6 +70,7 @@
           // and a child that is pushed carries the same value in both forms)
           const bool v0 = OK_MASKS ? ok[0] : c[0].d < __builtin_inff(), v1 = OK_MASKS ? ok[1] : c[1].d < __builtin_inff();
           const bool v2 = OK_MASKS ? ok[2] : c[2].d < __builtin_inff(), v3 = OK_MASKS ? ok[3] : c[3].d < __builtin_inff();
+          if (STATS == 2 && A.wave_log) wl_tag += 4u;
           if (v0 || v1 || v2 || v3) {
             bool more = true;
             if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
@@ -70,27 +81,67 @@
             pop_next(occ);
           }
         } else {
-          if (OK_MASKS) {
+          // RT_ORDER_PATHS: a run none of whose lanes holds more than one valid child has nothing to sort and nothing to push.  The test is
+          // wave-uniform, over the node lanes the phase ballot above ranged over; the conditions live in scalar masks.  The identity-root
+          // shadow frame kernels only (see the knob in rt_kernels.hip).
+          constexpr bool ORDER_PATHS = OK_MASKS && IDENT && job_base(JOB) == JOB_RENDER_SHADOW && RT_ORDER_PATHS != 0;
+          bool ordered = false;   // (wave-uniform: the step was taken without the network)
+          if (ORDER_PATHS) {
+            if (!__any(order_two_valid(ok))) {
+              ordered = true;
+              const bool any1 = order_any_valid(ok);
+              if (RT_ORDER_CHECK) {   // what the network decides: the child taken, nothing pushed, the new maximum
+                Cand n[4] = {c[0], c[1], c[2], c[3]};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) c[k].d = ok[k] ? c[k].d : __builtin_inff();
+                for (int k = 0; k < 4; ++k) n[k].d = ok[k] ? n[k].d : __builtin_inff();
+                order_children(n);
+                bool bad = any1 != (n[0].d < __builtin_inff()) || n[1].d < __builtin_inff() || n[2].d < __builtin_inff() || n[3].d < __builtin_inff();
+                if (any1) bad = bad || order_first_valid(c, ok).desc != n[0].desc || __float_as_uint(vmax_nonan(path_m, order_first_valid(c, ok).d)) != __float_as_uint(vmax_nonan(path_m, n[0].d));
+                if (bad) atomicOr(A.status, STATUS_ITER_LIMIT);
+              }
+              if (any1) {
+                // (the overflow test stands in front of every step that holds a valid child, whether it pushes or not)
+                if (sp + 4 > STACK_CAP) atomicOr(A.status, STATUS_STACK_OVERFLOW);
+                const Cand only = order_first_valid(c, ok);
+                cur = only.desc;
+                path_m = vmax_nonan(path_m, only.d);
+              } else {
+                pop_next(occ);
+              }
+            }
           }
-          order_children(c);   // valid children first (d < inf), nearest in c[0]
-          // (path_m and the candidates' distances are never NaN -- a filtered child carries +inf -- so the maxima need no
-          // canonicalising v_max x, x in front of them)
-          if (c[0].d < __builtin_inff()) {
-            bool more = true;
-            if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
-            // far first so that the nearest pending sibling is on top (:98-103)
-            push_pending(occ, more && c[3].d < __builtin_inff(), c[3].desc, vmax_nonan(path_m, c[3].d), more && c[2].d < __builtin_inff(), c[2].desc, vmax_nonan(path_m, c[2].d),
-                         more && c[1].d < __builtin_inff(), c[1].desc, vmax_nonan(path_m, c[1].d));
-            cur = c[0].desc;
-            path_m = vmax_nonan(path_m, c[0].d);
-          } else {
-            pop_next(occ);
+          if (!ordered) {
+            if (OK_MASKS) {
+#pragma unroll
+              for (int k = 0; k < 4; ++k) c[k].d = ok[k] ? c[k].d : __builtin_inff();
+            }
+            order_children(c);   // valid children first (d < inf), nearest in c[0]
+            // (path_m and the candidates' distances are never NaN -- a filtered child carries +inf -- so the maxima need no
+            // canonicalising v_max x, x in front of them)
+            if (c[0].d < __builtin_inff()) {
+              bool more = true;
+              if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
+              // far first so that the nearest pending sibling is on top (:98-103)
+              push_pending(occ, more && c[3].d < __builtin_inff(), c[3].desc, vmax_nonan(path_m, c[3].d), more && c[2].d < __builtin_inff(), c[2].desc, vmax_nonan(path_m, c[2].d),
+                           more && c[1].d < __builtin_inff(), c[1].desc, vmax_nonan(path_m, c[1].d));
+              cur = c[0].desc;
+              path_m = vmax_nonan(path_m, c[0].d);
+            } else {
+              pop_next(occ);
+            }
           }
         }
       }
       if (STATS && A.wave_log) { const unsigned long long t1 = __builtin_readcyclecounter(); wl_tn += t1 - wl_t0; wl_t0 = t1; }
+      if (STATS == 2 && A.wave_log) {
+        const unsigned long long tm = __ballot(wl_tag != 0u);
+        if (tm) {
+          const unsigned tag = __shfl(wl_tag, __ffsll((long long)tm) - 1) - 1u;   // (the same in every lane that took the run)
+#pragma unroll
+          for (unsigned k = 0; k < 8; ++k) wl_cc[k] += tag == k ? 1u : 0u;
+        }
+        wl_t0 = __builtin_readcyclecounter();   // (the count belongs to neither body's window)
+      }
       RT_LOOP_MARK("inst");
       if (!IDENT && __any(is_inst_desc(cur))) {
         if (is_inst_desc(cur)) {
