@@ -931,7 +931,8 @@ int vxrt_accel_read_emitters(vxrt_accel_t* accel, float* tri12 /* HOST, n x 12 *
  *   rays_traced also counts the emitter rays that were traced.
  * Returns -1 before anything is launched (dst untouched) for whatever vxrt_render_path refuses (a non-zero alpha table included), a
  * null `em`, nee > 1, a non-zero reserved word, scale negative or not finite, and nee = 1 without a valid table (none set, or stale).
- * There is no denoised, temporal, variance or adaptive form, and no multiple importance sampling. */
+ * There is no denoised, temporal, variance or adaptive form.  The two forms combined by multiple importance sampling are entry points
+ * of their own: "Multiple importance sampling" below. */
 typedef struct vxrt_emissive_params {
   uint32_t nee;          /* 0: emission at bounce hits; 1: emitter sampling from the accel's table */
   float scale;           /* multiplies every material's emissive; >= 0 and finite */
@@ -944,6 +945,67 @@ int vxrt_render_path_emissive(vxrt_accel_t* accel, const vxrt_camera_t* cam /* N
 int vxrt_emitter_rays(vxrt_accel_t* accel, uint64_t n, const float* points /* device, n x 6: I, N' */, const uint32_t* seeds /* device */,
                       float scale, float* rays /* device, n x 6 */, float* tmax /* device */, float* weight3 /* device, n x 3 */,
                       uint32_t* emitter /* device */, void* stream);
+
+/* Multiple importance sampling of area lights (extension): the two estimators of "Emissive geometry" in one frame, each weighted by the
+ * balance heuristic, so that a sample is bounded by the emitter's radiance where nee = 1 has the unbounded G (a vertex next to a large
+ * emitter) and the frame keeps nee = 1's error where nee = 0 needs many samples (small, far emitters).  The conventions are those of
+ * "Emissive geometry": every symbol one fp32 IEEE operation in the order written, no contraction, pi = 3.14159265f.
+ * tests/emissive_mis_ref.py restates all of it.
+ * One direction w from a vertex with facing normal N' has two solid-angle densities: cosx / pi for the bounce ray (cosine-weighted about
+ * N') and d2 * (q_e / Q) / an for the emitter ray.  Both weights below are the balance heuristic with numerator and denominator
+ * multiplied by an, so nothing is divided by an and a sample in the emitter's own plane (an = 0) stays defined.
+ *
+ * THE EMITTER-RAY SIDE, with d2, cosx, an, q_e, Q and G of THE EMITTER RAY above:
+ *   qf = (float)q_e / (float)Q;   pe = d2 * qf;   pb = (cosx / pi) * an;   wE = pe / (pe + pb);   Gm = G * wE per channel
+ * SKIPPED as the emitter ray is, and also if a channel of Gm is not finite.  Mathematically Gm <= Le * scale.
+ * vxrt_emitter_rays_mis is vxrt_emitter_rays with weight3 = Gm and one output more, mis (n: wE); a skipped entry gets Gm = 0 and
+ * wE = 0.  It refuses what vxrt_emitter_rays refuses, and a null `mis`.
+ *
+ * THE BOUNCE-RAY SIDE.  A bounce ray (o, w), as stored, that left a vertex with facing normal N' hits h' at distance t, and
+ * (h'.blasIdx & 0x7fffffff, h'.triIdx) is entry e of the table; with c = cross(E1, E2) of entry e and qf of entry e as above:
+ *   cosx = max(0, (N'.x * w.x + N'.y * w.y) + N'.z * w.z)      (std::max: a NaN gives 0)
+ *   an = 0.5f * |(c.x * w.x + c.y * w.y) + c.z * w.z|
+ *   pe = (t * t) * qf;   pb = (cosx / pi) * an;   den = pe + pb;   wB = den > 0 ? pb / den : 1
+ * A triangle that is not in the table has wB = 1: the caller's contract is unchanged, a triangle left out of the list keeps emitting
+ * through bounce rays at full weight.
+ * THE EMITTER INDEX finds e: the table's (blasIdx, triIdx, e), 12 bytes per entry, sorted ascending by (blasIdx, triIdx) and, for a pair
+ * listed more than once, by e -- so the order is unique.  The lookup takes the smallest position whose key is not below the wanted key
+ * (a binary search over [0, n-1] of at most 17 steps) and has found it if the key there is equal; of a pair listed twice it finds
+ * the smaller e.  The index holds no world-space data.  It is built when it is first needed after a vxrt_accel_set_emitters -- the first
+ * vxrt_render_path_emissive_mis or vxrt_emitter_hit_weights -- from the pair list the accel kept, sorted on the host and uploaded once:
+ * that call synchronises `stream` once, like a call whose buffers grow.  From then on vxrt_accel_bytes counts its 12 bytes per entry and
+ * vxrt_accel_info(accel, 8) is its entry count (0: none); vxrt_accel_set_emitters drops it.
+ * vxrt_emitter_hit_weights runs the lookup and wB alone on caller-owned DEVICE buffers: rays (n x 6: o, w), hits (n records as vxrt_trace
+ * writes them; dist is t), normals (n x 3: N') -> emitter (n: e, or 0xFFFFFFFF for a pair that is not listed) and mis (n: wB).  Every
+ * record is looked up, whether its material emits or not and whatever its dist.  One launch, asynchronous on `stream` (behind the index's
+ * build, if this call is the one that builds it).  Returns -1 before the launch for a null or stale accel, no valid table, a null
+ * buffer, n >= 2^31; 0 for n = 0.
+ *
+ * THE FRAME.  vxrt_render_path_emissive_mis is vxrt_render_path_emissive with nee = 1 -- the same emitter ray per vertex, the same seeds,
+ * the same any-hit launch, the same rays_traced -- except that
+ *   an unblocked emitter ray adds Lc = Lc + thr * Gm, and
+ *   at every bounce hit h' whose material emits, after Lc = Lc + thr * Lit(r', h') (where nee = 0 adds thr * Emi(h')):
+ *     Lc = Lc + thr * (Emi(h') * wB) per channel, with N' = the normal of the vertex the bounce ray left, turned against the direction the
+ *     path arrived from as the bounce ray's own sampling turns it, w = the bounce ray's direction, t = h'.dist.
+ * Emi(h_0) at the primary hit stays at full weight.  Every vertex a bounce ray leaves sends an emitter ray, so every bounce hit is
+ * weighted, wE + wB = 1 for one direction up to rounding, and the expectation is that of both forms of "Emissive geometry".  With
+ * bounces = 0 the frame is that of nee = 1.
+ * Returns -1 before anything is launched (dst untouched) for whatever vxrt_render_path_emissive with nee = 1 refuses (a non-zero alpha
+ * table, a missing or stale emitter table included), a null `em`, a non-zero reserved word, scale negative or not finite. */
+typedef struct vxrt_emissive_mis_params {
+  float scale;           /* multiplies every material's emissive; >= 0 and finite */
+  uint32_t reserved[3];  /* 0 */
+} vxrt_emissive_mis_params_t;
+int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
+                                  uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                  const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_mis_params_t* em,
+                                  uint32_t* dst, float* colors /* optional */, unsigned long long* rays_traced /* optional */, void* stream);
+int vxrt_emitter_rays_mis(vxrt_accel_t* accel, uint64_t n, const float* points /* device, n x 6: I, N' */, const uint32_t* seeds /* device */,
+                          float scale, float* rays /* device, n x 6 */, float* tmax /* device */, float* weight3 /* device, n x 3: Gm */,
+                          uint32_t* emitter /* device */, float* mis /* device, n: wE */, void* stream);
+int vxrt_emitter_hit_weights(vxrt_accel_t* accel, uint64_t n, const float* rays /* device, n x 6 */, const void* hits /* device, n records */,
+                             const float* normals /* device, n x 3: N' */, uint32_t* emitter /* device */, float* mis /* device, n: wB */,
+                             void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

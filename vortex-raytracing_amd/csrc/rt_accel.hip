@@ -461,7 +461,7 @@ static void accel_free(vxrt_accel* a) {
   (void)hipFree(a->uvtab); (void)hipFree(a->apriori);
   (void)hipFree(a->alpha_mat); (void)hipFree(a->alpha_tri);
   (void)hipFree(a->motion_blas); (void)hipFree(a->motion_tri);
-  (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum);
+  (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum); (void)hipFree(a->em_idx);
   for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) (void)hipFree(a->batch_order[k]);
   for (FrameCtx& c : a->ctx) {
     (void)hipFree(c.hitbuf); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
@@ -594,6 +594,32 @@ __global__ __launch_bounds__(64) void accel_emitter_cum_kernel(uint32_t n, const
   uint32_t inc = e < n ? q[e] : 0u;
   for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += y; }
   if (e < n) cum[e] = boff[blockIdx.x] + inc;
+}
+
+// The emitter index (the header's "Multiple importance sampling").  Dropped behind a synchronisation its caller has made: no frame in
+// flight reads it.
+static void emitter_index_drop(vxrt_accel* a) {
+  (void)hipFree(a->em_idx);
+  a->em_idx = nullptr; a->em_idx_n = 0u;
+}
+
+// Built on the host: at most 65,536 keys of 12 bytes sorted by (blasIdx, triIdx, e) -- a total order, so the same bits whatever the sort
+// does -- and uploaded once.  The index is a buffer that grows from nothing: one synchronisation of s, behind which the sorted keys may
+// leave the host; with an index held, nothing.  (Frames in flight on other streams do not read an index that does not exist yet.)
+int emitter_index_ensure(vxrt_accel* a, hipStream_t s) {
+  const uint32_t n = a->em_n;
+  if (a->em_idx) return 0;   // (every set drops it: an index held is the table's)
+  if (n == 0u || a->em_pairs.size() != n) return -1;
+  struct Key { uint32_t b, t, e; };   // (an entry of the index: three words)
+  std::vector<Key> ent(n);
+  for (uint32_t e = 0; e < n; ++e) ent[e] = Key{a->em_pairs[e].blasIdx, a->em_pairs[e].triIdx, e};
+  std::sort(ent.begin(), ent.end(), [](const Key& x, const Key& y) { return x.b != y.b ? x.b < y.b : (x.t != y.t ? x.t < y.t : x.e < y.e); });
+  uint32_t* d = nullptr;
+  if (hipMalloc((void**)&d, (size_t)n * 12) != hipSuccess) { (void)hipGetLastError(); return -1; }
+  const bool ok = hipMemcpyAsync(d, ent.data(), (size_t)n * 12, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) { (void)hipFree(d); return -1; }
+  a->em_idx = d; a->em_idx_n = n;
+  return 0;
 }
 
 extern "C" {
@@ -732,7 +758,8 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* a) {
          (uint64_t)a->ref.n_tris * WTRI_FLOATS * 4 + (uint64_t)a->ref.n_blas * 4 +
          ((a->motion_what & VXRT_REFIT_INSTANCES) ? (uint64_t)a->ref.n_blas * RT_BLAS_STRIDE : 0) +   // (the motion snapshot)
          ((a->motion_what & VXRT_REFIT_GEOMETRY) ? (uint64_t)a->ref.n_tris * RT_TRI_BYTES : 0) +
-         (uint64_t)a->em_n * 56u;   // (the emitter table: 12 floats, q and cum per entry)
+         (uint64_t)a->em_n * 56u +   // (the emitter table: 12 floats, q and cum per entry)
+         (uint64_t)a->em_idx_n * 12u;   // (the emitter index, from its build on: blasIdx, triIdx, e per entry)
 }
 
 int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
@@ -746,6 +773,7 @@ int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
   case 5: *value = ident_root_form(a) ? 1u : 0u; return 0; // timed plain / shadow frames take the identity-root kernels (no TLAS level in the loop)
   case 6: *value = a->motion_what; return 0;       // the VXRT_REFIT_* mask of the motion snapshot held (vxrt_accel_motion_snapshot)
   case 7: *value = emitters_valid(a) ? a->em_n : 0u; return 0; // emitters of a valid emitter table (vxrt_accel_set_emitters)
+  case 8: *value = a->em_idx_n; return 0;          // entries of the emitter index (0: none built since the last vxrt_accel_set_emitters)
   }
   return -1;
 }
@@ -856,6 +884,8 @@ int vxrt_accel_set_emitters(vxrt_accel_t* a, const vxrt_emitter_t* pairs, uint32
     if (hipStreamSynchronize(st) != hipSuccess) return -1;
     (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum);
     a->em_tri = nullptr; a->em_q = nullptr; a->em_cum = nullptr; a->em_n = 0u; a->em_Q = 0u; a->em_valid = false;
+    emitter_index_drop(a);
+    a->em_pairs.clear();
     return 0;
   }
   const uint32_t nb = (n + EM_BLOCK - 1u) / EM_BLOCK;
@@ -886,6 +916,8 @@ int vxrt_accel_set_emitters(vxrt_accel_t* a, const vxrt_emitter_t* pairs, uint32
   }
   (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum);
   a->em_tri = tri; a->em_q = q; a->em_cum = cum; a->em_n = n; a->em_Q = Q; a->em_valid = true;
+  emitter_index_drop(a);   // (the index is of the table replaced: the next call that needs one builds it from the pairs kept here)
+  a->em_pairs.assign(pairs, pairs + n);
   return 0;
 }
 

@@ -170,12 +170,24 @@ struct vxrt_accel {
   float* em_tri = nullptr; uint32_t* em_q = nullptr; uint32_t* em_cum = nullptr;
   uint32_t em_n = 0, em_Q = 0;
   bool em_valid = false;
+  // emitter index (the header's "Multiple importance sampling"): the table's (blasIdx, triIdx, e), three words per entry, sorted by
+  // (blasIdx, triIdx, e).  Built by emitter_index_ensure from em_pairs -- the caller's list as the last set took it -- when a MIS frame or
+  // vxrt_emitter_hit_weights first needs it; dropped by every set.  em_idx_n: its entries, 0 = none.
+  std::vector<vxrt_emitter_t> em_pairs;
+  uint32_t* em_idx = nullptr;
+  uint32_t em_idx_n = 0;
 };
 
 // What the emitter-sampling kernels read of the table (rt_path.hip)
 struct EmitterTab { const float* tri; const uint32_t* q; const uint32_t* cum; uint32_t n, Q; };
 static inline EmitterTab emitter_tab(const vxrt_accel* a) { return EmitterTab{a->em_tri, a->em_q, a->em_cum, a->em_n, a->em_Q}; }
 static inline bool emitters_valid(const vxrt_accel* a) { return a->em_valid && a->em_n != 0u && !a->stale; }
+// ... and of the emitter index
+struct EmitterIdx { const uint32_t* ent; uint32_t n; };
+static inline EmitterIdx emitter_idx(const vxrt_accel* a) { return EmitterIdx{a->em_idx, a->em_idx_n}; }
+// rt_accel.hip: the index of a valid table, built here if the accel holds none (one upload and one synchronisation of s; nothing when
+// it is held).  0, or -1 when a HIP call failed.
+int emitter_index_ensure(vxrt_accel* a, hipStream_t s);
 
 // What the previous-position guide reads besides the SceneDev (see the header, "Motion"): the snapshot's instance records, the vertices
 // (the snapshot's, or the scene's current ones) and the two bounds a hit record is checked against
@@ -262,6 +274,7 @@ struct RenderRequest {
   const vxrt_camera_t* cams = nullptr;              // camera frames: `batch` entries
   const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
   const vxrt_emissive_params_t* emissive = nullptr; // ... with emissive geometry (vxrt_render_path_emissive): a plain path frame otherwise
+  const vxrt_emissive_mis_params_t* emissive_mis = nullptr; // ... with both estimators of emissive geometry, weighted (vxrt_render_path_emissive_mis)
   const uint32_t* sample_counts = nullptr;          // ... with a sample count per pixel (vxrt_render_path_adaptive): device, addressed like dst; path->spp is the cap
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;
@@ -325,6 +338,12 @@ extern const uint64_t PATH_BATCH_PATHS;   // paths per batch of a path frame unl
 // rt_path.hip: the launch of vxrt_emitter_rays (n >= 1, a valid table; the checks are the entry point's)
 int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
                         uint32_t* emitter, hipStream_t s);
+// rt_path.hip: the launches of vxrt_emitter_rays_mis and vxrt_emitter_hit_weights (n >= 1, a valid table, for the second its index; the
+// checks are the entry points')
+int emitter_rays_mis_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                            uint32_t* emitter, float* mis, hipStream_t s);
+int emitter_hit_weights_launch(const vxrt_accel* a, uint32_t n, const float* rays, const HitRec* hits, const float* normals, uint32_t* emitter, float* mis,
+                               hipStream_t s);
 // rt_path.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
 int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
                          unsigned long long* total, hipStream_t s);

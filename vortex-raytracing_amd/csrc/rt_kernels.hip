@@ -1868,6 +1868,11 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if (r.emissive && (!r.path || r.sample_counts || r.denoise || r.aov || r.temporal || r.history || r.motion || r.variance || r.emissive->nee > 1u ||
                      r.emissive->reserved[0] != 0u || r.emissive->reserved[1] != 0u || !(r.emissive->scale >= 0.0f) || !std::isfinite(r.emissive->scale) ||
                      (r.emissive->nee == 1u && !emitters_valid(a)))) return -1;
+  // ... with both estimators of emissive geometry weighted: what the emissive frame with emitter sampling asks for, in a request field
+  // of its own (the entry point is its own; the two fields exclude each other)
+  if (r.emissive_mis && (!r.path || r.emissive || r.sample_counts || r.denoise || r.aov || r.temporal || r.history || r.motion || r.variance ||
+                         r.emissive_mis->reserved[0] != 0u || r.emissive_mis->reserved[1] != 0u || r.emissive_mis->reserved[2] != 0u ||
+                         !(r.emissive_mis->scale >= 0.0f) || !std::isfinite(r.emissive_mis->scale) || !emitters_valid(a))) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
   // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
@@ -2524,6 +2529,36 @@ int vxrt_emitter_rays(vxrt_accel_t* a, uint64_t n, const float* points, const ui
   if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
   if (n == 0) return 0;
   return emitter_rays_launch(a, (uint32_t)n, points, seeds, scale, rays, tmax, weight3, emitter, (hipStream_t)stream);
+}
+
+// Path frame with emissive geometry whose two estimators are weighted by the balance heuristic (see the header, "Multiple importance
+// sampling"): the frame of nee = 1 with the weighted kernels in its tail; the parameters are check_request's to refuse
+int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                  const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_mis_params_t* em, uint32_t* dst,
+                                  float* colors, unsigned long long* rays_traced, void* stream) {
+  if (!path || !em) return -1;
+  if (cam && !camera_ok(cam)) return -1;
+  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
+  r.emissive_mis = em;
+  return render_common(accel, r);
+}
+
+// The weighted emitter ray alone: one launch on caller-owned buffers, no host synchronisation
+int vxrt_emitter_rays_mis(vxrt_accel_t* a, uint64_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                          uint32_t* emitter, float* mis, void* stream) {
+  if (!a || !emitters_valid(a) || !points || !seeds || !rays || !tmax || !weight3 || !emitter || !mis) return -1;
+  if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  return emitter_rays_mis_launch(a, (uint32_t)n, points, seeds, scale, rays, tmax, weight3, emitter, mis, (hipStream_t)stream);
+}
+
+// The lookup in the emitter index and the bounce ray's weight alone: one launch on caller-owned buffers; the call that finds no index
+// builds it first (one synchronisation of `stream`, as for a buffer that grows)
+int vxrt_emitter_hit_weights(vxrt_accel_t* a, uint64_t n, const float* rays, const void* hits, const float* normals, uint32_t* emitter, float* mis, void* stream) {
+  if (!a || !emitters_valid(a) || !rays || !hits || !normals || !emitter || !mis || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  if (emitter_index_ensure(a, (hipStream_t)stream) != 0) return -1;
+  return emitter_hit_weights_launch(a, (uint32_t)n, rays, (const HitRec*)hits, normals, emitter, mis, (hipStream_t)stream);
 }
 
 // Sample counts from a variance buffer (see the header, "Adaptive sampling"): elementwise, one launch, no host synchronisation

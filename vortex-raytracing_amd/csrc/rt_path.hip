@@ -201,8 +201,11 @@ __global__ __launch_bounds__(256) void rt_path_bounce_rays_kernel(uint32_t cap, 
 // The emitter ray of the header's "Emissive geometry", operation for operation: from hash output `seed`, the surface point I and the
 // facing normal N' (nx, ny, nz).  ray6 = (o, w), tmax, G[3], e = the emitter chosen; false = skipped: the ray nothing can hit, tmax = -1,
 // G = 0.  The cumulative table is read from global memory (a binary search of at most 17 steps; n <= 65,536).
+// (MIS: the emitter-ray side of the header's "Multiple importance sampling" -- G is Gm = G * wE, wE goes to *wE_out (0 for a skipped ray),
+//  and a Gm that is not finite skips the ray as well)
+template <bool MIS = false>
 __device__ __forceinline__ bool emitter_sample(const EmitterTab& tab, float scale, uint32_t seed, float Ix, float Iy, float Iz, float nx, float ny, float nz,
-                                               float (&ray6)[6], float& tmax, float (&G)[3], uint32_t& e_out) {
+                                               float (&ray6)[6], float& tmax, float (&G)[3], uint32_t& e_out, float* wE_out = nullptr) {
   if (seed == 0u) seed = 1u;
   seed ^= seed << 13; seed ^= seed >> 17; seed ^= seed << 5;
   const uint32_t r0 = seed;
@@ -233,7 +236,17 @@ __device__ __forceinline__ bool emitter_sample(const EmitterTab& tab, float scal
   G[0] = (((T[9] * scale) * cosx) * an) / den;
   G[1] = (((T[10] * scale) * cosx) * an) / den;
   G[2] = (((T[11] * scale) * cosx) * an) / den;
-  if (cosx == 0.0f || d2 == 0.0f || !isfinite(G[0]) || !isfinite(G[1]) || !isfinite(G[2])) {
+  bool skip = cosx == 0.0f || d2 == 0.0f || !isfinite(G[0]) || !isfinite(G[1]) || !isfinite(G[2]);
+  if constexpr (MIS) {
+    const float qf = (float)tab.q[e] / (float)tab.Q;
+    const float pe = d2 * qf;
+    const float pb = (cosx / 3.14159265f) * an;
+    const float wE = pe / (pe + pb);
+    G[0] = G[0] * wE; G[1] = G[1] * wE; G[2] = G[2] * wE;
+    skip = skip || !isfinite(G[0]) || !isfinite(G[1]) || !isfinite(G[2]);
+    *wE_out = skip ? 0.0f : wE;
+  }
+  if (skip) {
     ray6[0] = 0.f; ray6[1] = 0.f; ray6[2] = 0.f; ray6[3] = 1.f; ray6[4] = 1.f; ray6[5] = 1.f;
     tmax = -1.0f;
     G[0] = 0.f; G[1] = 0.f; G[2] = 0.f;
@@ -247,9 +260,11 @@ __device__ __forceinline__ bool emitter_sample(const EmitterTab& tab, float scal
 // rt_path_bounce_rays_kernel of a frame with emitter sampling (nee = 1): besides the bounce ray of slot live[q], the emitter ray of the
 // same vertex -- user seed (seed + depth) ^ 0x80000000 in the bounce ray's hash input -- with its tmax and G (w = 1: real; a skipped
 // one is not counted).  One atomic per workgroup on the ray counter for the emitter rays, thread 0's for the bounce rays.
-__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+// (MIS: the frame of the header's "Multiple importance sampling" -- eG[q] = (Gm, real))
+template <bool MIS>
+__device__ __forceinline__ void path_bounce_emitter_rays(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
     const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
-    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, const EmitterTab& tab, float scale,
     float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
   __shared__ uint32_t s_real;
   if (threadIdx.x == 0) s_real = 0u;
@@ -275,7 +290,8 @@ __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32
     const uint32_t seed = wang_hash((x + y * W) * spp + smp + 1u + (user_seed ^ 0x80000000u) * 0x9E3779B9u);
     float e6[6], tm, G[3];
     uint32_t e;
-    real = emitter_sample(tab, scale, seed, I.x, I.y, I.z, nx, ny, nz, e6, tm, G, e);
+    float wE;
+    real = emitter_sample<MIS>(tab, scale, seed, I.x, I.y, I.z, nx, ny, nz, e6, tm, G, e, &wE);
     float* eo = erays + (size_t)q * 6;
 #pragma unroll
     for (int k = 0; k < 6; ++k) eo[k] = e6[k];
@@ -286,6 +302,88 @@ __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32
   if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
   __syncthreads();
   if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
+}
+
+__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  path_bounce_emitter_rays<false>(cap, W, y0, spp, s0, ns, user_seed, list, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+}
+
+__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_mis_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  path_bounce_emitter_rays<true>(cap, W, y0, spp, s0, ns, user_seed, list, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+}
+
+// The emitter index of the header's "Multiple importance sampling": the position of (blas, tri) among the sorted (blasIdx, triIdx, e)
+// -- the smallest position whose key is not below the wanted one, a binary search over [0, n - 1] of at most 17 steps -- and e of that
+// position if its key is equal; 0xFFFFFFFF: the pair is not listed
+__device__ __forceinline__ uint32_t emitter_lookup(const EmitterIdx& ix, uint32_t blas, uint32_t tri) {
+  if (ix.n == 0u) return 0xFFFFFFFFu;
+  const uint64_t want = ((uint64_t)blas << 32) | tri;
+  uint32_t lo = 0u, hi = ix.n - 1u;
+  for (int k = 0; k < 17; ++k) {
+    if (lo >= hi) break;
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    const uint64_t key = ((uint64_t)ix.ent[3 * (size_t)mid] << 32) | ix.ent[3 * (size_t)mid + 1];
+    if (key < want) lo = mid + 1u; else hi = mid;
+  }
+  const uint32_t* p = ix.ent + 3 * (size_t)lo;
+  return (p[0] == blas && p[1] == tri) ? p[2] : 0xFFFFFFFFu;
+}
+
+// wB of the header's "Multiple importance sampling", operation for operation: the bounce ray of direction w that left a vertex with
+// facing normal N' (nx, ny, nz) hit entry e of the table at distance t
+__device__ __forceinline__ float emitter_hit_weight(const EmitterTab& tab, uint32_t e, float nx, float ny, float nz, float wx, float wy, float wz, float t) {
+  const float* T = tab.tri + (size_t)e * 12;
+  const float e1x = T[3], e1y = T[4], e1z = T[5], e2x = T[6], e2y = T[7], e2z = T[8];
+  const float qf = (float)tab.q[e] / (float)tab.Q;
+  const float cosx = std_max(0.0f, (nx * wx + ny * wy) + nz * wz);
+  const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+  const float an = 0.5f * fabsf((cx * wx + cy * wy) + cz * wz);
+  const float pe = (t * t) * qf;
+  const float pb = (cosx / 3.14159265f) * an;
+  const float den = pe + pb;
+  return den > 0.0f ? pb / den : 1.0f;
+}
+
+// vxrt_emitter_hit_weights: lookup and wB of n caller-supplied bounce rays, hit records and N', one per thread (bit 31 of blasIdx is
+// masked; nothing of the scene is read, so a record may name any pair)
+__global__ __launch_bounds__(256) void rt_emitter_hit_weights_kernel(EmitterTab tab, EmitterIdx ix, uint32_t n, const float* __restrict__ rays,
+    const HitRec* __restrict__ hits, const float* __restrict__ normals, uint32_t* __restrict__ emitter, float* __restrict__ mis) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const HitRec h = hits[i];
+  const uint32_t e = emitter_lookup(ix, h.blasIdx & 0x7fffffffu, h.triIdx);
+  float w = 1.0f;
+  if (e < tab.n) {
+    const float* r = rays + (size_t)i * 6;
+    const float* nr = normals + (size_t)i * 3;
+    w = emitter_hit_weight(tab, e, nr[0], nr[1], nr[2], r[3], r[4], r[5], h.dist);
+  }
+  emitter[i] = e < tab.n ? e : 0xFFFFFFFFu;
+  mis[i] = w;
+}
+
+// vxrt_emitter_rays_mis: rt_emitter_rays_kernel with weight3 = Gm and mis = wE
+__global__ __launch_bounds__(256) void rt_emitter_rays_mis_kernel(EmitterTab tab, uint32_t n, const float* __restrict__ points, const uint32_t* __restrict__ seeds, float scale,
+    float* __restrict__ rays, float* __restrict__ tmax, float* __restrict__ weight3, uint32_t* __restrict__ emitter, float* __restrict__ mis) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const float* pt = points + (size_t)i * 6;
+  float e6[6], tm, G[3], wE;
+  uint32_t e;
+  emitter_sample<true>(tab, scale, seeds[i], pt[0], pt[1], pt[2], pt[3], pt[4], pt[5], e6, tm, G, e, &wE);
+  float* o = rays + (size_t)i * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = e6[k];
+  tmax[i] = tm;
+  weight3[3 * (size_t)i] = G[0]; weight3[3 * (size_t)i + 1] = G[1]; weight3[3 * (size_t)i + 2] = G[2];
+  emitter[i] = e;
+  mis[i] = wE;
 }
 
 // vxrt_emitter_rays: the emitter ray of n caller-supplied (I, N') and hash outputs, one per thread
@@ -339,13 +437,16 @@ __global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams
 // hit), then thr = thr * Alb and the hit becomes the slot's last vertex; with `next` the slot is appended to the next depth's live list.
 // (EMI: the frame with emissive geometry, the header's "Emissive geometry".  1, nee = 0: a hit adds thr * Emi(h') after thr * Lit.
 //  2, nee = 1: before the miss / hit arm Lc = Lc + thr * G for an emitter ray that is real -- eG[q].w -- and was not blocked -- ehits[q].)
+//  3, the header's "Multiple importance sampling": the emitter ray's term as for 2 -- eG holds Gm -- and a hit whose material emits adds
+//  thr * (Emi(h') * wB) after thr * Lit; only those lanes look the hit up in the emitter index and read the vertex the ray left.)
 struct ScatterEmi { float scale; const HitRec* ehits; const float4* eG; };
+struct ScatterMis { float scale; const HitRec* ehits; const float4* eG; EmitterTab tab; EmitterIdx idx; };
 struct ScatterNoEmi {};
 template <int EMI>
 __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadeParams& p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
     const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>& em) {
+    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>>& em) {
   const uint32_t total = min(*n_live, cap);
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   bool go[1] = {false};
@@ -357,7 +458,7 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
     h.blasIdx &= 0x7fffffffu;
     float4 L = pL[slot];
     const float4 T = pT[slot];
-    if constexpr (EMI == 2) {
+    if constexpr (EMI == 2 || EMI == 3) {
       const float4 G = em.eG[q];
       if (G.w != 0.f && em.ehits[q].dist == RT_LARGE_FLOAT) { L.x = L.x + T.x * G.x; L.y = L.y + T.y * G.y; L.z = L.z + T.z * G.z; }
     }
@@ -374,6 +475,20 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
       if constexpr (EMI == 1) {
         float e3[3];
         if (emission(sc, h.triIdx, em.scale, e3)) { L.x = L.x + T.x * e3[0]; L.y = L.y + T.y * e3[1]; L.z = L.z + T.z * e3[2]; }
+      }
+      if constexpr (EMI == 3) {
+        float e3[3];
+        if (emission(sc, h.triIdx, em.scale, e3)) {
+          float wB = 1.0f;
+          const uint32_t e = emitter_lookup(em.idx, h.blasIdx, h.triIdx);
+          if (e < em.tab.n) {
+            const float4 N = pN[slot], D = pD[slot];   // (the vertex the ray left: overwritten below)
+            float nx = N.x, ny = N.y, nz = N.z;
+            if (nx * D.x + ny * D.y + nz * D.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // (N' as ao_sample_ray turns it)
+            wB = emitter_hit_weight(em.tab, e, nx, ny, nz, rp[3], rp[4], rp[5], h.dist);
+          }
+          L.x = L.x + T.x * (e3[0] * wB); L.y = L.y + T.y * (e3[1] * wB); L.z = L.z + T.z * (e3[2] * wB);
+        }
       }
       if (next) {
         pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
@@ -402,6 +517,14 @@ __global__ __launch_bounds__(256) void rt_path_scatter_emissive_kernel(SceneDev 
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
     uint32_t* __restrict__ next, uint32_t* n_next, ScatterEmi em) {
   path_scatter<EMI>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em);
+}
+
+// (the frame with both estimators weighted, vxrt_render_path_emissive_mis: EMI = 3)
+__global__ __launch_bounds__(256) void rt_path_scatter_mis_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next, ScatterMis em) {
+  path_scatter<3>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em);
 }
 
 // after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
@@ -641,6 +764,9 @@ __global__ __launch_bounds__(256) void rt_sample_counts_kernel(uint32_t n, const
 // 4 M rays for a machine that holds 0.4 M lanes of the traversal kernel -- launch ramps and tails stay a small part of each.
 extern const uint64_t PATH_BATCH_PATHS = 4ull << 20;   // (secondary_knobs, rt_secondary.hip, reads it as VXRT_PATH_BATCH's default)
 
+// `scale` of a frame with emissive geometry, whichever of its two entry points asked for it
+static float emissive_scale(const RenderRequest& r) { return r.emissive ? r.emissive->scale : r.emissive_mis->scale; }
+
 // The prepare launch of a path frame over the n pixels of its window: which instantiation the request takes, and what that one takes
 // besides the arguments all of them share
 static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab, uint32_t n) {
@@ -649,8 +775,8 @@ static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderReques
     hipLaunchKernelGGL(kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
                        c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, flavour);
   };
-  if (r.emissive)      // (never with motion: check_request)
-    launch(r.cams ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, r.emissive->scale);
+  if (r.emissive || r.emissive_mis)      // (never with motion: check_request)
+    launch(r.cams ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, emissive_scale(r));
   else if (r.motion)   // (a camera frame: check_request)
     launch(rt_path_prepare_kernel<true, true>, PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position});
   else
@@ -680,7 +806,8 @@ static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r,
 // the live paths -> closest-hit launch -> (shadow, light sampling: occlusion rays -> any-hit launch) -> (emi = 2, emitter sampling: the
 // any-hit launch of the emitter rays the bounce-ray kernel wrote) -> scatter, which compacts the paths that go on into the next depth's
 // list.  bounce_rays(d, live, n_live, n_next) launches the tail's bounce-ray kernel for depth d; n_rays is the batch's ray count as
-// trace_on_ctx sizes its launch (the live count is read on the device).  emi: 0 none, 1 emission at bounce hits, 2 emitter sampling.
+// trace_on_ctx sizes its launch (the live count is read on the device).  emi: 0 none, 1 emission at bounce hits, 2 emitter sampling,
+// 3 both, weighted (the launches of 2; the scatter kernel looks emissive hits up in the emitter index).
 template <class BounceRays>
 static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, uint32_t cap, uint64_t n_rays, int emi, bool shadow,
                              const BounceRays& bounce_rays) {
@@ -701,8 +828,12 @@ static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& 
                          c->pt_srays, c->pt_stmax, r.counters);
       if (trace_on_ctx(a, c, c->pt_srays, n_rays, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
     }
-    if (emi == 2 && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-    if (emi)
+    if (emi >= 2 && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+    if (emi == 3)
+      hipLaunchKernelGGL(rt_path_scatter_mis_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
+                         (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
+                         ScatterMis{r.emissive_mis->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)});
+    else if (emi)
       hipLaunchKernelGGL(emi == 2 ? rt_path_scatter_emissive_kernel<2> : rt_path_scatter_emissive_kernel<1>, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
                          (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
                          ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
@@ -745,8 +876,11 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   if (path_cap > 0x7fffffffull) return -1;
   // emissive geometry (the header's "Emissive geometry"): 0 none, 1 emission at bounce hits, 2 emitter sampling -- one emitter ray per
   // live path and depth, generated with the bounce ray and traced by a second any-hit launch
-  const int emi = r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
-  if (emi == 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
+  // (3, the header's "Multiple importance sampling": the launches of 2 with the weighted kernels; its emitter index is built here if the
+  // accel holds none -- a buffer that grows, with the one synchronisation that takes)
+  const int emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
+  if (emi == 3 && emitter_index_ensure(a, s) != 0) return -1;
+  if (emi >= 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
                                path_cap, GrowSync::STREAM, s)) return -1;
   if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
@@ -757,10 +891,10 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
                        (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
     // slot -> (pixel, sample) through (s0, k); with emitter sampling the kernel that writes the emitter ray of the same vertex as well
     const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
-      if (emi == 2)
-        hipLaunchKernelGGL(rt_path_bounce_emitter_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
-                           n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, emitter_tab(a),
-                           r.emissive->scale, c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
+      if (emi >= 2)
+        hipLaunchKernelGGL(emi == 3 ? rt_path_bounce_emitter_rays_mis_kernel : rt_path_bounce_emitter_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k,
+                           pp.seed + d, (const uint32_t*)c->pt_list, live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
+                           c->pt_rays, emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
       else
         hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
                            n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
@@ -835,6 +969,19 @@ int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev
 int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
                         uint32_t* emitter, hipStream_t s) {
   hipLaunchKernelGGL(rt_emitter_rays_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), n, points, seeds, scale, rays, tmax, weight3, emitter);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// vxrt_emitter_rays_mis and vxrt_emitter_hit_weights behind their entry points' checks (rt_kernels.hip): one launch each, asynchronous on s
+int emitter_rays_mis_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                            uint32_t* emitter, float* mis, hipStream_t s) {
+  hipLaunchKernelGGL(rt_emitter_rays_mis_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), n, points, seeds, scale, rays, tmax, weight3, emitter, mis);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int emitter_hit_weights_launch(const vxrt_accel* a, uint32_t n, const float* rays, const HitRec* hits, const float* normals, uint32_t* emitter, float* mis,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(rt_emitter_hit_weights_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), emitter_idx(a), n, rays, hits, normals, emitter, mis);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -277,7 +277,7 @@ def wire_unpack(wire_all_ptr, wire_stride_bytes, width, tile_rows_per_rank, worl
 def accel_info(accel, which):
     """vxrt_accel_info: 0 -> internal levels of the deepest path (counted up to 17), 1 -> 48-entry stacks (depth class <= 16),
     2 -> single identity instance under the TLAS root, 3 -> ldexp decode, 4 -> a non-zero alpha table is set, 7 -> emitters of a
-    valid emitter table (0: none, or stale)."""
+    valid emitter table (0: none, or stale), 8 -> entries of the emitter index (0: none built since the last set_emitters)."""
     L = _lib()
     L.vxrt_accel_info.restype = C.c_int
     L.vxrt_accel_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -686,6 +686,10 @@ class EmissiveParams(C.Structure):   # vxrt_emissive_params_t
     _fields_ = [("nee", C.c_uint32), ("scale", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class EmissiveMisParams(C.Structure):   # vxrt_emissive_mis_params_t
+    _fields_ = [("scale", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 def _declare_path_family(L):
     """The prototypes of the path, denoise, temporal, motion, variance and adaptive families; _lib() calls this once with its own."""
     u32, vp, i32 = C.c_uint32, C.c_void_p, C.c_int
@@ -721,6 +725,9 @@ def _declare_path_family(L):
         "vxrt_accel_read_emitters": (i32, [vp, vp, vp, vp, vp]),
         "vxrt_render_path_emissive": (i32, frame + [C.POINTER(EmissiveParams), vp, vp, vp, vp]),
         "vxrt_emitter_rays": (i32, [vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
+        "vxrt_render_path_emissive_mis": (i32, frame + [C.POINTER(EmissiveMisParams), vp, vp, vp, vp]),
+        "vxrt_emitter_rays_mis": (i32, [vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
+        "vxrt_emitter_hit_weights": (i32, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
@@ -843,3 +850,26 @@ def emitter_rays(accel, n, points_ptr, seeds_ptr, scale, rays_ptr, tmax_ptr, wei
     """vxrt_emitter_rays: the emitter-sampling step alone on device buffers -- points (n x 6: I, N'), seeds (n hash outputs) -> rays (n x 6),
     tmax (n), weight (n x 3: G), emitter (n: the index chosen)."""
     check(_lib().vxrt_emitter_rays(accel, int(n), points_ptr, seeds_ptr, float(scale), rays_ptr, tmax_ptr, weight_ptr, emitter_ptr, stream), "vxrt_emitter_rays")
+
+
+# ---- multiple importance sampling of area lights (the header's "Multiple importance sampling") ----
+def render_path_emissive_mis(accel, cam, width, height, y0, y1, params, spp, bounces, emissive, dst_ptr, seed=0, shadow=0, colors_ptr=None, rays_ptr=None,
+                             stream=None):
+    """vxrt_render_path_emissive_mis: render_path_emissive with both estimators in one frame -- the emitter ray of nee = 1 and the emission the
+    bounce rays find, each weighted by the balance heuristic; `emissive`: an EmissiveMisParams (scale).  Needs a valid emitter table; the
+    first frame after a set_emitters builds the accel's emitter index (accel_info(accel, 8))."""
+    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    check(_lib().vxrt_render_path_emissive_mis(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+                                               C.byref(emissive), dst_ptr, colors_ptr, rays_ptr, stream), "vxrt_render_path_emissive_mis")
+
+
+def emitter_rays_mis(accel, n, points_ptr, seeds_ptr, scale, rays_ptr, tmax_ptr, weight_ptr, emitter_ptr, mis_ptr, stream=None):
+    """vxrt_emitter_rays_mis: emitter_rays with weight = Gm = G * wE and mis (n) = wE, the emitter ray's balance-heuristic weight."""
+    check(_lib().vxrt_emitter_rays_mis(accel, int(n), points_ptr, seeds_ptr, float(scale), rays_ptr, tmax_ptr, weight_ptr, emitter_ptr, mis_ptr, stream),
+          "vxrt_emitter_rays_mis")
+
+
+def emitter_hit_weights(accel, n, rays_ptr, hits_ptr, normals_ptr, emitter_ptr, mis_ptr, stream=None):
+    """vxrt_emitter_hit_weights: the bounce ray's side alone on device buffers -- rays (n x 6), hit records (n, as trace writes them), normals
+    (n x 3: the facing normal of the vertex each ray left) -> emitter (n: the table entry hit, 0xFFFFFFFF: not listed), mis (n: wB)."""
+    check(_lib().vxrt_emitter_hit_weights(accel, int(n), rays_ptr, hits_ptr, normals_ptr, emitter_ptr, mis_ptr, stream), "vxrt_emitter_hit_weights")
