@@ -313,7 +313,11 @@ int vxrt_render_interleaved(vxrt_accel_t* accel, uint32_t width, uint32_t height
  *   nodes    device, node_capacity x 52 B (bvh_quantized_node_t), node_capacity >= 2 * n_tris - 1 (the reference allocates
  *            2 * numTris, scene.cpp:40); node 0 is the root, children follow their parent
  * Synchronises `stream` a few times (the cluster count between groups of clustering rounds, the counts at the end).  Returns 0; -1 on bad arguments, allocation failure or a box that cannot
- * be quantised; -2 if the tree is deeper than the 32 levels the reference's trail supports (use the SAH builder). */
+ * be quantised; -2 if the tree is deeper than the 32 levels the reference's trail supports (use the SAH builder).
+ * Non-finite input is refused, the rule of vxrt_accel_refit: a NaN or infinite coordinate in any vertex returns -1 (a NaN would
+ * otherwise drop out of every min / max and leave a tree, and bounds, that do not cover the triangle).  So does a mesh whose extent
+ * along an axis overflows fp32 (no exponent quantises it).  After -1 or -2 tri / triEx may have been reordered, nodes and info hold
+ * no tree; the next build is unaffected. */
 typedef struct vxrt_bvh_info {
   uint32_t n_nodes, n_leaves, max_leaf, max_depth;
   float bounds[6];        /* of the mesh: lo xyz, hi xyz */
@@ -322,7 +326,8 @@ int vxrt_bvh_build(void* tri, void* triEx, uint32_t n_tris, uint32_t tri_offset,
                    void* nodes, uint32_t node_capacity, vxrt_bvh_info_t* info, void* stream);
 /* TLAS over instances on the GPU (reference: BVH::buildTLAS, bvh.cpp:266-421): instance_boxes = device, n_instances x 6 floats
  * (world-space lo xyz, hi xyz of instance i = blas record i); nodes = device, node_capacity >= 2 * n_instances - 1 entries of 52 B;
- * node 0 is the root, a leaf carries leafData = i, internal nodes UINT32_MAX, imask = 1.  Same return codes as vxrt_bvh_build. */
+ * node 0 is the root, a leaf carries leafData = i, internal nodes UINT32_MAX, imask = 1.  Same return codes as vxrt_bvh_build,
+ * the non-finite rule included: a NaN or infinite coordinate in any instance box returns -1. */
 int vxrt_tlas_build(const float* instance_boxes, uint32_t n_instances, void* nodes, uint32_t node_capacity,
                     vxrt_bvh_info_t* info, void* stream);
 /* The builder keeps one grow-only scratch allocation per process (about 170 B per triangle of the largest build) so that a

@@ -234,7 +234,7 @@ def refit(bufs, geometry=True):
     fb_bvh = np.zeros((len(bvh), 6), F)
     bases = np.unique(offs)
     leaves, levels = _walk(bvh, bases, bases, tlas=False)    # (the plan walks every tree, whatever the refit moves)
-    tleaves, tlevels = _walk(tlas, [0], [0], tlas=True)
+    tleaves, _ = _walk(tlas, [0], [0], tlas=True)
     if geometry:
         if len(leaves):
             lo, hi, ok = _tri_boxes(tri, bvh["lf"][leaves], bvh["ld"][leaves])
@@ -265,11 +265,26 @@ def refit(bufs, geometry=True):
     wl, wh = transform_box(m, olo, ohi)
     if not (fin and np.isfinite(m[:, :12]).all() and np.isfinite(wl).all() and np.isfinite(wh).all()):
         raise RefitError("a non-finite transform or box")
-    _set_origin(tlas, tleaves, wl, wh)
+    bw = np.zeros((len(rec), 6), F)
+    bw[inst, :3], bw[inst, 3:] = wl, wh
+    return refit_tlas_from_boxes(tlas, bw[:, :3], bw[:, 3:]), bvh.view(np.uint8).reshape(-1)
+
+
+def refit_tlas_from_boxes(tlas, wl, wh):
+    """The TLAS half of the refit: new bytes (uint8) of the TLAS `tlas` (uint8 or NODE records; topology kept) whose leaf of instance i
+    holds the world box wl[i] / wh[i] ([n_instances, 3] each, fp32), every internal node quantised bottom-up.  Also what
+    vxrt_tlas_build must emit for its own topology.  Raises RefitError on a non-finite box or one that cannot be quantised."""
+    tlas = np.array(np.asarray(tlas).view(np.uint8).reshape(-1), np.uint8).copy().view(NODE)
+    wl, wh = np.asarray(wl, F), np.asarray(wh, F)
+    tleaves, tlevels = _walk(tlas, [0], [0], tlas=True)
+    inst = tlas["ld"][tleaves].astype(np.int64)
+    if not (np.isfinite(wl[inst]).all() and np.isfinite(wh[inst]).all()):
+        raise RefitError("a non-finite box")
+    _set_origin(tlas, tleaves, wl[inst], wh[inst])
     fb_tlas = np.zeros((len(tlas), 6), F)
-    fb_tlas[tleaves, :3], fb_tlas[tleaves, 3:] = wl, wh
+    fb_tlas[tleaves, :3], fb_tlas[tleaves, 3:] = wl[inst], wh[inst]
     _refit_levels(tlas, tlevels, fb_tlas)
-    return tlas.view(np.uint8).reshape(-1), bvh.view(np.uint8).reshape(-1)
+    return tlas.view(np.uint8).reshape(-1)
 
 
 def instance_boxes(bufs):

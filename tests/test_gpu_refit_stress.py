@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import refit_ref as rr
+from builder_cases import aimed_rays as _aimed_rays
 from test_gpu_refit import KEYS, W, H, _agrees_with_fresh_and_oracle, _blob, _host, _put_tri, _render, _stream, _trace
 from test_refit_cpu import _blas_ranges, _check_blases
 from test_scene_builder import NODE, brute_force
@@ -49,22 +50,6 @@ def _tri_ranges(b):
         leaf = sub["ld"] != 0
         out.append((int(sub["lf"][leaf].min()), int((sub["lf"][leaf].astype(np.int64) + sub["ld"][leaf]).max())))
     return out
-
-
-def _aimed_rays(rng, lo, hi, n=64):
-    """Rays from around the box lo / hi at points inside it (unit directions, no zero component)."""
-    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
-    c = (lo + hi) / 2
-    size = float((hi - lo).max())
-    if not size > 0:
-        size = max(float(np.abs(c).max()) * 1e-3, 1e-30)
-    d = rng.normal(size=(n, 3))
-    org = c + 3 * size * d / np.linalg.norm(d, axis=1, keepdims=True)
-    tgt = lo + rng.random((n, 3)) * (hi - lo)
-    dirn = tgt - org
-    dirn /= np.linalg.norm(dirn, axis=1, keepdims=True)
-    rays = np.concatenate([org, dirn], 1).astype(F32)
-    return rays[(rays[:, 3:] != 0).all(1) & np.isfinite(rays).all(1)]
 
 
 # -------------------------------------------------------------------------------------------------------------------------------

@@ -88,14 +88,27 @@ __global__ void bb_init_kernel(int* cb, uint32_t* counters, uint32_t n_counters,
 }
 
 // ---- 1. bounds of the box centres ----
-__global__ __launch_bounds__(256) void bb_bounds_kernel(const float* __restrict__ tri, uint32_t n, int* __restrict__ cb, bool boxes) {
+// ... and, since this pass reads every primitive anyway, the non-finite check: a NaN or infinite coordinate raises BB_ERR_NONFINITE in
+// the error flags (counters[4]), which the host turns into -1.  (fminf / fmaxf drop a NaN: without the check the build succeeds on a
+// tree that does not cover the triangle.)  The kernels after this one still run on the bad values before the host looks at the flag;
+// no index, loop bound or address in them comes from a coordinate -- see the note at build_common.
+constexpr uint32_t BB_ERR_CAPACITY = 1u, BB_ERR_QUANT = 2u, BB_ERR_NONFINITE = 4u;
+__global__ __launch_bounds__(256) void bb_bounds_kernel(const float* __restrict__ tri, uint32_t n, int* __restrict__ cb, uint32_t* __restrict__ counters, bool boxes) {
   float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+  bool bad = false;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const Box3 b = prim_box(tri, i, boxes);
+    const float* p = tri + (size_t)i * (boxes ? 6 : 9);
+    float z = 0.0f;      // x - x is 0 for a finite x, NaN for NaN and +-inf: the sum stays 0 only if all coordinates are finite
+#pragma unroll
+    for (int k = 0; k < 6; ++k) z += p[k] - p[k];
+    if (!boxes) z += (p[6] - p[6]) + (p[7] - p[7]) + (p[8] - p[8]);
+    bad = bad || !(z == 0.0f);
     const float c[3] = {0.5f * (b.lx + b.hx), 0.5f * (b.ly + b.hy), 0.5f * (b.lz + b.hz)};
 #pragma unroll
     for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], c[a]); hi[a] = fmaxf(hi[a], c[a]); }
   }
+  if (bad) atomicOr(counters + 4, BB_ERR_NONFINITE);
 #pragma unroll
   for (int a = 0; a < 3; ++a)
     for (int off = 32; off > 0; off >>= 1) { lo[a] = fminf(lo[a], __shfl_down(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_down(hi[a], off)); }
@@ -178,7 +191,7 @@ __global__ __launch_bounds__(256) void bb_morton_kernel(const float* __restrict_
 // BB_RADIUS clusters on either side of it in the array for the one whose union with it has the smallest surface area; two clusters
 // that choose each other become a node; the array is compacted in place order and the round repeats.  Unlike the binary radix tree
 // of rounds 1-2 (which splits the Morton range at its highest differing bit, a spatial median) the pairs are chosen by the area of
-// the result, which is what the traversal pays for.  Everything is deterministic: ties go to the lower position, node ids and the
+// the result, which is what the traversal pays for.  Everything is deterministic: ties go to the lower position (to the buddy g ^ 1 where a whole window ties: bb_nearest), node ids and the
 // compacted positions come from prefix sums, nothing from the order in which atomics land.
 //   node ids: leaf j (sorted position) is n-1+j; internal ids are handed out downwards from n-2, so the last merge -- the root -- is 0.
 // A round that merges fewer than 1/16 of the clusters is followed by one of forced pairing (positions 2k, 2k+1): inputs where
@@ -238,7 +251,7 @@ __device__ __forceinline__ Cluster bb_merge(const Cluster& A, const Cluster& B, 
   if (A.f3 + B.f1 < g4) { g4 = A.f3 + B.f1; a4 = 3; }
   const float c_node = ar * BB_NODE_COST + g4;
   const float c_leaf = c.count <= leaf_max ? ar * (BB_NODE_COST + tri_cost * (float)c.count) : __builtin_inff();
-  const bool leaf = c_leaf <= c_node;
+  const bool leaf = c.count <= leaf_max && c_leaf <= c_node;   // (an area that overflows makes both +inf: not a leaf for that, whatever its size)
   c.f1 = leaf ? c_leaf : c_node;
   const bool s2 = c.f1 <= g2, s3 = c.f1 <= g3, s4 = c.f1 <= g4;
   c.f2 = s2 ? c.f1 : g2; c.f3 = s3 ? c.f1 : g3; c.f4 = s4 ? c.f1 : g4;
@@ -290,7 +303,7 @@ __global__ __launch_bounds__(256) void bb_leaves_kernel(const float* __restrict_
 // nearest neighbour of position g among [g - R, g + R] of boxes held in LDS (entry k of the tile = position s0 + k); -1 = none
 __device__ __forceinline__ int bb_nearest(const float (*sb)[6], int k, int g, int m, int s0, bool forced) {
   if (forced) { const int j = g ^ 1; return j < m ? j : -1; }
-  float best = __builtin_inff(); int bj = -1;
+  float best = __builtin_inff(), first = 0.0f; int bj = -1; bool all_tie = true;
   const float lx = sb[k][0], ly = sb[k][1], lz = sb[k][2], hx = sb[k][3], hy = sb[k][4], hz = sb[k][5];
 #pragma unroll
   for (int d = -BB_RADIUS; d <= BB_RADIUS; ++d) {
@@ -299,8 +312,15 @@ __device__ __forceinline__ int bb_nearest(const float (*sb)[6], int k, int g, in
     if (j < 0 || j >= m) continue;
     const float* o = sb[j - s0];
     const float a = box_area(fminf(lx, o[0]), fminf(ly, o[1]), fminf(lz, o[2]), fmaxf(hx, o[3]), fmaxf(hy, o[4]), fmaxf(hz, o[5]));
+    if (bj < 0) first = a;
+    else all_tie = all_tie && (a == first || (a != a && first != first));
     if (bj < 0 || a < best || (best != best && a == a)) { best = a; bj = j; }   // (ascending j, strict <: ties go to the lower position; a NaN area never wins over a number, first candidate or not)
   }
+  // Where EVERY union of the window has the same area (copies of one triangle, boxes without area, areas that all underflow or overflow)
+  // the lower position says nothing: it pairs positions 0 and 1 and no others, round after round -- below 32 clusters not even a forced
+  // round follows -- and the tree grows by a level per round: 300 triangles scaled by 1e-30 came out 25 levels deep, 5,000 instance
+  // boxes deeper than the traversal's 32.  Such a position takes its buddy g ^ 1, the partner of a forced round: all of 2k, 2k + 1 pair.
+  if (all_tie && (g ^ 1) < m) return g ^ 1;
   return bj;
 }
 
@@ -479,7 +499,7 @@ __global__ __launch_bounds__(1024) void bb_ploc_tail_kernel(const Cluster* __res
       sf[p][0] = c.f1; sf[p][1] = c.f2; sf[p][2] = c.f3; sf[p][3] = c.f4;
       s_id[p] = c.id; s_count[p] = c.count;
     }
-    forced = !forced && tl < (uint32_t)m / 16u;
+    forced = !forced && (tl < (uint32_t)m / 16u || tl == 0u);   // (below 16 clusters too: a round without a merge is followed by a forced one, so the loop ends)
     m = (int)tk; next -= tl; ++rounds;
     __syncthreads();
   }
@@ -968,7 +988,7 @@ __global__ __launch_bounds__(256) void bb_collapse_kernel(CollapseArgs A) {
       atomicMax(A.counters + 3, A.level + 1u);
     }
     if (!act) continue;
-    if (first + nc > A.node_capacity) { atomicOr(A.counters + 4, 1u); continue; }
+    if (first + nc > A.node_capacity) { atomicOr(A.counters + 4, BB_ERR_CAPACITY); continue; }
     uint32_t w[13];
     w[0] = __float_as_uint(bx.lx); w[1] = __float_as_uint(bx.ly); w[2] = __float_as_uint(bx.lz);
     int e[3] = {bb_pick_exp(bx.hx - bx.lx), bb_pick_exp(bx.hy - bx.ly), bb_pick_exp(bx.hz - bx.lz)};
@@ -983,7 +1003,7 @@ __global__ __launch_bounds__(256) void bb_collapse_kernel(CollapseArgs A) {
         cmin[k] = a == 0 ? cr[k].box.lx : (a == 1 ? cr[k].box.ly : cr[k].box.lz);
         cmax[k] = a == 0 ? cr[k].box.hx : (a == 1 ? cr[k].box.hy : cr[k].box.hz);
       }
-      if (!bb_quant_children(org[a], e[a], cmin, cmax, (1u << nc) - 1u, qla, qha)) atomicOr(A.counters + 4, 2u);
+      if (!bb_quant_children(org[a], e[a], cmin, cmax, (1u << nc) - 1u, qla, qha)) atomicOr(A.counters + 4, BB_ERR_QUANT);
 #pragma unroll
       for (int k = 0; k < 4; ++k) { ql[k][a] = qla[k]; qh[k][a] = qha[k]; }
     }
@@ -1091,6 +1111,24 @@ bool arena_reserve(size_t bytes) {
 
 }  // namespace
 
+// What a NaN or an infinite coordinate can reach (it is refused only at the end, when the host reads the flag bb_bounds_kernel raised):
+//   bounds       fminf / fmaxf drop a NaN, an inf stays; the atomics take ordered integers, `l <= h` guards the empty case.
+//   axis order   extents may be inf or NaN; the axis picked is always one with bits left (3 x 21 = 63 picks), NaN or not.
+//   Morton       t is clamped to [0, 2097151] -- a NaN by !(t >= 0) -- before the conversion to an integer; keys index nothing.
+//   sort         integers; vals stays a permutation of 0..n-1.
+//   clustering   a position's partner is a position of the window that exists (bb_nearest skips j < 0 and j >= m), chosen by comparisons
+//                (NaN orders after +inf, ties go to the lower position, or to the buddy g ^ 1 -- also in the window -- where all tie).  A
+//                round may merge nothing; it is then followed by a forced round, which pairs floor(m / 2): the tail's while loop ends
+//                after at most 2 m rounds, the global rounds are counted by the host.  Compacted positions and node ids come from
+//                ballots and prefix sums.
+//   reinsertion  gains only decide WHETHER a node asks to move (gain > best is false for NaN); the walks are bounded by BB_RI_LISTS and
+//                BB_RI_STEPS, the stack by BB_RI_STACK; locks, the ring guard and the rewiring work on ids.
+//   refit        arrival counters and lists of ids; boxes and costs are only carried.
+//   collapse     plan bits are comparisons (false for NaN: "node", a2 / a3 / a4 stay in range), a leaf needs count <= leaf_max besides
+//                its cost, ranges come from the integer counts; bb_emit_leaf walks by counts.
+//   quantiser    bb_pick_exp returns 0 for NaN / inf; bb_quant_axis maps NaN to 0 before the integer conversion, its loops run at
+//                most 255 steps, the exponent loop to 126.
+// No index, loop bound or LDS address depends on a coordinate.
 static int build_common(void* d_tri, void* d_triEx, uint32_t n_tris, uint32_t tri_offset, uint32_t leaf_max,
                         void* d_nodes, uint32_t node_capacity, vxrt_bvh_info_t* info, void* stream, bool boxes) {
   if (!d_tri || !d_nodes || n_tris == 0 || n_tris > 0x0fffffffu) return -1;
@@ -1140,7 +1178,7 @@ static int build_common(void* d_tri, void* d_triEx, uint32_t n_tris, uint32_t tr
   const float tri_cost = boxes ? 0.0f : tri_cost_env;
 
   hipLaunchKernelGGL(bb_init_kernel, dim3(1), dim3(256), 0, s, cb, counters, n_counters, q0);
-  hipLaunchKernelGGL(bb_bounds_kernel, dim3(wide < 512u ? wide : 512u), dim3(256), 0, s, (const float*)d_tri, n, cb, boxes);
+  hipLaunchKernelGGL(bb_bounds_kernel, dim3(wide < 512u ? wide : 512u), dim3(256), 0, s, (const float*)d_tri, n, cb, counters, boxes);
   hipLaunchKernelGGL(bb_axis_sequence_kernel, dim3(1), dim3(64), 0, s, (const int*)cb, seq);
   hipLaunchKernelGGL(bb_morton_kernel, dim3(blocks), dim3(256), 0, s, (const float*)d_tri, n, (const int*)cb, (const uint32_t*)seq, keys0, vals0, boxes);
   if (rocprim::radix_sort_pairs(tmp, tmp_bytes, keys0, keys1, vals0, vals1, (size_t)n, 0u, 63u, s) != hipSuccess) return -1;
@@ -1259,6 +1297,7 @@ static int build_common(void* d_tri, void* d_triEx, uint32_t n_tris, uint32_t tr
     info->bounds[0] = hroot.lx; info->bounds[1] = hroot.ly; info->bounds[2] = hroot.lz;
     info->bounds[3] = hroot.hx; info->bounds[4] = hroot.hy; info->bounds[5] = hroot.hz;
   }
+  if (hc[4] & BB_ERR_NONFINITE) return -1;                     // a NaN or infinite coordinate (bb_bounds_kernel): refused before anything else is judged
   if (hc[191] != 2u) return -2;                                 // the last refit did not reach the root: a binary tree of more than BB_RI_LISTS levels
   if (hc[192 + ST_N] != 1u || hc[192 + ST_NEXT] != 0u) return -1;   // the clustering did not end in one root with every id used
   if (hc[4] != 0u) return -1;                                  // capacity or exponent range exhausted

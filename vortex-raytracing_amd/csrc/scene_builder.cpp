@@ -89,9 +89,9 @@ static void par_jobs(size_t n, F&& f) {
 constexpr size_t kChunk = 65536;   // elements per job of a chunked pass (fixed: nothing depends on the thread count)
 
 struct Box {
-  V3 lo{kBig, kBig, kBig}, hi{-kBig, -kBig, -kBig};
+  V3 lo{INFINITY, INFINITY, INFINITY}, hi{-INFINITY, -INFINITY, -INFINITY};   // (empty.  Not +-RT_LARGE_FLOAT: a mesh may lie beyond 1e30, and min(1e30, v) was its box)
   void grow(V3 p) { lo = vmin(lo, p); hi = vmax(hi, p); }
-  void grow(const Box& b) { if (b.lo.x != kBig) { grow(b.lo); grow(b.hi); } }
+  void grow(const Box& b) { if (b.lo.x != INFINITY) { grow(b.lo); grow(b.hi); } }
   float half_area() const { V3 e = hi - lo; return e.x * e.y + e.y * e.z + e.z * e.x; }
 };
 
@@ -198,7 +198,10 @@ public:
   uint32_t max_depth_ = 0;
 
 private:
-  struct Split { int axis = -1; int pos = 0; float cost = INFINITY; };
+  // cost: the least (triangles x area) left + right over the candidate planes; nl: triangles left of that plane; worst / cands: the
+  // largest cost among the candidates and how many there were on the axis that offered most -- planes that separate the same triangles
+  // (across a run of empty bins) count once.  worst == cost with cands >= 2: the SAH does not tell the planes apart.
+  struct Split { int axis = -1; int pos = 0; float cost = INFINITY; uint32_t nl = 0; float worst = -INFINITY; uint32_t cands = 0; };
 
   // ---- binary SAH tree to the bottom + SAH-optimal collapse to 4-wide ----
   void build_collapsed() {
@@ -354,7 +357,7 @@ private:
       if (width_ == 2) {   // the raycast twin's BVH2: no collapse, only the leaf-or-node choice (32-byte nodes)
         const float c_node = ar * 32.0f + A[0] + B[0];
         const float c_leaf = (int)x.count <= kLeafMax ? ar * (32.0f + kTriCost * (float)x.count) : INFINITY;
-        const bool leaf = c_leaf <= c_node;
+        const bool leaf = (int)x.count <= kLeafMax && c_leaf <= c_node;      // (an overflowing area makes both INFINITY: not a leaf for that)
         x.f[0] = x.f[1] = x.f[2] = x.f[3] = leaf ? c_leaf : c_node;
         x.plan = 1u | (7u << 6) | (leaf ? kPlanLeaf : 0u);
         return;
@@ -367,7 +370,7 @@ private:
       if (A[2] + B[0] < g4) { g4 = A[2] + B[0]; a4 = 3; }
       const float c_node = ar * kNodeCost + g4;
       const float c_leaf = (int)x.count <= kLeafMax ? ar * (kNodeCost + kTriCost * (float)x.count) : INFINITY;
-      const bool leaf = c_leaf <= c_node;
+      const bool leaf = (int)x.count <= kLeafMax && c_leaf <= c_node;      // (an overflowing area makes both INFINITY: not a leaf for that)
       x.f[0] = leaf ? c_leaf : c_node;
       const bool s2 = x.f[0] <= g2, s3 = x.f[0] <= g3, s4 = x.f[0] <= g4;
       x.f[1] = s2 ? x.f[0] : g2; x.f[2] = s3 ? x.f[0] : g3; x.f[3] = s4 ? x.f[0] : g4;
@@ -475,7 +478,7 @@ private:
     if (!bn[root].left) return;
     struct Cand { float ci; uint32_t node; bool operator<(const Cand& o) const { return ci > o.ci; } };   // (min-heap on the induced cost)
     std::vector<Cand> heap;
-    std::vector<uint32_t> order, dfs;
+    std::vector<uint32_t> order, dfs, path;
     auto report = [&](int pass) {   // VXS_VERBOSE: surface-area cost of the binary tree (internal nodes' areas over the root's)
       if (kVerbose < 2 || root != 0u) return;     // (a walk over the whole tree per report: VXS_VERBOSE=2)
       double a = 0;
@@ -553,6 +556,21 @@ private:
             heap.push_back({ci, t.left}); std::push_heap(heap.begin(), heap.end());
             heap.push_back({ci, t.right}); std::push_heap(heap.begin(), heap.end());
           }
+        }
+        // A position that costs no less than the one X came from is not taken.  The search keeps the first position of the least cost it
+        // meets; where costs tie all over the tree (boxes without area, a thousand copies of one triangle) that is the top of the tree for
+        // every X, and a pass would turn the tree into a chain as long as the mesh is large.  The cost at S is summed down the path from
+        // the root's child exactly as the search sums it, so that a tie is a tie.
+        if (best != S) {
+          path.clear();
+          for (uint32_t a = S; a != root; a = parent[a]) path.push_back(a);
+          float ci = 0.0f, at_s = INFINITY;
+          for (size_t k = path.size(); k-- > 0;) {
+            const BinNode& t = bn[path[k]];
+            at_s = ci + unite(t.box, xb).half_area();
+            ci = at_s - t.box.half_area();
+          }
+          if (!(best_cost < at_s)) best = S;
         }
         // P goes where `best` was, over best and X
         const uint32_t T = best, Q = parent[T];
@@ -669,9 +687,15 @@ private:
       if (deferred && i != root && w.triCount < defer_below) { deferred->push_back(i); continue; }
       const bool shared = par_nodes_ && w.triCount >= kBigNode;      // (a property of the node, not of the thread count)
       const Split s = w.triCount <= kSmallNode ? best_split_small(w) : shared ? best_split_shared(w) : best_split_fused(w);
-      if (s.cost == INFINITY) continue;
+      // Where the SAH has nothing to say, a node too large for a leaf is still split, at the median by count (partition_median): no plane
+      // has a finite cost (every centroid in one place, or areas that overflow), or every plane costs the same (areas that underflow, boxes
+      // without area) and the first of them -- the one a strict minimum reports -- peels off less than an eighth of the triangles, which
+      // level after level makes a tree as deep as the mesh is large.  Smaller nodes end as before: a leaf, or the planes as they come.
+      const bool big = (int)w.triCount > kLeafMax;
+      const bool median = big && (s.cost == INFINITY || (s.cands >= 2 && s.worst == s.cost && 8u * std::min(s.nl, w.triCount - s.nl) < w.triCount));
+      if (s.cost == INFINITY && !median) continue;
       Box lb, lcb, rb, rcb;
-      const uint32_t lc = shared ? partition_shared(w, s, lb, lcb, rb, rcb) : partition_bounds(w, s, lb, lcb, rb, rcb), rc = w.triCount - lc;
+      const uint32_t lc = median ? partition_median(w, lb, lcb, rb, rcb) : shared ? partition_shared(w, s, lb, lcb, rb, rcb) : partition_bounds(w, s, lb, lcb, rb, rcb), rc = w.triCount - lc;
       if (lc == 0 || rc == 0) continue;
       const uint32_t l = (uint32_t)bn.size();
       bn.emplace_back(); bn.emplace_back();
@@ -819,6 +843,31 @@ private:
     return (uint32_t)i;
   }
 
+  // The split of last resort: the first half of the node's triangles by count, in the order of their centroids along the axis on which the
+  // centroids spread most (a stable sort: equal centroids keep their order), or -- every centroid in one place -- in the order they have.
+  // One thread, no state but the node's range: the outcome depends on nothing else.
+  uint32_t partition_median(const WideNode& nd, Box& lb, Box& lcb, Box& rb, Box& rcb) {
+    const uint32_t n = nd.triCount, f = nd.leftFirst, half = n / 2;
+    const V3 e = nd.cbox.hi - nd.cbox.lo;
+    int ax = -1; float widest = 0.0f;
+    for (int a = 0; a < 3; ++a) if (comp(e, a) > widest) { widest = comp(e, a); ax = a; }      // (a NaN extent is never the widest)
+    if (ax >= 0) {
+      std::vector<uint32_t> ord(n);
+      for (uint32_t k = 0; k < n; ++k) ord[k] = k;
+      auto key = [&](uint32_t k) { const float c = comp(cent_[f + k], ax); return c == c ? c : INFINITY; };
+      std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
+      std::vector<rt_tri_t> t2(n); std::vector<V3> c2(n); std::vector<rt_triex_t> x2(triEx_ ? n : 0);
+      for (uint32_t k = 0; k < n; ++k) { t2[k] = tri_[f + ord[k]]; c2[k] = cent_[f + ord[k]]; if (triEx_) x2[k] = triEx_[f + ord[k]]; }
+      std::copy(t2.begin(), t2.end(), tri_ + f); std::copy(c2.begin(), c2.end(), cent_.begin() + f);
+      if (triEx_) std::copy(x2.begin(), x2.end(), triEx_ + f);
+    }
+    WideNode l, r;
+    l.leftFirst = f; l.triCount = half; r.leftFirst = f + half; r.triCount = n - half;
+    bounds(l); bounds(r);
+    lb = l.box; lcb = l.cbox; rb = r.box; rcb = r.cbox;
+    return half;
+  }
+
   void bounds(WideNode& nd) const {
     nd.box = Box(); nd.cbox = Box();
     for (uint32_t i = 0; i < nd.triCount; ++i) {
@@ -870,8 +919,10 @@ private:
       for (uint32_t j = 0; j + 1 < m; ++j) {
         ls += gc[j]; lb.grow(gx[j]);
         const float c = ls * lb.half_area() + ra[j];
-        if (c < best.cost) { best.axis = a; best.pos = gb[j] + 1; best.cost = c; }
+        if (c < best.cost) { best.axis = a; best.pos = gb[j] + 1; best.cost = c; best.nl = (uint32_t)ls; }
+        if (!(c <= best.worst)) best.worst = c;
       }
+      best.cands = std::max(best.cands, m - 1);
     }
     return best;
   }
@@ -905,10 +956,14 @@ private:
       rs += cnt[kBins - 1 - i]; rb.grow(bb[kBins - 1 - i]);
       ra[kBins - 2 - i] = rs > 0 ? rs * rb.half_area() : INFINITY;
     }
+    uint32_t cands = 0; ls = 0;
     for (int i = 0; i < kBins - 1; ++i) {
       const float c = la[i] + ra[i];
-      if (c < best.cost) { best.axis = a; best.pos = i + 1; best.cost = c; }
+      ls += cnt[i];
+      if (c < best.cost) { best.axis = a; best.pos = i + 1; best.cost = c; best.nl = (uint32_t)ls; }
+      if (cnt[i] > 0) { ++cands; if (!(c <= best.worst)) best.worst = c; }      // (the first plane after an occupied bin: a partition of its own)
     }
+    best.cands = std::max(best.cands, cands);
   }
 
   uint32_t partition(const WideNode& nd, const Split& s) {   // bvh.cpp:111-133

@@ -111,6 +111,14 @@ def tlas_build(boxes_ptr, n_instances, nodes_ptr, node_capacity, stream=None):
     return info
 
 
+def release_scratch():
+    """vxrt_bvh_release_scratch: return the builders' grow-only scratch allocation to the device (the next build allocates again)."""
+    L = _lib()
+    L.vxrt_bvh_release_scratch.restype = None
+    L.vxrt_bvh_release_scratch.argtypes = []
+    L.vxrt_bvh_release_scratch()
+
+
 REFIT_INSTANCES, REFIT_GEOMETRY = 1, 2   # VXRT_REFIT_*
 
 
