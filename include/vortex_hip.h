@@ -936,8 +936,8 @@ int vxrt_accel_read_emitters(vxrt_accel_t* accel, float* tri12 /* HOST, n x 12 *
  *   rays_traced also counts the emitter rays that were traced.
  * Returns -1 before anything is launched (dst untouched) for whatever vxrt_render_path refuses (a non-zero alpha table included), a
  * null `em`, nee > 1, a non-zero reserved word, scale negative or not finite, and nee = 1 without a valid table (none set, or stale).
- * There is no denoised, temporal, variance or adaptive form.  The two forms combined by multiple importance sampling are entry points
- * of their own: "Multiple importance sampling" below. */
+ * The denoised, temporal, variance and adaptive forms of this frame are vxrt_render_path_frame's: "Path frames by descriptor" below.
+ * The two forms combined by multiple importance sampling are entry points of their own: "Multiple importance sampling" below. */
 typedef struct vxrt_emissive_params {
   uint32_t nee;          /* 0: emission at bounce hits; 1: emitter sampling from the accel's table */
   float scale;           /* multiplies every material's emissive; >= 0 and finite */
@@ -1011,6 +1011,65 @@ int vxrt_emitter_rays_mis(vxrt_accel_t* accel, uint64_t n, const float* points /
 int vxrt_emitter_hit_weights(vxrt_accel_t* accel, uint64_t n, const float* rays /* device, n x 6 */, const void* hits /* device, n records */,
                              const float* normals /* device, n x 3: N' */, uint32_t* emitter /* device */, float* mis /* device, n: wB */,
                              void* stream);
+
+/* Path frames by descriptor (extension): every path frame above, and the combinations no entry point above can name, through one call.
+ * The descriptor names what the frame is made of; a null part is absent.  The frame is a COMPOSITION of the sections above, and the
+ * meaning of every field is that of the argument of the same name of the entry points above:
+ *   path alone                              vxrt_render_path                       + counts               vxrt_render_path_adaptive
+ *   + denoise (aov optional)                vxrt_render_path_denoised              + emissive             vxrt_render_path_emissive
+ *   + temporal, history                     vxrt_render_path_temporal              + emissive_mis         vxrt_render_path_emissive_mis
+ *   + motion = 1 (prev_position optional)   vxrt_render_path_temporal_motion
+ *   + variance (variance_out optional)      vxrt_render_path_variance, + counts: vxrt_render_path_variance_adaptive
+ * and a descriptor that sets exactly the parts of one of these entry points IS that entry point, bit for bit: pixels, colours, guide
+ * outputs, the history's contents, rays traced (each is a test).  tests/path_frame_ref.py restates the compositions below from the
+ * restatements of the sections they are made of.  Only three things are new:
+ *
+ * EMITTER FORM x COUNTS.  Pixel p with n_p = min(max(counts[p], 1), path->spp) is exactly the vxrt_render_path_emissive /
+ * vxrt_render_path_emissive_mis pixel with spp := n_p, everywhere that definition uses spp -- the emitter ray's hash input
+ * (x + y * W) * n_p + s + 1 + u * 0x9E3779B9, u = ((seed + k) mod 2^32) ^ 0x80000000, included.  rays_traced also counts the emitter
+ * rays that were traced.  UNIFORM and MOSAIC of "Adaptive sampling" hold as stated there, against the emissive frames.
+ *
+ * EMITTER FORM x FILTER.  D, the deterministic term that demodulation subtracts and the `direct` guide reports, is Lit_0 + Emi(h_0) as
+ * the prepare launch forms it: where the material of h_0 does not emit NOTHING is added (the -0 rule of "Emissive geometry").  The
+ * stochastic term (c - D) / A then carries the emitter rays of h_0 -- whose thr is Alb_0 -- as well as the indirect light.  Nothing else
+ * of "Denoised path frames", "Temporal accumulation", "Motion" or "Variance guidance" changes.
+ *
+ * EMITTER TABLE x MOTION.  The table is world-space and goes stale with every vxrt_accel_set_transforms / vxrt_accel_refit, as ever: a
+ * frame with nee = 1 or emissive_mis after a move needs vxrt_accel_set_emitters again, and is refused until then.  The motion snapshot
+ * does not follow the emitters' own motion: as for the point light, a moved lamp changes the signal and the history follows it at the
+ * rate alpha allows.
+ *
+ * Returns -1 before anything is launched -- dst, the guide outputs and the history untouched, vxrt_status unchanged -- for a null
+ * `frame`, size != sizeof(vxrt_path_frame_t), a non-zero reserved word, emissive and emissive_mis both set, motion > 1, prev_position
+ * without motion, variance_out without variance, aov / temporal / history / motion / variance without denoise, and for everything the
+ * entry point of the same combination refuses: a null path / params / dst, a bad window or camera, temporal without history or the
+ * reverse, a history of the wrong kind (moments iff variance) or too small, motion or variance without temporal, motion without a
+ * snapshot, bad parameters of any part, a non-zero alpha table, a stale accel, nee = 1 / emissive_mis without a valid table.  0 for an
+ * empty window.  Asynchronous on `stream` as the entry points above; a counts frame with nee = 1 / emissive_mis holds 68 bytes more per
+ * path of a batch (VXRT_PATH_BATCH, docs/KNOBS.md) for the emitter rays. */
+typedef struct vxrt_path_frame {
+  uint32_t size;                                   /* sizeof(vxrt_path_frame_t) */
+  uint32_t width, height, y0, y1;
+  uint32_t motion;                                 /* 0 / 1 */
+  const vxrt_camera_t* cam;                        /* NULL = fixed camera */
+  const vxrt_shade_params_t* params;
+  const vxrt_path_params_t* path;                  /* with counts: spp is the cap */
+  const vxrt_emissive_params_t* emissive;          /* at most one of these two */
+  const vxrt_emissive_mis_params_t* emissive_mis;
+  const uint32_t* counts;                          /* device, addressed like dst; optional */
+  const vxrt_denoise_params_t* denoise;            /* optional; the rest of the chain needs it */
+  const vxrt_path_aov_t* aov;
+  const vxrt_temporal_params_t* temporal;          /* temporal and history: both or neither */
+  vxrt_history_t* history;
+  const vxrt_variance_params_t* variance;          /* needs temporal and a history with moments */
+  uint32_t* dst;
+  float* colors;                                   /* optional */
+  float* prev_position;                            /* optional, motion only */
+  float* variance_out;                             /* optional, variance only */
+  unsigned long long* rays_traced;                 /* optional */
+  uint32_t reserved[4];                            /* 0 */
+} vxrt_path_frame_t;
+int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* frame, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

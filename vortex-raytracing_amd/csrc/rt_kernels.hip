@@ -1864,13 +1864,14 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
                  r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
   // ... with a sample count per pixel: a path frame (a null buffer is the entry point's to refuse: here it means "no counts")
   if (r.sample_counts && !r.path) return -1;
-  // ... with emissive geometry: a plain path frame (no counts, no filter); the parameters, and for emitter sampling a valid table
-  if (r.emissive && (!r.path || r.sample_counts || r.denoise || r.aov || r.temporal || r.history || r.motion || r.variance || r.emissive->nee > 1u ||
+  // ... with emissive geometry: a path frame (with counts, a filter, a history as any other: only vxrt_render_path_frame can ask for
+  // them together); the parameters, and for emitter sampling a valid table
+  if (r.emissive && (!r.path || r.emissive->nee > 1u ||
                      r.emissive->reserved[0] != 0u || r.emissive->reserved[1] != 0u || !(r.emissive->scale >= 0.0f) || !std::isfinite(r.emissive->scale) ||
                      (r.emissive->nee == 1u && !emitters_valid(a)))) return -1;
   // ... with both estimators of emissive geometry weighted: what the emissive frame with emitter sampling asks for, in a request field
   // of its own (the entry point is its own; the two fields exclude each other)
-  if (r.emissive_mis && (!r.path || r.emissive || r.sample_counts || r.denoise || r.aov || r.temporal || r.history || r.motion || r.variance ||
+  if (r.emissive_mis && (!r.path || r.emissive ||
                          r.emissive_mis->reserved[0] != 0u || r.emissive_mis->reserved[1] != 0u || r.emissive_mis->reserved[2] != 0u ||
                          !(r.emissive_mis->scale >= 0.0f) || !std::isfinite(r.emissive_mis->scale) || !emitters_valid(a))) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
@@ -2540,6 +2541,30 @@ int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam,
   if (cam && !camera_ok(cam)) return -1;
   RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
   r.emissive_mis = em;
+  return render_common(accel, r);
+}
+
+// A path frame by descriptor (see the header, "Path frames by descriptor"): the request every vxrt_render_path* entry point above builds
+// from its arguments, built from the fields the caller set.  What the descriptor alone can get wrong is refused here; what an entry
+// point above refuses before render_common (a null part, a camera, the history against the window) is refused here the same way; the
+// rest is check_request's, as for them.
+int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void* stream) {
+  if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
+  for (int k = 0; k < 4; ++k) if (f->reserved[k] != 0u) return -1;
+  if (!f->path || (f->emissive && f->emissive_mis) || f->motion > 1u) return -1;
+  if ((f->prev_position && !f->motion) || (f->variance_out && !f->variance)) return -1;
+  if (f->cam && !camera_ok(f->cam)) return -1;
+  const bool chain = f->aov || f->temporal || f->history || f->motion || f->variance;   // (the rest of the chain needs the filter's parameters)
+  if (chain && !f->denoise) return -1;
+  if (f->temporal || f->history || f->motion || f->variance) {   // (a camera frame with both: the entry points' own order of checks)
+    if (!camera_ok(f->cam)) return -1;
+    const uint64_t pixels = f->y0 <= f->y1 ? (uint64_t)f->width * (f->y1 - f->y0) : 0;   // (a bad window is check_request's to refuse)
+    if (!tp_request_ok(f->history, f->temporal, pixels, f->variance != nullptr)) return -1;
+  }
+  RenderRequest r = path_request(f->cam, f->width, f->height, f->y0, f->y1, f->params, f->path, f->dst, f->colors, f->rays_traced, stream);
+  r.emissive = f->emissive; r.emissive_mis = f->emissive_mis; r.sample_counts = f->counts;
+  r.denoise = f->denoise; r.aov = f->aov; r.temporal = f->temporal; r.history = f->history; r.motion = f->motion == 1u; r.prev_position = f->prev_position;
+  r.variance = f->variance; r.variance_out = f->variance_out;
   return render_common(accel, r);
 }
 

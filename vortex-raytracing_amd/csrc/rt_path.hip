@@ -163,6 +163,14 @@ __global__ __launch_bounds__(256) void rt_path_prepare_emissive_kernel(SceneDev 
   path_prepare<CAM, false, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepEmi{scale});
 }
 
+// (the frame with emissive geometry and motion, vxrt_render_path_frame: both flavours at once; a camera frame, as every frame with motion)
+__global__ __launch_bounds__(256) void rt_path_prepare_emissive_motion_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, PrepMotion mo, float scale) {
+  path_prepare<true, true, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, mo, PrepEmi{scale});
+}
+
 // start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
 __global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
     const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
@@ -261,9 +269,21 @@ __device__ __forceinline__ bool emitter_sample(const EmitterTab& tab, float scal
 // same vertex -- user seed (seed + depth) ^ 0x80000000 in the bounce ray's hash input -- with its tmax and G (w = 1: real; a skipped
 // one is not counted).  One atomic per workgroup on the ray counter for the emitter rays, thread 0's for the bounce rays.
 // (MIS: the frame of the header's "Multiple importance sampling" -- eG[q] = (Gm, real))
-template <bool MIS>
-__device__ __forceinline__ void path_bounce_emitter_rays(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
-    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+// (SlotSrc: where slot -> (pixel of the window, sample, the spp of the hash inputs) comes from -- SlotUniform, the batches of whole
+//  samples of render_path_tail; SlotCounts, the slot tables and the pixel's own count of render_path_counts_tail.  No thread leaves
+//  before the barriers: a workgroup past the live count, and every workgroup of a batch without live paths, falls through with real =
+//  false in all its lanes and adds nothing.)
+struct SlotUniform {
+  uint32_t spp, s0, ns; const uint32_t* __restrict__ list;
+  __device__ __forceinline__ void get(uint32_t slot, uint32_t& t, uint32_t& smp, uint32_t& n) const { t = list[slot / ns]; smp = s0 + slot % ns; n = spp; }
+};
+struct SlotCounts {
+  const uint32_t* __restrict__ spix; const uint32_t* __restrict__ ssmp; const uint32_t* __restrict__ cnt;
+  __device__ __forceinline__ void get(uint32_t slot, uint32_t& t, uint32_t& smp, uint32_t& n) const { t = spix[slot]; smp = ssmp[slot]; n = cnt[t]; }
+};
+template <bool MIS, class SlotSrc>
+__device__ __forceinline__ void path_bounce_emitter_rays(uint32_t cap, uint32_t W, uint32_t y0, const SlotSrc& src, uint32_t user_seed,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
     const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, const EmitterTab& tab, float scale,
     float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
   __shared__ uint32_t s_real;
@@ -277,7 +297,9 @@ __device__ __forceinline__ void path_bounce_emitter_rays(uint32_t cap, uint32_t 
   }
   bool real = false;
   if (q < total) {
-    const uint32_t slot = live[q], t = list[slot / ns], smp = s0 + slot % ns;
+    const uint32_t slot = live[q];
+    uint32_t t, smp, spp;
+    src.get(slot, t, smp, spp);
     const uint32_t x = t % W, y = y0 + t / W;
     const float4 I = pI[slot], N = pN[slot], D = pD[slot];
     float r6[6];
@@ -308,14 +330,14 @@ __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_kernel(uint32
     const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
     const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
     float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
-  path_bounce_emitter_rays<false>(cap, W, y0, spp, s0, ns, user_seed, list, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+  path_bounce_emitter_rays<false>(cap, W, y0, SlotUniform{spp, s0, ns, list}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
 }
 
 __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_mis_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
     const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
     const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
     float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
-  path_bounce_emitter_rays<true>(cap, W, y0, spp, s0, ns, user_seed, list, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+  path_bounce_emitter_rays<true>(cap, W, y0, SlotUniform{spp, s0, ns, list}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
 }
 
 // The emitter index of the header's "Multiple importance sampling": the position of (blas, tri) among the sorted (blasIdx, triIdx, e)
@@ -693,6 +715,25 @@ __global__ __launch_bounds__(256) void rt_path_bounce_rays_counts_kernel(uint32_
   for (int k = 0; k < 6; ++k) o[k] = r6[k];
 }
 
+// rt_path_bounce_emitter_rays_kernel / its MIS twin with the slot's pixel, sample and the pixel's own sample count, as the kernel above
+// reads them: the emitter ray's hash input is (x + y * W) * n_p + s + 1 + u * 0x9E3779B9.  The body is path_bounce_emitter_rays, which
+// no thread leaves early -- unlike the kernel above, it ends in a barrier and one count per workgroup.
+__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_counts_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
+    const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  path_bounce_emitter_rays<false>(cap, W, y0, SlotCounts{spix, ssmp, cnt}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+}
+
+__global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_counts_mis_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
+    const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  path_bounce_emitter_rays<true>(cap, W, y0, SlotCounts{spix, ssmp, cnt}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+}
+
 // after a batch's last depth, one thread per pixel of the window: the Lc of the pixel's samples that are in the batch [g0, g0 + cap)
 // are added to its accumulator in ascending sample order; the pixel's first sample starts it.  A pixel's samples are contiguous in g
 // and may straddle batches; the trip count is at most the pixel's count.
@@ -775,7 +816,12 @@ static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderReques
     hipLaunchKernelGGL(kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
                        c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, flavour);
   };
-  if (r.emissive || r.emissive_mis)      // (never with motion: check_request)
+  const bool emi = r.emissive || r.emissive_mis;
+  if (emi && r.motion) {   // (a camera frame: check_request.  Two flavours: the one launch with an argument more)
+    hipLaunchKernelGGL(rt_path_prepare_emissive_motion_kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
+                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl,
+                       PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position}, emissive_scale(r));
+  } else if (emi)
     launch(r.cams ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, emissive_scale(r));
   else if (r.motion)   // (a camera frame: check_request)
     launch(rt_path_prepare_kernel<true, true>, PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position});
@@ -857,6 +903,20 @@ static int path_frame_end(FrameCtx* c, const RenderRequest& r, uint32_t n, uint3
 
 static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 
+// The emitter form of a path frame, which both tails derive alike (the header's "Emissive geometry"): emi = 0 none, 1 emission at bounce
+// hits, 2 emitter sampling -- one emitter ray per live path and depth, generated with the bounce ray and traced by a second any-hit
+// launch -- 3, the header's "Multiple importance sampling": the launches of 2 with the weighted kernels; its emitter index is built here
+// if the accel holds none (a buffer that grows, with the one synchronisation that takes).  For 2 and 3 the context's emitter-ray buffers
+// are grown to batches of path_cap paths.
+static int path_emitter_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, uint64_t path_cap, int& emi) {
+  hipStream_t s = (hipStream_t)r.stream;
+  emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
+  if (emi == 3 && emitter_index_ensure(a, s) != 0) return -1;
+  if (emi >= 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
+                               path_cap, GrowSync::STREAM, s)) return -1;
+  return 0;
+}
+
 // Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
 // occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
 // pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
@@ -874,14 +934,8 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
   const uint64_t path_cap = pp.bounces ? n * ns : 0;
   if (path_cap > 0x7fffffffull) return -1;
-  // emissive geometry (the header's "Emissive geometry"): 0 none, 1 emission at bounce hits, 2 emitter sampling -- one emitter ray per
-  // live path and depth, generated with the bounce ray and traced by a second any-hit launch
-  // (3, the header's "Multiple importance sampling": the launches of 2 with the weighted kernels; its emitter index is built here if the
-  // accel holds none -- a buffer that grows, with the one synchronisation that takes)
-  const int emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
-  if (emi == 3 && emitter_index_ensure(a, s) != 0) return -1;
-  if (emi >= 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
-                               path_cap, GrowSync::STREAM, s)) return -1;
+  int emi;
+  if (path_emitter_begin(a, c, r, path_cap, emi) != 0) return -1;
   if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
   const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u);
@@ -913,6 +967,8 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
 // pixel's count and the frame ends as every path frame, with spp = 1.  The number of paths stays on the device, so the host issues
 // ceil(pixels * spp / cap) batches whatever the counts: a batch past the end starts with zero live paths and its launches fall through.
 // Storage per path is bounded by cap.  No host synchronisation unless a buffer grows.
+// With an emitter form (vxrt_render_path_frame; the header's "Path frames by descriptor") emi is derived as in render_path_tail, the
+// emitter-ray buffers are grown to cap as well, and the bounce-ray kernel is the one that also writes the emitter ray of the slot's vertex.
 static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
   const vxrt_path_params_t& pp = *r.path;
   const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
@@ -928,6 +984,8 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
   if (!grow_device({{(void**)&c->pt_cnt, 4}, {(void**)&c->pt_off, 8}}, &c->pt_cnt_cap, n, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_bsum, 4}, {(void**)&c->pt_boff, 8}}, &c->pt_blk_cap, n_blocks, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_spix, 4}, {(void**)&c->pt_ssmp, 4}}, &c->pt_slot_cap, path_cap, GrowSync::STREAM, s)) return -1;
+  int emi;   // (as render_path_tail: the emitter rays of a batch are bounded by its capacity)
+  if (path_emitter_begin(a, c, r, path_cap, emi) != 0) return -1;
   if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
   const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u), sgrid((uint32_t)n_blocks);
@@ -942,13 +1000,19 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
                        (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
                        c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0], c->pt_spix, c->pt_ssmp);
     // slot -> (pixel, sample) through the slot tables the start kernel filled; the pixel's own count in place of spp
+    // (with emitter sampling the kernel that writes the emitter ray of the same vertex as well)
     const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
-      hipLaunchKernelGGL(rt_path_bounce_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp,
-                         (const uint32_t*)c->pt_cnt, live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
-                         c->pt_rays, r.counters);
+      if (emi >= 2)
+        hipLaunchKernelGGL(emi == 3 ? rt_path_bounce_emitter_rays_counts_mis_kernel : rt_path_bounce_emitter_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0,
+                           pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp, (const uint32_t*)c->pt_cnt, live, n_live, n_next,
+                           (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, emitter_tab(a), emissive_scale(r),
+                           c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
+      else
+        hipLaunchKernelGGL(rt_path_bounce_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp,
+                           (const uint32_t*)c->pt_cnt, live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
+                           c->pt_rays, r.counters);
     };
-    // (emi = 0: check_request refuses emissive geometry with a count per pixel)
-    if (path_batch_depths(a, c, r, p, cap, cap, 0, pp.shadow != 0, bounce_rays) != 0) return -1;
+    if (path_batch_depths(a, c, r, p, cap, cap, emi, pp.shadow != 0, bounce_rays) != 0) return -1;
     hipLaunchKernelGGL(rt_path_accumulate_counts_kernel, grid, block, 0, s, n32, cap, g0, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_off,
                        (const float4*)c->pt_L, c->pt_acc);
   }

@@ -698,6 +698,37 @@ class EmissiveMisParams(C.Structure):   # vxrt_emissive_mis_params_t
     _fields_ = [("scale", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
+class PathFrame(C.Structure):   # vxrt_path_frame_t: what a path frame is made of; a part left None is absent
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("y0", C.c_uint32), ("y1", C.c_uint32), ("motion", C.c_uint32),
+                ("cam", C.POINTER(Camera)), ("params", C.POINTER(ShadeParams)), ("path", C.POINTER(PathParams)),
+                ("emissive", C.POINTER(EmissiveParams)), ("emissive_mis", C.POINTER(EmissiveMisParams)), ("counts", C.c_void_p),
+                ("denoise", C.POINTER(DenoiseParams)), ("aov", C.POINTER(PathAov)), ("temporal", C.POINTER(TemporalParams)), ("history", C.c_void_p),
+                ("variance", C.POINTER(VarianceParams)), ("dst", C.c_void_p), ("colors", C.c_void_p), ("prev_position", C.c_void_p),
+                ("variance_out", C.c_void_p), ("rays_traced", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, width, height, y0, y1, params, path, dst, cam=None, emissive=None, emissive_mis=None, counts=None, denoise=None, aov=None,
+                 temporal=None, history=None, motion=0, variance=None, colors=None, prev_position=None, variance_out=None, rays_traced=None):
+        """`params`, `path` and the optional parts are the structures the render_path* calls take (`cam`: a Camera or 14 floats; `history`:
+        a History); `dst`, `counts` and the optional outputs are device pointers.  The structures are kept alive by the frame."""
+        super().__init__()
+        self.size = C.sizeof(PathFrame)
+        self.width, self.height, self.y0, self.y1, self.motion = int(width), int(height), int(y0), int(y1), int(motion)
+        self._keep = [None if cam is None else _camera(cam), params, path, emissive, emissive_mis, denoise, aov, temporal, variance]
+        for name, part in zip(("cam", "params", "path", "emissive", "emissive_mis", "denoise", "aov", "temporal", "variance"), self._keep):
+            if part is not None:
+                setattr(self, name, C.pointer(part))
+        h = None if history is None else _history(history)
+        self.history = h.value if isinstance(h, C.c_void_p) else h
+        self.counts, self.dst, self.colors, self.prev_position = counts, dst, colors, prev_position
+        self.variance_out, self.rays_traced = variance_out, rays_traced
+
+
+def render_path_frame(accel, frame, stream=None):
+    """vxrt_render_path_frame: the path frame `frame` (a PathFrame) describes -- every render_path* call above is the frame with that
+    call's parts, and the parts combine: an emitter form with counts, the filter, a history, motion, variance.  Raises on a refusal."""
+    check(_lib().vxrt_render_path_frame(accel, C.byref(frame) if frame is not None else None, stream), "vxrt_render_path_frame")
+
+
 def _declare_path_family(L):
     """The prototypes of the path, denoise, temporal, motion, variance and adaptive families; _lib() calls this once with its own."""
     u32, vp, i32 = C.c_uint32, C.c_void_p, C.c_int
@@ -736,6 +767,7 @@ def _declare_path_family(L):
         "vxrt_render_path_emissive_mis": (i32, frame + [C.POINTER(EmissiveMisParams), vp, vp, vp, vp]),
         "vxrt_emitter_rays_mis": (i32, [vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
         "vxrt_emitter_hit_weights": (i32, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "vxrt_render_path_frame": (i32, [vp, C.POINTER(PathFrame), vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
