@@ -478,7 +478,7 @@ int vxrt_render_diffuse_bounce_camera(vxrt_accel_t* accel, const vxrt_camera_t* 
  * by per-path state.  Every + and * below is an fp32 operation without contraction, in the order written, so the frame is
  * reproducible bit for bit (tests/path_ref.py restates it).  cam == NULL: the RTU test's fixed GenerateRay, as vxrt_render uses it;
  * else the pinhole ray of vxrt_camera_t.  params->max_depth is ignored (as vxrt_render_ao and vxrt_render_diffuse_bounce ignore it):
- * the mirror arm is never followed.  For pixel (x, y) of rows [y0, y1):
+ * the mirror arm is never followed (vxrt_render_path_frame_specular follows it: "Specular vertices" below).  For pixel (x, y) of rows [y0, y1):
  *   r_0 = the camera ray, h_0 = its closest hit; on a miss the pixel is the background and no further ray is traced.
  *   Lit(r, h) = the Lambert colour of the hit as vxrt_shade_rays computes it (term + background * reflectivity, the else arm of
  *     closest.cpp); with shadow != 0 the occlusion ray of vxrt_render is traced first (origin pushed 1e-3 along L, tmax = |L|,
@@ -1070,6 +1070,69 @@ typedef struct vxrt_path_frame {
   uint32_t reserved[4];                            /* 0 */
 } vxrt_path_frame_t;
 int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* frame, void* stream);
+
+/* Specular vertices (extension): path frames that follow blas_node_t::reflectivity, as vxrt_render[_camera] follow the reference's mirror
+ * arm.  Above, "the mirror arm is never followed": a reflective instance shows term + background * reflectivity.  Here a path vertex can
+ * be specular, and a lobe pick decides per sample whether the path leaves it along the mirror ray or along the diffuse bounce ray.
+ * Everything is "Path-traced frame" / "Emissive geometry" / "Multiple importance sampling" / "Adaptive sampling" as written, except what
+ * follows; every + and * is one fp32 operation without contraction, as ever.  tests/specular_ref.py restates all of it.
+ *
+ * rho(h) is the `reflectivity` of the hit instance.  A vertex h is SPECULAR iff rho(h) > 0 and rho(h) is finite: NaN, +-inf and
+ * rho <= 0 are not specular and behave exactly as above.  A vertex CONTINUES if a bounce ray will leave it: every vertex but the last
+ * of a path (the hit at depth index `bounces`; with bounces = 0 every vertex is last).
+ *
+ * LIT.  A specular vertex that continues adds `term` alone: the r, g, b of shade_terms, NdotL forced to 0 when occluded as above,
+ * WITHOUT background * rho -- the mirror ray now supplies what that stood for.  Every other vertex adds Lit as above, unchanged: the
+ * vertices that are not specular, and the last vertex, which is the reference's own bounce + 1 >= max_depth arm.
+ *
+ * THROUGHPUT.  thr = (1, 1, 1) before the primary vertex, and it is updated when a ray LEAVES a vertex, not when the vertex is hit.
+ *
+ * THE LOBE PICK at a continuing vertex h of depth k, for sample s of pixel (x, y):
+ *   seed = WangHash((x + y * W) * spp + s + 1 + u * 0x9E3779B9), u = ((path.seed + k) mod 2^32) ^ 0x40000000 -- the bounce ray's hash
+ *   input with another bit flipped than the emitter ray's 0x80000000; with counts spp is the pixel's own n_p, as for the emitter ray;
+ *   0 becomes 1.   xi = random_float(seed): one xorshift step, (float)state * 2.3283064365387e-10f.
+ *   MIRROR iff h is specular and (rho >= 1.0f or xi < rho); else DIFFUSE.  A vertex that is not specular takes no draw.
+ *   mirror:   thr is unchanged; r' = the mirror ray of closest.cpp:96-99 -- R = normalize(dir(r) - (2.0f * N) * dot(N, dir(r))), N NOT
+ *             turned, origin I + R * 0.001f -- traced for its closest hit, no tmax; the segment is marked specular.
+ *   diffuse:  thr = thr * Alb(h); r' = the vxrt_render_ao ray with user seed (seed + k) as above; the segment is not specular.
+ * The mirror lobe is picked with probability rho and weighs 1, the diffuse lobe with 1 - rho and weighs 1, and `term` already carries
+ * its (1 - rho): together they estimate term + rho * L(mirror) + (1 - rho) * Alb * L(diffuse), the reference's recursion extended by
+ * indirect light.
+ *
+ * EMITTER FORMS.  With nee = 1 and emissive_mis the emitter ray belongs to the diffuse lobe: a vertex that picks mirror sends none (a
+ * skipped ray: tmax = -1, G = 0, not counted in rays_traced), a vertex that picks diffuse sends it exactly as above, with thr after the
+ * multiplication.  A SPECULAR SEGMENT that hits an emitting material adds thr * Emi(h') in full in all three forms: nee = 0 as above;
+ * nee = 1, where a bounce hit adds no emission otherwise; emissive_mis with wB = 1 and no lookup in the emitter index.  A segment that
+ * is not specular is as above, and so is Emi(h_0) at the primary hit.
+ * rays_traced is unchanged in kind: the primaries, one per occlusion ray of a real hit, one per bounce ray of a live path (mirror or
+ * diffuse), one per emitter ray actually sent.
+ *
+ * Three identities follow (each is a test):
+ *   A  on a scene where no vertex any path meets is specular the frame is the same descriptor's vxrt_render_path_frame bit for bit --
+ *      pixels, colours, rays traced: 1 * x is x.
+ *   B  bounces = 0 is that frame bit for bit on any scene: every vertex is last.
+ *   C  with bounces = 1, spp a power of two and any `shadow`, a pixel whose primary hit has rho = 1 exactly is the vxrt_render_camera
+ *      pixel of the same camera with max_depth = 2, pixel and colour: 0 + 1 * Lit(h_1) against term_0 + C_1 * (1 * rho).
+ *
+ * THE CALL.  vxrt_path_frame_t cannot grow, so the specular part rides beside it.  specular == NULL or enable = 0 IS
+ * vxrt_render_path_frame(accel, frame, stream).  With enable = 1 the frame may carry `path`, `cam` or none, `counts`, and at most one
+ * emitter form.  Returns -1 before anything is launched -- dst untouched, vxrt_status unchanged -- for enable > 1, a non-zero reserved
+ * word, enable = 1 together with any of denoise / aov / temporal / history / motion / variance, and everything vxrt_render_path_frame
+ * refuses.  THE FILTER CHAIN IS OUT OF SCOPE on purpose: a mirror's primary-hit albedo, normal and position are the wrong guides,
+ * demodulation by Alb_0 no longer factors, and "the guides of the first vertex that is not specular" is a design of its own.
+ * Asynchronous on `stream` as vxrt_render_path_frame; a frame with enable = 1 holds 16 bytes more per path of a batch (VXRT_PATH_BATCH,
+ * docs/KNOBS.md): Alb and rho of the path's last vertex.
+ *
+ * vxrt_specular_pick runs the pick and the mirror ray alone on caller-owned DEVICE buffers: vertices = n x 10 floats (I, N, dir(r), rho),
+ * seeds = n hash outputs (0 becomes 1) -> lobe (n: 1 mirror, 0 diffuse) and rays (n x 6: the mirror ray for lobe 1, six zeros for lobe
+ * 0).  One launch, asynchronous on `stream`.  Returns -1 before the launch for a null buffer or n >= 2^31; 0 for n = 0. */
+typedef struct vxrt_specular_params {
+  uint32_t enable;       /* 0 / 1 */
+  uint32_t reserved[3];  /* 0 */
+} vxrt_specular_params_t;
+int vxrt_render_path_frame_specular(vxrt_accel_t* accel, const vxrt_path_frame_t* frame, const vxrt_specular_params_t* specular, void* stream);
+int vxrt_specular_pick(uint64_t n, const float* vertices /* device, n x 10: I, N, dir, rho */, const uint32_t* seeds /* device */,
+                       float* rays /* device, n x 6 */, uint32_t* lobe /* device */, void* stream);
 
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,

@@ -472,7 +472,7 @@ static void accel_free(vxrt_accel* a) {
                     (void*)c.pt_I, (void*)c.pt_N, (void*)c.pt_D, (void*)c.pt_L, (void*)c.pt_T, (void*)c.pt_live[0], (void*)c.pt_live[1], (void*)c.pt_rays,
                     (void*)c.pt_hits, (void*)c.pt_srays, (void*)c.pt_stmax, (void*)c.pt_shits, (void*)c.dn_sig[0], (void*)c.dn_sig[1], (void*)c.mo_pos, (void*)c.mo_nrm,
                     (void*)c.pt_cnt, (void*)c.pt_off, (void*)c.pt_bsum, (void*)c.pt_boff, (void*)c.pt_ctot, (void*)c.pt_spix, (void*)c.pt_ssmp,
-                    (void*)c.pt_erays, (void*)c.pt_etmax, (void*)c.pt_ehits, (void*)c.pt_eG}) (void)hipFree(q);
+                    (void*)c.pt_erays, (void*)c.pt_etmax, (void*)c.pt_ehits, (void*)c.pt_eG, (void*)c.pt_A}) (void)hipFree(q);
     for (FrameCtx::Level& l : c.lv) {
       (void)hipFree(l.rays); (void)hipFree(l.hits); (void)hipFree(l.parent); (void)hipFree(l.term); (void)hipFree(l.col);
       (void)hipFree(l.srays); (void)hipFree(l.stmax); (void)hipFree(l.shits);

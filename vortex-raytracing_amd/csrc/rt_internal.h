@@ -120,6 +120,10 @@ struct FrameCtx {
   // path frames with emitter sampling (vxrt_render_path_emissive, nee = 1; allocated on first use).  Per live path of a depth: the emitter
   // ray, its tmax and hit record, and G (w = 1: the ray is real, 0: skipped)
   float* pt_erays = nullptr; float* pt_etmax = nullptr; HitRec* pt_ehits = nullptr; float4* pt_eG = nullptr; uint64_t pt_em_cap = 0;
+  // path frames with specular vertices (vxrt_render_path_frame_specular; allocated on first use).  Per path of a batch: Alb of its last
+  // vertex and that vertex's reflectivity in .w -- in such a frame pt_T is thr BEFORE the last vertex's albedo, pt_D.w marks a specular
+  // segment in flight, and .w of pt_alb is the primary hit's reflectivity
+  float4* pt_A = nullptr; uint64_t pt_spec_cap = 0;
   // denoised path frames (vxrt_render_path_denoised; allocated on first use): the two signal buffers the a-trous iterations ping-pong
   // between, one float4 (E, lum(E)) per pixel of the window; the guides are pt_geo and pt_nrm
   float4* dn_sig[2] = {nullptr, nullptr}; uint64_t dn_cap = 0;
@@ -275,6 +279,7 @@ struct RenderRequest {
   const vxrt_path_params_t* path = nullptr;         // path frame (vxrt_render_path)
   const vxrt_emissive_params_t* emissive = nullptr; // ... with emissive geometry (vxrt_render_path_emissive): a plain path frame otherwise
   const vxrt_emissive_mis_params_t* emissive_mis = nullptr; // ... with both estimators of emissive geometry, weighted (vxrt_render_path_emissive_mis)
+  const vxrt_specular_params_t* specular = nullptr; // ... whose vertices may be specular (vxrt_render_path_frame_specular with enable = 1; null for enable = 0)
   const uint32_t* sample_counts = nullptr;          // ... with a sample count per pixel (vxrt_render_path_adaptive): device, addressed like dst; path->spp is the cap
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;
@@ -344,6 +349,8 @@ int emitter_rays_mis_launch(const vxrt_accel* a, uint32_t n, const float* points
                             uint32_t* emitter, float* mis, hipStream_t s);
 int emitter_hit_weights_launch(const vxrt_accel* a, uint32_t n, const float* rays, const HitRec* hits, const float* normals, uint32_t* emitter, float* mis,
                                hipStream_t s);
+// rt_path.hip: the launch of vxrt_specular_pick (n >= 1; the checks are the entry point's)
+int specular_pick_launch(uint32_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, hipStream_t s);
 // rt_path.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
 int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
                          unsigned long long* total, hipStream_t s);

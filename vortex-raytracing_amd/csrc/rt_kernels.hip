@@ -1874,6 +1874,9 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if (r.emissive_mis && (!r.path || r.emissive ||
                          r.emissive_mis->reserved[0] != 0u || r.emissive_mis->reserved[1] != 0u || r.emissive_mis->reserved[2] != 0u ||
                          !(r.emissive_mis->scale >= 0.0f) || !std::isfinite(r.emissive_mis->scale) || !emitters_valid(a))) return -1;
+  // ... whose vertices may be specular (enable = 1; the entry point passes none for enable = 0): a path frame without the filter chain
+  if (r.specular && (!r.path || r.specular->enable != 1u || r.specular->reserved[0] != 0u || r.specular->reserved[1] != 0u || r.specular->reserved[2] != 0u ||
+                     r.denoise || r.aov || r.temporal || r.history || r.motion || r.prev_position || r.variance || r.variance_out)) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
   // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
@@ -2548,7 +2551,8 @@ int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam,
 // from its arguments, built from the fields the caller set.  What the descriptor alone can get wrong is refused here; what an entry
 // point above refuses before render_common (a null part, a camera, the history against the window) is refused here the same way; the
 // rest is check_request's, as for them.
-int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void* stream) {
+// (specular: vxrt_render_path_frame_specular's part beside the descriptor, already checked and with enable = 1, or null)
+static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
   if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
   for (int k = 0; k < 4; ++k) if (f->reserved[k] != 0u) return -1;
   if (!f->path || (f->emissive && f->emissive_mis) || f->motion > 1u) return -1;
@@ -2565,7 +2569,25 @@ int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void
   r.emissive = f->emissive; r.emissive_mis = f->emissive_mis; r.sample_counts = f->counts;
   r.denoise = f->denoise; r.aov = f->aov; r.temporal = f->temporal; r.history = f->history; r.motion = f->motion == 1u; r.prev_position = f->prev_position;
   r.variance = f->variance; r.variance_out = f->variance_out;
+  r.specular = specular;
   return render_common(accel, r);
+}
+int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void* stream) { return render_path_frame(accel, f, nullptr, stream); }
+
+// A path frame whose vertices may be specular (see the header, "Specular vertices"): the descriptor's frame with the specular kernels in
+// its tail.  A null part or enable = 0 is vxrt_render_path_frame; what the part alone can get wrong is refused here, the filter chain
+// beside enable = 1 is check_request's to refuse.
+int vxrt_render_path_frame_specular(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
+  if (!specular) return render_path_frame(accel, f, nullptr, stream);
+  if (specular->enable > 1u || specular->reserved[0] != 0u || specular->reserved[1] != 0u || specular->reserved[2] != 0u) return -1;
+  return render_path_frame(accel, f, specular->enable ? specular : nullptr, stream);
+}
+
+// The lobe pick and the mirror ray alone (see the header, "Specular vertices"): one launch on caller-owned buffers, no host synchronisation
+int vxrt_specular_pick(uint64_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, void* stream) {
+  if (!vertices || !seeds || !rays || !lobe || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  return specular_pick_launch((uint32_t)n, vertices, seeds, rays, lobe, (hipStream_t)stream);
 }
 
 // The weighted emitter ray alone: one launch on caller-owned buffers, no host synchronisation

@@ -89,14 +89,28 @@ __device__ __forceinline__ bool emission(const SceneDev& sc, uint32_t triIdx, fl
 struct PrepEmi { float scale; };
 struct PrepNoEmi {};
 
+// The header's "Specular vertices": a vertex of reflectivity rho is specular iff rho > 0 and rho is finite
+__device__ __forceinline__ bool specular_vertex(float rho) { return rho > 0.0f && isfinite(rho); }
+
+// The lobe pick of that section at a continuing vertex of reflectivity rho, from hash output `seed` (0 becomes 1; one xorshift step):
+// true = mirror.  A vertex that is not specular takes no draw.
+__device__ __forceinline__ bool specular_pick(float rho, uint32_t seed) {
+  if (!specular_vertex(rho)) return false;
+  if (seed == 0u) seed = 1u;
+  const float xi = random_float(seed);
+  return rho >= 1.0f || xi < rho;
+}
+
 // The prepare launch of every path frame; its kernels are below.
 // (MOTION: the frame with motion -- the previous-position guide of the pixel's record, computed where the record is in registers)
-template <bool CAM, bool MOTION, bool EMI>
+// (SPEC: the frame with specular vertices -- alb[t].w = the primary hit's reflectivity, and with spec_cont, i.e. bounces > 0, a specular
+//  primary hit continues: lit[t] is `term` alone, without background * reflectivity)
+template <bool CAM, bool MOTION, bool EMI, bool SPEC = false>
 __device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadeParams& p, uint32_t n, uint32_t W, uint32_t y0,
     const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
     float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
     uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo,
-    std::conditional_t<EMI, PrepEmi, PrepNoEmi> em) {
+    std::conditional_t<EMI, PrepEmi, PrepNoEmi> em, uint32_t spec_cont = 0u) {
   if (ctl_reset && blockIdx.x == 0)
     for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
   bool hit_c[PREP_CHUNKS];
@@ -120,9 +134,11 @@ __device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadePara
       } else {
         float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
         shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-        float thr = 1.0f;
-        thr *= refl;
-        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+        if (!(SPEC && spec_cont && specular_vertex(refl))) {
+          float thr = 1.0f;
+          thr *= refl;
+          r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+        }
         if constexpr (EMI) {
           float e3[3];
           if (emission(sc, h.triIdx, em.scale, e3)) { r = r + e3[0]; g = g + e3[1]; b = b + e3[2]; }
@@ -131,7 +147,7 @@ __device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadePara
         nrm[t] = make_float4(Nx, Ny, Nz, 0.f);
         dir[t] = make_float4(dx, dy, dz, 0.f);
         lit[t] = make_float4(r, g, b, 0.f);
-        alb[t] = make_float4(a3[0], a3[1], a3[2], 0.f);
+        alb[t] = make_float4(a3[0], a3[1], a3[2], SPEC ? refl : 0.f);
         hit = true;
       }
       if constexpr (MOTION) {
@@ -171,6 +187,18 @@ __global__ __launch_bounds__(256) void rt_path_prepare_emissive_motion_kernel(Sc
   path_prepare<true, true, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, mo, PrepEmi{scale});
 }
 
+// (the frame with specular vertices, vxrt_render_path_frame_specular: the pixel's reflectivity goes into alb[t].w; `cont` = bounces > 0)
+template <bool CAM, bool EMI>
+__global__ __launch_bounds__(256) void rt_path_prepare_specular_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, float scale, uint32_t cont) {
+  if constexpr (EMI)
+    path_prepare<CAM, false, true, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepEmi{scale}, cont);
+  else
+    path_prepare<CAM, false, false, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepNoEmi{}, cont);
+}
+
 // start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
 __global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
     const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
@@ -182,6 +210,22 @@ __global__ __launch_bounds__(256) void rt_path_start_kernel(uint32_t cap, uint32
   if (i >= total) return;
   const uint32_t t = list[i / ns];
   pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = alb[t];
+  live[i] = i;
+}
+
+// (the frame with specular vertices: thr = 1 -- it is multiplied when a ray leaves the vertex -- and pA = (Alb, reflectivity) of the
+//  primary vertex, which the specular prepare launch left in alb[t])
+__global__ __launch_bounds__(256) void rt_path_start_specular_kernel(uint32_t cap, uint32_t ns, const uint32_t* __restrict__ list, uint32_t* hdr,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, float4* __restrict__ pA,
+    uint32_t* __restrict__ live) {
+  const uint64_t want = (uint64_t)hdr[0] * ns;
+  const uint32_t total = want < cap ? (uint32_t)want : cap;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i == 0) hdr[1] = total;
+  if (i >= total) return;
+  const uint32_t t = list[i / ns];
+  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = make_float4(1.f, 1.f, 1.f, 0.f); pA[i] = alb[t];
   live[i] = i;
 }
 
@@ -340,6 +384,112 @@ __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_mis_kernel(ui
   path_bounce_emitter_rays<true>(cap, W, y0, SlotUniform{spp, s0, ns, list}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
 }
 
+// The bounce rays of one depth of a frame with specular vertices (the header's "Specular vertices"): per-slot state holds thr BEFORE the
+// last vertex's albedo (pT) and that vertex's Alb and reflectivity (pA), and the ray that leaves is chosen by the lobe pick -- user seed
+// (seed + depth) ^ 0x40000000 in the bounce ray's hash input.  Mirror: mirror_ray about the unturned normal, thr unchanged, the segment
+// marked specular in pD[slot].w.  Diffuse: the ray of rt_path_bounce_rays_kernel, thr = thr * Alb written back, the mark cleared.
+// (EM: 0 no emitter ray -- the plain frame and nee = 0; 1 emitter sampling, 2 its weighted twin: the emitter ray of
+//  path_bounce_emitter_rays for a vertex that picks diffuse, a skipped one -- tmax = -1, G = 0, not counted -- for one that picks mirror.
+//  As there, no thread leaves before the barriers and the emitter rays cost one atomic per workgroup.)
+struct SpecNoEm {};
+struct SpecEm { EmitterTab tab; float scale; float* erays; float* etmax; float4* eG; };
+template <int EM, class SlotSrc>
+__device__ __forceinline__ void path_bounce_specular(uint32_t cap, uint32_t W, uint32_t y0, const SlotSrc& src, uint32_t user_seed,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pT, const float4* __restrict__ pA,
+    float* __restrict__ rays, const std::conditional_t<EM != 0, SpecEm, SpecNoEm>& em, unsigned long long* rays_traced) {
+  __shared__ uint32_t s_real;
+  if constexpr (EM != 0) {
+    if (threadIdx.x == 0) s_real = 0u;
+    __syncthreads();
+  }
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q == 0) {
+    *n_next = 0u;
+    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one bounce ray, mirror or diffuse)
+  }
+  bool real = false;
+  if (q < total) {
+    const uint32_t slot = live[q];
+    uint32_t t, smp, spp;
+    src.get(slot, t, smp, spp);
+    const uint32_t x = t % W, y = y0 + t / W;
+    const float4 I = pI[slot], N = pN[slot], D = pD[slot], A = pA[slot];
+    const bool mirror = specular_vertex(A.w) && specular_pick(A.w, wang_hash((x + y * W) * spp + smp + 1u + (user_seed ^ 0x40000000u) * 0x9E3779B9u));
+    float r6[6];
+    float4 T = pT[slot];
+    if (mirror) {
+      mirror_ray(D.x, D.y, D.z, I.x, I.y, I.z, N.x, N.y, N.z, r6);
+    } else {
+      ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
+      T = make_float4(T.x * A.x, T.y * A.y, T.z * A.z, 0.f);
+      pT[slot] = T;
+    }
+    pD[slot].w = mirror ? 1.0f : 0.0f;
+    float* o = rays + (size_t)q * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = r6[k];
+    if constexpr (EM != 0) {
+      float e6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f}, tm = -1.0f, G[3] = {0.f, 0.f, 0.f};
+      if (!mirror) {
+        float nx = N.x, ny = N.y, nz = N.z;
+        if (nx * D.x + ny * D.y + nz * D.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // (N' as ao_sample_ray turns it)
+        const uint32_t seed = wang_hash((x + y * W) * spp + smp + 1u + (user_seed ^ 0x80000000u) * 0x9E3779B9u);
+        uint32_t e;
+        float wE;
+        real = emitter_sample<EM == 2>(em.tab, em.scale, seed, I.x, I.y, I.z, nx, ny, nz, e6, tm, G, e, &wE);
+      }
+      float* eo = em.erays + (size_t)q * 6;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) eo[k] = e6[k];
+      em.etmax[q] = tm;
+      em.eG[q] = make_float4(G[0], G[1], G[2], real ? 1.0f : 0.0f);
+    }
+  }
+  if constexpr (EM != 0) {
+    const unsigned long long m = __ballot(real);
+    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
+  }
+}
+
+template <int EM>
+__global__ __launch_bounds__(256) void rt_path_bounce_specular_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pT, const float4* __restrict__ pA,
+    float* __restrict__ rays, std::conditional_t<EM != 0, SpecEm, SpecNoEm> em, unsigned long long* rays_traced) {
+  path_bounce_specular<EM>(cap, W, y0, SlotUniform{spp, s0, ns, list}, user_seed, live, n_live, n_next, pI, pN, pD, pT, pA, rays, em, rays_traced);
+}
+
+// (the slot's pixel, sample and the pixel's own sample count, as rt_path_bounce_rays_counts_kernel reads them: the pick's hash input is
+//  (x + y * W) * n_p + s + 1 + u * 0x9E3779B9 too)
+template <int EM>
+__global__ __launch_bounds__(256) void rt_path_bounce_specular_counts_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
+    const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pT, const float4* __restrict__ pA,
+    float* __restrict__ rays, std::conditional_t<EM != 0, SpecEm, SpecNoEm> em, unsigned long long* rays_traced) {
+  path_bounce_specular<EM>(cap, W, y0, SlotCounts{spix, ssmp, cnt}, user_seed, live, n_live, n_next, pI, pN, pD, pT, pA, rays, em, rays_traced);
+}
+
+// vxrt_specular_pick: the pick and the mirror ray of n caller-supplied vertices (I, N, dir, rho) and hash outputs, one per thread; a
+// vertex that picks diffuse gets six zeros
+__global__ __launch_bounds__(256) void rt_specular_pick_kernel(uint32_t n, const float* __restrict__ vertices, const uint32_t* __restrict__ seeds,
+    float* __restrict__ rays, uint32_t* __restrict__ lobe) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const float* v = vertices + (size_t)i * 10;
+  float r6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool mirror = specular_pick(v[9], seeds[i]);
+  if (mirror) mirror_ray(v[6], v[7], v[8], v[0], v[1], v[2], v[3], v[4], v[5], r6);
+  float* o = rays + (size_t)i * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = r6[k];
+  lobe[i] = mirror ? 1u : 0u;
+}
+
 // The emitter index of the header's "Multiple importance sampling": the position of (blas, tri) among the sorted (blasIdx, triIdx, e)
 // -- the smallest position whose key is not below the wanted one, a binary search over [0, n - 1] of at most 17 steps -- and e of that
 // position if its key is equal; 0xFFFFFFFF: the pair is not listed
@@ -464,11 +614,15 @@ __global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams
 struct ScatterEmi { float scale; const HitRec* ehits; const float4* eG; };
 struct ScatterMis { float scale; const HitRec* ehits; const float4* eG; EmitterTab tab; EmitterIdx idx; };
 struct ScatterNoEmi {};
-template <int EMI>
+// (SPEC: the frame of the header's "Specular vertices".  pT is thr as the ray left with it and is not touched here; a hit that goes on
+//  stores its Alb and reflectivity in pA instead, and if it is specular it adds `term` alone.  pD[slot].w marks the segment that arrives:
+//  after a specular one a hit whose material emits adds thr * Emi in full in all three emitter forms, without a lookup.)
+template <int EMI, bool SPEC = false>
 __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadeParams& p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
     const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>>& em) {
+    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>>& em,
+    float4* __restrict__ pA = nullptr) {
   const uint32_t total = min(*n_live, cap);
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   bool go[1] = {false};
@@ -480,6 +634,8 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
     h.blasIdx &= 0x7fffffffu;
     float4 L = pL[slot];
     const float4 T = pT[slot];
+    bool seg = false;   // (the segment that arrives is specular)
+    if constexpr (SPEC) seg = pD[slot].w != 0.f;
     if constexpr (EMI == 2 || EMI == 3) {
       const float4 G = em.eG[q];
       if (G.w != 0.f && em.ehits[q].dist == RT_LARGE_FLOAT) { L.x = L.x + T.x * G.x; L.y = L.y + T.y * G.y; L.z = L.z + T.z * G.z; }
@@ -490,10 +646,16 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
       const bool occ = shits != nullptr && shits[q].dist != RT_LARGE_FLOAT;
       float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
       shade_terms<false>(sc, p, rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
-      float thr = 1.0f;
-      thr *= refl;
-      r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+      if (!(SPEC && next && specular_vertex(refl))) {
+        float thr = 1.0f;
+        thr *= refl;
+        r = r + p.bg[0] * thr; g = g + p.bg[1] * thr; b = b + p.bg[2] * thr;
+      }
       L.x = L.x + T.x * r; L.y = L.y + T.y * g; L.z = L.z + T.z * b;
+      if constexpr (SPEC && EMI == 2) {
+        float e3[3];
+        if (seg && emission(sc, h.triIdx, em.scale, e3)) { L.x = L.x + T.x * e3[0]; L.y = L.y + T.y * e3[1]; L.z = L.z + T.z * e3[2]; }
+      }
       if constexpr (EMI == 1) {
         float e3[3];
         if (emission(sc, h.triIdx, em.scale, e3)) { L.x = L.x + T.x * e3[0]; L.y = L.y + T.y * e3[1]; L.z = L.z + T.z * e3[2]; }
@@ -502,7 +664,7 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
         float e3[3];
         if (emission(sc, h.triIdx, em.scale, e3)) {
           float wB = 1.0f;
-          const uint32_t e = emitter_lookup(em.idx, h.blasIdx, h.triIdx);
+          const uint32_t e = seg ? 0xFFFFFFFFu : emitter_lookup(em.idx, h.blasIdx, h.triIdx);
           if (e < em.tab.n) {
             const float4 N = pN[slot], D = pD[slot];   // (the vertex the ray left: overwritten below)
             float nx = N.x, ny = N.y, nz = N.z;
@@ -513,7 +675,8 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
         }
       }
       if (next) {
-        pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
+        if constexpr (SPEC) pA[slot] = make_float4(a3[0], a3[1], a3[2], refl);
+        else pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
         pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
         pN[slot] = make_float4(Nx, Ny, Nz, 0.f);
         pD[slot] = make_float4(rp[3], rp[4], rp[5], 0.f);
@@ -547,6 +710,15 @@ __global__ __launch_bounds__(256) void rt_path_scatter_mis_kernel(SceneDev sc, S
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
     uint32_t* __restrict__ next, uint32_t* n_next, ScatterMis em) {
   path_scatter<3>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em);
+}
+
+// (the frame with specular vertices: EMI as above, 0 for the plain frame)
+template <int EMI>
+__global__ __launch_bounds__(256) void rt_path_scatter_specular_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, float4* __restrict__ pA,
+    uint32_t* __restrict__ next, uint32_t* n_next, std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>> em) {
+  path_scatter<EMI, true>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em, pA);
 }
 
 // after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
@@ -693,6 +865,31 @@ __global__ __launch_bounds__(256) void rt_path_start_counts_kernel(uint32_t cap,
   live[i] = i;
 }
 
+// (the frame with specular vertices: thr = 1 and pA = (Alb, reflectivity) of the primary vertex, as rt_path_start_specular_kernel)
+__global__ __launch_bounds__(256) void rt_path_start_counts_specular_kernel(uint32_t cap, unsigned long long g0, uint32_t n, const unsigned long long* __restrict__ total,
+    const unsigned long long* __restrict__ off, uint32_t* hdr,
+    const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ dir, const float4* __restrict__ lit, const float4* __restrict__ alb,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, float4* __restrict__ pA, uint32_t* __restrict__ live,
+    uint32_t* __restrict__ spix, uint32_t* __restrict__ ssmp) {
+  const unsigned long long tot = *total;
+  const unsigned long long left = tot > g0 ? tot - g0 : 0ull;
+  const uint32_t n_live = left < (unsigned long long)cap ? (uint32_t)left : cap;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i == 0) hdr[1] = n_live;
+  if (i >= n_live) return;
+  const unsigned long long g = g0 + i;
+  uint32_t lo = 0u, hi = n;   // off[lo] <= g < off[hi] (off[n] = *total)
+  for (int k = 0; k < 32; ++k) {
+    if (hi - lo <= 1u) break;
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= g) lo = mid; else hi = mid;
+  }
+  const uint32_t t = lo;
+  spix[i] = t; ssmp[i] = (uint32_t)(g - off[t]);
+  pI[i] = geo[t]; pN[i] = nrm[t]; pD[i] = dir[t]; pL[i] = lit[t]; pT[i] = make_float4(1.f, 1.f, 1.f, 0.f); pA[i] = alb[t];
+  live[i] = i;
+}
+
 // rt_path_bounce_rays_kernel with the slot's pixel, sample and the pixel's own sample count in place of slot / ns, s0 + slot % ns and spp
 __global__ __launch_bounds__(256) void rt_path_bounce_rays_counts_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
     const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
@@ -817,7 +1014,13 @@ static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderReques
                        c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, flavour);
   };
   const bool emi = r.emissive || r.emissive_mis;
-  if (emi && r.motion) {   // (a camera frame: check_request.  Two flavours: the one launch with an argument more)
+  if (r.specular) {   // (no motion: check_request.  One launch with two arguments more: `scale`, read by the emissive flavour only, and bounces > 0)
+    const auto kernel = r.cams ? (emi ? rt_path_prepare_specular_kernel<true, true> : rt_path_prepare_specular_kernel<true, false>)
+                               : (emi ? rt_path_prepare_specular_kernel<false, true> : rt_path_prepare_specular_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
+                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, emi ? emissive_scale(r) : 0.0f,
+                       r.path->bounces ? 1u : 0u);
+  } else if (emi && r.motion) {   // (a camera frame: check_request.  Two flavours: the one launch with an argument more)
     hipLaunchKernelGGL(rt_path_prepare_emissive_motion_kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
                        c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl,
                        PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position}, emissive_scale(r));
@@ -840,6 +1043,7 @@ static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r,
   if (!grow_device({{(void**)&c->pt_I, 16}, {(void**)&c->pt_N, 16}, {(void**)&c->pt_D, 16}, {(void**)&c->pt_L, 16}, {(void**)&c->pt_T, 16}, {(void**)&c->pt_live[0], 4},
                     {(void**)&c->pt_live[1], 4}, {(void**)&c->pt_rays, 24}, {(void**)&c->pt_hits, sizeof(HitRec)}}, &c->pt_path_cap, path_cap, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_srays, 24}, {(void**)&c->pt_stmax, 4}, {(void**)&c->pt_shits, sizeof(HitRec)}}, &c->pt_shadow_cap, shadow_cap, GrowSync::STREAM, s)) return -1;
+  if (r.specular && !grow_device({{(void**)&c->pt_A, 16}}, &c->pt_spec_cap, path_cap, GrowSync::STREAM, s)) return -1;
   if (r.motion && !grow_device({{(void**)&c->mo_pos, 16}, {(void**)&c->mo_nrm, 16}}, &c->mo_cap, n, GrowSync::STREAM, s)) return -1;
   if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
   path_prepare_launch(a, c, r, p, utab, vtab, (uint32_t)n);
@@ -875,7 +1079,16 @@ static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& 
       if (trace_on_ctx(a, c, c->pt_srays, n_rays, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
     }
     if (emi >= 2 && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-    if (emi == 3)
+    if (r.specular) {   // (the specular instantiations: the same launch, per-slot Alb and reflectivity besides)
+      const auto scatter = [&](auto kernel, auto em) {
+        hipLaunchKernelGGL(kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits,
+                           c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_A, next, n_next, em);
+      };
+      if (emi == 3) scatter(rt_path_scatter_specular_kernel<3>, ScatterMis{r.emissive_mis->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)});
+      else if (emi == 2) scatter(rt_path_scatter_specular_kernel<2>, ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
+      else if (emi == 1) scatter(rt_path_scatter_specular_kernel<1>, ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
+      else scatter(rt_path_scatter_specular_kernel<0>, ScatterNoEmi{});
+    } else if (emi == 3)
       hipLaunchKernelGGL(rt_path_scatter_mis_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
                          (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
                          ScatterMis{r.emissive_mis->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)});
@@ -941,11 +1154,23 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u);
   for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
     const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
-    hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
-                       (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
+    if (r.specular)
+      hipLaunchKernelGGL(rt_path_start_specular_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
+                         (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_A, c->pt_live[0]);
+    else
+      hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
+                         (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
     // slot -> (pixel, sample) through (s0, k); with emitter sampling the kernel that writes the emitter ray of the same vertex as well
     const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
-      if (emi >= 2)
+      if (r.specular) {   // (the pick, then the mirror or the diffuse ray; the emitter ray of a vertex that picks diffuse)
+        const auto launch = [&](auto kernel, auto em) {
+          hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live, n_live, n_next,
+                             (const float4*)c->pt_I, (const float4*)c->pt_N, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, em, r.counters);
+        };
+        if (emi == 3) launch(rt_path_bounce_specular_kernel<2>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
+        else if (emi == 2) launch(rt_path_bounce_specular_kernel<1>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
+        else launch(rt_path_bounce_specular_kernel<0>, SpecNoEm{});
+      } else if (emi >= 2)
         hipLaunchKernelGGL(emi == 3 ? rt_path_bounce_emitter_rays_mis_kernel : rt_path_bounce_emitter_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k,
                            pp.seed + d, (const uint32_t*)c->pt_list, live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
                            c->pt_rays, emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
@@ -996,13 +1221,26 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
   const uint64_t n_batches = pp.bounces ? (all + batch - 1) / batch : 0;
   for (uint64_t b = 0; b < n_batches; ++b) {
     const unsigned long long g0 = b * batch;   // the batch's first path
-    hipLaunchKernelGGL(rt_path_start_counts_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
-                       (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
-                       c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0], c->pt_spix, c->pt_ssmp);
+    if (r.specular)
+      hipLaunchKernelGGL(rt_path_start_counts_specular_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
+                         (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
+                         c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_A, c->pt_live[0], c->pt_spix, c->pt_ssmp);
+    else
+      hipLaunchKernelGGL(rt_path_start_counts_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
+                         (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
+                         c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0], c->pt_spix, c->pt_ssmp);
     // slot -> (pixel, sample) through the slot tables the start kernel filled; the pixel's own count in place of spp
     // (with emitter sampling the kernel that writes the emitter ray of the same vertex as well)
     const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
-      if (emi >= 2)
+      if (r.specular) {   // (as render_path_tail's, from the slot tables)
+        const auto launch = [&](auto kernel, auto em) {
+          hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp, (const uint32_t*)c->pt_cnt,
+                             live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, em, r.counters);
+        };
+        if (emi == 3) launch(rt_path_bounce_specular_counts_kernel<2>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
+        else if (emi == 2) launch(rt_path_bounce_specular_counts_kernel<1>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
+        else launch(rt_path_bounce_specular_counts_kernel<0>, SpecNoEm{});
+      } else if (emi >= 2)
         hipLaunchKernelGGL(emi == 3 ? rt_path_bounce_emitter_rays_counts_mis_kernel : rt_path_bounce_emitter_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0,
                            pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp, (const uint32_t*)c->pt_cnt, live, n_live, n_next,
                            (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, emitter_tab(a), emissive_scale(r),
@@ -1026,6 +1264,12 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
 int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
                          unsigned long long* total, hipStream_t s) {
   hipLaunchKernelGGL(rt_sample_counts_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, variance, prev_counts, prm->gain, prm->min_spp, prm->max_spp, counts, total);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// vxrt_specular_pick behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
+int specular_pick_launch(uint32_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, hipStream_t s) {
+  hipLaunchKernelGGL(rt_specular_pick_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, vertices, seeds, rays, lobe);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

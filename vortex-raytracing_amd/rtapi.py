@@ -723,10 +723,30 @@ class PathFrame(C.Structure):   # vxrt_path_frame_t: what a path frame is made o
         self.variance_out, self.rays_traced = variance_out, rays_traced
 
 
-def render_path_frame(accel, frame, stream=None):
+class SpecularParams(C.Structure):   # vxrt_specular_params_t: rides beside a PathFrame (the header's "Specular vertices")
+    _fields_ = [("enable", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, enable=1):
+        super().__init__()
+        self.enable = int(enable)
+
+
+def render_path_frame(accel, frame, stream=None, specular=None):
     """vxrt_render_path_frame: the path frame `frame` (a PathFrame) describes -- every render_path* call above is the frame with that
-    call's parts, and the parts combine: an emitter form with counts, the filter, a history, motion, variance.  Raises on a refusal."""
-    check(_lib().vxrt_render_path_frame(accel, C.byref(frame) if frame is not None else None, stream), "vxrt_render_path_frame")
+    call's parts, and the parts combine: an emitter form with counts, the filter, a history, motion, variance.  Raises on a refusal.
+    specular (a SpecularParams): vxrt_render_path_frame_specular -- with enable = 1 the path follows reflective instances (a lobe pick
+    per vertex between the mirror ray and the diffuse bounce ray); a frame without the filter chain."""
+    f = C.byref(frame) if frame is not None else None
+    if specular is None:
+        check(_lib().vxrt_render_path_frame(accel, f, stream), "vxrt_render_path_frame")
+    else:
+        check(_lib().vxrt_render_path_frame_specular(accel, f, C.byref(specular), stream), "vxrt_render_path_frame_specular")
+
+
+def specular_pick(n, vertices_ptr, seeds_ptr, rays_ptr, lobe_ptr, stream=None):
+    """vxrt_specular_pick: the lobe pick alone on device buffers -- vertices (n x 10: I, N, dir, reflectivity), seeds (n hash outputs) ->
+    lobe (n: 1 mirror, 0 diffuse), rays (n x 6: the mirror ray of lobe 1, zeros for lobe 0)."""
+    check(_lib().vxrt_specular_pick(int(n), vertices_ptr, seeds_ptr, rays_ptr, lobe_ptr, stream), "vxrt_specular_pick")
 
 
 def _declare_path_family(L):
@@ -768,6 +788,8 @@ def _declare_path_family(L):
         "vxrt_emitter_rays_mis": (i32, [vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
         "vxrt_emitter_hit_weights": (i32, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "vxrt_render_path_frame": (i32, [vp, C.POINTER(PathFrame), vp]),
+        "vxrt_render_path_frame_specular": (i32, [vp, C.POINTER(PathFrame), C.POINTER(SpecularParams), vp]),
+        "vxrt_specular_pick": (i32, [C.c_uint64, vp, vp, vp, vp, vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
