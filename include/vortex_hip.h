@@ -509,6 +509,7 @@ typedef struct vxrt_path_params {
   uint32_t seed;     /* user seed of bounce 0; bounce k takes seed + k */
   uint32_t shadow;   /* 0 / 1: sample the light with an occlusion ray at every vertex */
 } vxrt_path_params_t;
+/* = vxrt_render_path_frame ("Path frames by descriptor" below) with the window, cam, params, path, dst, colors, rays_traced. */
 int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
                      uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                      const vxrt_shade_params_t* params, const vxrt_path_params_t* path,
@@ -568,6 +569,7 @@ typedef struct vxrt_path_aov {
   float* position;  /* 4 / pixel: I, hit flag (1 | 0) */
   float* normal;    /* 4 / pixel: N, 0 */
 } vxrt_path_aov_t;
+/* = vxrt_render_path_frame with vxrt_render_path's fields and denoise = dn (not NULL), aov. */
 int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
                               uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                               const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
@@ -666,8 +668,8 @@ int vxrt_history_read(vxrt_history_t* history, float* out4, void* stream);
 int vxrt_temporal_accumulate(vxrt_history_t* history, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                              const float* signal, const float* position, const float* normal, const vxrt_temporal_params_t* prm,
                              float* out4, void* stream);
-/* The frame.  cam must not be NULL (the fixed camera has no vxrt_camera_t); everything vxrt_render_path_denoised refuses is refused,
- * a non-zero alpha table included. */
+/* The frame = vxrt_render_path_frame with vxrt_render_path_denoised's fields and temporal, history (neither NULL); cam must not be
+ * NULL (the fixed camera has no vxrt_camera_t). */
 int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                               const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
                               const vxrt_temporal_params_t* temporal, vxrt_history_t* history,
@@ -727,6 +729,7 @@ int vxrt_temporal_accumulate_motion(vxrt_history_t* history, const vxrt_camera_t
                                     uint32_t y1, const float* signal, const float* position, const float* normal,
                                     const float* prev_position, const float* prev_normal, const vxrt_temporal_params_t* prm,
                                     float* out4, void* stream);
+/* = vxrt_render_path_frame with vxrt_render_path_temporal's fields and motion = 1, prev_position. */
 int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0,
                                      uint32_t y1, const vxrt_shade_params_t* params, const vxrt_path_params_t* path,
                                      const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, vxrt_history_t* history,
@@ -809,6 +812,8 @@ uint64_t vxrt_denoise_variance_scratch_bytes(uint32_t width, uint32_t rows);
 int vxrt_denoise_variance(uint32_t width, uint32_t rows, const float* signal, const float* variance, const float* position,
                           const float* normal, const vxrt_denoise_params_t* dn, const vxrt_variance_params_t* vp, float* out,
                           float* out_variance /* optional */, void* scratch, uint64_t scratch_bytes, void* stream);
+/* = vxrt_render_path_frame with vxrt_render_path_temporal's fields and variance = vp (not NULL), variance_out = variance, motion
+ * (outside {0, 1}: refused), prev_position. */
 int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                               const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
                               const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp, vxrt_history_t* history,
@@ -860,6 +865,7 @@ typedef struct vxrt_sample_count_params {
   uint32_t max_spp;  /* min_spp .. 4096 */
   uint32_t reserved; /* 0 */
 } vxrt_sample_count_params_t;
+/* = vxrt_render_path_frame with vxrt_render_path's / vxrt_render_path_variance's fields and counts (not NULL). */
 int vxrt_render_path_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
                               uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                               const vxrt_shade_params_t* params, const vxrt_path_params_t* path /* spp: the cap */,
@@ -943,6 +949,7 @@ typedef struct vxrt_emissive_params {
   float scale;           /* multiplies every material's emissive; >= 0 and finite */
   uint32_t reserved[2];  /* 0 */
 } vxrt_emissive_params_t;
+/* = vxrt_render_path_frame with vxrt_render_path's fields and emissive = em (not NULL). */
 int vxrt_render_path_emissive(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
                               uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                               const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_params_t* em,
@@ -1001,6 +1008,7 @@ typedef struct vxrt_emissive_mis_params {
   float scale;           /* multiplies every material's emissive; >= 0 and finite */
   uint32_t reserved[3];  /* 0 */
 } vxrt_emissive_mis_params_t;
+/* = vxrt_render_path_frame with vxrt_render_path's fields and emissive_mis = em (not NULL). */
 int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam /* NULL = fixed camera */,
                                   uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
                                   const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_mis_params_t* em,

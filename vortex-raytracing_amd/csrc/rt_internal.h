@@ -1,6 +1,6 @@
 // Internal to the HIP library (not installed, not part of include/vortex_hip.h): what rt_kernels.hip (traversal, shading, the
 // level-2 entry points), rt_accel.hip (acceleration-layout build, refit), rt_secondary.hip (the tails of mirror-bounce and
-// ambient-occlusion frames, the binning of secondary rays), rt_path.hip (the tail of a path frame) and rt_denoise.hip (the end of a
+// ambient-occlusion frames, the binning of secondary rays), rt_path.hip (the tail of a path frame, its entry points) and rt_denoise.hip (the end of a
 // denoised path frame's tail: a-trous filter, temporal accumulation, variance guidance) share: the types, and the few host functions one
 // unit calls in another.  The constants of the compact layout are in rt_types.h; the device arithmetic of shading, which rt_kernels.hip,
 // rt_secondary.hip and rt_path.hip share, is in rt_shading.h.
@@ -225,7 +225,7 @@ __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {  // c
 }
 
 // ---------------------------------------------------------------------------------------------
-// rt_denoise.hip: what an entry point of rt_kernels.hip checks before a denoised path frame is launched, and the two ends that
+// rt_denoise.hip: what render_path_frame (rt_path.hip) checks before a denoised path frame is launched, and the two ends that
 // render_path_tail (rt_path.hip) hands such a frame to.  The launches behind them, and their order, are that unit's own.
 // ---------------------------------------------------------------------------------------------
 struct RenderRequest;
@@ -319,6 +319,9 @@ constexpr int MODE_ANY_UNORDERED = 0x100;
 // ray buffer -> hit records on frame context c (rt_kernels.hip)
 int trace_on_ctx(vxrt_accel_t* a, FrameCtx* c, const float* rays, uint64_t n, const float* tmax, HitRec* hits, int mode, hipStream_t s,
                  const uint32_t* n_dev = nullptr, unsigned long long* stats_counters = nullptr, const uint32_t* order = nullptr);
+// a request -> its frame (rt_kernels.hip): what every vxrt_render* entry point ends in, those of rt_path.hip too.  -1: refused before
+// anything was launched, or a HIP call failed; 0: rendered, or an empty window
+int render_common(vxrt_accel_t* a, const RenderRequest& r);
 
 // rt_secondary.hip: what replaces the plain shading pass of a frame with reflective instances / an ambient-occlusion frame.
 // utab / vtab: the tables the traversal used (a camera frame's: the head and the tables of its camera block).
@@ -340,17 +343,3 @@ const SecondaryKnobs& secondary_knobs();
 // rt_path.hip: what replaces the plain shading pass of a path frame (denoised or not); as the two tails above
 int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
 extern const uint64_t PATH_BATCH_PATHS;   // paths per batch of a path frame unless VXRT_PATH_BATCH says otherwise
-// rt_path.hip: the launch of vxrt_emitter_rays (n >= 1, a valid table; the checks are the entry point's)
-int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                        uint32_t* emitter, hipStream_t s);
-// rt_path.hip: the launches of vxrt_emitter_rays_mis and vxrt_emitter_hit_weights (n >= 1, a valid table, for the second its index; the
-// checks are the entry points')
-int emitter_rays_mis_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                            uint32_t* emitter, float* mis, hipStream_t s);
-int emitter_hit_weights_launch(const vxrt_accel* a, uint32_t n, const float* rays, const HitRec* hits, const float* normals, uint32_t* emitter, float* mis,
-                               hipStream_t s);
-// rt_path.hip: the launch of vxrt_specular_pick (n >= 1; the checks are the entry point's)
-int specular_pick_launch(uint32_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, hipStream_t s);
-// rt_path.hip: the launch of vxrt_sample_counts (n >= 1; the checks are the entry point's)
-int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
-                         unsigned long long* total, hipStream_t s);

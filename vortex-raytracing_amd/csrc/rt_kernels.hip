@@ -16,7 +16,7 @@
 // per-lane stack whose entries carry m = max(entry distance along the path); DESIGN.md s3 proves
 // this returns the same hit (index included) as the reference's accept-and-re-descend loop.
 // What is not timed lives elsewhere: the acceleration-layout build and the refit in rt_accel.hip; the tails of the frames that trace
-// secondary rays and their kernels in rt_secondary.hip (mirror bounce, ambient occlusion) and rt_path.hip (path frames), the a-trous
+// secondary rays and their kernels in rt_secondary.hip (mirror bounce, ambient occlusion) and rt_path.hip (path frames, with their entry points), the a-trous
 // filter in rt_denoise.hip; the two ray-compaction experiments (VXRT_POOL) in rt_trace_experiments.inc.  The shading arithmetic the frame
 // kernels share with those tails (shade_terms, the camera rays, the sample rays) is in rt_shading.h; SceneDev, HitRec, ShadeParams,
 // FrameCtx, vxrt_accel, RenderRequest and the seam to the other units in rt_internal.h; the constants of the compact layout in
@@ -1862,7 +1862,7 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   // path frames: whole rows of single frames, the timed build only, colours the one optional output besides the ray count
   if (r.path && (r.path->spp == 0 || r.path->spp > 4096 || r.path->bounces > VXRT_PATH_MAX_BOUNCES || r.path->shadow > 1 || stats || r.wave_log || r.ao ||
                  r.hits || r.unoccluded || r.batch != 1 || r.stride != 1)) return -1;
-  // ... with a sample count per pixel: a path frame (a null buffer is the entry point's to refuse: here it means "no counts")
+  // ... with a sample count per pixel: a path frame (a null buffer is vxrt_render_path_adaptive's to refuse: here it means "no counts")
   if (r.sample_counts && !r.path) return -1;
   // ... with emissive geometry: a path frame (with counts, a filter, a history as any other: only vxrt_render_path_frame can ask for
   // them together); the parameters, and for emitter sampling a valid table
@@ -1879,11 +1879,11 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
                      r.denoise || r.aov || r.temporal || r.history || r.motion || r.prev_position || r.variance || r.variance_out)) return -1;
   // ... denoised: the filter's parameters (a path frame honours no alpha table, so neither does this one)
   if ((r.denoise || r.aov) && (!r.path || !dn_params_ok(r.denoise))) return -1;
-  // ... with temporal accumulation: a camera frame with a history (the entry point has checked the history against the window)
+  // ... with temporal accumulation: a camera frame with a history (render_path_frame, rt_path.hip, has checked the history against the window)
   if ((r.temporal || r.history) && (!r.denoise || !r.cams || !r.temporal || !r.history)) return -1;
   // ... through moved instances: the accel holds a motion snapshot
   if ((r.motion || r.prev_position) && (!r.motion || !r.temporal || a->motion_what == 0u)) return -1;
-  // ... with variance guidance: a temporal frame (the entry point has checked that the history holds moments)
+  // ... with variance guidance: a temporal frame (render_path_frame has checked that the history holds moments)
   if ((r.variance || r.variance_out) && (!r.temporal || !vr_params_ok(r.variance))) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
@@ -2183,7 +2183,7 @@ static bool shade_frame(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, cons
   return hipGetLastError() == hipSuccess;
 }
 
-static int render_common(vxrt_accel_t* a, const RenderRequest& r) {
+int render_common(vxrt_accel_t* a, const RenderRequest& r) {
   const int go = check_request(a, r);
   if (go <= 0) return go;
   uint32_t* st = status_word();
@@ -2230,15 +2230,6 @@ bool camera_ok(const vxrt_camera_t* c) {
   const float* f = &c->pos[0];
   for (int i = 0; i < 14; ++i) if (!std::isfinite(f[i])) return false;
   return true;
-}
-
-// What the vxrt_render_path* entry points ask for alike (path is not null: theirs to check, as the camera is); each adds its own fields
-static RenderRequest path_request(const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
-                                  const vxrt_path_params_t* path, uint32_t* dst, float* colors, unsigned long long* rays_traced, void* stream) {
-  RenderRequest r;
-  r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.shadow = path->shadow ? 1 : 0; r.cams = cam; r.path = path;
-  r.dst = dst; r.colors = colors; r.counters = rays_traced; r.stream = stream;
-  return r;
 }
 
 extern "C" {
@@ -2423,198 +2414,6 @@ int vxrt_render_ao_camera(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_
   r.width = width; r.height = height; r.y0 = y0; r.y1 = y1; r.params = params; r.ao = ao; r.cams = cam;
   r.dst = dst; r.colors = colors; r.unoccluded = unoccluded; r.counters = rays_traced; r.stream = stream;
   return render_common(accel, r);
-}
-
-// Path-traced frame (see the header): the plain or shadow frame launch, then render_path_tail
-int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                     const vxrt_shade_params_t* params, const vxrt_path_params_t* path, uint32_t* dst, float* colors,
-                     unsigned long long* rays_traced, void* stream) {
-  if (!path) return -1;
-  if (cam && !camera_ok(cam)) return -1;
-  return render_common(accel, path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream));
-}
-
-// Denoised path frame (see the header): vxrt_render_path whose tail ends in the a-trous filter of rt_denoise.hip
-int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn, uint32_t* dst, float* colors,
-                              const vxrt_path_aov_t* aov, unsigned long long* rays_traced, void* stream) {
-  if (!path || !dn) return -1;
-  if (cam && !camera_ok(cam)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.denoise = dn; r.aov = aov;
-  return render_common(accel, r);
-}
-
-// Denoised path frame with temporal accumulation (see the header): the step of rt_denoise.hip between demodulation and the filter
-int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
-                              const vxrt_temporal_params_t* temporal, vxrt_history_t* history, uint32_t* dst, float* colors,
-                              const vxrt_path_aov_t* aov, unsigned long long* rays_traced, void* stream) {
-  if (!path || !dn || !camera_ok(cam)) return -1;
-  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;   // (a bad window is check_request's to refuse)
-  if (!tp_request_ok(history, temporal, pixels)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history;
-  return render_common(accel, r);
-}
-
-// ... whose step reprojects through the accel's motion snapshot (see the header, "Motion"): the guides ride in the prepare launch
-int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                                     const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
-                                     const vxrt_temporal_params_t* temporal, vxrt_history_t* history, uint32_t* dst, float* colors,
-                                     const vxrt_path_aov_t* aov, float* prev_position, unsigned long long* rays_traced, void* stream) {
-  if (!path || !dn || !camera_ok(cam)) return -1;
-  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
-  if (!tp_request_ok(history, temporal, pixels)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = true; r.prev_position = prev_position;
-  return render_common(accel, r);
-}
-
-// ... on a history with moments, filtered by atrous_v (see the header, "Variance guidance"): T_v in place of T (motion = 0) or T_m (1)
-int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
-                              const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp, vxrt_history_t* history, int motion,
-                              uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, float* prev_position, float* variance,
-                              unsigned long long* rays_traced, void* stream) {
-  if (!path || !dn || !vp || !camera_ok(cam) || motion < 0 || motion > 1) return -1;
-  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
-  if (!tp_request_ok(history, temporal, pixels, true)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
-  r.variance = vp; r.variance_out = variance;
-  return render_common(accel, r);
-}
-
-// Path frame with a sample count per pixel (see the header, "Adaptive sampling"): vxrt_render_path whose tail packs the pixels' samples
-// into batches (render_path_counts_tail in rt_path.hip); path->spp is the cap
-int vxrt_render_path_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const uint32_t* counts, uint32_t* dst, float* colors,
-                              unsigned long long* rays_traced, void* stream) {
-  if (!path || !counts) return -1;
-  if (cam && !camera_ok(cam)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.sample_counts = counts;
-  return render_common(accel, r);
-}
-
-// ... as the path frame of vxrt_render_path_variance
-int vxrt_render_path_variance_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                                       const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const uint32_t* counts,
-                                       const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp,
-                                       vxrt_history_t* history, int motion, uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, float* prev_position,
-                                       float* variance, unsigned long long* rays_traced, void* stream) {
-  if (!path || !counts || !dn || !vp || !camera_ok(cam) || motion < 0 || motion > 1) return -1;
-  const uint64_t pixels = y0 <= y1 ? (uint64_t)width * (y1 - y0) : 0;
-  if (!tp_request_ok(history, temporal, pixels, true)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.sample_counts = counts;
-  r.denoise = dn; r.aov = aov; r.temporal = temporal; r.history = history; r.motion = motion == 1; r.prev_position = prev_position;
-  r.variance = vp; r.variance_out = variance;
-  return render_common(accel, r);
-}
-
-// Path frame with emissive geometry (see the header, "Emissive geometry"): vxrt_render_path whose tail adds emission at bounce hits
-// (nee = 0) or samples the accel's emitter table (nee = 1); the parameters are check_request's to refuse
-int vxrt_render_path_emissive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                              const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_params_t* em, uint32_t* dst, float* colors,
-                              unsigned long long* rays_traced, void* stream) {
-  if (!path || !em) return -1;
-  if (cam && !camera_ok(cam)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.emissive = em;
-  return render_common(accel, r);
-}
-
-// The emitter ray alone (see the header, "Emissive geometry"): one launch on caller-owned buffers, no host synchronisation
-int vxrt_emitter_rays(vxrt_accel_t* a, uint64_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                      uint32_t* emitter, void* stream) {
-  if (!a || !emitters_valid(a) || !points || !seeds || !rays || !tmax || !weight3 || !emitter) return -1;
-  if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
-  if (n == 0) return 0;
-  return emitter_rays_launch(a, (uint32_t)n, points, seeds, scale, rays, tmax, weight3, emitter, (hipStream_t)stream);
-}
-
-// Path frame with emissive geometry whose two estimators are weighted by the balance heuristic (see the header, "Multiple importance
-// sampling"): the frame of nee = 1 with the weighted kernels in its tail; the parameters are check_request's to refuse
-int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
-                                  const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_mis_params_t* em, uint32_t* dst,
-                                  float* colors, unsigned long long* rays_traced, void* stream) {
-  if (!path || !em) return -1;
-  if (cam && !camera_ok(cam)) return -1;
-  RenderRequest r = path_request(cam, width, height, y0, y1, params, path, dst, colors, rays_traced, stream);
-  r.emissive_mis = em;
-  return render_common(accel, r);
-}
-
-// A path frame by descriptor (see the header, "Path frames by descriptor"): the request every vxrt_render_path* entry point above builds
-// from its arguments, built from the fields the caller set.  What the descriptor alone can get wrong is refused here; what an entry
-// point above refuses before render_common (a null part, a camera, the history against the window) is refused here the same way; the
-// rest is check_request's, as for them.
-// (specular: vxrt_render_path_frame_specular's part beside the descriptor, already checked and with enable = 1, or null)
-static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
-  if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
-  for (int k = 0; k < 4; ++k) if (f->reserved[k] != 0u) return -1;
-  if (!f->path || (f->emissive && f->emissive_mis) || f->motion > 1u) return -1;
-  if ((f->prev_position && !f->motion) || (f->variance_out && !f->variance)) return -1;
-  if (f->cam && !camera_ok(f->cam)) return -1;
-  const bool chain = f->aov || f->temporal || f->history || f->motion || f->variance;   // (the rest of the chain needs the filter's parameters)
-  if (chain && !f->denoise) return -1;
-  if (f->temporal || f->history || f->motion || f->variance) {   // (a camera frame with both: the entry points' own order of checks)
-    if (!camera_ok(f->cam)) return -1;
-    const uint64_t pixels = f->y0 <= f->y1 ? (uint64_t)f->width * (f->y1 - f->y0) : 0;   // (a bad window is check_request's to refuse)
-    if (!tp_request_ok(f->history, f->temporal, pixels, f->variance != nullptr)) return -1;
-  }
-  RenderRequest r = path_request(f->cam, f->width, f->height, f->y0, f->y1, f->params, f->path, f->dst, f->colors, f->rays_traced, stream);
-  r.emissive = f->emissive; r.emissive_mis = f->emissive_mis; r.sample_counts = f->counts;
-  r.denoise = f->denoise; r.aov = f->aov; r.temporal = f->temporal; r.history = f->history; r.motion = f->motion == 1u; r.prev_position = f->prev_position;
-  r.variance = f->variance; r.variance_out = f->variance_out;
-  r.specular = specular;
-  return render_common(accel, r);
-}
-int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void* stream) { return render_path_frame(accel, f, nullptr, stream); }
-
-// A path frame whose vertices may be specular (see the header, "Specular vertices"): the descriptor's frame with the specular kernels in
-// its tail.  A null part or enable = 0 is vxrt_render_path_frame; what the part alone can get wrong is refused here, the filter chain
-// beside enable = 1 is check_request's to refuse.
-int vxrt_render_path_frame_specular(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
-  if (!specular) return render_path_frame(accel, f, nullptr, stream);
-  if (specular->enable > 1u || specular->reserved[0] != 0u || specular->reserved[1] != 0u || specular->reserved[2] != 0u) return -1;
-  return render_path_frame(accel, f, specular->enable ? specular : nullptr, stream);
-}
-
-// The lobe pick and the mirror ray alone (see the header, "Specular vertices"): one launch on caller-owned buffers, no host synchronisation
-int vxrt_specular_pick(uint64_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, void* stream) {
-  if (!vertices || !seeds || !rays || !lobe || n >= 0x80000000ull) return -1;
-  if (n == 0) return 0;
-  return specular_pick_launch((uint32_t)n, vertices, seeds, rays, lobe, (hipStream_t)stream);
-}
-
-// The weighted emitter ray alone: one launch on caller-owned buffers, no host synchronisation
-int vxrt_emitter_rays_mis(vxrt_accel_t* a, uint64_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                          uint32_t* emitter, float* mis, void* stream) {
-  if (!a || !emitters_valid(a) || !points || !seeds || !rays || !tmax || !weight3 || !emitter || !mis) return -1;
-  if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
-  if (n == 0) return 0;
-  return emitter_rays_mis_launch(a, (uint32_t)n, points, seeds, scale, rays, tmax, weight3, emitter, mis, (hipStream_t)stream);
-}
-
-// The lookup in the emitter index and the bounce ray's weight alone: one launch on caller-owned buffers; the call that finds no index
-// builds it first (one synchronisation of `stream`, as for a buffer that grows)
-int vxrt_emitter_hit_weights(vxrt_accel_t* a, uint64_t n, const float* rays, const void* hits, const float* normals, uint32_t* emitter, float* mis, void* stream) {
-  if (!a || !emitters_valid(a) || !rays || !hits || !normals || !emitter || !mis || n >= 0x80000000ull) return -1;
-  if (n == 0) return 0;
-  if (emitter_index_ensure(a, (hipStream_t)stream) != 0) return -1;
-  return emitter_hit_weights_launch(a, (uint32_t)n, rays, (const HitRec*)hits, normals, emitter, mis, (hipStream_t)stream);
-}
-
-// Sample counts from a variance buffer (see the header, "Adaptive sampling"): elementwise, one launch, no host synchronisation
-int vxrt_sample_counts(uint64_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
-                       unsigned long long* total, void* stream) {
-  if (!prm || !variance || !counts || n >= 0x80000000ull || prm->reserved != 0u) return -1;
-  if (!(prm->gain > 0.0f) || !std::isfinite(prm->gain) || prm->min_spp == 0u || prm->min_spp > prm->max_spp || prm->max_spp > 4096u) return -1;
-  if (n == 0) return 0;
-  return sample_counts_launch((uint32_t)n, variance, prev_counts, prm, counts, total, (hipStream_t)stream);
 }
 
 // vxrt_trace with the fetch counters compiled in (slower; never the timed path): counters = device u64[8],

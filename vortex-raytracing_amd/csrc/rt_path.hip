@@ -4,7 +4,10 @@
 //   - the prepare launch and its flavours (camera, motion, emissive);
 //   - the kernels of a batch: start, bounce rays (with the emitter ray of emitter sampling), occlusion rays, scatter, accumulate, final;
 //   - the same for a sample count per pixel (counts, scan, start, bounce rays, accumulate, divide), and vxrt_sample_counts;
-//   - host: the prepare launch, the depths of one batch, the end of the frame, the two tails (uniform, per-pixel counts).
+//   - host: the form of the request (path_form), the prepare launch, the depths of one batch, the end of the frame, the two tails
+//     (uniform, per-pixel counts);
+//   - host: the path API -- render_path_frame, the one builder of a path request, the vxrt_render_path* entry points that go through
+//     it, and the single-launch calls (vxrt_specular_pick, vxrt_emitter_rays[_mis], vxrt_emitter_hit_weights, vxrt_sample_counts).
 // A denoised frame ends in rt_denoise.hip.  None of it is timed by bench.py, and none of it can reach the traversal kernel's unit: the
 // seam is in rt_internal.h, as for rt_secondary.hip, which holds the knob reader (secondary_knobs).  Same build flags (-ffp-contract=off).
 #include <hip/hip_runtime.h>
@@ -995,6 +998,7 @@ __global__ __launch_bounds__(256) void rt_sample_counts_kernel(uint32_t n, const
 // host: the tail render_common (rt_kernels.hip) ends a path frame with
 // ---------------------------------------------------------------------------------------------
 #include <algorithm>
+#include <cmath>
 
 // Paths per batch of a path frame (VXRT_PATH_BATCH).  A path costs 136 bytes of frame-context storage -- 80 of state (I, N, dir, Lc, thr:
 // five float4), 24 + 24 of bounce ray and hit record, 2 x 4 of live-list entries -- and 52 more with light sampling (occlusion ray, tmax,
@@ -1002,70 +1006,85 @@ __global__ __launch_bounds__(256) void rt_sample_counts_kernel(uint32_t n, const
 // 4 M rays for a machine that holds 0.4 M lanes of the traversal kernel -- launch ramps and tails stay a small part of each.
 extern const uint64_t PATH_BATCH_PATHS = 4ull << 20;   // (secondary_knobs, rt_secondary.hip, reads it as VXRT_PATH_BATCH's default)
 
-// `scale` of a frame with emissive geometry, whichever of its two entry points asked for it
-static float emissive_scale(const RenderRequest& r) { return r.emissive ? r.emissive->scale : r.emissive_mis->scale; }
-
-// The prepare launch of a path frame over the n pixels of its window: which instantiation the request takes, and what that one takes
-// besides the arguments all of them share
-static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab, uint32_t n) {
-  const dim3 pgrid((n + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS));
-  const auto launch = [&](auto kernel, auto flavour) {
-    hipLaunchKernelGGL(kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
-                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, flavour);
-  };
-  const bool emi = r.emissive || r.emissive_mis;
-  if (r.specular) {   // (no motion: check_request.  One launch with two arguments more: `scale`, read by the emissive flavour only, and bounces > 0)
-    const auto kernel = r.cams ? (emi ? rt_path_prepare_specular_kernel<true, true> : rt_path_prepare_specular_kernel<true, false>)
-                               : (emi ? rt_path_prepare_specular_kernel<false, true> : rt_path_prepare_specular_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
-                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, emi ? emissive_scale(r) : 0.0f,
-                       r.path->bounces ? 1u : 0u);
-  } else if (emi && r.motion) {   // (a camera frame: check_request.  Two flavours: the one launch with an argument more)
-    hipLaunchKernelGGL(rt_path_prepare_emissive_motion_kernel, pgrid, dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab, (const HitRec*)c->hitbuf,
-                       c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl,
-                       PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position}, emissive_scale(r));
-  } else if (emi)
-    launch(r.cams ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, emissive_scale(r));
-  else if (r.motion)   // (a camera frame: check_request)
-    launch(rt_path_prepare_kernel<true, true>, PrepMotion{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position});
-  else
-    launch(r.cams ? rt_path_prepare_kernel<true> : rt_path_prepare_kernel<false>, PrepNoMotion{});
+// What picks the kernels of a path frame, resolved from the request once (render_path_tail) and read by every launch site below.
+// emi, the emitter form (the header's "Emissive geometry"): 0 none, 1 emission at bounce hits, 2 emitter sampling -- one emitter ray per
+// live path and depth, generated with the bounce ray and traced by a second any-hit launch -- 3, the header's "Multiple importance
+// sampling": the launches of 2 with the weighted kernels, whose scatter looks emissive hits up in the emitter index.  scale: that
+// form's, 0 without one.  spec: specular vertices; counts: a sample count per pixel; shadow: light sampling; cam: a camera frame.
+struct PathForm { int emi; float scale; bool spec, counts, shadow, motion, cam; };
+static PathForm path_form(const RenderRequest& r) {
+  PathForm f;
+  f.emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
+  f.scale = r.emissive_mis ? r.emissive_mis->scale : r.emissive ? r.emissive->scale : 0.0f;
+  f.spec = r.specular != nullptr; f.counts = r.sample_counts != nullptr; f.shadow = r.path->shadow != 0; f.motion = r.motion; f.cam = r.cams != nullptr;
+  return f;
 }
 
-// What both tails of a path frame begin with: the context's buffers for n pixels and batches of path_cap paths (per pixel; per path --
-// none without bounces; per occlusion ray -- none without light sampling; grown behind the stream), the zeroed header, and the prepare launch
-static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab, uint64_t n, uint64_t path_cap) {
+// What the kernels of an emitter form take besides, built once per frame behind path_tail_begin (which grows the buffers named here and
+// has the index built): rays for the bounce-ray kernels of emi >= 2, hits / weighted for the scatter kernels of emi 1, 2 / 3
+struct PathEmitters { SpecEm rays; ScatterEmi hits; ScatterMis weighted; };
+static PathEmitters path_emitters(const vxrt_accel* a, const FrameCtx* c, const PathForm& f) {
+  return PathEmitters{SpecEm{emitter_tab(a), f.scale, c->pt_erays, c->pt_etmax, c->pt_eG},
+                      ScatterEmi{f.scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG},
+                      ScatterMis{f.scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)}};
+}
+
+// The prepare launch of a path frame over the n pixels of its window: which instantiation the form takes, and what that one takes
+// besides the arguments all of them share
+static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const PathForm& f, const ShadeParams& p, const float* utab, const float* vtab, uint32_t n) {
+  const auto launch = [&](auto kernel, auto... flavour) {
+    hipLaunchKernelGGL(kernel, dim3((n + 256u * PREP_CHUNKS - 1u) / (256u * PREP_CHUNKS)), dim3(256), 0, (hipStream_t)r.stream, a->dev, p, n, r.width, r.y0, utab, vtab,
+                       (const HitRec*)c->hitbuf, c->pt_geo, c->pt_nrm, c->pt_dir, c->pt_lit, c->pt_alb, c->pt_list, c->pt_hdr, c->ctl, flavour...);
+  };
+  const PrepMotion mo{motion_src(a), c->mo_pos, c->mo_nrm, r.prev_position};   // (read by the flavours with motion: camera frames, check_request)
+  const bool emi = f.emi != 0;
+  if (f.spec)   // (no motion: check_request.  `scale` is read by the emissive flavour only; the last argument is bounces > 0)
+    launch(f.cam ? (emi ? rt_path_prepare_specular_kernel<true, true> : rt_path_prepare_specular_kernel<true, false>)
+                 : (emi ? rt_path_prepare_specular_kernel<false, true> : rt_path_prepare_specular_kernel<false, false>), f.scale, r.path->bounces ? 1u : 0u);
+  else if (emi && f.motion) launch(rt_path_prepare_emissive_motion_kernel, mo, f.scale);
+  else if (emi) launch(f.cam ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, f.scale);
+  else if (f.motion) launch(rt_path_prepare_kernel<true, true>, mo);
+  else launch(f.cam ? rt_path_prepare_kernel<true> : rt_path_prepare_kernel<false>, PrepNoMotion{});
+}
+
+// What both tails of a path frame begin with: the emitter index of emi = 3, built if the accel holds none (a buffer that grows, with the
+// one synchronisation that takes); the context's buffers for n pixels and batches of path_cap paths (per emitter ray -- emi >= 2; per
+// pixel; per path -- none without bounces; per occlusion ray -- none without light sampling; grown behind the stream); the zeroed header,
+// and the prepare launch
+static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const PathForm& f, const ShadeParams& p, const float* utab, const float* vtab, uint64_t n,
+                           uint64_t path_cap) {
   hipStream_t s = (hipStream_t)r.stream;
-  const uint64_t shadow_cap = r.path->shadow ? path_cap : 0;
+  const uint64_t shadow_cap = f.shadow ? path_cap : 0;
+  if (f.emi == 3 && emitter_index_ensure(a, s) != 0) return -1;
+  if (f.emi >= 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
+                                 path_cap, GrowSync::STREAM, s)) return -1;
   if (!c->pt_hdr && hipMalloc((void**)&c->pt_hdr, 16) != hipSuccess) return -1;
   if (!grow_device({{(void**)&c->pt_geo, 16}, {(void**)&c->pt_nrm, 16}, {(void**)&c->pt_dir, 16}, {(void**)&c->pt_lit, 16}, {(void**)&c->pt_alb, 16},
                     {(void**)&c->pt_acc, 16}, {(void**)&c->pt_list, 4}}, &c->pt_cap, n, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_I, 16}, {(void**)&c->pt_N, 16}, {(void**)&c->pt_D, 16}, {(void**)&c->pt_L, 16}, {(void**)&c->pt_T, 16}, {(void**)&c->pt_live[0], 4},
                     {(void**)&c->pt_live[1], 4}, {(void**)&c->pt_rays, 24}, {(void**)&c->pt_hits, sizeof(HitRec)}}, &c->pt_path_cap, path_cap, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_srays, 24}, {(void**)&c->pt_stmax, 4}, {(void**)&c->pt_shits, sizeof(HitRec)}}, &c->pt_shadow_cap, shadow_cap, GrowSync::STREAM, s)) return -1;
-  if (r.specular && !grow_device({{(void**)&c->pt_A, 16}}, &c->pt_spec_cap, path_cap, GrowSync::STREAM, s)) return -1;
-  if (r.motion && !grow_device({{(void**)&c->mo_pos, 16}, {(void**)&c->mo_nrm, 16}}, &c->mo_cap, n, GrowSync::STREAM, s)) return -1;
+  if (f.spec && !grow_device({{(void**)&c->pt_A, 16}}, &c->pt_spec_cap, path_cap, GrowSync::STREAM, s)) return -1;
+  if (f.motion && !grow_device({{(void**)&c->mo_pos, 16}, {(void**)&c->mo_nrm, 16}}, &c->mo_cap, n, GrowSync::STREAM, s)) return -1;
   if (hipMemsetAsync(c->pt_hdr, 0, 16, s) != hipSuccess) return -1;
-  path_prepare_launch(a, c, r, p, utab, vtab, (uint32_t)n);
+  path_prepare_launch(a, c, r, f, p, utab, vtab, (uint32_t)n);
   if (hipGetLastError() != hipSuccess) return -1;
   c->ctl_dirty = false;
   return 0;
 }
 
 // The depths of one batch of at most cap paths, started in c->pt_live[0] with their number in c->pt_hdr[1].  Per depth: bounce rays of
-// the live paths -> closest-hit launch -> (shadow, light sampling: occlusion rays -> any-hit launch) -> (emi = 2, emitter sampling: the
-// any-hit launch of the emitter rays the bounce-ray kernel wrote) -> scatter, which compacts the paths that go on into the next depth's
-// list.  bounce_rays(d, live, n_live, n_next) launches the tail's bounce-ray kernel for depth d; n_rays is the batch's ray count as
-// trace_on_ctx sizes its launch (the live count is read on the device).  emi: 0 none, 1 emission at bounce hits, 2 emitter sampling,
-// 3 both, weighted (the launches of 2; the scatter kernel looks emissive hits up in the emitter index).
+// the live paths -> closest-hit launch -> (light sampling: occlusion rays -> any-hit launch) -> (emi >= 2: the any-hit launch of the
+// emitter rays the bounce-ray kernel wrote) -> scatter, which compacts the paths that go on into the next depth's list.
+// bounce_rays(d, live, n_live, n_next) launches the tail's bounce-ray kernel for depth d; n_rays is the batch's ray count as
+// trace_on_ctx sizes its launch (the live count is read on the device).
 template <class BounceRays>
-static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, uint32_t cap, uint64_t n_rays, int emi, bool shadow,
-                             const BounceRays& bounce_rays) {
-  const SceneDev& sc = a->dev;
+static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const PathForm& f, const PathEmitters& E, const ShadeParams& p, uint32_t cap,
+                             uint64_t n_rays, const BounceRays& bounce_rays) {
   hipStream_t s = (hipStream_t)r.stream;
   const dim3 block(256), rgrid((cap + 255u) / 256u);
   const uint32_t bounces = r.path->bounces;
-  const HitRec* shits = shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr;
+  const HitRec* shits = f.shadow ? (const HitRec*)c->pt_shits : (const HitRec*)nullptr;
   for (uint32_t d = 0; d < bounces; ++d) {
     uint32_t* n_live = c->pt_hdr + 1 + (d & 1u);
     uint32_t* n_next = c->pt_hdr + 1 + ((d + 1u) & 1u);
@@ -1073,32 +1092,24 @@ static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& 
     uint32_t* next = d + 1u < bounces ? c->pt_live[(d + 1u) & 1u] : (uint32_t*)nullptr;
     bounce_rays(d, live, (const uint32_t*)n_live, n_next);
     if (trace_on_ctx(a, c, c->pt_rays, n_rays, nullptr, c->pt_hits, VXRT_MODE_CLOSEST, s, n_live) != 0) return -1;
-    if (shadow) {
+    if (f.shadow) {
       hipLaunchKernelGGL(rt_path_occlusion_rays_kernel, rgrid, block, 0, s, p, cap, (const uint32_t*)n_live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
                          c->pt_srays, c->pt_stmax, r.counters);
       if (trace_on_ctx(a, c, c->pt_srays, n_rays, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
     }
-    if (emi >= 2 && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
-    if (r.specular) {   // (the specular instantiations: the same launch, per-slot Alb and reflectivity besides)
-      const auto scatter = [&](auto kernel, auto em) {
-        hipLaunchKernelGGL(kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits,
-                           c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_A, next, n_next, em);
-      };
-      if (emi == 3) scatter(rt_path_scatter_specular_kernel<3>, ScatterMis{r.emissive_mis->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)});
-      else if (emi == 2) scatter(rt_path_scatter_specular_kernel<2>, ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
-      else if (emi == 1) scatter(rt_path_scatter_specular_kernel<1>, ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
-      else scatter(rt_path_scatter_specular_kernel<0>, ScatterNoEmi{});
-    } else if (emi == 3)
-      hipLaunchKernelGGL(rt_path_scatter_mis_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
-                         (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
-                         ScatterMis{r.emissive_mis->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)});
-    else if (emi)
-      hipLaunchKernelGGL(emi == 2 ? rt_path_scatter_emissive_kernel<2> : rt_path_scatter_emissive_kernel<1>, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live,
-                         (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next,
-                         ScatterEmi{r.emissive->scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG});
-    else
-      hipLaunchKernelGGL(rt_path_scatter_kernel, rgrid, block, 0, s, sc, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits,
-                         shits, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, next, n_next);
+    if (f.emi >= 2 && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+    // (the specular instantiations: the same launch, per-slot Alb and reflectivity besides)
+    const auto scatter = [&](auto kernel, auto... rest) {
+      hipLaunchKernelGGL(kernel, rgrid, block, 0, s, a->dev, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits,
+                         c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, rest...);
+    };
+    if (f.spec && f.emi == 3) scatter(rt_path_scatter_specular_kernel<3>, c->pt_A, next, n_next, E.weighted);
+    else if (f.spec && f.emi == 2) scatter(rt_path_scatter_specular_kernel<2>, c->pt_A, next, n_next, E.hits);
+    else if (f.spec && f.emi == 1) scatter(rt_path_scatter_specular_kernel<1>, c->pt_A, next, n_next, E.hits);
+    else if (f.spec) scatter(rt_path_scatter_specular_kernel<0>, c->pt_A, next, n_next, ScatterNoEmi{});
+    else if (f.emi == 3) scatter(rt_path_scatter_mis_kernel, next, n_next, E.weighted);
+    else if (f.emi) scatter(f.emi == 2 ? rt_path_scatter_emissive_kernel<2> : rt_path_scatter_emissive_kernel<1>, next, n_next, E.hits);
+    else scatter(rt_path_scatter_kernel, next, n_next);
   }
   return 0;
 }
@@ -1114,31 +1125,13 @@ static int path_frame_end(FrameCtx* c, const RenderRequest& r, uint32_t n, uint3
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab);
-
-// The emitter form of a path frame, which both tails derive alike (the header's "Emissive geometry"): emi = 0 none, 1 emission at bounce
-// hits, 2 emitter sampling -- one emitter ray per live path and depth, generated with the bounce ray and traced by a second any-hit
-// launch -- 3, the header's "Multiple importance sampling": the launches of 2 with the weighted kernels; its emitter index is built here
-// if the accel holds none (a buffer that grows, with the one synchronisation that takes).  For 2 and 3 the context's emitter-ray buffers
-// are grown to batches of path_cap paths.
-static int path_emitter_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, uint64_t path_cap, int& emi) {
-  hipStream_t s = (hipStream_t)r.stream;
-  emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
-  if (emi == 3 && emitter_index_ensure(a, s) != 0) return -1;
-  if (emi >= 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
-                               path_cap, GrowSync::STREAM, s)) return -1;
-  return 0;
-}
-
-// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
-// occlusion bit).  Prepare the per-pixel state and the list of hit pixels; then, in batches of whole samples (clamp(VXRT_PATH_BATCH /
-// pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths -> closest-hit launch -> (light sampling:
-// occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next depth's list; after the last depth the
-// batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack, write.  Every count stays on the
-// device (the launches are sized for the batch's capacity and read the live count): no host synchronisation unless a buffer grows.
-// The depths are path_batch_depths, the end is path_frame_end.
-int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
-  if (r.sample_counts) return render_path_counts_tail(a, c, r, p, utab, vtab);   // (a count per pixel: the tail below this one)
+// Tail of a path frame with one sample count for the window.  Prepare the per-pixel state and the list of hit pixels; then, in batches
+// of whole samples (clamp(VXRT_PATH_BATCH / pixels of the window, 1, spp) samples each), per depth: bounce rays of the live paths ->
+// closest-hit launch -> (light sampling: occlusion rays -> any-hit launch) -> scatter, which compacts the paths that go on into the next
+// depth's list; after the last depth the batch's Lc go into the pixels' accumulators in ascending sample order; at the end divide, pack,
+// write.  Every count stays on the device (the launches are sized for the batch's capacity and read the live count): no host
+// synchronisation unless a buffer grows.  The depths are path_batch_depths, the end is path_frame_end.
+static int render_path_uniform_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const PathForm& f, const ShadeParams& p, const float* utab, const float* vtab) {
   const vxrt_path_params_t& pp = *r.path;
   const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
   hipStream_t s = (hipStream_t)r.stream;
@@ -1147,38 +1140,34 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
   const uint32_t ns = (uint32_t)std::min<uint64_t>(pp.spp, std::max<uint64_t>(1, secondary_knobs().path_batch / n));   // samples per batch
   const uint64_t path_cap = pp.bounces ? n * ns : 0;
   if (path_cap > 0x7fffffffull) return -1;
-  int emi;
-  if (path_emitter_begin(a, c, r, path_cap, emi) != 0) return -1;
-  if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
+  if (path_tail_begin(a, c, r, f, p, utab, vtab, n, path_cap) != 0) return -1;
+  const PathEmitters E = path_emitters(a, c, f);
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
   const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u);
   for (uint32_t s0 = 0; pp.bounces && s0 < pp.spp; s0 += ns) {
     const uint32_t k = std::min(ns, pp.spp - s0);   // samples of this batch
-    if (r.specular)
-      hipLaunchKernelGGL(rt_path_start_specular_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
-                         (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_A, c->pt_live[0]);
-    else
-      hipLaunchKernelGGL(rt_path_start_kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
-                         (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0]);
-    // slot -> (pixel, sample) through (s0, k); with emitter sampling the kernel that writes the emitter ray of the same vertex as well
-    const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
-      if (r.specular) {   // (the pick, then the mirror or the diffuse ray; the emitter ray of a vertex that picks diffuse)
-        const auto launch = [&](auto kernel, auto em) {
-          hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live, n_live, n_next,
-                             (const float4*)c->pt_I, (const float4*)c->pt_N, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, em, r.counters);
-        };
-        if (emi == 3) launch(rt_path_bounce_specular_kernel<2>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
-        else if (emi == 2) launch(rt_path_bounce_specular_kernel<1>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
-        else launch(rt_path_bounce_specular_kernel<0>, SpecNoEm{});
-      } else if (emi >= 2)
-        hipLaunchKernelGGL(emi == 3 ? rt_path_bounce_emitter_rays_mis_kernel : rt_path_bounce_emitter_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k,
-                           pp.seed + d, (const uint32_t*)c->pt_list, live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
-                           c->pt_rays, emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
-      else
-        hipLaunchKernelGGL(rt_path_bounce_rays_kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live,
-                           n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, r.counters);
+    const auto start = [&](auto kernel, auto... rest) {
+      hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, k, (const uint32_t*)c->pt_list, c->pt_hdr, (const float4*)c->pt_geo, (const float4*)c->pt_nrm,
+                         (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb, c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, rest...);
     };
-    if (path_batch_depths(a, c, r, p, cap, (uint64_t)n * k, emi, pp.shadow != 0, bounce_rays) != 0) return -1;
+    if (f.spec) start(rt_path_start_specular_kernel, c->pt_A, c->pt_live[0]);
+    else start(rt_path_start_kernel, c->pt_live[0]);
+    // slot -> (pixel, sample) through (s0, k).  Specular: the pick, then the mirror or the diffuse ray, and the emitter ray of a vertex
+    // that picks diffuse; emi >= 2: the kernel that writes the emitter ray of the same vertex as well
+    const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
+      const auto launch = [&](auto kernel, auto... rest) {
+        hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, width, y0, pp.spp, s0, k, pp.seed + d, (const uint32_t*)c->pt_list, live, n_live, n_next,
+                           (const float4*)c->pt_I, (const float4*)c->pt_N, rest..., r.counters);
+      };
+      const SpecEm& e = E.rays;
+      if (f.spec && f.emi == 3) launch(rt_path_bounce_specular_kernel<2>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, e);
+      else if (f.spec && f.emi == 2) launch(rt_path_bounce_specular_kernel<1>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, e);
+      else if (f.spec) launch(rt_path_bounce_specular_kernel<0>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, SpecNoEm{});
+      else if (f.emi >= 2) launch(f.emi == 3 ? rt_path_bounce_emitter_rays_mis_kernel : rt_path_bounce_emitter_rays_kernel, (const float4*)c->pt_D, c->pt_rays,
+                                  e.tab, e.scale, e.erays, e.etmax, e.eG);
+      else launch(rt_path_bounce_rays_kernel, (const float4*)c->pt_D, c->pt_rays);
+    };
+    if (path_batch_depths(a, c, r, f, E, p, cap, (uint64_t)n * k, bounce_rays) != 0) return -1;
     hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
                        (const float4*)c->pt_L, c->pt_acc);
   }
@@ -1187,14 +1176,12 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
 
 // Tail of a path frame with a sample count per pixel (r.sample_counts; path->spp is the cap).  The prepare launch of every path frame;
 // then the clamped counts and their scan in window order (three launches: block sums, one workgroup over the block sums, per-pixel
-// offsets); then batches of cap = clamp(VXRT_PATH_BATCH, 1, pixels * spp) consecutive paths, each the depths of render_path_tail
-// (path_batch_depths) with the two kernels that read a slot's pixel and sample from the slot; after the last batch the accumulators are divided by their
+// offsets); then batches of cap = clamp(VXRT_PATH_BATCH, 1, pixels * spp) consecutive paths, each the depths of the tail above
+// (path_batch_depths) with the kernels that read a slot's pixel and sample from the slot; after the last batch the accumulators are divided by their
 // pixel's count and the frame ends as every path frame, with spp = 1.  The number of paths stays on the device, so the host issues
 // ceil(pixels * spp / cap) batches whatever the counts: a batch past the end starts with zero live paths and its launches fall through.
-// Storage per path is bounded by cap.  No host synchronisation unless a buffer grows.
-// With an emitter form (vxrt_render_path_frame; the header's "Path frames by descriptor") emi is derived as in render_path_tail, the
-// emitter-ray buffers are grown to cap as well, and the bounce-ray kernel is the one that also writes the emitter ray of the slot's vertex.
-static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+// Storage per path is bounded by cap, the emitter rays of a batch with it.  No host synchronisation unless a buffer grows.
+static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const PathForm& f, const ShadeParams& p, const float* utab, const float* vtab) {
   const vxrt_path_params_t& pp = *r.path;
   const uint32_t width = r.width, y0 = r.y0, y1 = r.y1;
   hipStream_t s = (hipStream_t)r.stream;
@@ -1209,9 +1196,8 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
   if (!grow_device({{(void**)&c->pt_cnt, 4}, {(void**)&c->pt_off, 8}}, &c->pt_cnt_cap, n, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_bsum, 4}, {(void**)&c->pt_boff, 8}}, &c->pt_blk_cap, n_blocks, GrowSync::STREAM, s)) return -1;
   if (!grow_device({{(void**)&c->pt_spix, 4}, {(void**)&c->pt_ssmp, 4}}, &c->pt_slot_cap, path_cap, GrowSync::STREAM, s)) return -1;
-  int emi;   // (as render_path_tail: the emitter rays of a batch are bounded by its capacity)
-  if (path_emitter_begin(a, c, r, path_cap, emi) != 0) return -1;
-  if (path_tail_begin(a, c, r, p, utab, vtab, n, path_cap) != 0) return -1;
+  if (path_tail_begin(a, c, r, f, p, utab, vtab, n, path_cap) != 0) return -1;
+  const PathEmitters E = path_emitters(a, c, f);
   const uint32_t n32 = (uint32_t)n, cap = (uint32_t)path_cap;
   const dim3 block(256), grid((n32 + 255u) / 256u), rgrid((cap + 255u) / 256u), sgrid((uint32_t)n_blocks);
   hipLaunchKernelGGL(rt_path_counts_kernel, sgrid, block, 0, s, n32, width, y0, pp.spp, (const float4*)c->pt_geo, r.sample_counts, c->pt_cnt, c->pt_bsum);
@@ -1221,36 +1207,29 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
   const uint64_t n_batches = pp.bounces ? (all + batch - 1) / batch : 0;
   for (uint64_t b = 0; b < n_batches; ++b) {
     const unsigned long long g0 = b * batch;   // the batch's first path
-    if (r.specular)
-      hipLaunchKernelGGL(rt_path_start_counts_specular_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
+    const auto start = [&](auto kernel, auto... rest) {
+      hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
                          (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
-                         c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_A, c->pt_live[0], c->pt_spix, c->pt_ssmp);
-    else
-      hipLaunchKernelGGL(rt_path_start_counts_kernel, rgrid, block, 0, s, cap, g0, n32, (const unsigned long long*)c->pt_ctot, (const unsigned long long*)c->pt_off, c->pt_hdr,
-                         (const float4*)c->pt_geo, (const float4*)c->pt_nrm, (const float4*)c->pt_dir, (const float4*)c->pt_lit, (const float4*)c->pt_alb,
-                         c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, c->pt_live[0], c->pt_spix, c->pt_ssmp);
-    // slot -> (pixel, sample) through the slot tables the start kernel filled; the pixel's own count in place of spp
-    // (with emitter sampling the kernel that writes the emitter ray of the same vertex as well)
-    const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
-      if (r.specular) {   // (as render_path_tail's, from the slot tables)
-        const auto launch = [&](auto kernel, auto em) {
-          hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp, (const uint32_t*)c->pt_cnt,
-                             live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, em, r.counters);
-        };
-        if (emi == 3) launch(rt_path_bounce_specular_counts_kernel<2>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
-        else if (emi == 2) launch(rt_path_bounce_specular_counts_kernel<1>, SpecEm{emitter_tab(a), emissive_scale(r), c->pt_erays, c->pt_etmax, c->pt_eG});
-        else launch(rt_path_bounce_specular_counts_kernel<0>, SpecNoEm{});
-      } else if (emi >= 2)
-        hipLaunchKernelGGL(emi == 3 ? rt_path_bounce_emitter_rays_counts_mis_kernel : rt_path_bounce_emitter_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0,
-                           pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp, (const uint32_t*)c->pt_cnt, live, n_live, n_next,
-                           (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D, c->pt_rays, emitter_tab(a), emissive_scale(r),
-                           c->pt_erays, c->pt_etmax, c->pt_eG, r.counters);
-      else
-        hipLaunchKernelGGL(rt_path_bounce_rays_counts_kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp,
-                           (const uint32_t*)c->pt_cnt, live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, (const float4*)c->pt_D,
-                           c->pt_rays, r.counters);
+                         c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, rest..., c->pt_live[0], c->pt_spix, c->pt_ssmp);
     };
-    if (path_batch_depths(a, c, r, p, cap, cap, emi, pp.shadow != 0, bounce_rays) != 0) return -1;
+    if (f.spec) start(rt_path_start_counts_specular_kernel, c->pt_A);
+    else start(rt_path_start_counts_kernel);
+    // slot -> (pixel, sample) through the slot tables the start kernel filled; the pixel's own count in place of spp.  The kernels are
+    // the twins of the tail above, form for form
+    const auto bounce_rays = [&](uint32_t d, const uint32_t* live, const uint32_t* n_live, uint32_t* n_next) {
+      const auto launch = [&](auto kernel, auto... rest) {
+        hipLaunchKernelGGL(kernel, rgrid, block, 0, s, cap, width, y0, pp.seed + d, (const uint32_t*)c->pt_spix, (const uint32_t*)c->pt_ssmp, (const uint32_t*)c->pt_cnt,
+                           live, n_live, n_next, (const float4*)c->pt_I, (const float4*)c->pt_N, rest..., r.counters);
+      };
+      const SpecEm& e = E.rays;
+      if (f.spec && f.emi == 3) launch(rt_path_bounce_specular_counts_kernel<2>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, e);
+      else if (f.spec && f.emi == 2) launch(rt_path_bounce_specular_counts_kernel<1>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, e);
+      else if (f.spec) launch(rt_path_bounce_specular_counts_kernel<0>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, SpecNoEm{});
+      else if (f.emi >= 2) launch(f.emi == 3 ? rt_path_bounce_emitter_rays_counts_mis_kernel : rt_path_bounce_emitter_rays_counts_kernel, (const float4*)c->pt_D, c->pt_rays,
+                                  e.tab, e.scale, e.erays, e.etmax, e.eG);
+      else launch(rt_path_bounce_rays_counts_kernel, (const float4*)c->pt_D, c->pt_rays);
+    };
+    if (path_batch_depths(a, c, r, f, E, p, cap, cap, bounce_rays) != 0) return -1;
     hipLaunchKernelGGL(rt_path_accumulate_counts_kernel, grid, block, 0, s, n32, cap, g0, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_off,
                        (const float4*)c->pt_L, c->pt_acc);
   }
@@ -1260,41 +1239,206 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
   return path_frame_end(c, r, n32, 1u, 0u);
 }
 
-// vxrt_sample_counts behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
-int sample_counts_launch(uint32_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
-                         unsigned long long* total, hipStream_t s) {
-  hipLaunchKernelGGL(rt_sample_counts_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, variance, prev_counts, prm->gain, prm->min_spp, prm->max_spp, counts, total);
+// Tail of a path frame (replaces the plain shading pass; the primary pass was the plain or shadow frame launch, whose records carry the
+// occlusion bit): the request's form, resolved here once, and the tail of its slot source
+int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const ShadeParams& p, const float* utab, const float* vtab) {
+  const PathForm f = path_form(r);
+  return f.counts ? render_path_counts_tail(a, c, r, f, p, utab, vtab) : render_path_uniform_tail(a, c, r, f, p, utab, vtab);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host: the path API (include/vortex_hip.h).  One door builds a path request, render_path_frame; every vxrt_render_path* entry point
+// checks that the parts its name promises are there, names them in a descriptor and goes through that door
+// ---------------------------------------------------------------------------------------------
+
+// A path frame by descriptor (see the header, "Path frames by descriptor"): the one place that turns arguments into a path request.
+// What a descriptor can get wrong before a request exists is refused here -- a null part is "absent", so a part that an entry point
+// promises is that entry point's to check; the rest is check_request's (rt_kernels.hip), whose empty window comes before its path tests.
+// (specular: vxrt_render_path_frame_specular's part beside the descriptor, already checked and with enable = 1, or null)
+static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
+  if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
+  for (int k = 0; k < 4; ++k) if (f->reserved[k] != 0u) return -1;
+  if (!f->path || (f->emissive && f->emissive_mis) || f->motion > 1u) return -1;
+  if (f->cam && !camera_ok(f->cam)) return -1;
+  const bool chain = f->aov || f->temporal || f->history || f->motion || f->variance;   // (the rest of the chain needs the filter's parameters)
+  if (chain && !f->denoise) return -1;
+  if (f->temporal || f->history || f->motion || f->variance) {   // (a camera frame with a history of its kind that holds the window)
+    if (!camera_ok(f->cam)) return -1;
+    const uint64_t pixels = f->y0 <= f->y1 ? (uint64_t)f->width * (f->y1 - f->y0) : 0;   // (a bad window is check_request's to refuse)
+    if (!tp_request_ok(f->history, f->temporal, pixels, f->variance != nullptr)) return -1;
+  }
+  RenderRequest req;
+  req.width = f->width; req.height = f->height; req.y0 = f->y0; req.y1 = f->y1; req.params = f->params; req.shadow = f->path->shadow ? 1 : 0; req.cams = f->cam; req.path = f->path;
+  req.dst = f->dst; req.colors = f->colors; req.counters = f->rays_traced; req.stream = stream;
+  req.emissive = f->emissive; req.emissive_mis = f->emissive_mis; req.sample_counts = f->counts;
+  req.denoise = f->denoise; req.aov = f->aov; req.temporal = f->temporal; req.history = f->history; req.motion = f->motion == 1u; req.prev_position = f->prev_position;
+  req.variance = f->variance; req.variance_out = f->variance_out;
+  req.specular = specular;
+  return render_common(accel, req);
+}
+
+// the fields every vxrt_render_path* entry point sets alike
+static vxrt_path_frame_t path_frame(const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                                    const vxrt_path_params_t* path, uint32_t* dst, float* colors, unsigned long long* rays_traced) {
+  vxrt_path_frame_t f{};
+  f.size = sizeof f; f.width = width; f.height = height; f.y0 = y0; f.y1 = y1; f.cam = cam; f.params = params; f.path = path;
+  f.dst = dst; f.colors = colors; f.rays_traced = rays_traced;
+  return f;
+}
+
+extern "C" {
+
+int vxrt_render_path(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                     const vxrt_path_params_t* path, uint32_t* dst, float* colors, unsigned long long* rays_traced, void* stream) {
+  const vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_denoised(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                              const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn, uint32_t* dst, float* colors, const vxrt_path_aov_t* aov,
+                              unsigned long long* rays_traced, void* stream) {
+  if (!dn) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.denoise = dn; f.aov = aov;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_temporal(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                              const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, vxrt_history_t* history,
+                              uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, unsigned long long* rays_traced, void* stream) {
+  if (!dn || !temporal || !history) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.denoise = dn; f.aov = aov; f.temporal = temporal; f.history = history;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_temporal_motion(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                     const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn,
+                                     const vxrt_temporal_params_t* temporal, vxrt_history_t* history, uint32_t* dst, float* colors,
+                                     const vxrt_path_aov_t* aov, float* prev_position, unsigned long long* rays_traced, void* stream) {
+  if (!dn || !temporal || !history) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.denoise = dn; f.aov = aov; f.temporal = temporal; f.history = history; f.motion = 1u; f.prev_position = prev_position;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+// (motion outside {0, 1} is refused before it becomes the descriptor's unsigned field)
+int vxrt_render_path_variance(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                              const vxrt_path_params_t* path, const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp,
+                              vxrt_history_t* history, int motion, uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, float* prev_position, float* variance,
+                              unsigned long long* rays_traced, void* stream) {
+  if (!dn || !temporal || !vp || !history || motion < 0 || motion > 1) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.denoise = dn; f.aov = aov; f.temporal = temporal; f.history = history; f.motion = (uint32_t)motion; f.prev_position = prev_position;
+  f.variance = vp; f.variance_out = variance;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                              const vxrt_path_params_t* path, const uint32_t* counts, uint32_t* dst, float* colors, unsigned long long* rays_traced, void* stream) {
+  if (!counts) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.counts = counts;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_variance_adaptive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                       const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const uint32_t* counts,
+                                       const vxrt_denoise_params_t* dn, const vxrt_temporal_params_t* temporal, const vxrt_variance_params_t* vp,
+                                       vxrt_history_t* history, int motion, uint32_t* dst, float* colors, const vxrt_path_aov_t* aov, float* prev_position,
+                                       float* variance, unsigned long long* rays_traced, void* stream) {
+  if (!counts || !dn || !temporal || !vp || !history || motion < 0 || motion > 1) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.counts = counts;
+  f.denoise = dn; f.aov = aov; f.temporal = temporal; f.history = history; f.motion = (uint32_t)motion; f.prev_position = prev_position;
+  f.variance = vp; f.variance_out = variance;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_emissive(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const vxrt_shade_params_t* params,
+                              const vxrt_path_params_t* path, const vxrt_emissive_params_t* em, uint32_t* dst, float* colors, unsigned long long* rays_traced,
+                              void* stream) {
+  if (!em) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.emissive = em;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+int vxrt_render_path_emissive_mis(vxrt_accel_t* accel, const vxrt_camera_t* cam, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1,
+                                  const vxrt_shade_params_t* params, const vxrt_path_params_t* path, const vxrt_emissive_mis_params_t* em, uint32_t* dst,
+                                  float* colors, unsigned long long* rays_traced, void* stream) {
+  if (!em) return -1;
+  vxrt_path_frame_t f = path_frame(cam, width, height, y0, y1, params, path, dst, colors, rays_traced);
+  f.emissive_mis = em;
+  return render_path_frame(accel, &f, nullptr, stream);
+}
+
+// A path frame whose vertices may be specular (see the header, "Specular vertices"): the descriptor's frame with the specular kernels in
+// its tail.  A null part or enable = 0 is vxrt_render_path_frame; what the part alone can get wrong is refused here, the filter chain
+// beside enable = 1 is check_request's to refuse.  So is an output without its part, which only a caller's descriptor can ask for ahead
+// of the empty window: the entry points above hand theirs to check_request as they always have.
+int vxrt_render_path_frame_specular(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
+  if (f && ((f->prev_position && !f->motion) || (f->variance_out && !f->variance))) return -1;
+  if (!specular) return render_path_frame(accel, f, nullptr, stream);
+  if (specular->enable > 1u || specular->reserved[0] != 0u || specular->reserved[1] != 0u || specular->reserved[2] != 0u) return -1;
+  return render_path_frame(accel, f, specular->enable ? specular : nullptr, stream);
+}
+int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void* stream) { return vxrt_render_path_frame_specular(accel, f, nullptr, stream); }
+
+// The single launches below run on caller-owned buffers, asynchronous on `stream`, without a host synchronisation.
+
+// The lobe pick and the mirror ray alone (see the header, "Specular vertices")
+int vxrt_specular_pick(uint64_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, void* stream) {
+  if (!vertices || !seeds || !rays || !lobe || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_specular_pick_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, (uint32_t)n, vertices, seeds, rays, lobe);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// vxrt_specular_pick behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
-int specular_pick_launch(uint32_t n, const float* vertices, const uint32_t* seeds, float* rays, uint32_t* lobe, hipStream_t s) {
-  hipLaunchKernelGGL(rt_specular_pick_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, n, vertices, seeds, rays, lobe);
+// The emitter ray alone (see the header, "Emissive geometry"), and its weighted twin ("Multiple importance sampling")
+int vxrt_emitter_rays(vxrt_accel_t* a, uint64_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                      uint32_t* emitter, void* stream) {
+  if (!a || !emitters_valid(a) || !points || !seeds || !rays || !tmax || !weight3 || !emitter) return -1;
+  if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_emitter_rays_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, emitter_tab(a), (uint32_t)n, points, seeds, scale,
+                     rays, tmax, weight3, emitter);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int vxrt_emitter_rays_mis(vxrt_accel_t* a, uint64_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
+                          uint32_t* emitter, float* mis, void* stream) {
+  if (!a || !emitters_valid(a) || !points || !seeds || !rays || !tmax || !weight3 || !emitter || !mis) return -1;
+  if (!(scale >= 0.0f) || !std::isfinite(scale) || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_emitter_rays_mis_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, emitter_tab(a), (uint32_t)n, points, seeds, scale,
+                     rays, tmax, weight3, emitter, mis);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// vxrt_emitter_rays behind its entry point's checks (rt_kernels.hip): one launch, asynchronous on s
-int emitter_rays_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                        uint32_t* emitter, hipStream_t s) {
-  hipLaunchKernelGGL(rt_emitter_rays_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), n, points, seeds, scale, rays, tmax, weight3, emitter);
+// The lookup in the emitter index and the bounce ray's weight alone; the call that finds no index builds it first (one synchronisation
+// of `stream`, as for a buffer that grows)
+int vxrt_emitter_hit_weights(vxrt_accel_t* a, uint64_t n, const float* rays, const void* hits, const float* normals, uint32_t* emitter, float* mis, void* stream) {
+  if (!a || !emitters_valid(a) || !rays || !hits || !normals || !emitter || !mis || n >= 0x80000000ull) return -1;
+  if (n == 0) return 0;
+  if (emitter_index_ensure(a, (hipStream_t)stream) != 0) return -1;
+  hipLaunchKernelGGL(rt_emitter_hit_weights_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, emitter_tab(a), emitter_idx(a), (uint32_t)n,
+                     rays, (const HitRec*)hits, normals, emitter, mis);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// vxrt_emitter_rays_mis and vxrt_emitter_hit_weights behind their entry points' checks (rt_kernels.hip): one launch each, asynchronous on s
-int emitter_rays_mis_launch(const vxrt_accel* a, uint32_t n, const float* points, const uint32_t* seeds, float scale, float* rays, float* tmax, float* weight3,
-                            uint32_t* emitter, float* mis, hipStream_t s) {
-  hipLaunchKernelGGL(rt_emitter_rays_mis_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), n, points, seeds, scale, rays, tmax, weight3, emitter, mis);
+// Sample counts from a variance buffer (see the header, "Adaptive sampling"): elementwise
+int vxrt_sample_counts(uint64_t n, const float* variance, const uint32_t* prev_counts, const vxrt_sample_count_params_t* prm, uint32_t* counts,
+                       unsigned long long* total, void* stream) {
+  if (!prm || !variance || !counts || n >= 0x80000000ull || prm->reserved != 0u) return -1;
+  if (!(prm->gain > 0.0f) || !std::isfinite(prm->gain) || prm->min_spp == 0u || prm->min_spp > prm->max_spp || prm->max_spp > 4096u) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_sample_counts_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, (uint32_t)n, variance, prev_counts, prm->gain,
+                     prm->min_spp, prm->max_spp, counts, total);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int emitter_hit_weights_launch(const vxrt_accel* a, uint32_t n, const float* rays, const HitRec* hits, const float* normals, uint32_t* emitter, float* mis,
-                               hipStream_t s) {
-  hipLaunchKernelGGL(rt_emitter_hit_weights_kernel, dim3((n - 1u) / 256u + 1u), dim3(256), 0, s, emitter_tab(a), emitter_idx(a), n, rays, hits, normals, emitter, mis);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// The previous-position guide of caller-owned hit records (see the header, "Motion"): one launch, asynchronous on `stream`
-extern "C" int vxrt_previous_positions(vxrt_accel_t* a, uint32_t n, const vxrt_hit_t* hits, float* prev_position4, float* prev_normal4, void* stream) {
+// The previous-position guide of caller-owned hit records (see the header, "Motion")
+int vxrt_previous_positions(vxrt_accel_t* a, uint32_t n, const vxrt_hit_t* hits, float* prev_position4, float* prev_normal4, void* stream) {
   if (!a || a->stale || a->motion_what == 0u || !a->ref.triEx) return -1;
   if (!hits || !prev_position4 || !prev_normal4 || (((uintptr_t)prev_position4 | (uintptr_t)prev_normal4) & 15u) != 0) return -1;
   if (n == 0) return 0;
@@ -1302,3 +1446,5 @@ extern "C" int vxrt_previous_positions(vxrt_accel_t* a, uint32_t n, const vxrt_h
                      (float4*)prev_position4, (float4*)prev_normal4);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+}  // extern "C"

@@ -446,6 +446,11 @@ def _camera(cam):
     return cam if isinstance(cam, Camera) else Camera.from_cam14(cam)
 
 
+def _camera_ref(cam):
+    """the `cam` argument of the calls that take the fixed camera as None"""
+    return None if cam is None else C.byref(_camera(cam))
+
+
 def look_at(eye, target, up, vfov_deg, width, height):
     """The camera tracer.cpp:184-202 sets up, in fp32: forward = normalize(target - eye), right = normalize(cross(forward, up)),
     up' = cross(right, forward), viewplane = (h * W / H, h) with h = 2 tan(vfov_deg * 0.5).  As in the reference, normalize multiplies
@@ -532,12 +537,17 @@ class PathParams(C.Structure):   # vxrt_path_params_t
     _fields_ = [("spp", C.c_uint32), ("bounces", C.c_uint32), ("seed", C.c_uint32), ("shadow", C.c_uint32)]
 
 
+def _path_params(spp, bounces, seed, shadow):
+    """the PathParams of the render_path* calls' arguments (the seed modulo 2^32)"""
+    return PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+
+
 def render_path(accel, cam, width, height, y0, y1, params, spp, bounces, dst_ptr, seed=0, shadow=0, colors_ptr=None, rays_ptr=None, stream=None):
     """vxrt_render_path: `spp` paths per pixel of `bounces` diffuse bounces each, the light sampled at every vertex with shadow=1, seen
     from pinhole camera `cam` (a Camera or 14 floats; None = the fixed camera of vxrt_render)."""
     L = _lib()
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
-    check(L.vxrt_render_path(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), dst_ptr,
+    pp = _path_params(spp, bounces, seed, shadow)
+    check(L.vxrt_render_path(accel, _camera_ref(cam), width, height, y0, y1, C.byref(params), C.byref(pp), dst_ptr,
                              colors_ptr, rays_ptr, stream), "vxrt_render_path")
 
 
@@ -557,8 +567,8 @@ def render_path_denoised(accel, cam, width, height, y0, y1, params, spp, bounces
     """vxrt_render_path_denoised: render_path whose demodulated indirect term goes through `denoise.iterations` passes of the guided a-trous
     filter (`denoise`: a DenoiseParams); `aov` (a PathAov of device pointers, optional) receives the guide buffers of the primary hit."""
     L = _denoise_lib()
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
-    check(L.vxrt_render_path_denoised(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+    pp = _path_params(spp, bounces, seed, shadow)
+    check(L.vxrt_render_path_denoised(accel, _camera_ref(cam), width, height, y0, y1, C.byref(params), C.byref(pp),
                                       C.byref(denoise), dst_ptr, colors_ptr, None if aov is None else C.byref(aov), rays_ptr, stream),
           "vxrt_render_path_denoised")
 
@@ -635,7 +645,7 @@ def render_path_temporal(accel, cam, width, height, y0, y1, params, spp, bounces
                          aov=None, rays_ptr=None, stream=None):
     """vxrt_render_path_temporal: render_path_denoised whose demodulated indirect term is first blended with `history` (a History),
     reprojected through the camera of the history's previous frame; `temporal`: a TemporalParams.  `cam` must be a camera."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    pp = _path_params(spp, bounces, seed, shadow)
     check(_temporal_lib().vxrt_render_path_temporal(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), C.byref(denoise),
                                                     C.byref(temporal), _history(history), dst_ptr, colors_ptr, None if aov is None else C.byref(aov),
                                                     rays_ptr, stream), "vxrt_render_path_temporal")
@@ -667,7 +677,7 @@ def render_path_temporal_motion(accel, cam, width, height, y0, y1, params, spp, 
                                 colors_ptr=None, aov=None, prev_position_ptr=None, rays_ptr=None, stream=None):
     """vxrt_render_path_temporal_motion: render_path_temporal whose history is looked up where the accel's motion snapshot puts every
     pixel's surface point; `prev_position_ptr` (optional) receives that position, 4 floats per pixel of the frame."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    pp = _path_params(spp, bounces, seed, shadow)
     check(_motion_lib().vxrt_render_path_temporal_motion(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
                                                          C.byref(denoise), C.byref(temporal), _history(history), dst_ptr, colors_ptr,
                                                          None if aov is None else C.byref(aov), prev_position_ptr, rays_ptr, stream),
@@ -828,7 +838,7 @@ def render_path_variance(accel, cam, width, height, y0, y1, params, spp, bounces
     """vxrt_render_path_variance: render_path_temporal (motion=0) or render_path_temporal_motion (motion=1) on a History(moments=True),
     filtered with a per-pixel luminance scale from the variance of the accumulated luminance; `variance`: a VarianceParams;
     `variance_ptr` (optional) receives the initial variance, 1 float per pixel of the frame."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    pp = _path_params(spp, bounces, seed, shadow)
     check(_variance_lib().vxrt_render_path_variance(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), C.byref(denoise),
                                                     C.byref(temporal), C.byref(variance), _history(history), int(motion), dst_ptr, colors_ptr,
                                                     None if aov is None else C.byref(aov), prev_position_ptr, variance_ptr, rays_ptr, stream),
@@ -840,15 +850,15 @@ def render_path_adaptive(accel, cam, width, height, y0, y1, params, spp, bounces
                          stream=None):
     """vxrt_render_path_adaptive: render_path whose pixel p takes min(max(counts[p], 1), spp) samples; `counts_ptr`: device, one uint32 per
     pixel of the frame, addressed like dst.  `spp` is the cap."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
-    check(_lib().vxrt_render_path_adaptive(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+    pp = _path_params(spp, bounces, seed, shadow)
+    check(_lib().vxrt_render_path_adaptive(accel, _camera_ref(cam), width, height, y0, y1, C.byref(params), C.byref(pp),
                                                     counts_ptr, dst_ptr, colors_ptr, rays_ptr, stream), "vxrt_render_path_adaptive")
 
 
 def render_path_variance_adaptive(accel, cam, width, height, y0, y1, params, spp, bounces, counts_ptr, denoise, temporal, variance, history, dst_ptr, motion=0,
                                   seed=0, shadow=0, colors_ptr=None, aov=None, prev_position_ptr=None, variance_ptr=None, rays_ptr=None, stream=None):
     """vxrt_render_path_variance_adaptive: render_path_variance whose path frame is render_path_adaptive's (`counts_ptr`, `spp` the cap)."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
+    pp = _path_params(spp, bounces, seed, shadow)
     check(_lib().vxrt_render_path_variance_adaptive(accel, C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp), counts_ptr,
                                                              C.byref(denoise), C.byref(temporal), C.byref(variance), _history(history), int(motion), dst_ptr,
                                                              colors_ptr, None if aov is None else C.byref(aov), prev_position_ptr, variance_ptr, rays_ptr,
@@ -903,8 +913,8 @@ def render_path_emissive(accel, cam, width, height, y0, y1, params, spp, bounces
                          stream=None):
     """vxrt_render_path_emissive: render_path with emissive triangles as area lights; `emissive`: an EmissiveParams (nee = 0: emission found
     by the bounce rays, nee = 1: emitter sampling from the accel's table; scale multiplies every material's emissive)."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
-    check(_lib().vxrt_render_path_emissive(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+    pp = _path_params(spp, bounces, seed, shadow)
+    check(_lib().vxrt_render_path_emissive(accel, _camera_ref(cam), width, height, y0, y1, C.byref(params), C.byref(pp),
                                            C.byref(emissive), dst_ptr, colors_ptr, rays_ptr, stream), "vxrt_render_path_emissive")
 
 
@@ -920,8 +930,8 @@ def render_path_emissive_mis(accel, cam, width, height, y0, y1, params, spp, bou
     """vxrt_render_path_emissive_mis: render_path_emissive with both estimators in one frame -- the emitter ray of nee = 1 and the emission the
     bounce rays find, each weighted by the balance heuristic; `emissive`: an EmissiveMisParams (scale).  Needs a valid emitter table; the
     first frame after a set_emitters builds the accel's emitter index (accel_info(accel, 8))."""
-    pp = PathParams(int(spp), int(bounces), int(seed) & 0xFFFFFFFF, int(shadow))
-    check(_lib().vxrt_render_path_emissive_mis(accel, None if cam is None else C.byref(_camera(cam)), width, height, y0, y1, C.byref(params), C.byref(pp),
+    pp = _path_params(spp, bounces, seed, shadow)
+    check(_lib().vxrt_render_path_emissive_mis(accel, _camera_ref(cam), width, height, y0, y1, C.byref(params), C.byref(pp),
                                                C.byref(emissive), dst_ptr, colors_ptr, rays_ptr, stream), "vxrt_render_path_emissive_mis")
 
 
