@@ -32,6 +32,7 @@
 #include <vector>
 #include "../../include/vortex_hip.h"
 #include "pinhole.h"
+#include "rt_launch_plan.h"
 
 #define RC_LARGE_FLOAT 1e30f
 #define RC_EPSILON 1e-6f
@@ -890,7 +891,9 @@ extern "C" int vxrc_render_accel(vxrc_accel_t* a, uint32_t width, uint32_t heigh
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rc_persistent_kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
   }
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * cus, (nt + 3) / 4);
+  // VXRC_GRID_MAX=n (n >= 1; unset or 0: none), a measurement knob: at most n workgroups (tests/test_gpu_launch_geometry.py)
+  static const int grid_max = [] { const char* e = getenv("VXRC_GRID_MAX"); return e ? atoi(e) : 0; }();
+  const uint32_t grid = (uint32_t)plan_grid_max(std::min<uint64_t>((uint64_t)per_cu * cus, (nt + 3) / 4), grid_max);
   hipLaunchKernelGGL(rc_persistent_kernel, dim3(grid ? grid : 1), dim3(256), 0, hs, d, p, A);
   if (hipGetLastError() != hipSuccess) return fail();
   if (lpt) {

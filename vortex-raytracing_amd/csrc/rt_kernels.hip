@@ -30,6 +30,7 @@
 #include "pinhole.h"
 #include "rt_shading.h"   // (up here for std_max, which the slab test below takes)
 #include "rt_order.h"
+#include "rt_launch_plan.h"
 
 // rt_traversal.cpp:318-339 with idir hoisted (1.0f/rd is recomputed per child there; same value).
 // EXACT selects the libstdc++ min/max forms; the fast form uses v_min/v_max, which differs only
@@ -1599,7 +1600,7 @@ struct HostKnobs {
   uint32_t shard_rot, lpt_batch_max;
   bool lpt, lpt_batch;                  // on unless the value begins with '0'
   bool unordered_any_off, debug;        // VXRT_UNORDERED_ANY is 0; VXRT_DEBUG is set at all
-  int lpt_batch_alone, side_reserve, packed, packed_batch, grid_div, pool, wgs_per_cu;   // side_reserve, packed: -1 = unset
+  int lpt_batch_alone, side_reserve, packed, packed_batch, grid_div, pool, wgs_per_cu, grid_max;   // side_reserve, packed: -1 = unset
 };
 static const HostKnobs& host_knobs() {
   static const HostKnobs knobs = [] {
@@ -1618,16 +1619,16 @@ static const HostKnobs& host_knobs() {
     k.pool = num("VXRT_POOL", 0);
     { const char* e = getenv("VXRT_UNORDERED_ANY"); k.unordered_any_off = e && atoi(e) == 0; }
     k.wgs_per_cu = num("VXRT_WGS_PER_CU", 0);
+    k.grid_max = num("VXRT_GRID_MAX", 0);
     k.debug = getenv("VXRT_DEBUG") != nullptr;
     return k;
   }();
   return knobs;
 }
 
-// grid of a persistent launch: what the device holds at once (occupancy x CUs, queried once per kernel
-// and device), capped by the job count
+// what the device holds of a persistent kernel at once: occupancy x CUs, queried once per kernel and device
 template <class K>
-static uint32_t persistent_grid(K kernel, uint64_t jobs, int wg_threads = RT_WG_THREADS) {
+static uint64_t persistent_held(K kernel, int wg_threads = RT_WG_THREADS) {
   static std::mutex mu;
   static std::map<std::pair<const void*, int>, uint64_t> cache;
   int dev = 0;
@@ -1649,9 +1650,12 @@ static uint32_t persistent_grid(K kernel, uint64_t jobs, int wg_threads = RT_WG_
     std::lock_guard<std::mutex> lk(mu);
     cache[{(const void*)kernel, dev}] = g;
   }
-  const uint64_t need = (jobs + (uint64_t)wg_threads - 1) / (uint64_t)wg_threads;
-  if (g > need) g = need;
-  return (uint32_t)(g ? g : 1);
+  return g;
+}
+// grid of a persistent launch: what the device holds at once, capped by the job count and by VXRT_GRID_MAX (rt_launch_plan.h)
+template <class K>
+static uint32_t persistent_grid(K kernel, uint64_t jobs, int wg_threads = RT_WG_THREADS) {
+  return plan_persistent_grid(persistent_held(kernel, wg_threads), jobs, (uint32_t)wg_threads, host_knobs().grid_max);
 }
 
 // next frame context, ordered on `s` behind its previous use
@@ -2076,21 +2080,17 @@ static LaunchPlan launch_plan(const vxrt_accel* a, const RenderRequest& r, uint3
   plan.packed = k.packed >= 0 ? k.packed != 0 : ((a->n_ctx > 1 || (k.packed_batch && r.batch > 1)) && n_tiles >= LPT_MIN_TILES);
   plan.side_launch = ap_count != 0;
   plan.side_wgs = plan.side_launch ? std::min<uint32_t>(EXACT_GRID, (ap_count + 255u) / 256u) : 0u;
-  plan.side_reserve = k.side_reserve >= 0 ? k.side_reserve != 0 : a->n_ctx == 1;
-  plan.grid_div = k.grid_div > 0 ? (uint32_t)k.grid_div : ((k.grid_div == 0 && a->n_ctx > 1) ? a->n_ctx : 1u);
-  plan.grid_div_small = k.grid_div == 0;
+  plan.side_reserve = plan_side_reserve(k.side_reserve, a->n_ctx);
+  plan.grid_div = plan_grid_div(k.grid_div, a->n_ctx);
+  plan.grid_div_small = plan_grid_div_small(k.grid_div);
   return plan;
 }
 
 // grid of the main launch: what the machine holds of `kernel`, less the slots reserved for the side launch, divided as the plan says
 template <class K>
 static uint32_t main_grid(K kernel, const LaunchPlan& plan, uint32_t total) {
-  const uint32_t side_wgs_r = plan.side_reserve ? plan.side_wgs : 0u;
-  uint32_t g = persistent_grid(kernel, total + (uint64_t)side_wgs_r * RT_WG_THREADS);
-  const uint32_t cap = persistent_grid(kernel, ~0ull >> 8);
-  const uint32_t div = (plan.grid_div_small && (uint64_t)total >= 2ull * 64ull * RT_WG_WAVES * cap) ? 1u : plan.grid_div;
-  if (div > 1u) g = std::min<uint32_t>(g, std::max<uint32_t>(cap / div, 1u));
-  return std::max<uint32_t>(1u, g > side_wgs_r ? g - side_wgs_r : 1u);
+  return plan_main_grid(persistent_held(kernel), total, plan.side_wgs, plan.side_reserve, plan.grid_div, plan.grid_div_small, RT_WG_WAVES,
+                        host_knobs().grid_max);
 }
 
 // what the three traversal launches of a frame share

@@ -189,6 +189,19 @@ def debug_read_control(accel, ctx=0, n_dwords=800, stream=None):
     return out
 
 
+END_LOG_WAVES = 8192   # wavefronts a vxrt_debug_end_log buffer holds: 2 u64 each
+
+
+def debug_end_log(accel, log_ptr):
+    """vxrt_debug_end_log: the main launches enqueued on `accel` from now on leave one entry per wavefront in the device buffer
+    `log_ptr` (2 x END_LOG_WAVES u64, zeroed by the caller: [0] the 100 MHz clock at the wavefront's end, [1] rays it started |
+    physical XCD << 56), indexed by workgroup x 4 + wavefront; None switches the log off."""
+    L = _lib()
+    L.vxrt_debug_end_log.restype = C.c_int
+    L.vxrt_debug_end_log.argtypes = [C.c_void_p, C.c_void_p]
+    check(L.vxrt_debug_end_log(accel, log_ptr), "vxrt_debug_end_log")
+
+
 def accel_bytes(accel):
     return int(_lib().vxrt_accel_bytes(accel))
 
