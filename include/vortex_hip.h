@@ -1142,6 +1142,59 @@ int vxrt_render_path_frame_specular(vxrt_accel_t* accel, const vxrt_path_frame_t
 int vxrt_specular_pick(uint64_t n, const float* vertices /* device, n x 10: I, N, dir, rho */, const uint32_t* seeds /* device */,
                        float* rays /* device, n x 6 */, uint32_t* lobe /* device */, void* stream);
 
+/* Russian roulette (extension): path frames that end dim paths early, unbiased.  Above a path ends only on a miss or after `bounces`
+ * vertices; here a vertex may end it by a draw whose survival probability is the path's throughput, and a survivor is divided by it.
+ * Everything is "Path-traced frame" / "Emissive geometry" / "Multiple importance sampling" / "Adaptive sampling" / "Path frames by
+ * descriptor" as written, except what follows; every operation is one fp32 operation.  tests/roulette_ref.py restates all of it.
+ *
+ * Vertex j of a path is the hit found by the bounce ray of depth index k = j - 1; the primary hit is vertex 0, shared by all samples,
+ * and never takes a draw.  A vertex h' with first <= j < bounces takes a draw -- a bounce ray would leave it; the last vertex,
+ * j = bounces, takes none.
+ *
+ * THE DRAW happens in the scatter step, after everything the step adds at h' above -- the emitter-ray term of the previous vertex,
+ * thr * Lit, the emission terms of all three emitter forms -- and after thr = thr * Alb(h'):
+ *   m = thr.x; if (thr.y > m) m = thr.y; if (thr.z > m) m = thr.z;
+ *   q = m; if (!(q >= q_min)) q = q_min;                  -- a NaN throughput takes q_min
+ *   if (q >= 1.0f) the path continues: no draw, thr untouched.  Otherwise
+ *   seed = WangHash((x + y * W) * spp + s + 1 + u * 0x9E3779B9), u = ((path.seed + k) mod 2^32) ^ 0x20000000 -- the bounce ray's hash
+ *   input with a third bit flipped (0x80000000 is the emitter ray's, 0x40000000 the lobe pick's); with counts spp is the pixel's own
+ *   n_p; 0 becomes 1.   xi = random_float(seed), as in the lobe pick.
+ *   The path SURVIVES iff xi < q, and then thr = (thr.x / q, thr.y / q, thr.z / q): three correctly rounded fp32 divisions, no
+ *   reciprocal.  Otherwise it ends here: its Lc is final and no ray leaves h'.
+ *
+ * What follows from that:
+ *   - with nee = 1 or emissive_mis the emitter ray of a vertex is generated with the bounce ray that leaves it: a killed vertex sends
+ *     none, a survivor's carries thr / q.  Everything after the draw is divided by the probability of getting there, so the estimator
+ *     is unbiased;
+ *   - rays_traced is unchanged in kind: one per bounce ray of a live path, one per occlusion ray of a real hit, one per emitter ray
+ *     sent.  A killed path traces no more rays;
+ *   - the filter chain is untouched: the primary vertex takes no draw, so c = D + Alb_0 * E factors as before, and denoise, aov,
+ *     temporal, history, motion, variance and counts combine with roulette with nothing else changed.
+ *
+ * THE CALL.  vxrt_path_frame_t and vxrt_specular_params_t cannot grow, so the roulette part rides beside them.  roulette == NULL or
+ * enable = 0 IS vxrt_render_path_frame_specular(accel, frame, specular, stream).  With enable = 1 it returns -1 before anything is
+ * launched -- dst, the guide outputs and the history untouched, vxrt_status unchanged -- for enable > 1, `first` outside
+ * 1..VXRT_PATH_MAX_BOUNCES, a q_min that is not finite, <= 0 or > 1, a non-zero reserved word, everything vxrt_render_path_frame
+ * refuses, and roulette together with specular->enable = 1.  THAT LAST REFUSAL IS ON PURPOSE: in a specular frame thr is updated when
+ * the ray leaves, one vertex later, and dividing it before or after the albedo gives different bits -- either choice breaks identity A
+ * of "Specular vertices" under roulette.  It is a design of its own.  first >= bounces, q_min = 1 and a scene whose albedos have a
+ * component >= 1 everywhere are vxrt_render_path_frame bit for bit.  Asynchronous on `stream`; no launch, buffer or synchronisation
+ * is added.
+ *
+ * vxrt_roulette runs the draw alone on caller-owned DEVICE buffers: thr = n x 3 floats, seeds = n hash outputs (0 becomes 1) -> alive
+ * (n: 1 continues, 0 ended) and thr_out (n x 3: thr untouched for q >= 1, thr / q for a survivor, three zeros for a dead entry).  One
+ * launch, asynchronous on `stream`.  Returns -1 before the launch for a null buffer, n >= 2^31 or a bad q_min; 0 for n = 0. */
+typedef struct vxrt_roulette_params {
+  uint32_t enable;    /* 0 / 1 */
+  uint32_t first;     /* first vertex index that takes a draw, 1..VXRT_PATH_MAX_BOUNCES */
+  float    q_min;     /* floor of the survival probability, finite, 0 < q_min <= 1 */
+  uint32_t reserved;  /* 0 */
+} vxrt_roulette_params_t;
+int vxrt_render_path_frame_ex(vxrt_accel_t* accel, const vxrt_path_frame_t* frame, const vxrt_specular_params_t* specular /* may be NULL */,
+                              const vxrt_roulette_params_t* roulette /* may be NULL */, void* stream);
+int vxrt_roulette(uint64_t n, const float* thr /* device, n x 3 */, const uint32_t* seeds /* device */, float q_min,
+                  float* thr_out /* device, n x 3 */, uint32_t* alive /* device */, void* stream);
+
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,
  * invTransform, bvh_offset@128, tex_offset@136, tex_width@144, tex_height@148, reflectivity@152),

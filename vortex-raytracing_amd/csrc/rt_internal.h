@@ -280,6 +280,7 @@ struct RenderRequest {
   const vxrt_emissive_params_t* emissive = nullptr; // ... with emissive geometry (vxrt_render_path_emissive): a plain path frame otherwise
   const vxrt_emissive_mis_params_t* emissive_mis = nullptr; // ... with both estimators of emissive geometry, weighted (vxrt_render_path_emissive_mis)
   const vxrt_specular_params_t* specular = nullptr; // ... whose vertices may be specular (vxrt_render_path_frame_specular with enable = 1; null for enable = 0)
+  const vxrt_roulette_params_t* roulette = nullptr; // ... whose dim paths end early (vxrt_render_path_frame_ex with enable = 1; null for enable = 0); never with `specular`
   const uint32_t* sample_counts = nullptr;          // ... with a sample count per pixel (vxrt_render_path_adaptive): device, addressed like dst; path->spp is the cap
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;

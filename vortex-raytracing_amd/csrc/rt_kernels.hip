@@ -1891,6 +1891,11 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if ((r.variance || r.variance_out) && (!r.temporal || !vr_params_ok(r.variance))) return -1;
   // one diffuse bounce: a plain frame of the timed build
   if (gi_fused_frame(r) && (stats || r.shadow || r.unoccluded)) return -1;
+  // a path frame with Russian roulette (enable = 1; the entry point passes none for enable = 0): its parameters, and no specular
+  // vertices beside it -- there thr is updated when the ray leaves, and a division before or after the albedo breaks that section's identity A
+  if (r.roulette && (!r.path || r.roulette->enable != 1u || r.roulette->first < 1u || r.roulette->first > VXRT_PATH_MAX_BOUNCES ||
+                     !std::isfinite(r.roulette->q_min) || !(r.roulette->q_min > 0.0f) || !(r.roulette->q_min <= 1.0f) || r.roulette->reserved != 0u ||
+                     r.specular)) return -1;
   return 1;
 }
 

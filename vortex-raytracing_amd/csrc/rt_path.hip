@@ -7,7 +7,7 @@
 //   - host: the form of the request (path_form), the prepare launch, the depths of one batch, the end of the frame, the two tails
 //     (uniform, per-pixel counts);
 //   - host: the path API -- render_path_frame, the one builder of a path request, the vxrt_render_path* entry points that go through
-//     it, and the single-launch calls (vxrt_specular_pick, vxrt_emitter_rays[_mis], vxrt_emitter_hit_weights, vxrt_sample_counts).
+//     it, and the single-launch calls (vxrt_specular_pick, vxrt_roulette, vxrt_emitter_rays[_mis], vxrt_emitter_hit_weights, vxrt_sample_counts).
 // A denoised frame ends in rt_denoise.hip.  None of it is timed by bench.py, and none of it can reach the traversal kernel's unit: the
 // seam is in rt_internal.h, as for rt_secondary.hip, which holds the knob reader (secondary_knobs).  Same build flags (-ffp-contract=off).
 #include <hip/hip_runtime.h>
@@ -620,12 +620,53 @@ struct ScatterNoEmi {};
 // (SPEC: the frame of the header's "Specular vertices".  pT is thr as the ray left with it and is not touched here; a hit that goes on
 //  stores its Alb and reflectivity in pA instead, and if it is specular it adds `term` alone.  pD[slot].w marks the segment that arrives:
 //  after a specular one a hit whose material emits adds thr * Emi in full in all three emitter forms, without a lookup.)
-template <int EMI, bool SPEC = false>
+// The header's "Russian roulette", operation for operation.  roulette_q: the survival probability of throughput t -- its largest
+// component as the three compares form it, floored by q_min (a NaN takes q_min).  q >= 1 takes no draw.  roulette_draw: the draw of a
+// vertex with q < 1 from hash output `seed` (0 becomes 1; one xorshift step, as the lobe pick) -- true = the path survives and t is
+// divided by q, three correctly rounded divisions and no reciprocal.
+__device__ __forceinline__ float roulette_q(const float (&t)[3], float q_min) {
+  float m = t[0];
+  if (t[1] > m) m = t[1];
+  if (t[2] > m) m = t[2];
+  float q = m;
+  if (!(q >= q_min)) q = q_min;
+  return q;
+}
+__device__ __forceinline__ bool roulette_draw(float (&t)[3], float q, uint32_t seed) {
+  if (seed == 0u) seed = 1u;
+  const float xi = random_float(seed);
+  if (!(xi < q)) return false;
+  t[0] = t[0] / q; t[1] = t[1] / q; t[2] = t[2] / q;
+  return true;
+}
+
+// vxrt_roulette: the step alone on n caller-supplied throughputs and hash outputs, one per thread; a dead entry gets three zeros
+__global__ __launch_bounds__(256) void rt_roulette_kernel(uint32_t n, const float* __restrict__ thr, const uint32_t* __restrict__ seeds, float q_min,
+    float* __restrict__ thr_out, uint32_t* __restrict__ alive) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  float t[3] = {thr[3 * (size_t)i], thr[3 * (size_t)i + 1], thr[3 * (size_t)i + 2]};
+  const float q = roulette_q(t, q_min);
+  const bool lives = q >= 1.0f || roulette_draw(t, q, seeds[i]);
+  float* o = thr_out + 3 * (size_t)i;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[k] = lives ? t[k] : 0.f;
+  alive[i] = lives ? 1u : 0u;
+}
+
+// (RR: the scatter step of a depth whose hits take the draw of the header's "Russian roulette" -- launched with `next` only, and never
+//  with SPEC.  After thr = thr * Alb the vertex forms q; with q < 1 it draws from the bounce ray's hash input with bit 29 of the user seed
+//  flipped, which takes the slot's pixel and sample from the slot source the bounce-ray kernels read.  A path that dies keeps its Lc and
+//  is not appended; nothing else of its slot is written.)
+struct ScatterNoRoulette {};
+template <class SlotSrc> struct ScatterRoulette { SlotSrc src; uint32_t W, y0, user_seed; float q_min; };
+template <int EMI, bool SPEC = false, bool RR = false, class SlotSrc = SlotUniform>
 __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadeParams& p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
     const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
     uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>>& em,
-    float4* __restrict__ pA = nullptr) {
+    float4* __restrict__ pA = nullptr, const std::conditional_t<RR, ScatterRoulette<SlotSrc>, ScatterNoRoulette>& rr = {}) {
+  static_assert(!(RR && SPEC), "a specular frame takes no roulette (check_request)");
   const uint32_t total = min(*n_live, cap);
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   bool go[1] = {false};
@@ -677,7 +718,26 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
           L.x = L.x + T.x * (e3[0] * wB); L.y = L.y + T.y * (e3[1] * wB); L.z = L.z + T.z * (e3[2] * wB);
         }
       }
-      if (next) {
+      if constexpr (RR) {
+        if (next) {
+          float t3[3] = {T.x * a3[0], T.y * a3[1], T.z * a3[2]};
+          const float q = roulette_q(t3, rr.q_min);
+          bool lives = true;
+          if (!(q >= 1.0f)) {
+            uint32_t t, smp, spp;
+            rr.src.get(slot, t, smp, spp);
+            const uint32_t x = t % rr.W, y = rr.y0 + t / rr.W;
+            lives = roulette_draw(t3, q, wang_hash((x + y * rr.W) * spp + smp + 1u + (rr.user_seed ^ 0x20000000u) * 0x9E3779B9u));
+          }
+          if (lives) {
+            pT[slot] = make_float4(t3[0], t3[1], t3[2], 0.f);
+            pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
+            pN[slot] = make_float4(Nx, Ny, Nz, 0.f);
+            pD[slot] = make_float4(rp[3], rp[4], rp[5], 0.f);
+            go[0] = true; val[0] = slot;
+          }
+        }
+      } else if (next) {
         if constexpr (SPEC) pA[slot] = make_float4(a3[0], a3[1], a3[2], refl);
         else pT[slot] = make_float4(T.x * a3[0], T.y * a3[1], T.z * a3[2], 0.f);
         pI[slot] = make_float4(Ix, Iy, Iz, 1.0f);
@@ -722,6 +782,17 @@ __global__ __launch_bounds__(256) void rt_path_scatter_specular_kernel(SceneDev 
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT, float4* __restrict__ pA,
     uint32_t* __restrict__ next, uint32_t* n_next, std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>> em) {
   path_scatter<EMI, true>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em, pA);
+}
+
+// (the depths of a frame with Russian roulette whose hits take a draw: EMI as above; SlotSrc = SlotUniform for the uniform tail,
+//  SlotCounts for the counts tail -- the pixel's own count is then the spp of the hash input)
+template <int EMI, class SlotSrc>
+__global__ __launch_bounds__(256) void rt_path_scatter_roulette_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next, std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>> em,
+    ScatterRoulette<SlotSrc> rr) {
+  path_scatter<EMI, false, true, SlotSrc>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em, nullptr, rr);
 }
 
 // after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
@@ -1011,12 +1082,14 @@ extern const uint64_t PATH_BATCH_PATHS = 4ull << 20;   // (secondary_knobs, rt_s
 // live path and depth, generated with the bounce ray and traced by a second any-hit launch -- 3, the header's "Multiple importance
 // sampling": the launches of 2 with the weighted kernels, whose scatter looks emissive hits up in the emitter index.  scale: that
 // form's, 0 without one.  spec: specular vertices; counts: a sample count per pixel; shadow: light sampling; cam: a camera frame.
-struct PathForm { int emi; float scale; bool spec, counts, shadow, motion, cam; };
+// roulette (the header's "Russian roulette"): vertices rr_first .. bounces - 1 take a draw with floor q_min; never with spec.
+struct PathForm { int emi; float scale; bool spec, counts, shadow, motion, cam, roulette; uint32_t rr_first; float q_min; };
 static PathForm path_form(const RenderRequest& r) {
   PathForm f;
   f.emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
   f.scale = r.emissive_mis ? r.emissive_mis->scale : r.emissive ? r.emissive->scale : 0.0f;
   f.spec = r.specular != nullptr; f.counts = r.sample_counts != nullptr; f.shadow = r.path->shadow != 0; f.motion = r.motion; f.cam = r.cams != nullptr;
+  f.roulette = r.roulette != nullptr; f.rr_first = r.roulette ? r.roulette->first : 0u; f.q_min = r.roulette ? r.roulette->q_min : 0.0f;
   return f;
 }
 
@@ -1077,10 +1150,12 @@ static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r,
 // the live paths -> closest-hit launch -> (light sampling: occlusion rays -> any-hit launch) -> (emi >= 2: the any-hit launch of the
 // emitter rays the bounce-ray kernel wrote) -> scatter, which compacts the paths that go on into the next depth's list.
 // bounce_rays(d, live, n_live, n_next) launches the tail's bounce-ray kernel for depth d; n_rays is the batch's ray count as
-// trace_on_ctx sizes its launch (the live count is read on the device).
-template <class BounceRays>
+// trace_on_ctx sizes its launch (the live count is read on the device).  slots: the tail's slot source, which the scatter step of a
+// depth with Russian roulette reads for its draw -- the hit of depth d is vertex d + 1, and it draws iff rr_first <= d + 1 < bounces;
+// every other depth of such a frame takes the scatter kernel it always took.
+template <class SlotSrc, class BounceRays>
 static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const PathForm& f, const PathEmitters& E, const ShadeParams& p, uint32_t cap,
-                             uint64_t n_rays, const BounceRays& bounce_rays) {
+                             uint64_t n_rays, const SlotSrc& slots, const BounceRays& bounce_rays) {
   hipStream_t s = (hipStream_t)r.stream;
   const dim3 block(256), rgrid((cap + 255u) / 256u);
   const uint32_t bounces = r.path->bounces;
@@ -1103,7 +1178,13 @@ static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& 
       hipLaunchKernelGGL(kernel, rgrid, block, 0, s, a->dev, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits,
                          c->pt_I, c->pt_N, c->pt_D, c->pt_L, c->pt_T, rest...);
     };
-    if (f.spec && f.emi == 3) scatter(rt_path_scatter_specular_kernel<3>, c->pt_A, next, n_next, E.weighted);
+    if (f.roulette && next && d + 1u >= f.rr_first) {
+      const ScatterRoulette<SlotSrc> rr{slots, r.width, r.y0, r.path->seed + d, f.q_min};
+      if (f.emi == 3) scatter(rt_path_scatter_roulette_kernel<3, SlotSrc>, next, n_next, E.weighted, rr);
+      else if (f.emi == 2) scatter(rt_path_scatter_roulette_kernel<2, SlotSrc>, next, n_next, E.hits, rr);
+      else if (f.emi == 1) scatter(rt_path_scatter_roulette_kernel<1, SlotSrc>, next, n_next, E.hits, rr);
+      else scatter(rt_path_scatter_roulette_kernel<0, SlotSrc>, next, n_next, ScatterNoEmi{}, rr);
+    } else if (f.spec && f.emi == 3) scatter(rt_path_scatter_specular_kernel<3>, c->pt_A, next, n_next, E.weighted);
     else if (f.spec && f.emi == 2) scatter(rt_path_scatter_specular_kernel<2>, c->pt_A, next, n_next, E.hits);
     else if (f.spec && f.emi == 1) scatter(rt_path_scatter_specular_kernel<1>, c->pt_A, next, n_next, E.hits);
     else if (f.spec) scatter(rt_path_scatter_specular_kernel<0>, c->pt_A, next, n_next, ScatterNoEmi{});
@@ -1167,7 +1248,7 @@ static int render_path_uniform_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRe
                                   e.tab, e.scale, e.erays, e.etmax, e.eG);
       else launch(rt_path_bounce_rays_kernel, (const float4*)c->pt_D, c->pt_rays);
     };
-    if (path_batch_depths(a, c, r, f, E, p, cap, (uint64_t)n * k, bounce_rays) != 0) return -1;
+    if (path_batch_depths(a, c, r, f, E, p, cap, (uint64_t)n * k, SlotUniform{pp.spp, s0, k, c->pt_list}, bounce_rays) != 0) return -1;
     hipLaunchKernelGGL(rt_path_accumulate_kernel, grid, block, 0, s, n32, (const uint32_t*)c->pt_list, (const uint32_t*)c->pt_hdr, k, s0 == 0 ? 1u : 0u,
                        (const float4*)c->pt_L, c->pt_acc);
   }
@@ -1229,7 +1310,7 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
                                   e.tab, e.scale, e.erays, e.etmax, e.eG);
       else launch(rt_path_bounce_rays_counts_kernel, (const float4*)c->pt_D, c->pt_rays);
     };
-    if (path_batch_depths(a, c, r, f, E, p, cap, cap, bounce_rays) != 0) return -1;
+    if (path_batch_depths(a, c, r, f, E, p, cap, cap, SlotCounts{c->pt_spix, c->pt_ssmp, c->pt_cnt}, bounce_rays) != 0) return -1;
     hipLaunchKernelGGL(rt_path_accumulate_counts_kernel, grid, block, 0, s, n32, cap, g0, (const uint32_t*)c->pt_cnt, (const unsigned long long*)c->pt_off,
                        (const float4*)c->pt_L, c->pt_acc);
   }
@@ -1254,8 +1335,10 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
 // A path frame by descriptor (see the header, "Path frames by descriptor"): the one place that turns arguments into a path request.
 // What a descriptor can get wrong before a request exists is refused here -- a null part is "absent", so a part that an entry point
 // promises is that entry point's to check; the rest is check_request's (rt_kernels.hip), whose empty window comes before its path tests.
-// (specular: vxrt_render_path_frame_specular's part beside the descriptor, already checked and with enable = 1, or null)
-static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream) {
+// (specular: vxrt_render_path_frame_specular's part beside the descriptor, already checked and with enable = 1, or null; roulette:
+//  vxrt_render_path_frame_ex's, likewise)
+static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream,
+                             const vxrt_roulette_params_t* roulette = nullptr) {
   if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
   for (int k = 0; k < 4; ++k) if (f->reserved[k] != 0u) return -1;
   if (!f->path || (f->emissive && f->emissive_mis) || f->motion > 1u) return -1;
@@ -1273,7 +1356,7 @@ static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, co
   req.emissive = f->emissive; req.emissive_mis = f->emissive_mis; req.sample_counts = f->counts;
   req.denoise = f->denoise; req.aov = f->aov; req.temporal = f->temporal; req.history = f->history; req.motion = f->motion == 1u; req.prev_position = f->prev_position;
   req.variance = f->variance; req.variance_out = f->variance_out;
-  req.specular = specular;
+  req.specular = specular; req.roulette = roulette;
   return render_common(accel, req);
 }
 
@@ -1385,6 +1468,20 @@ int vxrt_render_path_frame_specular(vxrt_accel_t* accel, const vxrt_path_frame_t
 }
 int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void* stream) { return vxrt_render_path_frame_specular(accel, f, nullptr, stream); }
 
+// A path frame that ends dim paths early (see the header, "Russian roulette"): the descriptor's frame whose scatter step draws at the
+// vertices first .. bounces - 1.  A null part or enable = 0 is vxrt_render_path_frame_specular; with enable = 1 what the part alone can
+// get wrong is refused here, and so is the specular part with enable = 1 beside it (check_request refuses the pair as well, behind its
+// empty window).  A specular part with enable = 0 is checked as its own entry point checks it.
+static bool roulette_q_min_ok(float q_min) { return std::isfinite(q_min) && q_min > 0.0f && q_min <= 1.0f; }
+int vxrt_render_path_frame_ex(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, const vxrt_roulette_params_t* roulette,
+                              void* stream) {
+  if (!roulette || roulette->enable == 0u) return vxrt_render_path_frame_specular(accel, f, specular, stream);
+  if (roulette->enable > 1u || roulette->first < 1u || roulette->first > VXRT_PATH_MAX_BOUNCES || !roulette_q_min_ok(roulette->q_min) || roulette->reserved != 0u) return -1;
+  if (f && ((f->prev_position && !f->motion) || (f->variance_out && !f->variance))) return -1;
+  if (specular && (specular->enable != 0u || specular->reserved[0] != 0u || specular->reserved[1] != 0u || specular->reserved[2] != 0u)) return -1;
+  return render_path_frame(accel, f, nullptr, stream, roulette);
+}
+
 // The single launches below run on caller-owned buffers, asynchronous on `stream`, without a host synchronisation.
 
 // The lobe pick and the mirror ray alone (see the header, "Specular vertices")
@@ -1392,6 +1489,14 @@ int vxrt_specular_pick(uint64_t n, const float* vertices, const uint32_t* seeds,
   if (!vertices || !seeds || !rays || !lobe || n >= 0x80000000ull) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(rt_specular_pick_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, (uint32_t)n, vertices, seeds, rays, lobe);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The roulette step alone (see the header, "Russian roulette")
+int vxrt_roulette(uint64_t n, const float* thr, const uint32_t* seeds, float q_min, float* thr_out, uint32_t* alive, void* stream) {
+  if (!thr || !seeds || !thr_out || !alive || n >= 0x80000000ull || !roulette_q_min_ok(q_min)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rt_roulette_kernel, dim3(((uint32_t)n - 1u) / 256u + 1u), dim3(256), 0, (hipStream_t)stream, (uint32_t)n, thr, seeds, q_min, thr_out, alive);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

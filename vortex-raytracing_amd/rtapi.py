@@ -754,13 +754,26 @@ class SpecularParams(C.Structure):   # vxrt_specular_params_t: rides beside a Pa
         self.enable = int(enable)
 
 
-def render_path_frame(accel, frame, stream=None, specular=None):
+class RouletteParams(C.Structure):   # vxrt_roulette_params_t: rides beside a PathFrame (the header's "Russian roulette")
+    _fields_ = [("enable", C.c_uint32), ("first", C.c_uint32), ("q_min", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self, enable=1, first=2, q_min=0.05):
+        super().__init__()
+        self.enable, self.first, self.q_min = int(enable), int(first), float(q_min)
+
+
+def render_path_frame(accel, frame, stream=None, specular=None, roulette=None):
     """vxrt_render_path_frame: the path frame `frame` (a PathFrame) describes -- every render_path* call above is the frame with that
     call's parts, and the parts combine: an emitter form with counts, the filter, a history, motion, variance.  Raises on a refusal.
     specular (a SpecularParams): vxrt_render_path_frame_specular -- with enable = 1 the path follows reflective instances (a lobe pick
-    per vertex between the mirror ray and the diffuse bounce ray); a frame without the filter chain."""
+    per vertex between the mirror ray and the diffuse bounce ray); a frame without the filter chain.
+    roulette (a RouletteParams): vxrt_render_path_frame_ex -- with enable = 1 the vertices first .. bounces - 1 end their path with
+    probability 1 - max(q_min, largest component of the throughput) and a survivor is divided by what it survived with; not together
+    with specular vertices."""
     f = C.byref(frame) if frame is not None else None
-    if specular is None:
+    if roulette is not None:
+        check(_lib().vxrt_render_path_frame_ex(accel, f, None if specular is None else C.byref(specular), C.byref(roulette), stream), "vxrt_render_path_frame_ex")
+    elif specular is None:
         check(_lib().vxrt_render_path_frame(accel, f, stream), "vxrt_render_path_frame")
     else:
         check(_lib().vxrt_render_path_frame_specular(accel, f, C.byref(specular), stream), "vxrt_render_path_frame_specular")
@@ -770,6 +783,12 @@ def specular_pick(n, vertices_ptr, seeds_ptr, rays_ptr, lobe_ptr, stream=None):
     """vxrt_specular_pick: the lobe pick alone on device buffers -- vertices (n x 10: I, N, dir, reflectivity), seeds (n hash outputs) ->
     lobe (n: 1 mirror, 0 diffuse), rays (n x 6: the mirror ray of lobe 1, zeros for lobe 0)."""
     check(_lib().vxrt_specular_pick(int(n), vertices_ptr, seeds_ptr, rays_ptr, lobe_ptr, stream), "vxrt_specular_pick")
+
+
+def roulette(n, thr_ptr, seeds_ptr, q_min, thr_out_ptr, alive_ptr, stream=None):
+    """vxrt_roulette: the roulette draw alone on device buffers -- thr (n x 3), seeds (n hash outputs) -> alive (n: 1 continues, 0 ended),
+    thr_out (n x 3: untouched where q >= 1, thr / q for a survivor, zeros for a dead entry)."""
+    check(_lib().vxrt_roulette(int(n), thr_ptr, seeds_ptr, float(q_min), thr_out_ptr, alive_ptr, stream), "vxrt_roulette")
 
 
 def _declare_path_family(L):
@@ -813,6 +832,8 @@ def _declare_path_family(L):
         "vxrt_render_path_frame": (i32, [vp, C.POINTER(PathFrame), vp]),
         "vxrt_render_path_frame_specular": (i32, [vp, C.POINTER(PathFrame), C.POINTER(SpecularParams), vp]),
         "vxrt_specular_pick": (i32, [C.c_uint64, vp, vp, vp, vp, vp]),
+        "vxrt_render_path_frame_ex": (i32, [vp, C.POINTER(PathFrame), C.POINTER(SpecularParams), C.POINTER(RouletteParams), vp]),
+        "vxrt_roulette": (i32, [C.c_uint64, vp, vp, C.c_float, vp, vp, vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
