@@ -212,7 +212,8 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* accel);
  * takes the ldexp decode / generic slab form; 4 -> 1 while a non-zero alpha table is set (vxrt_accel_set_alpha_test); 5 -> 1 if the
  * timed plain / shadow frames take the identity-root kernels (2 holds, 1 holds, 3 and 4 do not); 6 -> the VXRT_REFIT_* mask of the
  * motion snapshot the accel holds (vxrt_accel_motion_snapshot), 0 for none; 7 -> the number of emitters of a valid emitter table
- * (vxrt_accel_set_emitters), 0 for none or a stale one. */
+ * (vxrt_accel_set_emitters), 0 for none or a stale one; 9 -> 1 if the accel holds a path table (one 32-bit word per triangle, counted by
+ * vxrt_accel_bytes: see vxrt_debug_set_shadow_hints). */
 int vxrt_accel_info(const vxrt_accel_t* accel, uint32_t which, uint64_t* value);
 
 /* Refit: new boxes for a scene whose instances or vertices moved, in place, without a rebuild (extension; the reference has no refit,
@@ -1301,6 +1302,29 @@ int vxrt_trace_reference_quirks(const void* image, uint64_t image_size, uint32_t
  * [288 + 32 k] of the EXACT launch over the deferred list, [544 + 32 k] of the a-priori EXACT launch.  A vxrt_trace call leaves the
  * block as its launches left it (the next call clears it). */
 int vxrt_debug_read_control(vxrt_accel_t* accel, uint32_t ctx, uint32_t* out, uint32_t n_dwords, void* stream);
+/* Tests only: the shadow hints.  A timed shadow frame (fixed or caller camera, single or batch) of an accel that holds a path table
+ * (vxrt_accel_info(accel, 9) == 1: built as one identity instance of at most 16 levels with the fma decode) and takes the identity-root
+ * kernels (index 5) keeps, per frame context, one word per hit-record slot -- tile-major: tile * 64 + (y & 7) * 8 + (x & 7), a batch's frames
+ * one after the other -- that names the triangle which blocked the slot's occlusion ray last (0xFFFFFFFF: none yet).  Only a frame that
+ * REPEATS the context's last such frame (same window, same light in every frame of the set, same cameras, no refit in between) is handed
+ * the words: its first repeat starts from none and leaves its blockers, the next descends towards them first.  Any other frame runs the
+ * kernels without hints and makes the context's words void.  Hints choose a visiting order only: every frame is the same bits whatever the words hold.
+ * VXRT_SHADOW_HINTS=0 in the environment renders without them.  set overwrites, get reads, the first n words of the context `stream` rendered such
+ * a frame on last (host memory), after synchronising `stream`; -1 if there is none or n exceeds its capacity. */
+int vxrt_debug_set_shadow_hints(vxrt_accel_t* accel, void* stream, const uint32_t* hints, uint64_t n);
+int vxrt_debug_get_shadow_hints(vxrt_accel_t* accel, void* stream, uint32_t* hints, uint64_t n);
+/* Tests only: on = 0 renders without shadow hints whatever the environment says, 1 with them, -1 goes back to the environment
+ * (VXRT_SHADOW_HINTS, read once per process).  A frame without hints launches the kernels without them and touches no hint word.
+ * Process-wide; takes effect with the next frame. */
+int vxrt_debug_shadow_hints_enable(int on);
+/* Tests only: the first n words (n <= n_tris) of the accel's path table to `out` (host memory), after synchronising `stream`: per
+ * triangle the child slot at each internal level from the BLAS root to the triangle's leaf, 2 bits per level, the root's in the low
+ * bits.  -1 if the accel holds no table. */
+int vxrt_debug_read_path_table(vxrt_accel_t* accel, uint32_t* out, uint64_t n, void* stream);
+/* Diagnostic (libraries built with -DRT_SHADOW_HINT_COUNT=1 only; -1 otherwise): out[0] = occlusion rays of hinted frames that ended
+ * blocked in the main launch, out[1] = those of them that were blocked while still guided by their hint (no hinted slot failed its box
+ * test, no pending sibling taken); sums over the current device since the last reset.  Synchronises `stream`. */
+int vxrt_debug_shadow_hint_counts(unsigned long long* out, int reset, void* stream);
 /* Diagnostic (tools/xcd_tail.py): from now on every main traversal launch on this layout -- the TIMED kernels included -- leaves per
  * wavefront (index = workgroup * 4 + wavefront of the workgroup) [0] the constant 100 MHz clock at its end and [1] rays it started |
  * physical XCD << 56 in `log` (device memory, 2 u64 per wavefront, room for 8,192 wavefronts); NULL switches it off.  One store per

@@ -77,7 +77,9 @@ def write_selectors():
 # here (hipcc cross-compiles without a GPU) so that the GPU box loads it instead of compiling it.
 # -DRT_ORDER_CHECK=1: the node step's paths without the sorting network (RT_ORDER_PATHS) evaluate the network as well and report a
 # difference in the status word (tests/test_gpu_order_paths.py runs its cases on this library too).
-TEST_VARIANT_FLAGS = ["-DRT_TOP_NODES=84", "-DRT_LDS_STACK_RENDER=5", "-DRT_LDS_STACK_RENDER_PACKED=4", "-DRT_TRI_LDS=4", "-DRT_TRI_LDS_MIN=2", "-DRT_ORDER_CHECK=1"]
+# -DRT_SHADOW_HINT_COUNT=1: the hinted shadow kernels count blocked occlusion rays and those that stopped while guided
+# (vxrt_debug_shadow_hint_counts; tests/test_gpu_shadow_hints.py, tools/moving_light_time.py).
+TEST_VARIANT_FLAGS = ["-DRT_TOP_NODES=84", "-DRT_LDS_STACK_RENDER=5", "-DRT_LDS_STACK_RENDER_PACKED=4", "-DRT_TRI_LDS=4", "-DRT_TRI_LDS_MIN=2", "-DRT_ORDER_CHECK=1", "-DRT_SHADOW_HINT_COUNT=1"]
 
 
 def build_test_variant(force=False):

@@ -10,6 +10,7 @@
 #include <utility>
 #include "rt_internal.h"
 #include "bvh_quant.h"
+#include "rt_path_code.h"
 
 // ---------------------------------------------------------------------------------------------
 // acceleration-layout build (one pass over the reference-format buffers; validates every index the
@@ -143,6 +144,13 @@ __global__ void accel_depth_kernel(const uint4* __restrict__ nodes_c, uint32_t n
   const uint4* np = nodes_c + (size_t)i * CNODE_VEC4;
   const uint4 q2 = np[2], q3 = np[3];
   reach(q2.z); reach(q2.w); reach(q3.x); reach(q3.y);
+}
+
+// Path table (vxrt_accel::tri_path; the layout and the pass are rt_path_code.h's): one launch per level, top down, one thread per compact
+// node; the host marks the BLAS root (level 1, code 0) first.
+__global__ void accel_path_kernel(const uint4* __restrict__ nodes_c, uint32_t n_nodes, uint32_t level, uint32_t* lvl, uint32_t* ncode,
+                                  const uint32_t* __restrict__ ref_bvh, uint32_t n_bvh, uint32_t n_tris, uint32_t* __restrict__ tri_path) {
+  path_pass_node((const uint32_t*)nodes_c, n_nodes, blockIdx.x * blockDim.x + threadIdx.x, level, lvl, ncode, ref_bvh, n_bvh, n_tris, tri_path);
 }
 
 // Top of the tree for LDS staging: breadth-first from the TLAS root through the instance roots, the first `cap` internal
@@ -456,7 +464,7 @@ static void accel_free(vxrt_accel* a) {
   if (!a) return;
   (void)hipDeviceSynchronize();
   (void)hipFree(a->nodes_c); (void)hipFree(a->tri_w); (void)hipFree(a->blas_root);
-  (void)hipFree(a->top_img); (void)hipFree(a->top_roots);
+  (void)hipFree(a->top_img); (void)hipFree(a->top_roots); (void)hipFree(a->tri_path);
   refit_plan_free(a->refit);
   (void)hipFree(a->uvtab); (void)hipFree(a->apriori);
   (void)hipFree(a->alpha_mat); (void)hipFree(a->alpha_tri);
@@ -464,7 +472,7 @@ static void accel_free(vxrt_accel* a) {
   (void)hipFree(a->em_tri); (void)hipFree(a->em_q); (void)hipFree(a->em_cum); (void)hipFree(a->em_idx);
   for (uint32_t k = 0; k <= VXRT_MAX_BATCH; ++k) (void)hipFree(a->batch_order[k]);
   for (FrameCtx& c : a->ctx) {
-    (void)hipFree(c.hitbuf); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
+    (void)hipFree(c.hitbuf); (void)hipFree(c.hints); (void)hipFree(c.defer); (void)hipFree(c.ctl); (void)hipFree(c.bcount);
     for (FrameCtx::Lpt& l : c.lpt) { (void)hipFree(l.cost); (void)hipFree(l.order); }
     (void)hipFree(c.ao_geo); (void)hipFree(c.ao_nrm); (void)hipFree(c.ao_col); (void)hipFree(c.ao_cnt); (void)hipFree(c.ao_rays); (void)hipFree(c.ao_tmax); (void)hipFree(c.ao_hits); (void)hipFree(c.ao_list); (void)hipFree(c.ao_hdr);
     (void)hipFree(c.bin_hist); (void)hipFree(c.bin_keys); (void)hipFree(c.bin_order);
@@ -742,6 +750,29 @@ int vxrt_accel_build(const vxrt_scene_t* s, void* stream, vxrt_accel_t** out) {
   a->dev.top_img = (const uint4*)a->top_img; a->dev.n_top = n_top; a->dev.tlas_root_top = troot_top;
   a->dev.blas_root_top = n_top ? a->top_roots + 2 : (const uint32_t*)a->blas_root;
   if (getenv("VXRT_DEBUG")) fprintf(stderr, "[vxrt] accel: %u top-of-tree nodes staged for LDS (cap %u)\n", n_top, TOP_CAP);
+  // path table: for the accels whose shadow frames take the identity-root kernels as built (see vxrt_accel::tri_path).  Without it the
+  // accel renders as it always did, so a failure here only leaves the table out.
+  if (RT_SHALLOW_LEVELS <= PATH_LEVELS_MAX && ident_root_form(a)) {
+    const uint32_t nc = s->n_tlas_nodes + s->n_bvh_nodes;
+    uint32_t root = DESC_DONE;
+    uint32_t* d_lvl = nullptr;   // level, then code, per compact node
+    bool pok = hipMemcpy(&root, (const uint32_t*)a->blas_root + (troot & PAYLOAD_MASK), 4, hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMalloc((void**)&a->tri_path, (size_t)s->n_tris * 4) == hipSuccess && hipMemsetAsync(a->tri_path, 0, (size_t)s->n_tris * 4, st) == hipSuccess;
+    if (pok && root < 0x80000000u && (root & PAYLOAD_MASK) < nc) {   // (a root that is a leaf: every code is 0)
+      const uint32_t one = 1u;
+      pok = hipMalloc((void**)&d_lvl, (size_t)nc * 8) == hipSuccess && hipMemsetAsync(d_lvl, 0, (size_t)nc * 8, st) == hipSuccess &&
+            hipMemcpyAsync(d_lvl + (root & PAYLOAD_MASK), &one, 4, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+      if (pok) {
+        for (uint32_t level = 1; level <= RT_SHALLOW_LEVELS; ++level)
+          hipLaunchKernelGGL(accel_path_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, (const uint4*)a->nodes_c, nc, level, d_lvl, d_lvl + nc,
+                             (const uint32_t*)s->bvh, s->n_bvh_nodes, s->n_tris, a->tri_path);
+        pok = hipGetLastError() == hipSuccess;
+      }
+    }
+    pok = hipStreamSynchronize(st) == hipSuccess && pok;
+    (void)hipFree(d_lvl);
+    if (!pok) { (void)hipFree(a->tri_path); a->tri_path = nullptr; }
+  }
   *out = a;
   return 0;
 }
@@ -756,6 +787,7 @@ uint64_t vxrt_accel_bytes(const vxrt_accel_t* a) {
   if (!a) return 0;
   return (uint64_t)a->ref.n_tlas_nodes * CNODE_VEC4 * 16 + (uint64_t)a->ref.n_bvh_nodes * CNODE_VEC4 * 16 +
          (uint64_t)a->ref.n_tris * WTRI_FLOATS * 4 + (uint64_t)a->ref.n_blas * 4 +
+         (a->tri_path ? (uint64_t)a->ref.n_tris * 4 : 0) +   // (the path table)
          ((a->motion_what & VXRT_REFIT_INSTANCES) ? (uint64_t)a->ref.n_blas * RT_BLAS_STRIDE : 0) +   // (the motion snapshot)
          ((a->motion_what & VXRT_REFIT_GEOMETRY) ? (uint64_t)a->ref.n_tris * RT_TRI_BYTES : 0) +
          (uint64_t)a->em_n * 56u +   // (the emitter table: 12 floats, q and cum per entry)
@@ -774,6 +806,7 @@ int vxrt_accel_info(const vxrt_accel_t* a, uint32_t which, uint64_t* value) {
   case 6: *value = a->motion_what; return 0;       // the VXRT_REFIT_* mask of the motion snapshot held (vxrt_accel_motion_snapshot)
   case 7: *value = emitters_valid(a) ? a->em_n : 0u; return 0; // emitters of a valid emitter table (vxrt_accel_set_emitters)
   case 8: *value = a->em_idx_n; return 0;          // entries of the emitter index (0: none built since the last vxrt_accel_set_emitters)
+  case 9: *value = a->tri_path ? 1u : 0u; return 0; // the accel holds a path table (shadow hints: see vxrt_accel::tri_path)
   }
   return -1;
 }
@@ -1024,6 +1057,7 @@ static RefitPlan* refit_plan_build(vxrt_accel* a, hipStream_t st) {
 // Everything of one refit after the plan exists: the box passes, the re-layout, one host synchronisation, the flags.  `xf_first` /
 // `xf_count`: set_transforms' records (its two kernels run first, on the same stream); xf_count == 0 for a plain refit.
 static int refit_run(vxrt_accel* a, uint32_t what, hipStream_t st, const float* xf_in, uint32_t xf_first, uint32_t xf_count) {
+  ++a->scene_gen;   // (whatever comes of it: hints a frame context holds were written for the scene before this call)
   RefitPlan* p = a->refit;
   const vxrt_scene_t& s = a->ref;
   // ordered after every call already issued on this accel, on any stream

@@ -75,6 +75,12 @@ struct ShadeParams { float amb[3], lcol[3], lpos[3], bg[3]; uint32_t max_depth; 
 struct FrameCtx {
   void* hitbuf = nullptr;      // W*H hit records between the traversal and the shading pass
   uint64_t hitbuf_pixels = 0;
+  // shadow hints (RT_SHADOW_HINTS, rt_kernels.hip): per hit-record slot the triangle that blocked the slot's occlusion ray last, 0xFFFFFFFF =
+  // none; reset on the stream when the window the slots belong to (hint_key) changes
+  uint32_t* hints = nullptr; uint64_t hints_cap = 0; uint32_t hint_key[6] = {0, 0, 0, 0, 0, 0}; bool hints_valid = false; uint64_t hint_seq = 0;
+  // what the context's last shadow frame that could take hints was rendered from -- the light of every frame of the set, the cameras of a
+  // camera frame, the accel's scene_gen: a frame is handed hints only if it is that frame again (ensure_shadow_hints)
+  std::vector<float> hint_sig; uint64_t hint_gen = 0; bool hint_sig_set = false;
   uint32_t* defer = nullptr;   // job list of the EXACT launch
   uint64_t defer_cap = 0;
   uint32_t* ctl = nullptr;     // control block (CTL_DWORDS), zero between frames
@@ -142,6 +148,12 @@ struct vxrt_accel {
   vxrt_scene_t ref{};
   void* nodes_c = nullptr; void* tri_w = nullptr; void* blas_root = nullptr;
   void* top_img = nullptr; uint32_t* top_roots = nullptr;   // LDS-staged top of the tree: image; [0] n, [1] TLAS root, [2..] BLAS roots
+  // path table (accel_path_kernel, rt_accel.hip): per triangle the child slot at each internal level from the BLAS root to its leaf, 2 bits per
+  // level, root in the low bits.  Only for an accel built as one identity instance of at most RT_SHALLOW_LEVELS levels with the fma decode
+  // (what ident_root_form asks of the build); nullptr otherwise.  A refit keeps the topology, hence the table.
+  uint32_t* tri_path = nullptr;
+  uint64_t scene_gen = 0;          // counts the refits (vxrt_accel_refit, vxrt_accel_set_transforms), successful or not
+  uint64_t hint_seq = 0;           // counts the hinted frames of the accel's contexts (FrameCtx::hint_seq)
   FrameCtx ctx[MAX_FRAMES_IN_FLIGHT];
   uint32_t n_ctx = 1, next_ctx = 0;
   bool stream_seen = false, multi_stream = false; hipStream_t first_stream = nullptr;   // (see release_ctx)

@@ -350,8 +350,11 @@ __host__ __device__ constexpr bool is_trace_job(int job) { return job == JOB_TRA
 // JOB_CAM: a render job seen from a caller-supplied pinhole camera (vxrt_render_camera) instead of the fixed GenerateRay: its own
 // instantiations, so the fixed-camera kernels do not change.  JOB_RENDER | JOB_CAM, JOB_RENDER_SHADOW | JOB_CAM and
 // JOB_RENDER_GI | JOB_CAM (vxrt_render_diffuse_bounce_camera); job_base() names the job without the bit.
-enum { JOB_CAM = 8 };
-__host__ __device__ constexpr int job_base(int job) { return job & ~JOB_CAM; }
+// JOB_NOHINTS: the shadow frame job of a launch that carries no shadow hints (RT_SHADOW_HINTS below: the host knob is off, or the accel has
+// no path table) -- its own instantiations of the three kernels that know hints, WITHOUT them: such a launch runs the kernel it ran before
+// hints existed, instruction for instruction.  No other job is instantiated with the bit.
+enum { JOB_CAM = 8, JOB_NOHINTS = 16 };
+__host__ __device__ constexpr int job_base(int job) { return job & ~(JOB_CAM | JOB_NOHINTS); }
 __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) != 0; }
 // JOB_RENDER_GI: the whole "one diffuse bounce" frame (BASELINE configs[2] as worded; recipe: oracle/rt_oracle.c:orc_render_gi) in ONE
 // persistent launch -- a lane traces its pixel's primary ray, shades the hit (closest.cpp's else arm), draws the pixel's bounce ray
@@ -417,6 +420,24 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #ifndef RT_ORDER_CHECK
 #define RT_ORDER_CHECK 0
 #endif
+// RT_SHADOW_HINTS: the occlusion-only loop descends first along the path of the triangle that blocked the same pixel's occlusion ray in
+// the context's frame before.  The accel holds one 32-bit path code per triangle (accel_path_kernel, rt_accel.hip: the child slot taken at
+// each internal level from the BLAS root to the triangle's leaf, 2 bits per level, root in the low bits), the frame context one hint word
+// per hit-record slot (the blocker's triangle index, 0xFFFFFFFF = none).  A lane that starts an occlusion ray reads its hint and, if it
+// names a triangle, that triangle's code: while the lane is "guided" (F_GUIDED) a node step takes the child in the hinted slot if its box
+// test passed and pushes the other valid children in slot order; a hinted slot that failed, or the lane's first pop, ends the guidance.
+// This only chooses a visiting order: the set of triangles an any-hit traversal can reach does not depend on it (RT_UNORDERED_OCCLUSION),
+// so the occlusion bit is the same whatever the hints hold -- stale, hostile or none.  A blocked ray leaves its blocker in the hint word.
+// No register is added: the occlusion-only loop has no use for path_m, which carries the code (and, once the ray is blocked, the blocker).
+// The three kernels that hold the occlusion-only loop only; 0 = their listings are the parent form's.  Host knob VXRT_SHADOW_HINTS=0/1.
+#ifndef RT_SHADOW_HINTS
+#define RT_SHADOW_HINTS 1
+#endif
+// -DRT_SHADOW_HINT_COUNT=1 (variant libraries only; in build.py's TEST_VARIANT_FLAGS): the hinted kernels count their blocked occlusion rays
+// and the ones that stopped while guided (g_hint_counts, two atomics per wavefront and finish section)
+#ifndef RT_SHADOW_HINT_COUNT
+#define RT_SHADOW_HINT_COUNT 0
+#endif
 // (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
 
 // -DRT_ISA_MARKS: comment-only markers in the listing (hipcc -S) that delimit the regions of the traversal loop for
@@ -478,7 +499,12 @@ struct PersistArgs {
   // frame_tiles is shaded and lit with pbatch[f]; nullptr = one frame
   const ShadeParams* pbatch; uint32_t frame_tiles;
   // JOB_RENDER_GI: the frame itself (pixel (x, y) at dst[x + y * W]), optional f32 colours, seed of the bounce rays
-  uint32_t* dst; float* colors; uint32_t gi_seed;
+  // -- and, in their place in a timed plain / shadow frame launch (which has no use for them; the block keeps its size and every other member
+  // its offset), RT_SHADOW_HINTS' three words, read by the kernels with the occlusion-only loop only: the accel's path code per triangle, the
+  // context's hint words (indexed like `hits`; nullptr = off for this launch), the number of triangles (a hint at or above it names none)
+  union { uint32_t* dst; const uint32_t* tri_path; };
+  union { float* colors; uint32_t* hints; };
+  union { uint32_t gi_seed; uint32_t n_path_tris; };
   // ALPHA instantiations only (vxrt_accel_set_alpha_test): per triangle, the threshold of its material (0 = opaque)
   const uint8_t* alpha_tri;
 };
@@ -502,6 +528,8 @@ __device__ __forceinline__ bool ray_in_fast_domain(float ox, float oy, float oz,
 #define F_SHADOW 8u      // render job is in its occlusion-ray phase
 #define F_WORLD 16u      // the active ray registers hold the world-space ray (TLAS level)
 #define F_RESUMED 32u    // EXACT launch: occlusion ray handed over by the main launch (its primary hit record is in memory)
+#define F_GUIDED 64u     // RT_SHADOW_HINTS: the lane's occlusion ray still follows its hint's path code, which path_m holds (bit pattern)
+#define F_HINTW 128u     // RT_SHADOW_HINTS: the lane's occlusion ray was blocked in the occlusion-only loop; path_m holds the blocker's triangle index
 
 // Register budget is the lever here (profiles/r01_c_*: at 4 waves/SIMD the VALU pipe idles 58 % of
 // the time waiting on dependent loads), so a lane keeps in VGPRs only what every step touches: the
@@ -529,6 +557,9 @@ __device__ __forceinline__ bool ray_in_fast_domain(float ox, float oy, float oz,
 // diagnostic (vxrt_debug_child_counts): node-body runs of the wave-log launches on this device by the largest number of valid children any
 // node lane of the run holds -- [0..3] ordered arm with 0, 1, 2, >= 3, [4..7] occlusion arm -- summed over their wavefronts
 __device__ unsigned long long g_child_counts[8];
+// diagnostic (vxrt_debug_shadow_hint_counts; -DRT_SHADOW_HINT_COUNT=1 libraries only): occlusion rays of hinted launches that finished in the
+// main kernel blocked, and those of them that were blocked in the occlusion-only loop while still guided (no failed hinted slot, no pop)
+__device__ unsigned long long g_hint_counts[2];
 
 template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false, bool ALPHA = false, bool IDENT = false>
 __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
@@ -608,6 +639,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   // VGPRs, some of them reloaded inside both loops (profiles/r13_a_isa_sections.txt; DESIGN.md s5, rejected)
   constexpr bool OCC_LOOP = RT_OCC_LOOP && IDENT && RT_BATCH_PUSH && RT_UNORDERED_OCCLUSION && RT_OCC_OK_MASKS && job_base(JOB) == JOB_RENDER_SHADOW &&
                             DEAD_MAX >= 64u && FINISH_MIN > 64u && STACK_CAP > 2 * LSTK;
+  constexpr bool HINTS = RT_SHADOW_HINTS && OCC_LOOP && (JOB & JOB_NOHINTS) == 0;   // (RT_SHADOW_HINTS above; the host launches the JOB_NOHINTS form when A.hints is null)
   // wave-uniform job-queue state
   bool queue_empty = false;
   // Home shard = the PHYSICAL XCD the wavefront runs on (HW_REG_XCC_ID, 0..7), so that band s of the frame is traced by the same XCD in every
@@ -652,6 +684,12 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     uint32_t j = job;
     asm volatile("" : "+v"(j));
     return A.hits + j;
+  };
+  // the lane's hint word (RT_SHADOW_HINTS): the same index, formed where it is used for the same reason
+  auto hint_slot = [&]() -> uint32_t* {
+    uint32_t j = job;
+    asm volatile("" : "+v"(j));
+    return A.hints + j;
   };
   // the primary ray of pixel (x, y) of the lane's job
   auto pixel_ray = [&](uint32_t x, uint32_t y, float& ox, float& oy, float& oz, float& dx, float& dy, float& dz) {
@@ -866,6 +904,7 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       // (every entry passes the re-filter, see above: the top is taken as it is)
       cur = tos_d;
       tos_d = DESC_DONE;
+      if constexpr (HINTS) flags &= ~F_GUIDED;   // (the hint's path ends where the lane first takes a pending sibling)
       if (cur != DESC_DONE && sp > 0) { --sp; float m; stack_load(occ, sp, tos_d, m); }
       return;
     }
@@ -1034,7 +1073,13 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       if (RT_OCC_LOOP_CHECK && is_work_desc(cur) && (sp != 0 || tos_d != DESC_DONE)) atomicOr(A.status, STATUS_ITER_LIMIT);
       // (is_work_desc: a lane that is finished or idle keeps the flags of its last ray)
       if (__all(!is_work_desc(cur) || (flags & F_ANYHIT) != 0u)) traverse(std::true_type());
-      else traverse(std::false_type());
+      else {
+        // (a mixed wavefront: the general loop needs path_m as start_ray left it -- every ray in front of the loop is fresh -- and knows no hints.
+        // INVARIANT: while F_GUIDED or F_HINTW is set, path_m holds a bit pattern, not a path maximum; whatever reads path_m as a float must
+        // run behind this restore or in a lane without those flags)
+        if constexpr (HINTS) { if (flags & F_GUIDED) { path_m = -__builtin_inff(); flags &= ~F_GUIDED; } }
+        traverse(std::false_type());
+      }
     } else {
       constexpr bool OCC = false;
       const std::false_type occ;
@@ -1105,6 +1150,9 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
         if (STATS && found) nhit++;
         if (job_base(JOB) == JOB_RENDER_SHADOW && found) {
           // continue this lane with the pixel's occlusion ray; the record is written when that ray has finished
+          // (RT_SHADOW_HINTS: the hint's load is issued first, its round trip lies behind the ray arithmetic)
+          uint32_t hint = 0xFFFFFFFFu;
+          if constexpr (HINTS) { if (A.hints) hint = *hint_slot(); }
           uint32_t x, y;
           pixel_of(job, x, y);
           float ox, oy, oz, dx, dy, dz, sox, soy, soz, sdx, sdy, sdz, sdist;
@@ -1115,6 +1163,10 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
           CTX(5) = __float_as_uint(hitd);
           flags = F_SHADOW;
           start_ray(sox, soy, soz, sdx, sdy, sdz, sdist, true);
+          if constexpr (HINTS) {
+            // (a ray that start_ray handed to the EXACT launch left the lane idle: it keeps path_m and its flags as start_ray left them)
+            if (hint < A.n_path_tris && is_work_desc(cur)) { path_m = __uint_as_float(A.tri_path[hint]); flags |= F_GUIDED; }
+          }
         } else {
           if (found) {
             h.dist = hitd; h.bx = __uint_as_float(CTX(3)); h.by = __uint_as_float(CTX(4)); h.bz = 1 - h.bx - h.by;
@@ -1131,6 +1183,12 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
         h.bx = __uint_as_float(CTX(3)); h.by = __uint_as_float(CTX(4)); h.bz = 1 - h.bx - h.by;
         h.dist = __uint_as_float(CTX(5)); h.blasIdx = CTX(6) | (found ? 0x80000000u : 0u); h.triIdx = CTX(7);   // found = occluded
         *hit_slot() = h;
+        // (RT_SHADOW_HINTS: a ray blocked in the occlusion-only loop leaves its blocker for the pixel's next frame; unblocked rays write nothing)
+        if constexpr (HINTS) { if (A.hints && (flags & F_HINTW) != 0u) *hint_slot() = __float_as_uint(path_m); }
+        if constexpr (HINTS && RT_SHADOW_HINT_COUNT != 0) {   // (counting variant: blocked rays, and those that were still guided when they stopped)
+          const unsigned long long all = __ballot(true), nb = __ballot(found), ng = __ballot(found && (flags & F_HINTW) != 0u && (flags & F_GUIDED) != 0u);
+          if (lane == (uint32_t)__ffsll((long long)all) - 1u) { atomicAdd(&g_hint_counts[0], (unsigned long long)__popcll(nb)); atomicAdd(&g_hint_counts[1], (unsigned long long)__popcll(ng)); }
+        }
         cur = DESC_IDLE;
       }
     }
@@ -1570,6 +1628,7 @@ __global__ __launch_bounds__(256) void wire_unpack_kernel(const uint32_t* __rest
 #include <cstring>
 #include <initializer_list>
 #include <map>
+#include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <utility>
@@ -1600,6 +1659,7 @@ struct HostKnobs {
   uint32_t shard_rot, lpt_batch_max;
   bool lpt, lpt_batch;                  // on unless the value begins with '0'
   bool unordered_any_off, debug;        // VXRT_UNORDERED_ANY is 0; VXRT_DEBUG is set at all
+  bool shadow_hints;                    // on unless VXRT_SHADOW_HINTS begins with '0'
   int lpt_batch_alone, side_reserve, packed, packed_batch, grid_div, pool, wgs_per_cu, grid_max;   // side_reserve, packed: -1 = unset
 };
 static const HostKnobs& host_knobs() {
@@ -1610,6 +1670,7 @@ static const HostKnobs& host_knobs() {
     k.shard_rot = (uint32_t)num("VXRT_SHARD_ROT", 0);
     k.lpt = not_off("VXRT_LPT");
     k.lpt_batch = not_off("VXRT_LPT_BATCH");
+    k.shadow_hints = not_off("VXRT_SHADOW_HINTS");
     { const char* e = getenv("VXRT_LPT_BATCH_MAX"); k.lpt_batch_max = e ? (uint32_t)atoll(e) : LPT_BATCH_MAX_TILES; }
     k.lpt_batch_alone = num("VXRT_LPT_BATCH_ALONE", 1);
     k.side_reserve = num("VXRT_SIDE_RESERVE", -1);
@@ -1998,6 +2059,48 @@ static bool ensure_lpt_tables(FrameCtx* c, const RenderRequest& r, uint32_t n_ti
   return true;
 }
 
+// Shadow hints (RT_SHADOW_HINTS): the context's hint words for the frame's hit-record slots, handed to the launch in A.  Only a timed shadow
+// frame of an accel that takes the identity-root kernels and holds a path table can get them, and only when it REPEATS the frame the context
+// rendered last -- same window, same light (every frame of a set), same cameras, no refit since: a hint for another light fails too often,
+// and a failed hint costs more than a right one saves (a light that moves 1 - 5 units per frame: 24 - 30 % of the blocked rays still guided,
+// the sequence 0.15 - 0.3 % slower than without hints).  Every other launch leaves A without them and takes the kernels without hints
+// (JOB_NOHINTS): a sequence whose light, camera or geometry moves runs exactly what it ran before hints existed.  The first repeat of a
+// frame starts from 0xFFFFFFFF words (no hint), set on the stream in front of the launch, and leaves its blockers; the second follows them.
+// The buffer has a capacity of its own, apart from hitbuf's: most contexts never repeat a frame and never allocate it.
+// VXRT_SHADOW_HINTS=0 (host_knobs) leaves the hints out; vxrt_debug_shadow_hints_enable overrides it for the tests.
+static std::atomic<int> g_shadow_hints_override{-1};   // -1: as the environment says
+static bool ensure_shadow_hints(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, uint64_t slots, PersistArgs& A, hipStream_t s) {
+  if (!RT_SHADOW_HINTS || !r.shadow || r.ao || r.path || r.counting != Counting::TIMED || !a->tri_path || !ident_root_form(a)) return true;
+  if (const int ov = g_shadow_hints_override.load(); ov == 0 || (ov < 0 && !host_knobs().shadow_hints)) return true;
+  // Is this the frame the context rendered last?  Same window, same light in every frame of the set, same cameras, no refit in between.
+  const uint32_t key[6] = {r.width, r.height, r.y0, r.y1, (uint32_t)r.shadow | (r.stride << 1), (r.batch << 1) | (r.cams ? 0x80000000u : 0u)};
+  std::vector<float> sig;
+  sig.reserve((size_t)r.batch * (3 + (r.cams ? 14 : 0)));
+  for (uint32_t f = 0; f < r.batch; ++f) {
+    sig.insert(sig.end(), r.params[f].light_pos, r.params[f].light_pos + 3);
+    if (r.cams) { const float* cf = (const float*)&r.cams[f]; sig.insert(sig.end(), cf, cf + sizeof(vxrt_camera_t) / sizeof(float)); }
+  }
+  const bool again = c->hint_sig_set && memcmp(key, c->hint_key, sizeof key) == 0 && c->hint_gen == a->scene_gen && sig.size() == c->hint_sig.size() &&
+                     memcmp(sig.data(), c->hint_sig.data(), sig.size() * sizeof(float)) == 0;   // (bit patterns: a NaN light never repeats itself)
+  if (!again) {
+    // another frame: its hints would be stale, and a hint that fails costs more than it saves (profiles/r25_d_moving_light.txt).  The launch
+    // goes without (JOB_NOHINTS: the kernel it ran before hints existed); what the context holds is void from here on.
+    memcpy(c->hint_key, key, sizeof key); c->hint_sig.swap(sig); c->hint_gen = a->scene_gen; c->hint_sig_set = true;
+    c->hints_valid = false;
+    return true;
+  }
+  const bool grows = c->hints_cap < slots;
+  if (!grow_device({{(void**)&c->hints, sizeof(uint32_t)}}, &c->hints_cap, slots, GrowSync::STREAM, s)) return false;
+  if (grows || !c->hints_valid) {   // the first repeat of a frame starts from no hints and leaves its own
+    c->hints_valid = false;
+    if (hipMemsetAsync(c->hints, 0xFF, (size_t)c->hints_cap * sizeof(uint32_t), s) != hipSuccess) return false;
+    c->hints_valid = true;
+  }
+  A.hints = c->hints; A.tri_path = a->tri_path; A.n_path_tris = a->ref.n_tris;
+  c->hint_seq = ++a->hint_seq;   // (which context a stream hinted last: vxrt_debug_set_shadow_hints)
+  return true;
+}
+
 // a-priori EXACT list (camera rays with u == 0 or v == 0), rebuilt only when the window changes.  The list of a batch is the
 // frames' lists one after the other, so a list built for F frames serves every batch <= F: the launch takes a prefix.
 static bool ensure_apriori(vxrt_accel* a, const RenderRequest& r, const Tiles& t, hipStream_t s) {
@@ -2049,6 +2152,7 @@ static bool frame_resources(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, 
   A.shard_rot = host_knobs().shard_rot;
   A.alpha_tri = a->alpha_on ? a->alpha_tri : nullptr;   // (check_request has refused every request that cannot honour it)
   if (lpt && !ensure_lpt_tables(c, r, n_tiles, A, s)) return false;
+  if (!ensure_shadow_hints(a, c, r, pixels, A, s)) return false;
   // (camera frames have no a-priori list: their primary rays outside the fast domain are deferred to the EXACT launch behind the main one)
   return r.cams || ensure_apriori(a, r, t, s);
 }
@@ -2119,6 +2223,13 @@ static void launch_traversal(const FrameLaunch& l) {
   };
   if constexpr (RT_IDENT_ROOT_KERNEL && STATS == 0 && !ALPHA && job_base(JOB) != JOB_RENDER_GI) {
     if (ident_root_form(l.a)) {
+      // (a shadow frame without hint words runs the kernel without hints: see JOB_NOHINTS)
+      if constexpr (RT_SHADOW_HINTS && job_base(JOB) == JOB_RENDER_SHADOW) {
+        if (!l.A.hints) {
+          launch(rt_persistent_kernel<JOB | JOB_NOHINTS, 0, false, false, PACKED, true, false, true>, rt_persistent_kernel<JOB, 0, false, true, false, false, false>);
+          return;
+        }
+      }
       launch(rt_persistent_kernel<JOB, 0, false, false, PACKED, true, false, true>, rt_persistent_kernel<JOB, 0, false, true, false, false, false>);
       return;
     }
@@ -2151,6 +2262,8 @@ static bool traverse_frame(vxrt_accel* a, FrameCtx* c, const RenderRequest& r, c
   if (gi_fused_frame(r)) {
     // one diffuse bounce: the whole frame in the persistent launches (JOB_RENDER_GI).  (The multi-pass form it replaced -- list the hit
     // pixels, generate the rays, a 2 M-ray trace launch, accumulate, final -- took the same 1.18 ms: profiles/r03_f_gi_fused_ab.txt)
+    // (dst, colors and gi_seed share their storage with the shadow hints' three words: ensure_shadow_hints leaves those out of every frame with
+    // r.ao, and only the kernels of the timed shadow job read them -- a kernel that read A.dst in such a launch would write into the path table)
     for (PersistArgs* g : {&l.A, &l.X, &l.X0}) { g->dst = r.dst; g->colors = r.colors; g->gi_seed = r.ao->seed; }
     // (a camera frame has no a-priori list -- plan.side_launch is false: its primary rays outside the fast domain are deferred)
     if (r.cams) launch_traversal<JOB_RENDER_GI | JOB_CAM, 0, false>(l); else launch_traversal<JOB_RENDER_GI, 0, false>(l);
@@ -2571,6 +2684,47 @@ int vxrt_debug_read_lpt(vxrt_accel_t* a, uint32_t ctx, uint32_t batch, uint32_t*
   if (cost && hipMemcpy(cost, L.cost, (size_t)std::min<uint32_t>(cost_cap, 4u * L.cap) * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (order && hipMemcpy(order, L.order, (size_t)std::min(order_cap, L.cap) * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return (int)L.cap;
+}
+
+// tests: the hint words (RT_SHADOW_HINTS) of the frame context that `stream` rendered a hinted shadow frame on last
+static FrameCtx* hinted_ctx_of(vxrt_accel_t* a, hipStream_t s) {
+  FrameCtx* pick = nullptr;
+  // (a context whose words are void -- it rendered another frame since -- still shows them: the tests look whether they were touched)
+  for (FrameCtx& c : a->ctx) if (c.hints && c.last_stream == s && (!pick || c.hint_seq > pick->hint_seq)) pick = &c;
+  return pick;
+}
+int vxrt_debug_set_shadow_hints(vxrt_accel_t* a, void* stream, const uint32_t* hints, uint64_t n) {
+  if (!a || !hints) return -1;
+  FrameCtx* c = hinted_ctx_of(a, (hipStream_t)stream);
+  if (!c || n > c->hints_cap) return -1;
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
+  return hipMemcpy(c->hints, hints, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+int vxrt_debug_read_path_table(vxrt_accel_t* a, uint32_t* out, uint64_t n, void* stream) {
+  if (!a || !out || !a->tri_path || n > a->ref.n_tris) return -1;
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
+  return hipMemcpy(out, a->tri_path, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+int vxrt_debug_shadow_hints_enable(int on) {
+  g_shadow_hints_override.store(on < 0 ? -1 : (on ? 1 : 0));
+  return 0;
+}
+int vxrt_debug_shadow_hint_counts(unsigned long long* out, int reset, void* stream) {
+  if (!RT_SHADOW_HINT_COUNT) return -1;   // (the library does not count)
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hint_counts), 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long zero[2] = {0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_hint_counts), zero, sizeof(zero)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+int vxrt_debug_get_shadow_hints(vxrt_accel_t* a, void* stream, uint32_t* hints, uint64_t n) {
+  if (!a || !hints) return -1;
+  FrameCtx* c = hinted_ctx_of(a, (hipStream_t)stream);
+  if (!c || n > c->hints_cap) return -1;
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
+  return hipMemcpy(hints, c->hints, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 
 int vxrt_status(void* stream, uint32_t* status) {

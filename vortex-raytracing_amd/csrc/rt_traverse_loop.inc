@@ -71,6 +71,33 @@
           const bool v0 = OK_MASKS ? ok[0] : c[0].d < __builtin_inff(), v1 = OK_MASKS ? ok[1] : c[1].d < __builtin_inff();
           const bool v2 = OK_MASKS ? ok[2] : c[2].d < __builtin_inff(), v3 = OK_MASKS ? ok[3] : c[3].d < __builtin_inff();
           if (STATS == 2 && A.wave_log) wl_tag += 4u;
+          if constexpr (OCC && HINTS) {
+            // RT_SHADOW_HINTS (occlusion-only loop): the step below on the children in the order d0 .. d3 / w0 .. w3.  A run without a guided
+            // lane (wave-uniform test) leaves them in slot order: today's step.  In a run with one, a guided lane whose hinted slot passed its
+            // box test moves that child to the front -- the others keep their slot order behind it -- and shifts its code; a guided lane whose
+            // hinted slot failed is guided no more.  All of it selects: no per-lane branch.
+            uint32_t d0 = c[0].desc, d1 = c[1].desc, d2 = c[2].desc, d3 = c[3].desc;
+            bool w0 = v0, w1 = v1, w2 = v2, w3 = v3;
+            if (__any((flags & F_GUIDED) != 0u)) {
+              const uint32_t code = __float_as_uint(path_m), hs = code & 3u;
+              // (conditions as and / or of lane masks: written as selects they become per-lane branches)
+              const bool g = (flags & F_GUIDED) != 0u && ((hs == 0u && v0) || (hs == 1u && v1) || (hs == 2u && v2) || (hs == 3u && v3));
+              path_m = __uint_as_float(g ? code >> 2 : code);
+              flags = g ? flags : (flags & ~F_GUIDED);
+              const bool m1 = g && hs >= 1u, m2 = g && hs >= 2u, m3 = g && hs == 3u;   // slot 0 .. 2 moves one place back
+              const uint32_t dh = hs == 1u ? d1 : (hs == 2u ? d2 : d3);
+              d3 = m3 ? d2 : d3; d2 = m2 ? d1 : d2; d1 = m1 ? d0 : d1; d0 = m1 ? dh : d0;
+              w3 = (m3 && w2) || (!m3 && w3); w2 = (m2 && w1) || (!m2 && w2); w1 = (m1 && w0) || (!m1 && w1); w0 = m1 || w0;
+            }
+            if (w0 || w1 || w2 || w3) {
+              bool more = true;
+              if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
+              cur = w0 ? d0 : (w1 ? d1 : (w2 ? d2 : d3));
+              push_pending(occ, more && w1 && w0, d1, 0.f, more && w2 && (w0 || w1), d2, 0.f, more && w3 && (w0 || w1 || w2), d3, 0.f);   // (no path maximum in this loop's entries)
+            } else {
+              pop_next(occ);
+            }
+          } else
           if (v0 || v1 || v2 || v3) {
             bool more = true;
             if (sp + 4 > STACK_CAP) { atomicOr(A.status, STATUS_STACK_OVERFLOW); more = false; }
@@ -214,7 +241,8 @@
               if constexpr (OCC) {
                 // an occlusion ray's accepted candidate ends it: the ray only feeds "is anything hit before the light" (no record: slots
                 // 3-7 keep the pixel's primary hit; no flag tests; hitd is not read again once the ray has stopped)
-                if (d < hitd) { flags |= F_FOUND; stop = true; break; }
+                if constexpr (HINTS) { if (d < hitd) { flags |= F_FOUND | F_HINTW; path_m = __uint_as_float(triIdx); stop = true; break; } }   // (the blocker, for the finish section)
+                else if (d < hitd) { flags |= F_FOUND; stop = true; break; }
               } else
               if (d < hitd) {
                 // a rejected candidate is a triangle the ray missed: no record, no abandon test, no stop, on to the leaf's next triangle

@@ -189,6 +189,59 @@ def debug_read_control(accel, ctx=0, n_dwords=800, stream=None):
     return out
 
 
+def debug_set_shadow_hints(accel, hints, stream=None):
+    """vxrt_debug_set_shadow_hints: overwrite the first len(hints) hint words (numpy u32, tile-major like the hit records) of the frame
+    context `stream` rendered a hinted shadow frame on last."""
+    import numpy as np
+    L = _lib()
+    L.vxrt_debug_set_shadow_hints.restype = C.c_int
+    L.vxrt_debug_set_shadow_hints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    h = np.ascontiguousarray(hints, dtype=np.uint32)
+    check(L.vxrt_debug_set_shadow_hints(accel, stream, h.ctypes.data, h.size), "vxrt_debug_set_shadow_hints")
+
+
+def debug_get_shadow_hints(accel, n, stream=None):
+    """vxrt_debug_get_shadow_hints: the first n hint words of that context (numpy u32; 0xFFFFFFFF = no hint)."""
+    import numpy as np
+    L = _lib()
+    L.vxrt_debug_get_shadow_hints.restype = C.c_int
+    L.vxrt_debug_get_shadow_hints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    out = np.zeros(int(n), np.uint32)
+    check(L.vxrt_debug_get_shadow_hints(accel, stream, out.ctypes.data, out.size), "vxrt_debug_get_shadow_hints")
+    return out
+
+
+def debug_read_path_table(accel, n, stream=None):
+    """vxrt_debug_read_path_table: the path codes of triangles 0 .. n - 1 (numpy u32)."""
+    import numpy as np
+    L = _lib()
+    L.vxrt_debug_read_path_table.restype = C.c_int
+    L.vxrt_debug_read_path_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    out = np.zeros(int(n), np.uint32)
+    check(L.vxrt_debug_read_path_table(accel, out.ctypes.data, out.size, stream), "vxrt_debug_read_path_table")
+    return out
+
+
+def debug_shadow_hints_enable(on):
+    """vxrt_debug_shadow_hints_enable: 0 = frames without shadow hints, 1 = with, -1 = as VXRT_SHADOW_HINTS says (process-wide)."""
+    L = _lib()
+    L.vxrt_debug_shadow_hints_enable.restype = C.c_int
+    L.vxrt_debug_shadow_hints_enable.argtypes = [C.c_int]
+    check(L.vxrt_debug_shadow_hints_enable(int(on)), "vxrt_debug_shadow_hints_enable")
+
+
+def debug_shadow_hint_counts(reset=False, stream=None):
+    """vxrt_debug_shadow_hint_counts: (blocked occlusion rays of hinted frames, those blocked while still guided) since the last
+    reset, or None if the library was built without -DRT_SHADOW_HINT_COUNT=1."""
+    L = _lib()
+    L.vxrt_debug_shadow_hint_counts.restype = C.c_int
+    L.vxrt_debug_shadow_hint_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    out = (C.c_ulonglong * 2)()
+    if L.vxrt_debug_shadow_hint_counts(out, int(bool(reset)), stream) != 0:
+        return None
+    return int(out[0]), int(out[1])
+
+
 END_LOG_WAVES = 8192   # wavefronts a vxrt_debug_end_log buffer holds: 2 u64 each
 
 
@@ -298,7 +351,8 @@ def wire_unpack(wire_all_ptr, wire_stride_bytes, width, tile_rows_per_rank, worl
 def accel_info(accel, which):
     """vxrt_accel_info: 0 -> internal levels of the deepest path (counted up to 17), 1 -> 48-entry stacks (depth class <= 16),
     2 -> single identity instance under the TLAS root, 3 -> ldexp decode, 4 -> a non-zero alpha table is set, 7 -> emitters of a
-    valid emitter table (0: none, or stale), 8 -> entries of the emitter index (0: none built since the last set_emitters)."""
+    valid emitter table (0: none, or stale), 8 -> entries of the emitter index (0: none built since the last set_emitters),
+    9 -> the accel holds a path table (shadow hints)."""
     L = _lib()
     L.vxrt_accel_info.restype = C.c_int
     L.vxrt_accel_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
