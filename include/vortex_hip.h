@@ -1325,6 +1325,12 @@ int vxrt_debug_read_path_table(vxrt_accel_t* accel, uint32_t* out, uint64_t n, v
  * blocked in the main launch, out[1] = those of them that were blocked while still guided by their hint (no hinted slot failed its box
  * test, no pending sibling taken); sums over the current device since the last reset.  Synchronises `stream`. */
 int vxrt_debug_shadow_hint_counts(unsigned long long* out, int reset, void* stream);
+/* Diagnostic (libraries built with -DRT_PHASE_COUNT=1 only; -1 otherwise): what the wavefronts of the shadow frame kernels that hold the
+ * occlusion-only loop ran.  out[0..2] = passes through a form of the traversal loop: the occlusion-only form, the general form with no
+ * any-hit lane, the general form holding primary and any-hit rays; out[3..5] = the node-body runs inside them, by the same classes (a run
+ * of the general form is classed by the lanes that hold work when it starts).  Sums over the current device since the last reset.
+ * Synchronises `stream`. */
+int vxrt_debug_phase_counts(unsigned long long* out, int reset, void* stream);
 /* Diagnostic (tools/xcd_tail.py): from now on every main traversal launch on this layout -- the TIMED kernels included -- leaves per
  * wavefront (index = workgroup * 4 + wavefront of the workgroup) [0] the constant 100 MHz clock at its end and [1] rays it started |
  * physical XCD << 56 in `log` (device memory, 2 u64 per wavefront, room for 8,192 wavefronts); NULL switches it off.  One store per

@@ -79,7 +79,14 @@ def write_selectors():
 # difference in the status word (tests/test_gpu_order_paths.py runs its cases on this library too).
 # -DRT_SHADOW_HINT_COUNT=1: the hinted shadow kernels count blocked occlusion rays and those that stopped while guided
 # (vxrt_debug_shadow_hint_counts; tests/test_gpu_shadow_hints.py, tools/moving_light_time.py).
-TEST_VARIANT_FLAGS = ["-DRT_TOP_NODES=84", "-DRT_LDS_STACK_RENDER=5", "-DRT_LDS_STACK_RENDER_PACKED=4", "-DRT_TRI_LDS=4", "-DRT_TRI_LDS_MIN=2", "-DRT_ORDER_CHECK=1", "-DRT_SHADOW_HINT_COUNT=1"]
+# -DRT_PHASE_COUNT=1: the shadow kernels that hold the occlusion-only loop count their passes through each form of the traversal loop and
+# the node-body runs inside them (vxrt_debug_phase_counts; tests/test_gpu_tile_phases.py, tools/phase_counts.py).
+# -DRT_OCC_LOOP_CHECK=1: those kernels report a lane that enters the loop with a stack that is not empty, and a pass that holds both a
+# primary and an any-hit ray (RT_TILE_PHASES), in the status word.
+# -DRT_TILE_REFILL_MIN=65: whole-tile phases without any partial refill (the shipped library still refills a wavefront half of whose lanes
+# are idle): the form in which no pass holds both kinds of ray, which the check above and the counters assert on every test window.
+TEST_VARIANT_FLAGS = ["-DRT_TOP_NODES=84", "-DRT_LDS_STACK_RENDER=5", "-DRT_LDS_STACK_RENDER_PACKED=4", "-DRT_TRI_LDS=4", "-DRT_TRI_LDS_MIN=2", "-DRT_ORDER_CHECK=1", "-DRT_SHADOW_HINT_COUNT=1",
+                      "-DRT_PHASE_COUNT=1", "-DRT_OCC_LOOP_CHECK=1", "-DRT_TILE_REFILL_MIN=65"]
 
 
 def build_test_variant(force=False):

@@ -30,6 +30,7 @@
 #include "pinhole.h"
 #include "rt_shading.h"   // (up here for std_max, which the slab test below takes)
 #include "rt_order.h"
+#include "rt_tile_refill.h"
 #include "rt_launch_plan.h"
 
 // rt_traversal.cpp:318-339 with idir hoisted (1.0f/rd is recomputed per child there; same value).
@@ -438,6 +439,35 @@ __host__ __device__ constexpr bool is_cam_job(int job) { return (job & JOB_CAM) 
 #ifndef RT_SHADOW_HINT_COUNT
 #define RT_SHADOW_HINT_COUNT 0
 #endif
+// RT_TILE_PHASES: in the kernels that hold the occlusion-only loop (OCC_LOOP) a wavefront keeps a tile's primary and occlusion phases apart:
+// the fetch section hands out jobs only when no lane of the wavefront holds work.  The parent form handed them to whatever lanes were idle,
+// and every shadow tile leaves some idle behind its primary phase wherever a pixel misses, belongs to the a-priori EXACT list, is
+// defer()ed or lies outside the window: those lanes took the next tile's first primary rays beside this tile's occlusion rays, the rest of
+// that tile went to the other lanes at the next finish, and the wavefront stayed shifted by part of a tile -- both kinds of ray in every
+// pass, the general loop's ordered arm for all of them, no hints -- for as long as it lived.  With whole-tile phases those lanes stay idle
+// through the tile's occlusion phase, as they are through its primary phase.  Which lane traces a job never entered a result, and an
+// occlusion ray's answer does not depend on the visiting order: same records, same rays.  Queue reservation, tile-cost accounting, the
+// end of the queue, DEAD_MAX and FINISH_MIN are untouched.  0 = every kernel's listing is the parent form's; every kernel without the
+// occlusion-only loop is the parent form's at either value.
+// RT_TILE_REFILL_MIN: the number of idle lanes from which a partial refill is still taken in those kernels (the one trade: a tile in which
+// many lanes miss runs its occlusion phase with those lanes empty).  65 = never (a wavefront all of whose lanes are idle always fetches),
+// 1 = the parent form's behaviour.  Shipped: 32 -- a wavefront at least half of whose lanes are idle is refilled as before (a frame whose
+// every tile is half background lost 1.9 % with 65 and nothing with 32 or 16); a tile that leaves fewer lanes idle keeps its phases apart
+// (the headline's a-priori lines, most silhouette tiles, narrow window edges).  Behind a tile that leaves 32 or more idle the wavefront
+// is shifted again and, in full tiles, stays so (tests/tile_phases_check.cpp replays it; the bunny-class frame keeps 16 mixed passes of
+// 24,585).  DESIGN.md s5 has the table.  The rule itself is rt_tile_refill.h.  The test variant library is built with 65, where "no pass
+// holds both kinds of ray" is an invariant that RT_OCC_LOOP_CHECK and the counters hold.
+#ifndef RT_TILE_PHASES
+#define RT_TILE_PHASES 1
+#endif
+#ifndef RT_TILE_REFILL_MIN
+#define RT_TILE_REFILL_MIN 32
+#endif
+// -DRT_PHASE_COUNT=1 (variant libraries only; in build.py's TEST_VARIANT_FLAGS): the kernels that hold the occlusion-only loop count, per
+// wavefront, their passes through a loop form and the node-body runs inside them (g_phase_counts, added up once per wavefront at its end)
+#ifndef RT_PHASE_COUNT
+#define RT_PHASE_COUNT 0
+#endif
 // (RT_IDENT_ROOT_KERNEL, rt_internal.h: the IDENT instantiations of rt_persistent_kernel)
 
 // -DRT_ISA_MARKS: comment-only markers in the listing (hipcc -S) that delimit the regions of the traversal loop for
@@ -560,6 +590,11 @@ __device__ unsigned long long g_child_counts[8];
 // diagnostic (vxrt_debug_shadow_hint_counts; -DRT_SHADOW_HINT_COUNT=1 libraries only): occlusion rays of hinted launches that finished in the
 // main kernel blocked, and those of them that were blocked in the occlusion-only loop while still guided (no failed hinted slot, no pop)
 __device__ unsigned long long g_hint_counts[2];
+// diagnostic (vxrt_debug_phase_counts; -DRT_PHASE_COUNT=1 libraries only): passes of the wavefronts of the kernels that hold the
+// occlusion-only loop through [0] that form, [1] the general form with no any-hit lane, [2] the general form holding both kinds of ray (a
+// pass is classed where it enters the loop); [3..5] the node-body runs inside them, a run of the general form classed by the lanes that
+// hold work when it starts
+__device__ unsigned long long g_phase_counts[6];
 
 template <int JOB, int STATS, bool LDEXP, bool EXACT, bool PACKED = false, bool SHALLOW = false, bool ALPHA = false, bool IDENT = false>
 __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_job(JOB) ? RT_WAVES_TRACE : (job_base(JOB) == JOB_RENDER_GI ? RT_WAVES_GI : (PACKED ? RT_WAVES_RENDER_PACKED : RT_WAVES_RENDER)))) void rt_persistent_kernel(SceneDev sc, ShadeParams p, PersistArgs A) {
@@ -640,6 +675,9 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
   constexpr bool OCC_LOOP = RT_OCC_LOOP && IDENT && RT_BATCH_PUSH && RT_UNORDERED_OCCLUSION && RT_OCC_OK_MASKS && job_base(JOB) == JOB_RENDER_SHADOW &&
                             DEAD_MAX >= 64u && FINISH_MIN > 64u && STACK_CAP > 2 * LSTK;
   constexpr bool HINTS = RT_SHADOW_HINTS && OCC_LOOP && (JOB & JOB_NOHINTS) == 0;   // (RT_SHADOW_HINTS above; the host launches the JOB_NOHINTS form when A.hints is null)
+  constexpr bool TILE_PHASES = RT_TILE_PHASES && OCC_LOOP;        // (RT_TILE_PHASES above: whole-tile phases, the kernels with the occlusion-only loop only)
+  constexpr bool PHASE_COUNT = RT_PHASE_COUNT != 0 && OCC_LOOP;   // (counting variant, RT_PHASE_COUNT above)
+  uint32_t ph_cnt[6] = {0u, 0u, 0u, 0u, 0u, 0u};                  // (wave-uniform; g_phase_counts' layout)
   // wave-uniform job-queue state
   bool queue_empty = false;
   // Home shard = the PHYSICAL XCD the wavefront runs on (HW_REG_XCC_ID, 0..7), so that band s of the frame is traced by the same XCD in every
@@ -946,7 +984,11 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
     // RT_CHUNK jobs); lanes then draw from the wavefront's private range.
     {
       const unsigned long long idle = __ballot(cur == DESC_IDLE);
-      if (!queue_empty && idle != 0ull && (is_trace_job(JOB) || FINISH_MIN > 64u || idle == ~0ull || RT_DEAD_MAX < 64)) {
+      // (TILE_PHASES: jobs only to a wavefront none of whose lanes holds work -- the `idle == ~0ull` arm -- or, RT_TILE_REFILL_MIN <= 64, to
+      // one with at least that many idle lanes)
+      bool refill = is_trace_job(JOB) || FINISH_MIN > 64u || idle == ~0ull || RT_DEAD_MAX < 64;
+      if constexpr (TILE_PHASES) refill = tile_refill(idle, (uint32_t)RT_TILE_REFILL_MIN);   // (rt_tile_refill.h)
+      if (!queue_empty && idle != 0ull && refill) {
         const uint32_t wl_tries0 = tries; const unsigned long long wl_tpoll0 = (STATS && A.wave_log) ? __builtin_readcyclecounter() : 0ull;
         if (loc_next == loc_end) {   // wave-uniform: reserve the next chunk, stealing from other shards when the home shard is dry
           // shards a wavefront of this WORKGROUP has found handed out (LDS: no memory traffic): not polled again by its other three.  Every
@@ -1072,6 +1114,14 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       // the loop holds a ray fresh from start_ray, with an empty stack -- reported as STATUS_ITER_LIMIT, which every test reads as a failure
       if (RT_OCC_LOOP_CHECK && is_work_desc(cur) && (sp != 0 || tos_d != DESC_DONE)) atomicOr(A.status, STATUS_ITER_LIMIT);
       // (is_work_desc: a lane that is finished or idle keeps the flags of its last ray)
+      // (TILE_PHASES without partial refills: a pass holds one kind of ray.  The checking variant reports one that holds both.)
+      if (RT_OCC_LOOP_CHECK && TILE_PHASES && RT_TILE_REFILL_MIN > 64 && __any(is_work_desc(cur) && (flags & F_ANYHIT) != 0u) && __any(is_work_desc(cur) && (flags & F_ANYHIT) == 0u))
+        atomicOr(A.status, STATUS_ITER_LIMIT);
+      if constexpr (PHASE_COUNT) {
+        if (__all(!is_work_desc(cur) || (flags & F_ANYHIT) != 0u)) ++ph_cnt[0];
+        else if (__any(is_work_desc(cur) && (flags & F_ANYHIT) != 0u)) ++ph_cnt[2];
+        else ++ph_cnt[1];
+      }
       if (__all(!is_work_desc(cur) || (flags & F_ANYHIT) != 0u)) traverse(std::true_type());
       else {
         // (a mixed wavefront: the general loop needs path_m as start_ray left it -- every ray in front of the loop is fresh -- and knows no hints.
@@ -1210,6 +1260,12 @@ __global__ __launch_bounds__(EXACT ? 256 : RT_WG_THREADS, EXACT ? 4 : (is_trace_
       // (the 16 words are taken and their layout is read by tools: the child-count classes are summed over the wavefronts, vxrt_debug_child_counts)
 #pragma unroll
       for (int k = 0; k < 8; ++k) if (wl_cc[k]) atomicAdd(&g_child_counts[k], (unsigned long long)wl_cc[k]);
+    }
+  }
+  if constexpr (PHASE_COUNT) {   // (the counts are wave-uniform: one lane adds them up)
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) if (ph_cnt[k]) atomicAdd(&g_phase_counts[k], (unsigned long long)ph_cnt[k]);
     }
   }
   if (!EXACT && A.end_log) {
@@ -2716,6 +2772,16 @@ int vxrt_debug_shadow_hint_counts(unsigned long long* out, int reset, void* stre
   if (reset) {
     const unsigned long long zero[2] = {0, 0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_hint_counts), zero, sizeof(zero)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+int vxrt_debug_phase_counts(unsigned long long* out, int reset, void* stream) {
+  if (!RT_PHASE_COUNT) return -1;   // (the library does not count)
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_counts), 6 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long zero[6] = {0, 0, 0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_counts), zero, sizeof(zero)) != hipSuccess) return -1;
   }
   return 0;
 }

@@ -15,6 +15,13 @@
       }
       if (STATS && A.wave_log) wl_t0 = __builtin_readcyclecounter();
       unsigned wl_tag = 0;   // wave log: 1 + class + 4 * arm of this iteration's node-body run, in the lanes that took it
+      if constexpr (PHASE_COUNT) {   // (counting variant: this iteration's node-body run by the form of the loop and the rays its wavefront holds)
+        if (__any(is_node_desc(cur))) {
+          if (OCC) ++ph_cnt[3];
+          else if (__any(is_work_desc(cur) && (flags & F_ANYHIT) != 0u)) ++ph_cnt[5];
+          else ++ph_cnt[4];
+        }
+      }
       RT_LOOP_MARK("node");
       if (is_node_desc(cur)) {
         // ---- internal node: 4 box tests, order, push the far ones, continue with the nearest ----

@@ -242,6 +242,19 @@ def debug_shadow_hint_counts(reset=False, stream=None):
     return int(out[0]), int(out[1])
 
 
+def debug_phase_counts(reset=False, stream=None):
+    """vxrt_debug_phase_counts: (passes through the occlusion-only form, the general form with no any-hit lane, the general form holding
+    both kinds of ray; node-body runs inside them, same classes) of the shadow frame kernels with the occlusion-only loop since the last
+    reset, or None if the library was built without -DRT_PHASE_COUNT=1."""
+    L = _lib()
+    L.vxrt_debug_phase_counts.restype = C.c_int
+    L.vxrt_debug_phase_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    out = (C.c_ulonglong * 6)()
+    if L.vxrt_debug_phase_counts(out, int(bool(reset)), stream) != 0:
+        return None
+    return tuple(int(v) for v in out)
+
+
 END_LOG_WAVES = 8192   # wavefronts a vxrt_debug_end_log buffer holds: 2 u64 each
 
 
