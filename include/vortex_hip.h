@@ -1196,6 +1196,96 @@ int vxrt_render_path_frame_ex(vxrt_accel_t* accel, const vxrt_path_frame_t* fram
 int vxrt_roulette(uint64_t n, const float* thr /* device, n x 3 */, const uint32_t* seeds /* device */, float q_min,
                   float* thr_out /* device, n x 3 */, uint32_t* alive /* device */, void* stream);
 
+/* Environment light (extension): an octahedral radiance map lights path frames -- what a ray that leaves the scene sees, in place of the
+ * constant params->background, and with sample = 1 a second estimator that aims rays at the map's bright texels, weighted against the
+ * bounce ray by the balance heuristic.  The conventions are those of "Emissive geometry": every symbol is one fp32 IEEE operation (add,
+ * mul, div, compare, sqrtf) in the order written, without contraction; pi = 3.14159265f; sign(t) = t >= 0 ? 1.0f : -1.0f; max is
+ * std::max (a NaN gives 0); xorshift and random_float are those of THE EMITTER RAY.  tests/env_ref.py restates all of it.
+ *
+ * THE MAP.  vxrt_envmap_t is an object of its own, not part of an accel: it holds world-space directions only, so no refit and no
+ * vxrt_accel_set_transforms makes it stale, and one map may light frames of any accel.  It is made from HOST texels: n x n x 3 floats of
+ * RGB radiance, texel (i, j) at 3 * (i + j * n); n is a power of two, 4 <= n <= 256 -- at most 65,536 entries, so the cumulative table
+ * fits uint32 exactly as the emitter table's does.  The texel square [-1, 1]^2 is the octahedral unfolding with y as the pole (the
+ * fixed camera's up).
+ * TEXEL OF A DIRECTION w = (x, y, z):
+ *   s = (|x| + |y|) + |z|;   px = x / s;  py = y / s;  pz = z / s
+ *   u = px;  v = pz;   if (py < 0) { u = (1 - |pz|) * sign(px);  v = (1 - |px|) * sign(pz); }      (px, pz: the values before the fold)
+ *   fu = (u * 0.5f + 0.5f) * (float)n;   i = fu >= 0 ? min((uint32_t)fu, n - 1) : 0;   j likewise from v;   e = i + j * n
+ *   r2 = (px * px + py * py) + pz * pz;   r = sqrtf(r2)
+ * A NaN direction and the zero vector give texel 0.  Env(w) = texel_e * scale per channel.  The solid-angle density of choosing w through
+ * the table is
+ *   pe(w) = (qf_e * nn4) * (r2 * r),   qf_e = (float)q_e / (float)Q,   nn4 = (float)(n * n) * 0.25f
+ * since an area element du dv of the unfolding subtends du dv / r^3, which integrates to 4 pi over the square.
+ * THE TABLE, built on the device at creation:
+ *   centre of texel (i, j):  u = (((float)i + 0.5f) / (float)n) * 2.0f - 1.0f,  v likewise from j
+ *   c = (1 - |u|) - |v|;   if (c < 0) { u' = (1 - |v|) * sign(u);  v' = (1 - |u|) * sign(v); } else { u' = u;  v' = v; }
+ *   P = (u', c, v');   r2 = (P.x * P.x + P.y * P.y) + P.z * P.z;   r = sqrtf(r2)
+ *   w_e = max(max(L.r, L.g), L.b) / (r2 * r);   wmax = the maximum over the table (exact in any order)
+ *   q_e = max(1, (uint32_t)((w_e / wmax) * 65535.0f));   cum_e = q_0 + .. + q_e in uint32;   Q = cum_{n * n - 1}
+ * vxrt_envmap_create returns -1 and makes nothing for n out of range or not a power of two, a null pointer, a texel that is negative
+ * or not finite, a map with no positive texel, and a weight w_e that is not finite.  It is synchronous with respect to `stream`, like
+ * vxrt_accel_set_emitters.  vxrt_envmap_bytes is the device storage held (20 bytes per texel); vxrt_envmap_read (test / diagnostic;
+ * synchronous) copies q and cum to HOST memory, either pointer may be NULL.  A map must outlive every frame that reads it.
+ *
+ * THE ENVIRONMENT RAY of a vertex (I, N') -- N' faces the viewer -- from hash output `seed` (0 becomes 1):
+ *   r0 = xorshift(state);  a = random_float;  b = random_float
+ *   t = ((uint64_t)r0 * Q) >> 32;   e = the smallest index with cum_e > t;   (i, j) = (e % n, e / n)
+ *   u = (((float)i + a) / (float)n) * 2.0f - 1.0f,  v likewise from j and b;   c, the fold and P as for the table;  r2, r of P;  w = P / r
+ *   o = I + N' * 0.001f;  tmax = 1e30f;  any-hit
+ *   cosx = max(0, (N'.x * w.x + N'.y * w.y) + N'.z * w.z)
+ *   pE = (qf_e * nn4) * (r2 * r);   pb = cosx / pi
+ *   G = ((L_e * scale) * cosx) / (pi * pE) per channel;   wE = pE / (pE + pb);   Gm = G * wE
+ * Any search that returns the smallest index with cum_e > t is legal (the kernels search the row ends first, then the row): the result
+ * is defined, the walk is not.  The radiance is texel e's by index, not by a second lookup.  SKIPPED -- not traced, not counted, without
+ * a contribution -- if cosx == 0, if every channel of L_e * scale is 0, or if a channel of Gm is not finite.
+ *
+ * THE FRAME.  vxrt_render_path_frame_env(accel, frame, roulette, env, stream): env == NULL IS vxrt_render_path_frame_ex(accel, frame,
+ * NULL, roulette, stream).  With env set the frame is the descriptor's (with the roulette part, if enabled) except for two rules; the
+ * background * reflectivity term inside Lit stays params->background (it is the reference's term, and specular vertices are not part
+ * of this frame -- there is no specular parameter, on purpose).
+ *   Every ray that misses.  A primary miss is Env(dir(r_0)): the pixel, its `colors`, and what the filter chain shows for a miss.  With
+ *     sample = 0 a bounce ray w that misses adds Lc = Lc + thr * Env(w) and the path ends; no launch is added.
+ *   sample = 1.  Every vertex a bounce ray leaves sends THE ENVIRONMENT RAY (the last vertex none), with
+ *     seed = WangHash((x + y * W) * spp + s + 1 + u * 0x9E3779B9), u = ((path.seed + k) mod 2^32) ^ 0x10000000 -- a fourth bit beside
+ *     0x80000000, 0x40000000 and 0x20000000; with counts spp is the pixel's own n_p.  It is traced by the any-hit launch the emitter rays
+ *     take in their frames, and in the scatter step, before the miss / hit arm, an unblocked ray adds Lc = Lc + thr * Gm, thr as the
+ *     vertex has it (Alb included).  A bounce ray w from a vertex with facing normal N' that misses adds Lc = Lc + thr * (Env(w) * wB):
+ *       cosx = max(0, (N'.x * w.x + N'.y * w.y) + N'.z * w.z);   pb = cosx / pi;   pe = pe(w) of TEXEL OF A DIRECTION
+ *       den = pe + pb;   wB = den > 0 ? pb / den : 1
+ *     rays_traced also counts the environment rays that were traced.  Under roulette the ray is generated with the bounce ray that
+ *     leaves the vertex: a killed vertex sends none, a survivor's carries thr / q.
+ * counts, roulette and the whole filter chain (denoise, aov, temporal, history, motion, variance) combine with it unchanged: D stays
+ * Lit_0 (Env(dir(r_0)) at a miss), and the environment rays of h_0 are part of the stochastic term, as in EMITTER FORM x FILTER.
+ * A map whose every texel is c, with scale = 1, sample = 0 and params->background = c, is vxrt_render_path_frame bit for bit.
+ * Returns -1 before anything is launched, dst untouched, for env together with emissive or emissive_mis (three-way weighting is a
+ * design of its own), a null map, sample > 1, a scale that is negative or not finite, a non-zero reserved word, and everything
+ * vxrt_render_path_frame_ex refuses (a non-zero alpha table included).  Asynchronous on `stream`; sample = 1 holds and launches what
+ * nee = 1 does.
+ *
+ * The steps alone, on caller-owned DEVICE buffers, one launch each, asynchronous on `stream`; -1 before the launch for a null map or
+ * buffer, a scale that is negative or not finite, n >= 2^31; 0 for n = 0:
+ *   vxrt_envmap_lookup: dirs (n x 3) -> radiance3 (n x 3: Env(w)), texel (n: e), pdf (n: pe(w)).
+ *   vxrt_env_rays: points (n x 6: I, N'), seeds (n hash outputs) -> rays (n x 6: o, w), tmax (n), weight3 (n x 3: Gm), texel (n: e),
+ *     mis (n: wE); a skipped entry gets the ray (0,0,0; 1,1,1), tmax = -1, Gm = 0 and wE = 0, and keeps the e it chose. */
+typedef struct vxrt_envmap vxrt_envmap_t;
+typedef struct vxrt_env_params {
+  vxrt_envmap_t* map;    /* not NULL */
+  float scale;           /* multiplies every texel; >= 0 and finite */
+  uint32_t sample;       /* 0: the map is seen by rays that miss; 1: and sampled, both weighted */
+  uint32_t reserved;     /* 0 */
+} vxrt_env_params_t;
+int vxrt_envmap_create(const float* texels /* HOST, n x n x 3 */, uint32_t n, void* stream, vxrt_envmap_t** map);
+int vxrt_envmap_destroy(vxrt_envmap_t* map);
+uint64_t vxrt_envmap_bytes(const vxrt_envmap_t* map);
+int vxrt_envmap_read(vxrt_envmap_t* map, uint32_t* q /* HOST, n x n, or NULL */, uint32_t* cum /* HOST, n x n, or NULL */, void* stream);
+int vxrt_render_path_frame_env(vxrt_accel_t* accel, const vxrt_path_frame_t* frame, const vxrt_roulette_params_t* roulette /* may be NULL */,
+                               const vxrt_env_params_t* env /* may be NULL */, void* stream);
+int vxrt_envmap_lookup(vxrt_envmap_t* map, uint64_t n, const float* dirs /* device, n x 3 */, float scale, float* radiance3 /* device, n x 3 */,
+                       uint32_t* texel /* device */, float* pdf /* device */, void* stream);
+int vxrt_env_rays(vxrt_envmap_t* map, uint64_t n, const float* points /* device, n x 6: I, N' */, const uint32_t* seeds /* device */, float scale,
+                  float* rays /* device, n x 6 */, float* tmax /* device */, float* weight3 /* device, n x 3: Gm */, uint32_t* texel /* device */,
+                  float* mis /* device, n: wE */, void* stream);
+
 /* ---- software twin: the reference's raycast test (tests/regression/raycast) ----
  * Buffers in the reference's formats (raycast/common.h): tlas_node_t 32 B, blas_node_t 160 B (transform,
  * invTransform, bvh_offset@128, tex_offset@136, tex_width@144, tex_height@148, reflectivity@152),

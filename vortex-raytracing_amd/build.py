@@ -30,7 +30,7 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-ffp-contract=off", "-fno-slp-vec
 HIP_FLAGS += os.environ.get("VXRT_EXTRA_HIPFLAGS", "").split()   # experiments only (e.g. -DLDS_STACK=8)
 CXX_FLAGS = ["-O2", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall"]
 
-PRODUCT_HIP_SOURCES = ("rt_kernels.hip", "rt_accel.hip", "rt_secondary.hip", "rt_path.hip", "rt_denoise.hip", "rc_kernels.hip", "vx_backend.hip", "bvh_builder.hip")
+PRODUCT_HIP_SOURCES = ("rt_kernels.hip", "rt_accel.hip", "rt_secondary.hip", "rt_path.hip", "rt_env.hip", "rt_denoise.hip", "rc_kernels.hip", "vx_backend.hip", "bvh_builder.hip")
 
 
 def hip_library_deps():

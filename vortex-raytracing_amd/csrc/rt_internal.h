@@ -205,6 +205,18 @@ static inline EmitterIdx emitter_idx(const vxrt_accel* a) { return EmitterIdx{a-
 // it is held).  0, or -1 when a HIP call failed.
 int emitter_index_ensure(vxrt_accel* a, hipStream_t s);
 
+// Environment map (vxrt_envmap_create, rt_env.hip; the definition is in the header, "Environment light"): n x n RGB texels of the
+// octahedral unfolding, the quantised weight q of every texel and its inclusive prefix sum cum in texel order; Q = cum[n * n - 1].
+// World-space directions only: nothing an accel does makes it stale.
+struct vxrt_envmap { float* texels = nullptr; uint32_t* q = nullptr; uint32_t* cum = nullptr; uint32_t n = 0, Q = 0; };
+// What the kernels read of it (rt_env.h), with the scale of the call
+struct EnvTab { const float* texels; const uint32_t* q; const uint32_t* cum; uint32_t n, Q; float scale; };
+static inline EnvTab env_tab(const vxrt_envmap* m, float scale) { return EnvTab{m->texels, m->q, m->cum, m->n, m->Q, scale}; }
+// the checks of vxrt_env_params_t every door shares (rt_path.hip, rt_kernels.hip)
+static inline bool env_params_ok(const vxrt_env_params_t* e) {
+  return e->map && e->map->n != 0u && e->sample <= 1u && e->reserved == 0u && e->scale >= 0.0f && e->scale <= 3.402823466e+38f;
+}
+
 // What the previous-position guide reads besides the SceneDev (see the header, "Motion"): the snapshot's instance records, the vertices
 // (the snapshot's, or the scene's current ones) and the two bounds a hit record is checked against
 struct MotionSrc { const uint32_t* blas; const float* tri; uint32_t n_blas, n_tris; };
@@ -293,6 +305,7 @@ struct RenderRequest {
   const vxrt_emissive_mis_params_t* emissive_mis = nullptr; // ... with both estimators of emissive geometry, weighted (vxrt_render_path_emissive_mis)
   const vxrt_specular_params_t* specular = nullptr; // ... whose vertices may be specular (vxrt_render_path_frame_specular with enable = 1; null for enable = 0)
   const vxrt_roulette_params_t* roulette = nullptr; // ... whose dim paths end early (vxrt_render_path_frame_ex with enable = 1; null for enable = 0); never with `specular`
+  const vxrt_env_params_t* env = nullptr;           // ... lit by an environment map (vxrt_render_path_frame_env); never with an emitter form or `specular`
   const uint32_t* sample_counts = nullptr;          // ... with a sample count per pixel (vxrt_render_path_adaptive): device, addressed like dst; path->spp is the cap
   const vxrt_denoise_params_t* denoise = nullptr;   // ... denoised (vxrt_render_path_denoised), with its optional guide outputs
   const vxrt_path_aov_t* aov = nullptr;

@@ -2013,6 +2013,9 @@ static int check_request(const vxrt_accel* a, const RenderRequest& r) {
   if (r.roulette && (!r.path || r.roulette->enable != 1u || r.roulette->first < 1u || r.roulette->first > VXRT_PATH_MAX_BOUNCES ||
                      !std::isfinite(r.roulette->q_min) || !(r.roulette->q_min > 0.0f) || !(r.roulette->q_min <= 1.0f) || r.roulette->reserved != 0u ||
                      r.specular)) return -1;
+  // a path frame lit by an environment map: its parameters, and neither an emitter form (three-way weighting is a design of its own)
+  // nor specular vertices beside it
+  if (r.env && (!r.path || !env_params_ok(r.env) || r.emissive || r.emissive_mis || r.specular)) return -1;
   return 1;
 }
 

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "rt_internal.h"
 #include "rt_shading.h"
+#include "rt_env.h"
 
 // ---------------------------------------------------------------------------------------------
 // Path frames (vxrt_render_path; the definition is in include/vortex_hip.h, the launch sequence in render_path_tail and DESIGN.md s2,
@@ -91,6 +92,8 @@ __device__ __forceinline__ bool emission(const SceneDev& sc, uint32_t triIdx, fl
 // what the emissive flavour of the prepare launch takes besides (EMI: lit[t] = Lit_0 + Emi(h_0))
 struct PrepEmi { float scale; };
 struct PrepNoEmi {};
+// ... and the flavour lit by an environment map (ENV: a miss pixel's lit[t] = Env(dir(r_0)) in place of the background)
+struct PrepNoEnv {};
 
 // The header's "Specular vertices": a vertex of reflectivity rho is specular iff rho > 0 and rho is finite
 __device__ __forceinline__ bool specular_vertex(float rho) { return rho > 0.0f && isfinite(rho); }
@@ -108,12 +111,12 @@ __device__ __forceinline__ bool specular_pick(float rho, uint32_t seed) {
 // (MOTION: the frame with motion -- the previous-position guide of the pixel's record, computed where the record is in registers)
 // (SPEC: the frame with specular vertices -- alb[t].w = the primary hit's reflectivity, and with spec_cont, i.e. bounces > 0, a specular
 //  primary hit continues: lit[t] is `term` alone, without background * reflectivity)
-template <bool CAM, bool MOTION, bool EMI, bool SPEC = false>
+template <bool CAM, bool MOTION, bool EMI, bool SPEC = false, bool ENV = false>
 __device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadeParams& p, uint32_t n, uint32_t W, uint32_t y0,
     const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
     float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
     uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo,
-    std::conditional_t<EMI, PrepEmi, PrepNoEmi> em, uint32_t spec_cont = 0u) {
+    std::conditional_t<EMI, PrepEmi, PrepNoEmi> em, uint32_t spec_cont = 0u, std::conditional_t<ENV, EnvTab, PrepNoEnv> env = {}) {
   if (ctl_reset && blockIdx.x == 0)
     for (uint32_t i = threadIdx.x; i < CTL_DWORDS; i += 256u) ctl_reset[i] = 0u;
   bool hit_c[PREP_CHUNKS];
@@ -133,7 +136,13 @@ __device__ __forceinline__ void path_prepare(const SceneDev& sc, const ShadePara
       else generate_ray(utab[x], vtab[y], ox, oy, oz, dx, dy, dz);
       if (h.dist == RT_LARGE_FLOAT) {
         geo[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        lit[t] = make_float4(p.bg[0], p.bg[1], p.bg[2], 0.f);
+        if constexpr (ENV) {
+          float L[3], pe;
+          env_lookup(env, dx, dy, dz, L, pe);
+          lit[t] = make_float4(L[0], L[1], L[2], 0.f);
+        } else {
+          lit[t] = make_float4(p.bg[0], p.bg[1], p.bg[2], 0.f);
+        }
       } else {
         float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
         shade_terms<false>(sc, p, ox, oy, oz, dx, dy, dz, h, occ, r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, nullptr, a3);
@@ -200,6 +209,15 @@ __global__ __launch_bounds__(256) void rt_path_prepare_specular_kernel(SceneDev 
     path_prepare<CAM, false, true, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepEmi{scale}, cont);
   else
     path_prepare<CAM, false, false, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, PrepNoMotion{}, PrepNoEmi{}, cont);
+}
+
+// (the frame lit by an environment map, vxrt_render_path_frame_env: with or without motion)
+template <bool CAM, bool MOTION>
+__global__ __launch_bounds__(256) void rt_path_prepare_env_kernel(SceneDev sc, ShadeParams p, uint32_t n, uint32_t W, uint32_t y0,
+    const float* __restrict__ utab, const float* __restrict__ vtab, const HitRec* __restrict__ hb,
+    float4* __restrict__ geo, float4* __restrict__ nrm, float4* __restrict__ dir, float4* __restrict__ lit, float4* __restrict__ alb,
+    uint32_t* __restrict__ list, uint32_t* hdr, uint32_t* ctl_reset, std::conditional_t<MOTION, PrepMotion, PrepNoMotion> mo, EnvTab env) {
+  path_prepare<CAM, MOTION, false, false, true>(sc, p, n, W, y0, utab, vtab, hb, geo, nrm, dir, lit, alb, list, hdr, ctl_reset, mo, PrepNoEmi{}, 0u, env);
 }
 
 // start of a batch of ns samples: every slot takes its pixel's primary vertex (Lc = Lit, thr = Alb) and is live; hdr[1] = their number
@@ -385,6 +403,63 @@ __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_mis_kernel(ui
     const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EmitterTab tab, float scale,
     float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
   path_bounce_emitter_rays<true>(cap, W, y0, SlotUniform{spp, s0, ns, list}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
+}
+
+// rt_path_bounce_rays_kernel of a frame that samples its environment map (the header's "Environment light", sample = 1): besides the
+// bounce ray of slot live[q], the environment ray of the same vertex -- user seed (seed + depth) ^ 0x10000000 in the bounce ray's hash
+// input -- where path_bounce_emitter_rays writes the emitter ray: erays, etmax, eG[q] = (Gm, real).  The two forms exclude each other,
+// so the buffers and the any-hit launch behind them serve both.  The row ends of the map's table are staged in LDS first; as there, no
+// thread leaves before the barriers and the environment rays cost one atomic per workgroup.
+template <class SlotSrc>
+__device__ __forceinline__ void path_bounce_env_rays(uint32_t cap, uint32_t W, uint32_t y0, const SlotSrc& src, uint32_t user_seed,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, const EnvTab& env,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  __shared__ uint32_t s_real;
+  __shared__ uint32_t s_rows[ENV_MAX_N];
+  if (threadIdx.x == 0) s_real = 0u;
+  env_stage_rows(env, s_rows);
+  const uint32_t total = min(*n_live, cap);
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q == 0) {
+    *n_next = 0u;
+    if (rays_traced && total) atomicAdd(rays_traced, (unsigned long long)total);   // (every live path traces one bounce ray)
+  }
+  bool real = false;
+  if (q < total) {
+    const uint32_t slot = live[q];
+    uint32_t t, smp, spp;
+    src.get(slot, t, smp, spp);
+    const uint32_t x = t % W, y = y0 + t / W;
+    const float4 I = pI[slot], N = pN[slot], D = pD[slot];
+    float r6[6];
+    ao_sample_ray(x, y, W, spp, smp, user_seed, I.x, I.y, I.z, N.x, N.y, N.z, D.x, D.y, D.z, r6);
+    float* o = rays + (size_t)q * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = r6[k];
+    float nx = N.x, ny = N.y, nz = N.z;
+    if (nx * D.x + ny * D.y + nz * D.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // (N' as ao_sample_ray turns it)
+    const uint32_t seed = wang_hash((x + y * W) * spp + smp + 1u + (user_seed ^ 0x10000000u) * 0x9E3779B9u);
+    float e6[6], tm, G[3], wE;
+    uint32_t e;
+    real = env_sample(env, s_rows, seed, I.x, I.y, I.z, nx, ny, nz, e6, tm, G, e, wE);
+    float* eo = erays + (size_t)q * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) eo[k] = e6[k];
+    etmax[q] = tm;
+    eG[q] = make_float4(G[0], G[1], G[2], real ? 1.0f : 0.0f);
+  }
+  const unsigned long long m = __ballot(real);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_real, (uint32_t)__popcll(m));
+  __syncthreads();
+  if (threadIdx.x == 0 && rays_traced && s_real) atomicAdd(rays_traced, (unsigned long long)s_real);
+}
+
+__global__ __launch_bounds__(256) void rt_path_bounce_env_rays_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t spp, uint32_t s0, uint32_t ns, uint32_t user_seed,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EnvTab env,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  path_bounce_env_rays(cap, W, y0, SlotUniform{spp, s0, ns, list}, user_seed, live, n_live, n_next, pI, pN, pD, rays, env, erays, etmax, eG, rays_traced);
 }
 
 // The bounce rays of one depth of a frame with specular vertices (the header's "Specular vertices"): per-slot state holds thr BEFORE the
@@ -617,6 +692,12 @@ __global__ __launch_bounds__(256) void rt_path_occlusion_rays_kernel(ShadeParams
 struct ScatterEmi { float scale; const HitRec* ehits; const float4* eG; };
 struct ScatterMis { float scale; const HitRec* ehits; const float4* eG; EmitterTab tab; EmitterIdx idx; };
 struct ScatterNoEmi {};
+// (EMI 4 and 5: the frame lit by an environment map, the header's "Environment light", sample = 0 and 1.  A miss adds thr * Env(w) in
+//  place of thr * background -- with 5 weighted by wB, from N' of the vertex the ray left, which a miss leaves in its slot -- and 5 adds
+//  the environment ray's term as 2 adds the emitter ray's: eG holds Gm.  The lookup's divisions and square root run in the lanes that
+//  missed only.)
+struct ScatterEnv { const HitRec* ehits; const float4* eG; EnvTab tab; };
+template <int EMI> using ScatterEm = std::conditional_t<EMI >= 4, ScatterEnv, std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>>>;
 // (SPEC: the frame of the header's "Specular vertices".  pT is thr as the ray left with it and is not touched here; a hit that goes on
 //  stores its Alb and reflectivity in pA instead, and if it is specular it adds `term` alone.  pD[slot].w marks the segment that arrives:
 //  after a specular one a hit whose material emits adds thr * Emi in full in all three emitter forms, without a lookup.)
@@ -664,9 +745,10 @@ template <int EMI, bool SPEC = false, bool RR = false, class SlotSrc = SlotUnifo
 __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadeParams& p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
     const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
     float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
-    uint32_t* __restrict__ next, uint32_t* n_next, const std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>>& em,
+    uint32_t* __restrict__ next, uint32_t* n_next, const ScatterEm<EMI>& em,
     float4* __restrict__ pA = nullptr, const std::conditional_t<RR, ScatterRoulette<SlotSrc>, ScatterNoRoulette>& rr = {}) {
   static_assert(!(RR && SPEC), "a specular frame takes no roulette (check_request)");
+  static_assert(!(EMI >= 4 && SPEC), "a frame lit by an environment map has no specular vertices (check_request)");
   const uint32_t total = min(*n_live, cap);
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   bool go[1] = {false};
@@ -680,12 +762,25 @@ __device__ __forceinline__ void path_scatter(const SceneDev& sc, const ShadePara
     const float4 T = pT[slot];
     bool seg = false;   // (the segment that arrives is specular)
     if constexpr (SPEC) seg = pD[slot].w != 0.f;
-    if constexpr (EMI == 2 || EMI == 3) {
+    if constexpr (EMI == 2 || EMI == 3 || EMI == 5) {
       const float4 G = em.eG[q];
       if (G.w != 0.f && em.ehits[q].dist == RT_LARGE_FLOAT) { L.x = L.x + T.x * G.x; L.y = L.y + T.y * G.y; L.z = L.z + T.z * G.z; }
     }
     if (h.dist == RT_LARGE_FLOAT) {
-      L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
+      if constexpr (EMI >= 4) {
+        float E3[3], pe;
+        env_lookup(em.tab, rp[3], rp[4], rp[5], E3, pe);
+        if constexpr (EMI == 5) {
+          const float4 N = pN[slot], D = pD[slot];   // (the vertex the ray left)
+          float nx = N.x, ny = N.y, nz = N.z;
+          if (nx * D.x + ny * D.y + nz * D.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // (N' as ao_sample_ray turns it)
+          const float wB = env_miss_weight(pe, nx, ny, nz, rp[3], rp[4], rp[5]);
+          E3[0] = E3[0] * wB; E3[1] = E3[1] * wB; E3[2] = E3[2] * wB;
+        }
+        L.x = L.x + T.x * E3[0]; L.y = L.y + T.y * E3[1]; L.z = L.z + T.z * E3[2];
+      } else {
+        L.x = L.x + T.x * p.bg[0]; L.y = L.y + T.y * p.bg[1]; L.z = L.z + T.z * p.bg[2];
+      }
     } else {
       const bool occ = shits != nullptr && shits[q].dist != RT_LARGE_FLOAT;
       float r, g, b, refl, Ix, Iy, Iz, Nx, Ny, Nz, a3[3];
@@ -793,6 +888,16 @@ __global__ __launch_bounds__(256) void rt_path_scatter_roulette_kernel(SceneDev 
     uint32_t* __restrict__ next, uint32_t* n_next, std::conditional_t<EMI == 3, ScatterMis, std::conditional_t<EMI != 0, ScatterEmi, ScatterNoEmi>> em,
     ScatterRoulette<SlotSrc> rr) {
   path_scatter<EMI, false, true, SlotSrc>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em, nullptr, rr);
+}
+
+// (the frame lit by an environment map: EMI = 4 for sample = 0, 5 for sample = 1; RR and SlotSrc as for the kernel above -- without
+//  roulette the slot source is not read)
+template <int EMI, bool RR, class SlotSrc>
+__global__ __launch_bounds__(256) void rt_path_scatter_env_kernel(SceneDev sc, ShadeParams p, uint32_t cap, const uint32_t* n_live, const uint32_t* __restrict__ live,
+    const float* __restrict__ rays, const HitRec* __restrict__ hits, const HitRec* __restrict__ shits,
+    float4* __restrict__ pI, float4* __restrict__ pN, float4* __restrict__ pD, float4* __restrict__ pL, float4* __restrict__ pT,
+    uint32_t* __restrict__ next, uint32_t* n_next, ScatterEnv em, std::conditional_t<RR, ScatterRoulette<SlotSrc>, ScatterNoRoulette> rr) {
+  path_scatter<EMI, false, RR, SlotSrc>(sc, p, cap, n_live, live, rays, hits, shits, pI, pN, pD, pL, pT, next, n_next, em, nullptr, rr);
 }
 
 // after a batch's last depth: the Lc of its ns samples are added to the pixel's accumulator in ascending s (the frame's first sample
@@ -1005,6 +1110,15 @@ __global__ __launch_bounds__(256) void rt_path_bounce_emitter_rays_counts_mis_ke
   path_bounce_emitter_rays<true>(cap, W, y0, SlotCounts{spix, ssmp, cnt}, user_seed, live, n_live, n_next, pI, pN, pD, rays, tab, scale, erays, etmax, eG, rays_traced);
 }
 
+// (rt_path_bounce_env_rays_kernel likewise: the environment ray's hash input takes the pixel's own n_p)
+__global__ __launch_bounds__(256) void rt_path_bounce_env_rays_counts_kernel(uint32_t cap, uint32_t W, uint32_t y0, uint32_t user_seed,
+    const uint32_t* __restrict__ spix, const uint32_t* __restrict__ ssmp, const uint32_t* __restrict__ cnt,
+    const uint32_t* __restrict__ live, const uint32_t* n_live, uint32_t* n_next,
+    const float4* __restrict__ pI, const float4* __restrict__ pN, const float4* __restrict__ pD, float* __restrict__ rays, EnvTab env,
+    float* __restrict__ erays, float* __restrict__ etmax, float4* __restrict__ eG, unsigned long long* rays_traced) {
+  path_bounce_env_rays(cap, W, y0, SlotCounts{spix, ssmp, cnt}, user_seed, live, n_live, n_next, pI, pN, pD, rays, env, erays, etmax, eG, rays_traced);
+}
+
 // after a batch's last depth, one thread per pixel of the window: the Lc of the pixel's samples that are in the batch [g0, g0 + cap)
 // are added to its accumulator in ascending sample order; the pixel's first sample starts it.  A pixel's samples are contiguous in g
 // and may straddle batches; the trip count is at most the pixel's count.
@@ -1083,23 +1197,28 @@ extern const uint64_t PATH_BATCH_PATHS = 4ull << 20;   // (secondary_knobs, rt_s
 // sampling": the launches of 2 with the weighted kernels, whose scatter looks emissive hits up in the emitter index.  scale: that
 // form's, 0 without one.  spec: specular vertices; counts: a sample count per pixel; shadow: light sampling; cam: a camera frame.
 // roulette (the header's "Russian roulette"): vertices rr_first .. bounces - 1 take a draw with floor q_min; never with spec.
-struct PathForm { int emi; float scale; bool spec, counts, shadow, motion, cam, roulette; uint32_t rr_first; float q_min; };
+// env (the header's "Environment light"): 0 none, 1 the map is seen by rays that miss (sample = 0), 2 and sampled -- the launches of
+// emi = 2 with the environment kernels (sample = 1); never with an emitter form or spec.  map: what the kernels read of it, with the scale.
+struct PathForm { int emi; float scale; bool spec, counts, shadow, motion, cam, roulette; uint32_t rr_first; float q_min; int env; EnvTab map; };
 static PathForm path_form(const RenderRequest& r) {
   PathForm f;
   f.emi = r.emissive_mis ? 3 : r.emissive ? (r.emissive->nee ? 2 : 1) : 0;
   f.scale = r.emissive_mis ? r.emissive_mis->scale : r.emissive ? r.emissive->scale : 0.0f;
   f.spec = r.specular != nullptr; f.counts = r.sample_counts != nullptr; f.shadow = r.path->shadow != 0; f.motion = r.motion; f.cam = r.cams != nullptr;
   f.roulette = r.roulette != nullptr; f.rr_first = r.roulette ? r.roulette->first : 0u; f.q_min = r.roulette ? r.roulette->q_min : 0.0f;
+  f.env = r.env ? (r.env->sample ? 2 : 1) : 0;
+  f.map = r.env ? env_tab(r.env->map, r.env->scale) : EnvTab{nullptr, nullptr, nullptr, 0u, 0u, 0.0f};
   return f;
 }
 
 // What the kernels of an emitter form take besides, built once per frame behind path_tail_begin (which grows the buffers named here and
 // has the index built): rays for the bounce-ray kernels of emi >= 2, hits / weighted for the scatter kernels of emi 1, 2 / 3
-struct PathEmitters { SpecEm rays; ScatterEmi hits; ScatterMis weighted; };
+struct PathEmitters { SpecEm rays; ScatterEmi hits; ScatterMis weighted; ScatterEnv env; };
 static PathEmitters path_emitters(const vxrt_accel* a, const FrameCtx* c, const PathForm& f) {
   return PathEmitters{SpecEm{emitter_tab(a), f.scale, c->pt_erays, c->pt_etmax, c->pt_eG},
                       ScatterEmi{f.scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG},
-                      ScatterMis{f.scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)}};
+                      ScatterMis{f.scale, (const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, emitter_tab(a), emitter_idx(a)},
+                      ScatterEnv{(const HitRec*)c->pt_ehits, (const float4*)c->pt_eG, f.map}};
 }
 
 // The prepare launch of a path frame over the n pixels of its window: which instantiation the form takes, and what that one takes
@@ -1114,6 +1233,8 @@ static void path_prepare_launch(vxrt_accel_t* a, FrameCtx* c, const RenderReques
   if (f.spec)   // (no motion: check_request.  `scale` is read by the emissive flavour only; the last argument is bounces > 0)
     launch(f.cam ? (emi ? rt_path_prepare_specular_kernel<true, true> : rt_path_prepare_specular_kernel<true, false>)
                  : (emi ? rt_path_prepare_specular_kernel<false, true> : rt_path_prepare_specular_kernel<false, false>), f.scale, r.path->bounces ? 1u : 0u);
+  else if (f.env && f.motion) launch(rt_path_prepare_env_kernel<true, true>, mo, f.map);
+  else if (f.env) launch(f.cam ? rt_path_prepare_env_kernel<true, false> : rt_path_prepare_env_kernel<false, false>, PrepNoMotion{}, f.map);
   else if (emi && f.motion) launch(rt_path_prepare_emissive_motion_kernel, mo, f.scale);
   else if (emi) launch(f.cam ? rt_path_prepare_emissive_kernel<true> : rt_path_prepare_emissive_kernel<false>, f.scale);
   else if (f.motion) launch(rt_path_prepare_kernel<true, true>, mo);
@@ -1129,7 +1250,7 @@ static int path_tail_begin(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r,
   hipStream_t s = (hipStream_t)r.stream;
   const uint64_t shadow_cap = f.shadow ? path_cap : 0;
   if (f.emi == 3 && emitter_index_ensure(a, s) != 0) return -1;
-  if (f.emi >= 2 && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
+  if ((f.emi >= 2 || f.env == 2) && !grow_device({{(void**)&c->pt_erays, 24}, {(void**)&c->pt_etmax, 4}, {(void**)&c->pt_ehits, sizeof(HitRec)}, {(void**)&c->pt_eG, 16}}, &c->pt_em_cap,
                                  path_cap, GrowSync::STREAM, s)) return -1;
   if (!c->pt_hdr && hipMalloc((void**)&c->pt_hdr, 16) != hipSuccess) return -1;
   if (!grow_device({{(void**)&c->pt_geo, 16}, {(void**)&c->pt_nrm, 16}, {(void**)&c->pt_dir, 16}, {(void**)&c->pt_lit, 16}, {(void**)&c->pt_alb, 16},
@@ -1172,7 +1293,7 @@ static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& 
                          c->pt_srays, c->pt_stmax, r.counters);
       if (trace_on_ctx(a, c, c->pt_srays, n_rays, c->pt_stmax, c->pt_shits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
     }
-    if (f.emi >= 2 && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
+    if ((f.emi >= 2 || f.env == 2) && trace_on_ctx(a, c, c->pt_erays, n_rays, c->pt_etmax, c->pt_ehits, MODE_ANY_UNORDERED, s, n_live) != 0) return -1;
     // (the specular instantiations: the same launch, per-slot Alb and reflectivity besides)
     const auto scatter = [&](auto kernel, auto... rest) {
       hipLaunchKernelGGL(kernel, rgrid, block, 0, s, a->dev, p, cap, (const uint32_t*)n_live, live, (const float*)c->pt_rays, (const HitRec*)c->pt_hits, shits,
@@ -1180,11 +1301,14 @@ static int path_batch_depths(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& 
     };
     if (f.roulette && next && d + 1u >= f.rr_first) {
       const ScatterRoulette<SlotSrc> rr{slots, r.width, r.y0, r.path->seed + d, f.q_min};
-      if (f.emi == 3) scatter(rt_path_scatter_roulette_kernel<3, SlotSrc>, next, n_next, E.weighted, rr);
+      if (f.env) scatter(f.env == 2 ? rt_path_scatter_env_kernel<5, true, SlotSrc> : rt_path_scatter_env_kernel<4, true, SlotSrc>, next, n_next, E.env, rr);
+      else if (f.emi == 3) scatter(rt_path_scatter_roulette_kernel<3, SlotSrc>, next, n_next, E.weighted, rr);
       else if (f.emi == 2) scatter(rt_path_scatter_roulette_kernel<2, SlotSrc>, next, n_next, E.hits, rr);
       else if (f.emi == 1) scatter(rt_path_scatter_roulette_kernel<1, SlotSrc>, next, n_next, E.hits, rr);
       else scatter(rt_path_scatter_roulette_kernel<0, SlotSrc>, next, n_next, ScatterNoEmi{}, rr);
-    } else if (f.spec && f.emi == 3) scatter(rt_path_scatter_specular_kernel<3>, c->pt_A, next, n_next, E.weighted);
+    } else if (f.env) scatter(f.env == 2 ? rt_path_scatter_env_kernel<5, false, SlotUniform> : rt_path_scatter_env_kernel<4, false, SlotUniform>, next, n_next, E.env,
+                              ScatterNoRoulette{});   // (no draw: the slot source is not read, one instantiation serves both tails)
+    else if (f.spec && f.emi == 3) scatter(rt_path_scatter_specular_kernel<3>, c->pt_A, next, n_next, E.weighted);
     else if (f.spec && f.emi == 2) scatter(rt_path_scatter_specular_kernel<2>, c->pt_A, next, n_next, E.hits);
     else if (f.spec && f.emi == 1) scatter(rt_path_scatter_specular_kernel<1>, c->pt_A, next, n_next, E.hits);
     else if (f.spec) scatter(rt_path_scatter_specular_kernel<0>, c->pt_A, next, n_next, ScatterNoEmi{});
@@ -1246,6 +1370,7 @@ static int render_path_uniform_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRe
       else if (f.spec) launch(rt_path_bounce_specular_kernel<0>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, SpecNoEm{});
       else if (f.emi >= 2) launch(f.emi == 3 ? rt_path_bounce_emitter_rays_mis_kernel : rt_path_bounce_emitter_rays_kernel, (const float4*)c->pt_D, c->pt_rays,
                                   e.tab, e.scale, e.erays, e.etmax, e.eG);
+      else if (f.env == 2) launch(rt_path_bounce_env_rays_kernel, (const float4*)c->pt_D, c->pt_rays, f.map, e.erays, e.etmax, e.eG);
       else launch(rt_path_bounce_rays_kernel, (const float4*)c->pt_D, c->pt_rays);
     };
     if (path_batch_depths(a, c, r, f, E, p, cap, (uint64_t)n * k, SlotUniform{pp.spp, s0, k, c->pt_list}, bounce_rays) != 0) return -1;
@@ -1308,6 +1433,7 @@ static int render_path_counts_tail(vxrt_accel_t* a, FrameCtx* c, const RenderReq
       else if (f.spec) launch(rt_path_bounce_specular_counts_kernel<0>, c->pt_D, c->pt_T, (const float4*)c->pt_A, c->pt_rays, SpecNoEm{});
       else if (f.emi >= 2) launch(f.emi == 3 ? rt_path_bounce_emitter_rays_counts_mis_kernel : rt_path_bounce_emitter_rays_counts_kernel, (const float4*)c->pt_D, c->pt_rays,
                                   e.tab, e.scale, e.erays, e.etmax, e.eG);
+      else if (f.env == 2) launch(rt_path_bounce_env_rays_counts_kernel, (const float4*)c->pt_D, c->pt_rays, f.map, e.erays, e.etmax, e.eG);
       else launch(rt_path_bounce_rays_counts_kernel, (const float4*)c->pt_D, c->pt_rays);
     };
     if (path_batch_depths(a, c, r, f, E, p, cap, cap, SlotCounts{c->pt_spix, c->pt_ssmp, c->pt_cnt}, bounce_rays) != 0) return -1;
@@ -1338,7 +1464,7 @@ int render_path_tail(vxrt_accel_t* a, FrameCtx* c, const RenderRequest& r, const
 // (specular: vxrt_render_path_frame_specular's part beside the descriptor, already checked and with enable = 1, or null; roulette:
 //  vxrt_render_path_frame_ex's, likewise)
 static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, void* stream,
-                             const vxrt_roulette_params_t* roulette = nullptr) {
+                             const vxrt_roulette_params_t* roulette = nullptr, const vxrt_env_params_t* env = nullptr) {
   if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
   for (int k = 0; k < 4; ++k) if (f->reserved[k] != 0u) return -1;
   if (!f->path || (f->emissive && f->emissive_mis) || f->motion > 1u) return -1;
@@ -1356,7 +1482,7 @@ static int render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, co
   req.emissive = f->emissive; req.emissive_mis = f->emissive_mis; req.sample_counts = f->counts;
   req.denoise = f->denoise; req.aov = f->aov; req.temporal = f->temporal; req.history = f->history; req.motion = f->motion == 1u; req.prev_position = f->prev_position;
   req.variance = f->variance; req.variance_out = f->variance_out;
-  req.specular = specular; req.roulette = roulette;
+  req.specular = specular; req.roulette = roulette; req.env = env;
   return render_common(accel, req);
 }
 
@@ -1473,13 +1599,32 @@ int vxrt_render_path_frame(vxrt_accel_t* accel, const vxrt_path_frame_t* f, void
 // get wrong is refused here, and so is the specular part with enable = 1 beside it (check_request refuses the pair as well, behind its
 // empty window).  A specular part with enable = 0 is checked as its own entry point checks it.
 static bool roulette_q_min_ok(float q_min) { return std::isfinite(q_min) && q_min > 0.0f && q_min <= 1.0f; }
+// (what a roulette part with enable != 0 can get wrong alone: both doors that take one ask here)
+static bool roulette_part_ok(const vxrt_roulette_params_t* r) {
+  return r->enable == 1u && r->first >= 1u && r->first <= VXRT_PATH_MAX_BOUNCES && roulette_q_min_ok(r->q_min) && r->reserved == 0u;
+}
 int vxrt_render_path_frame_ex(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_specular_params_t* specular, const vxrt_roulette_params_t* roulette,
                               void* stream) {
   if (!roulette || roulette->enable == 0u) return vxrt_render_path_frame_specular(accel, f, specular, stream);
-  if (roulette->enable > 1u || roulette->first < 1u || roulette->first > VXRT_PATH_MAX_BOUNCES || !roulette_q_min_ok(roulette->q_min) || roulette->reserved != 0u) return -1;
+  if (!roulette_part_ok(roulette)) return -1;
   if (f && ((f->prev_position && !f->motion) || (f->variance_out && !f->variance))) return -1;
   if (specular && (specular->enable != 0u || specular->reserved[0] != 0u || specular->reserved[1] != 0u || specular->reserved[2] != 0u)) return -1;
   return render_path_frame(accel, f, nullptr, stream, roulette);
+}
+
+// A path frame lit by an environment map (see the header, "Environment light"): the descriptor's frame, with the roulette part if it is
+// enabled, whose misses see the map and, with sample = 1, whose vertices send an environment ray.  A null part IS
+// vxrt_render_path_frame_ex without a specular part.  The descriptor's size comes first -- nothing of a shorter one is read -- then what
+// the parts alone can get wrong and an emitter form beside the map: all of it ahead of check_request's empty window, which is why
+// check_request, the one place that sees every request, cannot be the only one to refuse them.
+int vxrt_render_path_frame_env(vxrt_accel_t* accel, const vxrt_path_frame_t* f, const vxrt_roulette_params_t* roulette, const vxrt_env_params_t* env, void* stream) {
+  if (!env) return vxrt_render_path_frame_ex(accel, f, nullptr, roulette, stream);
+  if (!f || f->size != sizeof(vxrt_path_frame_t)) return -1;
+  if (!env_params_ok(env) || f->emissive || f->emissive_mis) return -1;
+  if ((f->prev_position && !f->motion) || (f->variance_out && !f->variance)) return -1;
+  const bool rr = roulette && roulette->enable != 0u;
+  if (rr && !roulette_part_ok(roulette)) return -1;
+  return render_path_frame(accel, f, nullptr, stream, rr ? roulette : nullptr, env);
 }
 
 // The single launches below run on caller-owned buffers, asynchronous on `stream`, without a host synchronisation.

@@ -829,16 +829,81 @@ class RouletteParams(C.Structure):   # vxrt_roulette_params_t: rides beside a Pa
         self.enable, self.first, self.q_min = int(enable), int(first), float(q_min)
 
 
-def render_path_frame(accel, frame, stream=None, specular=None, roulette=None):
+class EnvMap:
+    """vxrt_envmap_t: an octahedral radiance map (the header's "Environment light"), made from host texels (n, n, 3) float32 with texel
+    (i, j) at [j, i]; n a power of two in 4..256.  A context manager; the map must outlive the frames that read it."""
+
+    def __init__(self, texels, stream=None):
+        import numpy as np
+        t = np.ascontiguousarray(texels, np.float32)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3:
+            raise ValueError("texels must be (n, n, 3)")
+        self.n = int(t.shape[0])
+        h = C.c_void_p()
+        check(_lib().vxrt_envmap_create(t.ctypes.data, self.n, stream, C.byref(h)), "vxrt_envmap_create")
+        self.handle = h
+
+    def close(self):
+        if self.handle is not None:
+            _lib().vxrt_envmap_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def bytes(self):
+        return int(_lib().vxrt_envmap_bytes(self.handle))
+
+    def read(self, stream=None):
+        """(q, cum): the table's quantised weights and their inclusive prefix sums, (n * n,) uint32 each, in texel order"""
+        import numpy as np
+        q, cum = np.zeros(self.n * self.n, np.uint32), np.zeros(self.n * self.n, np.uint32)
+        check(_lib().vxrt_envmap_read(self.handle, q.ctypes.data, cum.ctypes.data, stream), "vxrt_envmap_read")
+        return q, cum
+
+
+class EnvParams(C.Structure):   # vxrt_env_params_t: rides beside a PathFrame (the header's "Environment light")
+    _fields_ = [("map", C.c_void_p), ("scale", C.c_float), ("sample", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, map, scale=1.0, sample=1):
+        super().__init__()
+        self._keep = map
+        self.map = map.handle if isinstance(map, EnvMap) else map
+        self.scale, self.sample = float(scale), int(sample)
+
+
+def env_lookup(map, n, dirs_ptr, scale, radiance_ptr, texel_ptr, pdf_ptr, stream=None):
+    """vxrt_envmap_lookup: the map seen along n device directions (n x 3) -> radiance (n x 3: Env(w)), texel (n), pdf (n: the solid-angle
+    density of choosing that direction through the table)."""
+    check(_lib().vxrt_envmap_lookup(map.handle, int(n), dirs_ptr, float(scale), radiance_ptr, texel_ptr, pdf_ptr, stream), "vxrt_envmap_lookup")
+
+
+def env_rays(map, n, points_ptr, seeds_ptr, scale, rays_ptr, tmax_ptr, weight_ptr, texel_ptr, mis_ptr, stream=None):
+    """vxrt_env_rays: the environment ray alone on device buffers -- points (n x 6: I, N'), seeds (n hash outputs) -> rays (n x 6), tmax
+    (n), weight (n x 3: Gm), texel (n), mis (n: wE); a skipped entry has tmax = -1 and zero weights."""
+    check(_lib().vxrt_env_rays(map.handle, int(n), points_ptr, seeds_ptr, float(scale), rays_ptr, tmax_ptr, weight_ptr, texel_ptr, mis_ptr, stream), "vxrt_env_rays")
+
+
+def render_path_frame(accel, frame, stream=None, specular=None, roulette=None, env=None):
     """vxrt_render_path_frame: the path frame `frame` (a PathFrame) describes -- every render_path* call above is the frame with that
     call's parts, and the parts combine: an emitter form with counts, the filter, a history, motion, variance.  Raises on a refusal.
     specular (a SpecularParams): vxrt_render_path_frame_specular -- with enable = 1 the path follows reflective instances (a lobe pick
     per vertex between the mirror ray and the diffuse bounce ray); a frame without the filter chain.
     roulette (a RouletteParams): vxrt_render_path_frame_ex -- with enable = 1 the vertices first .. bounces - 1 end their path with
     probability 1 - max(q_min, largest component of the throughput) and a survivor is divided by what it survived with; not together
-    with specular vertices."""
+    with specular vertices.
+    env (an EnvParams): vxrt_render_path_frame_env -- rays that leave the scene see the environment map in place of the background, and
+    with sample = 1 every vertex also aims a ray at the map's bright texels, both weighted; not together with an emitter form or
+    specular vertices."""
     f = C.byref(frame) if frame is not None else None
-    if roulette is not None:
+    if env is not None:
+        if specular is not None:
+            raise ValueError("an environment map takes no specular part")
+        check(_lib().vxrt_render_path_frame_env(accel, f, None if roulette is None else C.byref(roulette), C.byref(env), stream), "vxrt_render_path_frame_env")
+    elif roulette is not None:
         check(_lib().vxrt_render_path_frame_ex(accel, f, None if specular is None else C.byref(specular), C.byref(roulette), stream), "vxrt_render_path_frame_ex")
     elif specular is None:
         check(_lib().vxrt_render_path_frame(accel, f, stream), "vxrt_render_path_frame")
@@ -901,6 +966,13 @@ def _declare_path_family(L):
         "vxrt_specular_pick": (i32, [C.c_uint64, vp, vp, vp, vp, vp]),
         "vxrt_render_path_frame_ex": (i32, [vp, C.POINTER(PathFrame), C.POINTER(SpecularParams), C.POINTER(RouletteParams), vp]),
         "vxrt_roulette": (i32, [C.c_uint64, vp, vp, C.c_float, vp, vp, vp]),
+        "vxrt_envmap_create": (i32, [vp, u32, vp, C.POINTER(vp)]),
+        "vxrt_envmap_destroy": (i32, [vp]),
+        "vxrt_envmap_bytes": (C.c_uint64, [vp]),
+        "vxrt_envmap_read": (i32, [vp, vp, vp, vp]),
+        "vxrt_render_path_frame_env": (i32, [vp, C.POINTER(PathFrame), C.POINTER(RouletteParams), C.POINTER(EnvParams), vp]),
+        "vxrt_envmap_lookup": (i32, [vp, C.c_uint64, vp, C.c_float, vp, vp, vp, vp]),
+        "vxrt_env_rays": (i32, [vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
     }
     for name, (restype, argtypes) in protos.items():
         f = getattr(L, name)
